@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: samples/sec/epoch of the batch-SOM hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--full] [--dump-outputs DIR]
+
+A plain run is lean: it sets up, runs the W warm-up epochs, times the K epochs, writes their outputs (`--dump-outputs`) and
+prints the line -- the contract fields and the roofline of the dominant kernel, both taken from the timed epochs themselves.
+`--full` adds everything else the line has carried: the per-kernel breakdown pass, the throughput mode, the run without block
+skipping, the schedule / data-variant / query blocks, the batch-65536 launch and the precision modes, the rank spread and the
+codebook check across ranks, the strong-scaling probe and the CPU baseline (each `--no-*` switch still drops its block).
+The blocks that replay whole schedules run on at most FULL_WARMUP + FULL_STEPS epochs (`other_blocks_schedule`), so that
+`--full` costs about the same at any --steps.
+`--dump-outputs DIR` writes what the last timed epoch computed, as a caller of the epoch receives it: DIR/codebook.npy (the
+trained codebook, units x features, float32) and DIR/bmu.npy (the last epoch's BMU id of every resident row of rank 0, float64);
+beyond 60 MiB in all, every array is cut to the same fixed, seeded sample share of its rows.
 
 `--gpus N` (N > 1) needs no launcher: when no rank environment is present this process starts its own N rank
 processes (`python -m torch.distributed.run`, one per GPU) BEFORE it touches the GPU, relays their output and
@@ -21,8 +32,8 @@ the rows of a smooth mid-schedule map); `precision_modes_at_batch65536` quantifi
   --scaling strong configs[3]'s 8,388,608 rows IN TOTAL split over the N ranks (N = 1 holds all of them)
 
 One JSON line on rank 0: the driver's contract fields + `roofline` (dominant kernel = the fused distance+BMU
-kernel, MFMA-bound, hipEvent-timed inside the timed region; `roofline.batch65536` = the same kernel at the
-north-star's batch of 65 536 rows, timed in the same process) + `cpu_baseline` (the NumPy port of the reference
+kernel, MFMA-bound, hipEvent-timed inside the timed region; with --full, `roofline.batch65536` = the same kernel at the
+north-star's batch of 65 536 rows, timed in the same process, and `cpu_baseline` = the NumPy port of the reference
 path, timed on this host's cores, N = 1 only).
 """
 import argparse
@@ -43,6 +54,7 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0        # dense bf16, /opt/skills/guides/MI355X_MI
 MFMA_F32_PEAK_TFLOPS = 157.3          # v_mfma_f32_32x32x2_f32
 STRONG_TOTAL_ROWS = 8 * (1 << 20)     # BASELINE configs[3]
 NORTH_STAR_BATCH = 65536
+FULL_WARMUP, FULL_STEPS = 5, 20       # the longest schedule --full's other blocks replay (the default --warmup / --steps)
 
 # `c3` is the configuration BASELINE.json's metric is quoted on and the default; the other two put the
 # remaining GPU configs through the same harness (python bench.py --workload c5).
@@ -108,6 +120,23 @@ def kernel_name_for(precision, features, units=1 << 16):
         wide = units >= 4096 and features <= 800 and _hook("SOM_BF16_WIDE", "1") != "0"
         return "bmu_bf16_wide_kernel" if wide else "bmu_bf16_tiled_kernel"
     return "bmu_bf16_k16_kernel"
+
+
+DUMP_BUDGET_BYTES = 60 << 20                # (npy headers on top: under 64 MB in all)
+DUMP_SAMPLE_SEED = 20240611
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: array} as out_dir/<name>.npy.  Beyond DUMP_BUDGET_BYTES in all, every array keeps the same share of its
+    rows (axis 0), drawn with a fixed seed and kept in order: the same arguments dump the same entries on every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    share = min(1.0, DUMP_BUDGET_BYTES / max(1, total))
+    for name, a in arrays.items():
+        if share < 1.0:
+            m = max(1, int(len(a) * share))
+            a = a[np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(len(a), m, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_model():
@@ -231,6 +260,10 @@ def main():
     ap.add_argument("--shard", default="contiguous", choices=["contiguous", "strided"],
                     help="strong scaling: which rows of the one data set a rank takes (strided: rank, rank + N, ...: no rank skew from the file's order)")
     ap.add_argument("--no-variants", action="store_true", help="skip the data_variants / survey_schedule / queries blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: every other measurement and check of the line (the --no-* switches apply to them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed epoch's codebook and BMU ids as DIR/<name>.npy (under 64 MB in all)")
     args = ap.parse_args()
 
     have_rank_env = "RANK" in os.environ and "WORLD_SIZE" in os.environ
@@ -307,15 +340,16 @@ def main():
 
     first_epoch = {}
 
-    def timed_run(precision):
-        """W warm-up epochs, then exactly K timed epochs between fences; max over ranks.  Returns the engine too."""
+    def timed_run(precision, sc=sched, warm=args.warmup, steps=args.steps, headline=False):
+        """`warm` warm-up epochs of schedule `sc`, then exactly `steps` timed epochs between fences; max over ranks.  Returns the
+        engine too."""
         eng = HipEngine(MAP_X, MAP_Y, FEATURES, precision=precision, device=dev, distance=wl["distance"],
                         neighborhood=wl["neighborhood"])
         eng.set_weights(w)
         eng.set_data(rows_host)
-        for t in range(args.warmup):
-            D.epoch(eng, sched[t][0], sched[t][1], True)
-            if t == 0 and precision == args.precision:
+        for t in range(warm):
+            D.epoch(eng, sc[t][0], sc[t][1], True)
+            if t == 0 and headline and args.full and args.scaling == "strong":
                 first_epoch["w"] = eng.get_weights()      # the codebook one epoch from the seed (strong scaling: probe)
         fence(eng)
         D.TIME_ALLREDUCE = dist is not None                # (events around every collective: what the epoch waits for)
@@ -328,8 +362,8 @@ def main():
         eng.profile_enable("bmu")
         sk0 = eng.exact_skip_stats() if precision == "exact" else (0, 0)
         t0 = time.perf_counter()
-        for t in range(args.warmup, total):
-            D.epoch(eng, sched[t][0], sched[t][1], True)
+        for t in range(warm, warm + steps):
+            D.epoch(eng, sc[t][0], sc[t][1], True)
         fence(eng)
         dt = time.perf_counter() - t0
         eng.profile_enable(False)
@@ -345,12 +379,14 @@ def main():
             dt = float(tt.item())
         return eng, dt
 
-    eng, dt = timed_run(args.precision)
+    eng, dt = timed_run(args.precision, headline=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"codebook": eng.get_weights(), "bmu": eng.epoch_fetch()[2].astype(np.float64)})
     head_share = getattr(eng, "executed_share", 1.0)
     # N > 1: the all-reduce waits for the slowest rank, and under block skipping a rank's BMU search depends on ITS rows:
     # every rank's own search time per epoch (hipEvents around its BMU kernels: no waiting in it) and executed share
     rank_spread = None
-    if dist is not None:
+    if dist is not None and args.full:
         ar_ms, ar_n = getattr(eng, "allreduce_ms", (0.0, 0))
         mine = torch.tensor([eng.profile_get("bmu")[0] / max(1, args.steps), head_share, ar_ms / max(1, args.steps)], dtype=torch.float64, device="cuda")
         allv = [torch.zeros_like(mine) for _ in range(world)]
@@ -370,43 +406,59 @@ def main():
                                                 "what": "per epoch, per rank: from the all-reduce's issue on its stream to its end (waiting for the slowest rank included)"},
                        "epoch_ms_max_minus_mean_over_ranks": max(ms_r) - sum(ms_r) / world,
                        "shard": args.shard if args.scaling == "strong" else "own rows per rank (weak scaling)"}
-    w_after_timed = eng.get_weights() if args.precision == "exact" else None
+    # --full's other blocks replay whole schedules, several of them through the float32 kernels (~50x the headline's epoch):
+    # they run on the schedule of the default invocation (at most FULL_WARMUP + FULL_STEPS epochs), whatever --warmup / --steps
+    # say, so that --full takes about the same time at any K.  With the default flags it is the headline's own schedule.
+    side_w, side_k = min(args.warmup, FULL_WARMUP), min(args.steps, FULL_STEPS)
+    side_total = side_w + side_k
+    side_is_headline = (side_w, side_k) == (args.warmup, args.steps)
+    side_sched = sched if side_is_headline else \
+        [(exponential_decay(min(MAP_X, MAP_Y) / 2, 1, t, side_total), exponential_decay(0.5, 0.01, t, side_total)) for t in range(side_total)]
+    w_after_timed = None                               # the exact mode's codebook after the side schedule
+    if args.precision == "exact" and args.full:
+        if side_is_headline:
+            w_after_timed = eng.get_weights()
+        else:
+            e_h, _ = timed_run(args.precision, side_sched, side_w, side_k)
+            w_after_timed = e_h.get_weights()
+            e_h.close()
     bmu_ms, bmu_n = eng.profile_get("bmu")
     scr_ms, scr_n = eng.profile_get("screen")
-    # per-kernel-family breakdown: the same epochs once more (the same schedule entries, at most 20), untimed, every
-    # family under events
-    nb = max(1, min(args.steps, 20))
-    eng.profile_reset()
-    eng.profile_enable(True)
-    for t in range(args.warmup, args.warmup + nb):
-        D.epoch(eng, sched[t][0], sched[t][1], True)
-    fence(eng)
-    eng.profile_enable(False)
-    parts = {k: eng.profile_get(k)[0] / nb for k in ("prep", "bmu", "segsum", "kron", "merge")}
-    if args.precision == "exact":
-        parts["bmu_of_which_screen"] = eng.profile_get("screen")[0] / nb
-    w_end = eng.get_weights()
-    assert np.isfinite(w_end).all()
-    exact_stats = eng.exact_stats() if args.precision == "exact" else None
-    # N > 1: every rank merged the same all-reduced sums, so the codebooks must be the same bits on every rank
-    ranks_agree = None
-    import zlib
-    w_crc = zlib.crc32(np.ascontiguousarray(w_end).tobytes())
-    if dist is not None:
-        lo_t = torch.tensor([float(w_crc)], dtype=torch.float64, device="cuda")
-        hi_t = lo_t.clone()
-        dist.all_reduce(lo_t, op=dist.ReduceOp.MIN)
-        dist.all_reduce(hi_t, op=dist.ReduceOp.MAX)
-        ranks_agree = bool(lo_t.item() == hi_t.item())
+    parts, nb, exact_stats, ranks_agree, w_crc = None, 0, None, None, None
+    if args.full:
+        # per-kernel-family breakdown: the same epochs once more (the same schedule entries, at most 20), untimed, every
+        # family under events
+        nb = max(1, min(args.steps, 20))
+        eng.profile_reset()
+        eng.profile_enable(True)
+        for t in range(args.warmup, args.warmup + nb):
+            D.epoch(eng, sched[t][0], sched[t][1], True)
+        fence(eng)
+        eng.profile_enable(False)
+        parts = {k: eng.profile_get(k)[0] / nb for k in ("prep", "bmu", "segsum", "kron", "merge")}
+        if args.precision == "exact":
+            parts["bmu_of_which_screen"] = eng.profile_get("screen")[0] / nb
+        w_end = eng.get_weights()
+        assert np.isfinite(w_end).all()
+        exact_stats = eng.exact_stats() if args.precision == "exact" else None
+        # N > 1: every rank merged the same all-reduced sums, so the codebooks must be the same bits on every rank
+        import zlib
+        w_crc = zlib.crc32(np.ascontiguousarray(w_end).tobytes())
+        if dist is not None:
+            lo_t = torch.tensor([float(w_crc)], dtype=torch.float64, device="cuda")
+            hi_t = lo_t.clone()
+            dist.all_reduce(lo_t, op=dist.ReduceOp.MIN)
+            dist.all_reduce(hi_t, op=dist.ReduceOp.MAX)
+            ranks_agree = bool(lo_t.item() == hi_t.item())
 
     # the throughput mode beside the parity-grade headline: the same K epochs through the plain bf16 kernel
     thr = None
-    if args.precision == "exact" and exact_has_screen(FEATURES, MAP_X * MAP_Y, wl["distance"]) and not args.no_throughput_mode:
+    if args.full and args.precision == "exact" and exact_has_screen(FEATURES, MAP_X * MAP_Y, wl["distance"]) and not args.no_throughput_mode:
         eng.close()
-        e_t, dt_t = timed_run("bf16")
+        e_t, dt_t = timed_run("bf16", side_sched, side_w, side_k)
         t_ms, t_n = e_t.profile_get("bmu")
-        thr = {"precision": "bf16", "value": total_rows / (dt_t / args.steps), "unit": "samples/sec/epoch",
-               "ms_per_step": 1e3 * dt_t / args.steps, "kernel": kernel_name_for("bf16", FEATURES, MAP_X * MAP_Y),
+        thr = {"precision": "bf16", "value": total_rows / (dt_t / side_k), "unit": "samples/sec/epoch",
+               "ms_per_step": 1e3 * dt_t / side_k, "kernel": kernel_name_for("bf16", FEATURES, MAP_X * MAP_Y),
                "avg_launch_ms": t_ms / max(1, t_n),
                "roofline_frac": 2.0 * (MAP_X * MAP_Y) * FEATURES * my_rows / (t_ms / max(1, t_n) * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
                "note": "BMUs NOT those of float32 (see precision_modes_at_batch65536): the parity contract holds in the headline mode"}
@@ -418,18 +470,18 @@ def main():
     # when nothing can be skipped (the first epoch on fresh rows; data without structure)
     full_scan = None
     # (the condition is the same on every rank -- the run below holds collectives: never a rank's own measured share)
-    if args.precision == "exact" and exact_has_screen(FEATURES, MAP_X * MAP_Y, wl["distance"]) and not args.no_throughput_mode \
+    if args.full and args.precision == "exact" and exact_has_screen(FEATURES, MAP_X * MAP_Y, wl["distance"]) and not args.no_throughput_mode \
             and (FEATURES <= 128 or wl["distance"] == "euclidean") and MAP_X * MAP_Y >= 4096 and os.environ.get("SOM_EXACT_SKIP", "1") != "0":
         old_env = os.environ.get("SOM_EXACT_SKIP")
         os.environ["SOM_EXACT_SKIP"] = "0"
-        e_f, dt_f = timed_run("exact")
+        e_f, dt_f = timed_run("exact", side_sched, side_w, side_k)
         if old_env is None:
             del os.environ["SOM_EXACT_SKIP"]
         else:
             os.environ["SOM_EXACT_SKIP"] = old_env
         f_ms, f_n = e_f.profile_get("screen")
-        full_scan = {"SOM_EXACT_SKIP": 0, "value": total_rows / (dt_f / args.steps), "unit": "samples/sec/epoch",
-                     "ms_per_step": 1e3 * dt_f / args.steps, "avg_launch_ms": f_ms / max(1, f_n), "launches": f_n,
+        full_scan = {"SOM_EXACT_SKIP": 0, "value": total_rows / (dt_f / side_k), "unit": "samples/sec/epoch",
+                     "ms_per_step": 1e3 * dt_f / side_k, "avg_launch_ms": f_ms / max(1, f_n), "launches": f_n,
                      "codebook_equal_to_headline_run": bool(np.array_equal(e_f.get_weights(), w_after_timed))}
         e_f.close()
     # What `value` is and is not.  `value` = the mean of the K timed epochs BEHIND the W warm-up epochs of a (W + K)-epoch
@@ -439,17 +491,17 @@ def main():
     # train(data, W + K) costs as a whole (`whole_schedule`), the same run on rows WITHOUT structure (`unstructured_rows`), and
     # the headline codebook against precision='f32' run over the same schedule (`codebook_equal_to_f32_run`).
     schedule_block, unstructured, equal_f32 = None, None, None
-    if args.precision == "exact" and not args.no_schedule and dist is None:
+    if args.full and args.precision == "exact" and not args.no_schedule and dist is None:
         def one_by_one(rows, prec="exact"):
             e = HipEngine(MAP_X, MAP_Y, FEATURES, precision=prec, device=dev, distance=wl["distance"], neighborhood=wl["neighborhood"])
             e.set_weights(w)
             e.set_data(rows)
             e.sync()
             ms, sh = [], []
-            for t in range(total):
+            for t in range(side_total):
                 s0 = e.exact_skip_stats() if prec == "exact" else (0, 0)
                 t0 = time.perf_counter()
-                D.epoch(e, sched[t][0], sched[t][1], True)
+                D.epoch(e, side_sched[t][0], side_sched[t][1], True)
                 e.sync()
                 ms.append(1e3 * (time.perf_counter() - t0))
                 s1 = e.exact_skip_stats() if prec == "exact" else (0, 0)
@@ -462,16 +514,16 @@ def main():
         schedule_block = {
             "per_epoch_ms": [round(v, 4) for v in ms_s], "executed_share_per_epoch": [round(v, 5) for v in sh_s],
             "first_epoch_ms": ms_s[0],
-            "whole_schedule": {"epochs": total, "ms_per_epoch": sum(ms_s) / total, "value": my_rows / (sum(ms_s) / total * 1e-3),
+            "whole_schedule": {"epochs": side_total, "ms_per_epoch": sum(ms_s) / side_total, "value": my_rows / (sum(ms_s) / side_total * 1e-3),
                                "unit": "samples/sec/epoch",
-                               "note": "a fresh engine, epochs 0..%d one by one with a host sync after each (what train(data, %d) costs)" % (total - 1, total)},
+                               "note": "a fresh engine, epochs 0..%d one by one with a host sync after each (what train(data, %d) costs)" % (side_total - 1, side_total)},
             "epochs_under_a_plan": res[0], "of_which_sorted_the_rows": res[1],
             "codebook_equal_to_headline_run": bool(np.array_equal(w_sched, w_after_timed)),
         }
         if not args.no_f32_check and (FEATURES <= 128 or wl["distance"] == "euclidean"):
             e_f, ms_f, _ = one_by_one(rows_host, "f32")
             equal_f32 = bool(np.array_equal(e_f.get_weights(), w_sched))
-            schedule_block["f32_run_ms_per_epoch"] = sum(ms_f) / total
+            schedule_block["f32_run_ms_per_epoch"] = sum(ms_f) / side_total
             e_f.close()
             assert equal_f32, "the exact mode's trained codebook is not the float32 mode's"
         # rows without structure: N(0, I), no centres -- nothing for a centroid bound to separate
@@ -483,18 +535,18 @@ def main():
         res_u = e_u.exact_resident_stats()
         e_u.close()
         del rows_u
-        k_ms = ms_u[args.warmup:]
+        k_ms = ms_u[side_w:]
         unstructured = {"rows": "N(0, I) rows, no centres (same map, same schedule)", "value": my_rows / (sum(k_ms) / len(k_ms) * 1e-3),
                         "unit": "samples/sec/epoch", "ms_per_step": sum(k_ms) / len(k_ms),
-                        "executed_share": sum(sh_u[args.warmup:]) / len(k_ms), "epochs_under_a_plan": res_u[0],
-                        "plan_paused_epochs": total - 1 - res_u[0], "whole_schedule_ms_per_epoch": sum(ms_u) / total}
+                        "executed_share": sum(sh_u[side_w:]) / len(k_ms), "epochs_under_a_plan": res_u[0],
+                        "plan_paused_epochs": side_total - 1 - res_u[0], "whole_schedule_ms_per_epoch": sum(ms_u) / side_total}
 
     # What the headline is worth elsewhere.  `survey_schedule`: SURVEY 8(d)'s own definition of the metric -- a 10-epoch schedule
     # from the seeded codebook, the mean of epochs 1..9.  `data_variants`: the same map and (W + K)-epoch schedule on rows
     # between "64 separated blobs" and "no structure" (xpysom_dask_amd/synthetic.py, variant()), each with block skipping on
     # and off and against precision='f32'.  `queries`: winner() / quantization_error() on device-resident rows of the trained map.
     survey, variants, queries = None, None, None
-    if args.precision == "exact" and not args.no_schedule and not args.no_variants and dist is None and FEATURES <= 128 \
+    if args.full and args.precision == "exact" and not args.no_schedule and not args.no_variants and dist is None and FEATURES <= 128 \
             and exact_has_screen(FEATURES, MAP_X * MAP_Y, wl["distance"]):
         from xpysom_dask_amd import synthetic
 
@@ -537,18 +589,18 @@ def main():
         variants = {}
         for kind in ("overlap", "manifold", "heavy"):
             rows_k = synthetic.variant(kind, my_rows, FEATURES, seed=1234 + rank)
-            e_k, ms_k, sh_k, w_k = run_schedule(rows_k, total)
+            e_k, ms_k, sh_k, w_k = run_schedule(rows_k, side_total)
             res_k, sc_k = e_k.exact_resident_stats(), e_k.exact_scout_stats()
             e_k.close()
-            e_0, ms_0, _, w_0 = run_schedule(rows_k, total, skip="0")
+            e_0, ms_0, _, w_0 = run_schedule(rows_k, side_total, skip="0")
             e_0.close()
-            e_f, ms_f, _, w_f = run_schedule(rows_k, total, prec="f32")
+            e_f, ms_f, _, w_f = run_schedule(rows_k, side_total, prec="f32")
             e_f.close()
-            k_ms, k_0 = ms_k[args.warmup:], ms_0[args.warmup:]
+            k_ms, k_0 = ms_k[side_w:], ms_0[side_w:]
             variants[kind] = {
                 "ms_per_step": sum(k_ms) / len(k_ms), "value": my_rows / (sum(k_ms) / len(k_ms) * 1e-3), "unit": "samples/sec/epoch",
-                "executed_share": sum(sh_k[args.warmup:]) / len(k_ms), "whole_schedule_ms_per_epoch": sum(ms_k) / total,
-                "without_block_skipping_ms_per_step": sum(k_0) / len(k_0), "without_block_skipping_whole_schedule_ms_per_epoch": sum(ms_0) / total,
+                "executed_share": sum(sh_k[side_w:]) / len(k_ms), "whole_schedule_ms_per_epoch": sum(ms_k) / side_total,
+                "without_block_skipping_ms_per_step": sum(k_0) / len(k_0), "without_block_skipping_whole_schedule_ms_per_epoch": sum(ms_0) / side_total,
                 "slowest_epoch_vs_without_skipping": max(a / b for a, b in zip(ms_k, ms_0)),
                 "epochs_under_a_plan": res_k[0], "launches_scouted": sc_k[0],
                 "codebook_equal_to_f32_run": bool(np.array_equal(w_k, w_f)), "codebook_equal_without_skipping": bool(np.array_equal(w_k, w_0)),
@@ -557,7 +609,7 @@ def main():
             del rows_k
         variants["what"] = ("the headline's map and %d-epoch schedule on other rows (synthetic.variant): overlap = 1024 centres whose noise has the centres' own "
                             "spread; manifold = a 2-D sheet embedded in %d-D; heavy = 64 blobs with power-law sizes; ms_per_step = mean of epochs %d..%d as in "
-                            "`value`" % (total, FEATURES, args.warmup, total - 1))
+                            "`value`" % (side_total, FEATURES, side_w, side_total - 1))
         # queries on the trained map: rows already in HBM (a torch tensor), other rows of the same mixture
         qrows = torch.from_numpy(workload_rows(args.workload, my_rows, 99 + rank)).cuda()
         torch.cuda.synchronize()
@@ -613,7 +665,7 @@ def main():
 
     # the north-star's launch: the same kernel over a batch of 65 536 resident rows, same process
     batch = None
-    do_batch = rank == 0 and world == 1 and not args.no_batch65536 and my_rows >= NORTH_STAR_BATCH
+    do_batch = args.full and rank == 0 and world == 1 and not args.no_batch65536 and my_rows >= NORTH_STAR_BATCH
     if do_batch:
         eng.set_weights(w)
         eng.set_data(rows_host[:NORTH_STAR_BATCH])
@@ -772,7 +824,7 @@ def main():
     # seeded codebook the answer is a number (later epochs amplify float32 summation-order noise chaotically):
     # 4096 fixed entries of the codebook against the probe a --gpus 1 --scaling strong run stored under profiles/.
     probe = None
-    if rank == 0 and args.scaling == "strong" and "w" in first_epoch:
+    if args.full and rank == 0 and args.scaling == "strong" and "w" in first_epoch:
         idx = np.random.RandomState(99).randint(0, first_epoch["w"].size, 4096)
         mine = first_epoch["w"].reshape(-1)[idx].astype(np.float64)
         key = {"workload": args.workload, "total_rows": total_rows, "precision": args.precision}
@@ -811,7 +863,6 @@ def main():
         out = {
             "metric": "samples/sec/epoch", "value": total_rows / (dt / args.steps), "unit": "samples/sec/epoch",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
-            "codebooks_identical_on_all_ranks": ranks_agree,
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": {"f32": "f32", "f16": "f16", "exact": "f16"}.get(args.precision, "bf16"), "data": "synthetic",
             "config": {"workload": "batch-SOM epoch, %dx%d map, %d features, %d Gaussian-blob rows %s resident "
@@ -826,12 +877,11 @@ def main():
                                   "float32 parity mode itself" if args.precision in ("f32", "exact") else
                                   "throughput mode: BMUs within the operand rounding of float32's, not equal to them"),
                        "update": "bucketed (segment sum by BMU + separable neighbourhood transform; exact algebra of "
-                                 "the reference's g^T.x GEMM, xpysom.py:434-438; both forms timed: update_forms)",
+                                 "the reference's g^T.x GEMM, xpysom.py:434-438; both forms timed with --full: update_forms)",
                        "parallelism": "dp%d (sample shards, 1 all-reduce/epoch)" % world,
                        "epochs_per_sec": args.steps / dt, "build": build_hash,
                        "value_is": "mean of epochs %d..%d of a %d-epoch schedule (the %d warm-up epochs hold the schedule's full scans)"
-                                   % (args.warmup, total - 1, total, args.warmup),
-                       "codebook_crc32_after_run": w_crc},
+                                   % (args.warmup, total - 1, total, args.warmup)},
             "roofline": {"bound": "mfma", "kernel": kernel_name + (" (IEEE-half distance GEMM of the exact mode's screen, fused "
                                                                    "argmin + per-group minima)" if is_exact else " (fused distance GEMM + argmin)"),
                          "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
@@ -845,9 +895,15 @@ def main():
                          "full_scan_flops_per_launch": KD2 * rows_launch,
                          "full_scan_equivalent_tflops": KD2 * rows_launch / (k_avg * 1e-3) / 1e12,
                          "whole_bmu_search_ms_per_step": bmu_ms / max(1, bmu_n)},
-            "ms_per_step_by_kernel": parts,
-            "ms_per_step_by_kernel_pass": "separate untimed pass of %d epochs after the timed region (events around every kernel family)" % nb,
         }
+        if args.full:
+            out["codebooks_identical_on_all_ranks"] = ranks_agree
+            out["config"]["codebook_crc32_after_run"] = w_crc
+            out["ms_per_step_by_kernel"] = parts
+            out["ms_per_step_by_kernel_pass"] = "separate untimed pass of %d epochs after the timed region (events around every kernel family)" % nb
+            out["other_blocks_schedule"] = {"warmup": side_w, "steps": side_k, "epochs": side_total, "is_the_headline_schedule": side_is_headline,
+                                            "what": "the schedule the throughput mode, the run without block skipping, the whole-schedule, "
+                                                    "unstructured-rows and data-variant blocks ran: at most %d + %d epochs" % (FULL_WARMUP, FULL_STEPS)}
         if exact_stats is not None:
             out["parity_mode"] = {"precision": "exact", "is_headline": True, "value": out["value"], "unit": out["unit"],
                                   "roofline_frac": achieved / peak, "rows_screened": exact_stats[0],
@@ -885,7 +941,7 @@ def main():
             out["precision_modes_at_batch65536"] = modes   # 'f32' = the parity mode itself, 'exact' = its BMUs at MFMA-half speed, 'f16' = IEEE half operands
         if update_forms is not None:
             out["update_forms"] = update_forms
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -159,7 +159,7 @@ def test_bench_launches_its_own_ranks(scaling):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SOM_DIST_BACKEND"] = "gloo"                           # two ranks on this box's one GPU
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--scaling", scaling]
+           "--full", "--no-cpu-baseline", "--scaling", scaling]
     cmd += ["--rows", "65536"] if scaling == "weak" else ["--total-rows", "131073"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-5000:]
@@ -181,7 +181,7 @@ def test_bench_reports_the_rank_spread_when_shards_differ_in_structure():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SOM_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "4", "--steps", "6", "--warmup", "3", "--rows", "65536",
-           "--no-cpu-baseline", "--no-throughput-mode", "--no-batch65536", "--no-modes", "--unstructured-ranks", "1"]
+           "--full", "--no-cpu-baseline", "--no-throughput-mode", "--no-batch65536", "--no-modes", "--unstructured-ranks", "1"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-5000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

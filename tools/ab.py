@@ -21,7 +21,7 @@ for r in range(reps):
         env = dict(os.environ)
         if lib != "default":
             env["SOM_LIB_PATH"] = os.path.abspath(lib)
-        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--no-cpu-baseline"] + bench_args,
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--no-cpu-baseline"] + bench_args,
                              env=env, capture_output=True, text=True, cwd=REPO)
         line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
         if not line:

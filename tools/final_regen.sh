@@ -12,14 +12,14 @@ cp gpurun_out/${TAG}_pmc_traffic_rows1048576.json gpurun_out/${TAG}_pmc_traffic_
 cp gpurun_out/${TAG}_bf16_pmc_traffic_rows1048576.json gpurun_out/${TAG}_c5_pmc_traffic_rows250000.json profiles/
 cp gpurun_out/${TAG}_kernel_stats_rows1048576.csv gpurun_out/${TAG}_kernel_stats_rows65536.csv gpurun_out/${TAG}_c5_kernel_stats_rows250000.csv profiles/
 cp gpurun_out/${TAG}_dispatches_rows1048576.csv gpurun_out/${TAG}_dispatches_rows65536.csv profiles/
-python3 bench.py > gpurun_out/${TAG}_bench_c3.json
-python3 bench.py --precision bf16 --no-modes > gpurun_out/${TAG}_bench_c3_bf16.json
-python3 bench.py --workload c5 > gpurun_out/${TAG}_bench_c5.json
-python3 bench.py --workload c2 > gpurun_out/${TAG}_bench_c2.json
-python3 bench.py --scaling strong --no-modes > gpurun_out/${TAG}_bench_strong_n1.json
+python3 bench.py --full > profiles/${TAG}_bench_c3.json
+python3 bench.py --full --precision bf16 --no-modes > profiles/${TAG}_bench_c3_bf16.json
+python3 bench.py --full --workload c5 > profiles/${TAG}_bench_c5.json
+python3 bench.py --full --workload c2 > profiles/${TAG}_bench_c2.json
+python3 bench.py --full --scaling strong --no-modes > profiles/${TAG}_bench_strong_n1.json
 for w in c3 c3_bf16 c5 c2 strong_n1; do python3 - <<PY
 import json
-d = json.loads(open("gpurun_out/${TAG}_bench_$w.json").read().strip().splitlines()[-1])
+d = json.loads(open("profiles/${TAG}_bench_$w.json").read().strip().splitlines()[-1])
 r = d["roofline"]
 print("$w", round(d["ms_per_step"], 3), "ms", round(d["value"] / 1e6, 2), "M/s frac", round(r["frac"], 4), "traffic", r.get("traffic"), (r.get("traffic_source") or {}).get("same_build"), (r.get("batch65536") or {}).get("epoch_ms"))
 PY
