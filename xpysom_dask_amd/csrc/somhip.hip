@@ -1183,7 +1183,7 @@ int run_transform_stage1(som_handle* h, double sigma, double eta, int neigh_f64)
     if (h->swapped) {
         // mexican_hat + compact_support, rectangular (X == Y): the row stage first, V_t = Fx_t (X x X) * SC (X x Y*D1p),
         // laid out T[i][t][b][:] (rows of term t: T + t*slab, nt*slab apart); then the reference's second mask,
-        // m2(i, b), on the three masked terms; the column stage follows in run_transform_stage2
+        // m2(i, b), on terms 0 and 1 and its complement on term 3 (update.hpp, neigh_factor); the column stage follows in run_transform_stage2
         const int nxb = (int)cdiv(h->X, LM_BM);
         for (int t1 = 0; t1 < h->nt; ++t1)
             launch_leftmul(h, h->P1 + (long)t1 * h->X * h->X, h->X, h->X, h->SC, 0, h->T + (long)t1 * slab, 0, slab, slab, nxb,
@@ -1191,7 +1191,7 @@ int run_transform_stage1(som_handle* h, double sigma, double eta, int neigh_f64)
         const NeighParams p = make_neigh_params(h, sigma, eta, neigh_f64);
         const long total = (long)h->X * h->nt * slab;
         mask_rows_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
-            p, h->capturing ? (const NeighParams*)h->np_dev : nullptr, h->T, h->nt - 1, h->D1p);
+            p, h->capturing ? (const NeighParams*)h->np_dev : nullptr, h->T, h->D1p);
         HIPCHK(h, hipGetLastError());
         return 0;
     }

@@ -465,20 +465,24 @@ __device__ double neigh_factor(int which, int t, double n, double c, const Neigh
         // compact_support as the reference computes it (neighborhoods.py:69-71, :91-93): px is multiplied by a mask M,
         // py is not, so with A = ex (1 - 2 px / d), Q = (2 py / d) ey:
         //     h = M (A ey - ex Q) + (1 - M)(ey - Q)
-        // Hexagonal (generic): M = mx(i; ci) my(j; cj), four separable terms
-        //     [mx A][my ey]  +  [-mx ex][my Q]  +  [-mx][my (ey - Q)]  +  [1][ey - Q].
+        // Hexagonal (generic): M = mx(i; ci) my(j; cj), and 1 - M = (1 - mx) + mx (1 - my): four separable terms
+        //     [mx A][my ey]  +  [-mx ex][my Q]  +  [1 - mx][ey - Q]  +  [mx][(1 - my)(ey - Q)].
+        // The last two never overlap (at most one is nonzero for a pair of units), so nothing cancels: written as
+        // [-mx][my (ey - Q)] + [1][ey - Q] they would, inside the box, add and subtract ey - Q -- up to exp(px / d)
+        // times the h they sum to -- and leave its float32 rounding behind.
         // Rectangular: M = m1(i; ci) m2(i; cj) -- the second mask compares the ROW index with the BMU's COLUMN --:
-        // the same four terms with my = 1; m2 is applied between the row stage and the column stage (`swapped`).
+        // the same four terms with my = m2, which is applied between the row stage and the column stage (`swapped`,
+        // mask_rows_kernel: terms 0 and 1 times m2, term 3 times 1 - m2).
         const double m = neigh_box(n, c, p);
         if (which == 0) {
             if (t == 0) return neigh_round(m * e * (1.0 - q), p);
-            return t == 1 ? -m * e : t == 2 ? -m : 1.0;
+            return t == 1 ? -m * e : t == 2 ? 1.0 - m : m;
         }
         const double my = p.hex ? m : 1.0;
         const double qe = neigh_round(q * e, p);
         if (t == 0) return my * e;
         if (t == 1) return my * qe;
-        return (t == 2 ? my : 1.0) * neigh_round(e - qe, p);
+        return (t == 3 && p.hex ? 1.0 - m : 1.0) * neigh_round(e - qe, p);
     }
     case 2:     // bubble
         return neigh_box(n, c, p);
@@ -553,10 +557,11 @@ __global__ __launch_bounds__(256) void neigh_tables_kernel(NeighParams p_val, co
     }
 }
 
-// `swapped` pipeline, between its two stages: V[i][t][b][:] *= m2(i, b) for the masked terms t < nt_masked, where
-// m2 is the reference's second mask on px -- row index i against BMU column b (neighborhoods.py:70).
+// `swapped` pipeline, between its two stages: V[i][t][b][:] *= m2(i, b) for terms 0 and 1 and *= 1 - m2(i, b) for term
+// 3 (neigh_factor), where m2 is the reference's second mask on px -- row index i against BMU column b
+// (neighborhoods.py:70).
 __global__ __launch_bounds__(256) void mask_rows_kernel(NeighParams p_val, const NeighParams* __restrict__ p_dev,
-                                                        float* __restrict__ V, int nt_masked, int D1p) {
+                                                        float* __restrict__ V, int D1p) {
     const NeighParams p = p_dev ? *p_dev : p_val;
     const long id = (long)blockIdx.x * 256 + threadIdx.x;
     const long per_i = (long)p.nt * p.Y * D1p;
@@ -566,7 +571,8 @@ __global__ __launch_bounds__(256) void mask_rows_kernel(NeighParams p_val, const
     const long r = id - (long)i * per_i;
     const int t = (int)(r / ((long)p.Y * D1p));
     const int b = (int)((r / D1p) % p.Y);
-    if (t < nt_masked && neigh_box((double)i, (double)b, p) == 0.0) V[id] = 0.0f;
+    if (t == 2) return;
+    if ((neigh_box((double)i, (double)b, p) != 0.0) == (t == 3)) V[id] = 0.0f;
 }
 
 // ---- OUT[b] = H (Ro x Ri) * M[b] (Ri x C), exact float32 on v_mfma_f32_32x32x2_f32 ---------------
