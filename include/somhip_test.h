@@ -20,6 +20,10 @@ int som_debug_corrupt_operands(som_handle* h, int32_t which);
 int som_debug_mfma16(som_handle* h, const uint16_t* a_host, const uint16_t* b_host, const float* c_host, float* d_host,
                      int32_t is_f16);
 
+/* bytes of device memory the engines of this process hold right now (every handle's buffers, scratch included): a closed
+ * handle gives back all it took (tests/test_gpu_exact.py).  Returns non-zero for a NULL argument. */
+int som_debug_device_bytes(int64_t* out);
+
 /* diagnostic builds only (-DSOM_STAMPS, tools/stamps.py builds one on demand): out_host == NULL attaches a buffer of n_pairs
  * (shader-clock ticks, 100 MHz ticks) pairs, one per workgroup of the next BMU launches (n_pairs == 0 detaches);
  * out_host != NULL reads n_pairs pairs back.  The product build refuses both. */

@@ -807,3 +807,56 @@ def test_exact_new_rows_of_the_same_size_drop_the_resident_order():
             f.epoch_merge(); x.epoch_merge()
     assert x.exact_resident_stats()[1] >= 3               # at least one sort per row set
     f.close(); x.close()
+
+
+# ----------------------------------------------------------------------------- device memory ownership
+def _device_bytes():
+    import ctypes as C
+    from xpysom_dask_amd import _lib
+    v = C.c_int64()
+    assert _lib.load().som_debug_device_bytes(C.byref(v)) == 0
+    return v.value
+
+
+def test_closed_engines_give_back_every_device_byte(monkeypatch):
+    """Every device buffer belongs to its handle and is freed with it: after close() the process holds exactly the device
+    bytes it held before -- the exact mode's pass scratch and plan buffers (the listed screen's work queue among them), the
+    query, streaming and canary scratch, the float32 / bf16 tile images and the float32 sample tiles included."""
+    import gc
+    monkeypatch.setenv("SOM_EXACT_SKIP", "2")
+    gc.collect()                                          # (engines of earlier tests still waiting for their __del__)
+    start = _device_bytes()
+    X, Y, D, n = 64, 64, 32, 20000
+    data = O.gaussian_blobs(n, D, seed=4)
+    x = engine(X, Y, D, precision="exact")
+    x.set_weights(O.default_codebook(X, Y, D, 6).astype(F32))
+    x.set_data(data)
+    T = 6
+    for t in range(T):
+        x.epoch_accumulate(O.exponential_decay(X / 2.0, 1.0, t, T), O.exponential_decay(0.5, 0.01, t, T), True)
+        x.epoch_merge()
+    assert x.exact_resident_stats()[0] > 0               # (epochs ran under a plan)
+    x.bmu(data[:5000])
+    bufs = [x.pinned_empty((1000, D)), x.pinned_empty((1000, D))]
+
+    def chunks():
+        for i, lo in enumerate(range(0, 6000, 1000)):
+            bufs[i & 1][:] = data[lo:lo + 1000]
+            yield bufs[i & 1]
+    x.stream_epoch_accumulate(chunks(), 1.0, 0.1, True)
+    x.set_verify(64)
+    x.epoch_accumulate(1.0, 0.1, True)
+    assert x.verify_stats()[0] > 0
+    assert _device_bytes() > start
+    wide = O.gaussian_blobs(3000, 200, seed=2)
+    for p in ("bf16", "f32"):                             # input_len > 128: the tiled images, the float32 sample tiles
+        e = engine(16, 16, 200, precision=p)
+        e.set_weights(O.default_codebook(16, 16, 200, 2).astype(F32))
+        e.set_data(wide)
+        e.epoch_accumulate(2.0, 0.3, True)
+        e.bmu(wide[:100])
+        if p == "f32":
+            e.bmu_top2(wide[:100]); e.distance_matrix(wide[:100]); e.bmu_f64(wide[:100].astype(np.float64))
+        e.close()
+    x.close()
+    assert _device_bytes() == start

@@ -1,7 +1,7 @@
 // precision 'exact': the HOST side of the screen + re-score pipeline (bmu_exact.hpp), of block skipping (exact_skip.hpp,
 // exact_skip_wide.hpp) and of the scout -- buffers, launch geometry, the per-pass kernel sequence, the policy's bookkeeping.
 // Included by somhip.hip INSIDE its anonymous namespace, behind the handle (som_handle, ExactScratch) and the helpers it uses
-// (dev_alloc, kernel_per_cu, choose_parts, refresh_codebook_operands, launch_bmu_f32_any, Timed, HIPCHK ...): one translation
+// (DevBuf, kernel_per_cu, choose_parts, refresh_codebook_operands, launch_bmu_f32_any, Timed, HIPCHK ...): one translation
 // unit, two files.  The decisions themselves -- commit a scouted plan, level 2, did a sort pay, is a plan idle -- are pure
 // functions of measured numbers in exact_policy.hpp (unit-tested without a GPU through som_policy_eval, include/somhip_test.h).
 // (no #pragma once / include guard on purpose: not a header of its own)
@@ -73,9 +73,7 @@ int exact_reserve_stride(som_handle* h, long stride) {
     auto& ex = h->ex;
     // TEST HOOK (tests/test_gpu_exact.py; SOM_TEST_HOOKS=1): behave as a device that refuses the scratch of passes above n rows
     if (ex.hook_refuse_above > 0 && stride > ex.hook_refuse_above) return fail(h, "exact: pass scratch refused (test hook)");
-    void* old[] = {ex.gmin, ex.gflags, ex.rowcnt, ex.rowarg, ex.seed, ex.fb_list, ex.plist, ex.tile_tab};
-    for (void* p : old) if (p) (void)hipFree(p);
-    ex.gmin = nullptr; ex.gflags = nullptr; ex.rowcnt = nullptr; ex.rowarg = nullptr; ex.seed = nullptr; ex.fb_list = nullptr; ex.plist = nullptr; ex.tile_tab = nullptr;
+    ex.gmin.reset(); ex.gflags.reset(); ex.rowcnt.reset(); ex.rowarg.reset(); ex.seed.reset(); ex.fb_list.reset(); ex.plist.reset(); ex.tile_tab.reset();
     ex.stride = 0;
     ex.res_valid = false;                               // (the resident order was built pass by pass: new passes, new order)
     const long n_groups = cdiv(h->K, EX_GROUP);
@@ -84,17 +82,17 @@ int exact_reserve_stride(som_handle* h, long stride) {
     ex.pairs = std::max<long>(EX_PAIRS, std::min<long>(n_groups / 4, 512));
     if (ex.hook_pairs > 0) ex.pairs = ex.hook_pairs;
     if (stride * ex.pairs > 0x7fffffffL) return fail(h, "exact: pass too large");
-    if (int rc = dev_alloc(h, &ex.gmin, (size_t)n_groups * stride)) return rc;
-    if (int rc = dev_alloc(h, &ex.gflags, (size_t)n_groups * (stride / 64))) return rc;
-    if (int rc = dev_alloc(h, &ex.rowcnt, (size_t)stride)) return rc;
-    if (int rc = dev_alloc(h, &ex.rowarg, (size_t)stride)) return rc;
-    if (int rc = dev_alloc(h, &ex.seed, (size_t)stride)) return rc;
-    if (int rc = dev_alloc(h, &ex.plist, (size_t)n_groups * stride)) return rc;   // every group: room for the whole pass
-    if (int rc = dev_alloc(h, &ex.fb_list, (size_t)stride)) return rc;
+    if (int rc = ex.gmin.alloc(h, (size_t)n_groups * stride)) return rc;
+    if (int rc = ex.gflags.alloc(h, (size_t)n_groups * (stride / 64))) return rc;
+    if (int rc = ex.rowcnt.alloc(h, (size_t)stride)) return rc;
+    if (int rc = ex.rowarg.alloc(h, (size_t)stride)) return rc;
+    if (int rc = ex.seed.alloc(h, (size_t)stride)) return rc;
+    if (int rc = ex.plist.alloc(h, (size_t)n_groups * stride)) return rc;   // every group: room for the whole pass
+    if (int rc = ex.fb_list.alloc(h, (size_t)stride)) return rc;
     ex.max_tiles = cdiv(stride * ex.pairs, EX_TR) + n_groups;
-    if (int rc = dev_alloc(h, &ex.tile_tab, (size_t)ex.max_tiles)) return rc;
+    if (int rc = ex.tile_tab.alloc(h, (size_t)ex.max_tiles)) return rc;
     if (!ex.ctr) {
-        if (int rc = dev_alloc(h, &ex.ctr, (size_t)3 * n_groups + 16)) return rc;
+        if (int rc = ex.ctr.alloc(h, (size_t)3 * n_groups + 16)) return rc;
         HIPCHK(h, hipHostMalloc((void**)&ex.fb_count_host, 8 * sizeof(int), hipHostMallocDefault));   // fb_count | n_tiles | overflow | 16-unit blocks run | groups run | pairs selected | pairs kept by the refinement
     }
     ex.stride = stride;
@@ -132,7 +130,7 @@ int exact_screen(som_handle* h, const __bf16* Xb, long n, unsigned long long* be
         h->ex.screen_slots = (int)std::min<long>(slots, h->ex.item_slots);
         bmu_bf16_k16_kernel<KS32, E, true, true><<<dim3((unsigned)h->ex.screen_slots), block, lds, h->stream>>>(
             Xb, n, h->Wst, h->n_stages, h->K, best64, h->ex.gmin, h->ex.stride, h->ex.gflags, xsq, xerr, xmax2, h->wmax2, h->wmax2 + 1, eb,
-            seed, glist, gcnt, h->ex.items + 8, (const int*)h->ex.items, (int*)h->ex.items + 1);
+            seed, glist, gcnt, h->ex.items + 8, (const int*)h->ex.items.p, (int*)h->ex.items.p + 1);
     } else if (tl)
         bmu_bf16_k16_kernel<KS32, E, true, true><<<grid, block, lds, h->stream>>>(
             Xb, n, h->Wst, h->n_stages, h->K, best64, h->ex.gmin, h->ex.stride, h->ex.gflags, xsq, xerr, xmax2, h->wmax2, h->wmax2 + 1, eb,
@@ -168,13 +166,13 @@ int exact_screen_wide(som_handle* h, const __bf16* Ximg, long n, unsigned long l
             // (the plan's lists as a work queue: a workgroup per slot of the chip -- bmu_bf16_wide.hpp; the next plan cuts for this many)
             h->ex.screen_slots = (int)std::min<long>(slots, h->ex.item_slots);
             bmu_bf16_wide_kernel<KS32, E, true, true><<<dim3((unsigned)h->ex.screen_slots), dim3(64 * WD_NW), lds, h->stream>>>(
-                (const char*)Ximg, n, h->Wst, h->n_stages, best64, h->ex.gmin, h->ex.stride, (uint32_t*)h->ex.gflags, xsq, xerr, xmax2,
-                h->wmax2, h->wmax2 + 1, eb, glist, gcnt, n_groups, nullptr, nullptr, nullptr, 0, h->ex.items + 8, (const int*)h->ex.items,
-                (int*)h->ex.items + 1);
+                (const char*)Ximg, n, h->Wst, h->n_stages, best64, h->ex.gmin, h->ex.stride, (uint32_t*)h->ex.gflags.p, xsq, xerr, xmax2,
+                h->wmax2, h->wmax2 + 1, eb, glist, gcnt, n_groups, nullptr, nullptr, nullptr, 0, h->ex.items + 8, (const int*)h->ex.items.p,
+                (int*)h->ex.items.p + 1);
             return 0;
         }
         bmu_bf16_wide_kernel<KS32, E, true, true><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
-            (const char*)Ximg, n, h->Wst, h->n_stages, best64, h->ex.gmin, h->ex.stride, (uint32_t*)h->ex.gflags, xsq, xerr, xmax2,
+            (const char*)Ximg, n, h->Wst, h->n_stages, best64, h->ex.gmin, h->ex.stride, (uint32_t*)h->ex.gflags.p, xsq, xerr, xmax2,
             h->wmax2, h->wmax2 + 1, eb, glist, gcnt, n_groups);
         return 0;
     }
@@ -201,7 +199,7 @@ int exact_screen_wide(som_handle* h, const __bf16* Ximg, long n, unsigned long l
         std::fprintf(stderr, "[somhip] exact screen (wide): blocks=%ld per_cu=%d slots=%ld parts=%d groups=%d\n", blocks, per_cu, slots,
                      parts, n_groups);
     bmu_bf16_wide_kernel<KS32, E, true><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
-        (const char*)Ximg, n, h->Wst, h->n_stages, best64, h->ex.gmin, h->ex.stride, (uint32_t*)h->ex.gflags, xsq, xerr, xmax2,
+        (const char*)Ximg, n, h->Wst, h->n_stages, best64, h->ex.gmin, h->ex.stride, (uint32_t*)h->ex.gflags.p, xsq, xerr, xmax2,
         h->wmax2, h->wmax2 + 1, eb);
     return 0;
 }
@@ -264,11 +262,7 @@ int exact_skip_reserve(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
     const long n_groups = cdiv(h->K, EX_GROUP);
     if (!ex.cen_ready) {
         // (a refusal part of the way leaves cen_ready unset: the whole block is tried again, nothing half allocated is used)
-        for (auto& c : ex.cen) {
-            void* cb[] = {c.Cc, c.rg, c.csq, c.cmax2, c.Cst, c.Cst_plain};
-            for (void* q : cb) if (q) (void)hipFree(q);
-            c = som_handle::ExactScratch::Centroids();
-        }
+        for (auto& c : ex.cen) c = som_handle::ExactScratch::Centroids{};
         const int ncs = (int)cdiv(n_groups, K16_STAGE_UNITS);
         for (int lv = 0; lv < (h->wide ? 1 : 2); ++lv) {
             auto& c = ex.cen[lv];
@@ -278,14 +272,14 @@ int exact_skip_reserve(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
             // (the centroid image's own stages: 64 centroids each up to 128 features, 32 on the wide kernel's tiling -- where
             //  n_cstages stays the number of 64-group WORDS of the need bitmaps)
             c.n_img_stages = h->wide ? (int)cdiv(n_groups, WD_STAGE_UNITS) : c.n_cstages;
-            if (int rc = dev_alloc(h, &c.Cc, (size_t)c.n_slots * h->D)) return rc;
-            if (int rc = dev_alloc(h, &c.rg, (size_t)c.n_slots)) return rc;
-            if (int rc = dev_alloc(h, &c.csq, (size_t)c.n_slots)) return rc;
-            if (int rc = dev_alloc(h, &c.cmax2, 2)) return rc;
-            if (int rc = dev_alloc(h, &c.Cst, (size_t)c.n_img_stages * h->stage_bytes)) return rc;
+            if (int rc = c.Cc.alloc(h, (size_t)c.n_slots * h->D)) return rc;
+            if (int rc = c.rg.alloc(h, (size_t)c.n_slots)) return rc;
+            if (int rc = c.csq.alloc(h, (size_t)c.n_slots)) return rc;
+            if (int rc = c.cmax2.alloc(h, 2)) return rc;
+            if (int rc = c.Cst.alloc(h, (size_t)c.n_img_stages * h->stage_bytes)) return rc;
             HIPCHK(h, hipMemsetAsync(c.Cst, 0, (size_t)c.n_img_stages * h->stage_bytes, h->stream));
             if (lv == 0) {
-                if (int rc = dev_alloc(h, &c.Cst_plain, (size_t)c.n_img_stages * h->stage_bytes)) return rc;
+                if (int rc = c.Cst_plain.alloc(h, (size_t)c.n_img_stages * h->stage_bytes)) return rc;
                 HIPCHK(h, hipMemsetAsync(c.Cst_plain, 0, (size_t)c.n_img_stages * h->stage_bytes, h->stream));
             }
         }
@@ -295,50 +289,42 @@ int exact_skip_reserve(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
     if (need_rows > sr.cap) {
         // (kernels of an earlier launch may still read the old copies: a transient set's buffers are reused launch after launch)
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        void* old[] = {sr.order, sr.Xb_s, sr.Xl_s, sr.Xf_s, sr.xsq_s, sr.xerr_s, sr.seed_s, sr.sU_s, sr.lastpos_s};
-        for (void* p : old) if (p) (void)hipFree(p);
-        sr = som_handle::ExactScratch::SortedRows();
+        sr = som_handle::ExactScratch::SortedRows{};
         if (&sr == &ex.srt[0]) ex.res_valid = false;
-        if (int rc = dev_alloc(h, &sr.order, (size_t)need_rows)) return rc;
-        if (int rc = dev_alloc(h, &sr.Xb_s, (size_t)need_rows * h->dp)) return rc;
+        if (int rc = sr.order.alloc(h, (size_t)need_rows)) return rc;
+        if (int rc = sr.Xb_s.alloc(h, (size_t)need_rows * h->dp)) return rc;
         // (sr.Xl_s, the rows' second half image: allocated by the first launch whose refinement pass engages -- launch_bmu_exact)
-        if (int rc = dev_alloc(h, &sr.Xf_s, (size_t)need_rows * h->D)) return rc;
-        if (int rc = dev_alloc(h, &sr.xsq_s, (size_t)need_rows)) return rc;
-        if (int rc = dev_alloc(h, &sr.xerr_s, (size_t)need_rows)) return rc;
-        if (int rc = dev_alloc(h, &sr.seed_s, (size_t)need_rows)) return rc;
-        if (int rc = dev_alloc(h, &sr.sU_s, (size_t)need_rows)) return rc;
-        if (int rc = dev_alloc(h, &sr.lastpos_s, (size_t)need_rows)) return rc;
+        if (int rc = sr.Xf_s.alloc(h, (size_t)need_rows * h->D)) return rc;
+        if (int rc = sr.xsq_s.alloc(h, (size_t)need_rows)) return rc;
+        if (int rc = sr.xerr_s.alloc(h, (size_t)need_rows)) return rc;
+        if (int rc = sr.seed_s.alloc(h, (size_t)need_rows)) return rc;
+        if (int rc = sr.sU_s.alloc(h, (size_t)need_rows)) return rc;
+        if (int rc = sr.lastpos_s.alloc(h, (size_t)need_rows)) return rc;
         sr.cap = need_rows;
     }
     if (stride <= ex.sk_stride) return 0;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    void* old[] = {ex.sk_keys, ex.sk_keys2, ex.sk_vals, ex.sk_tmp, ex.need, ex.need2, ex.glist, ex.gcnt, ex.tile_counts, ex.tlist, ex.tcnt, ex.scout_g, ex.items};
-    for (void* p : old) if (p) (void)hipFree(p);
-    ex.sk_keys = ex.sk_keys2 = ex.sk_vals = nullptr; ex.sk_tmp = nullptr; ex.need = ex.need2 = nullptr; ex.glist = ex.gcnt = nullptr; ex.tile_counts = nullptr; ex.tlist = ex.tcnt = nullptr;
-    ex.scout_g = nullptr; ex.items = nullptr;
+    ex.sk_keys.reset(); ex.sk_keys2.reset(); ex.sk_vals.reset(); ex.sk_tmp.reset(); ex.need.reset(); ex.need2.reset(); ex.glist.reset(); ex.gcnt.reset();
+    ex.tile_counts.reset(); ex.tlist.reset(); ex.tcnt.reset(); ex.scout_g.reset(); ex.items.reset();
     ex.sk_stride = 0;
     const long tiles = stride / SK_TILE;
-    if (int rc = dev_alloc(h, &ex.sk_keys, (size_t)stride)) return rc;
-    if (int rc = dev_alloc(h, &ex.sk_keys2, (size_t)stride)) return rc;
-    if (int rc = dev_alloc(h, &ex.sk_vals, (size_t)stride)) return rc;
-    if (int rc = dev_alloc(h, &ex.scout_g, (size_t)stride)) return rc;
-    if (h->wide) {
-        (void)hipFree(ex.tq); ex.tq = nullptr;
-        if (int rc = dev_alloc(h, &ex.tq, (size_t)stride)) return rc;
-    }
-    if (int rc = dev_alloc(h, &ex.need, (size_t)tiles * ex.cen[0].n_cstages)) return rc;
-    if (int rc = dev_alloc(h, &ex.need2, (size_t)tiles * ex.cen[1].n_cstages)) return rc;
-    if (int rc = dev_alloc(h, &ex.glist, (size_t)tiles * n_groups)) return rc;
-    if (int rc = dev_alloc(h, &ex.gcnt, (size_t)tiles)) return rc;
-    if (int rc = dev_alloc(h, &ex.tile_counts, (size_t)tiles)) return rc;
-    if (int rc = dev_alloc(h, &ex.tlist, (size_t)tiles * n_groups * K16_T)) return rc;
-    if (int rc = dev_alloc(h, &ex.tcnt, (size_t)tiles)) return rc;
+    if (int rc = ex.sk_keys.alloc(h, (size_t)stride)) return rc;
+    if (int rc = ex.sk_keys2.alloc(h, (size_t)stride)) return rc;
+    if (int rc = ex.sk_vals.alloc(h, (size_t)stride)) return rc;
+    if (int rc = ex.scout_g.alloc(h, (size_t)stride)) return rc;
+    if (h->wide)
+        if (int rc = ex.tq.alloc(h, (size_t)stride)) return rc;
+    if (int rc = ex.need.alloc(h, (size_t)tiles * ex.cen[0].n_cstages)) return rc;
+    if (int rc = ex.need2.alloc(h, (size_t)tiles * ex.cen[1].n_cstages)) return rc;
+    if (int rc = ex.glist.alloc(h, (size_t)tiles * n_groups)) return rc;
+    if (int rc = ex.gcnt.alloc(h, (size_t)tiles)) return rc;
+    if (int rc = ex.tile_counts.alloc(h, (size_t)tiles)) return rc;
+    if (int rc = ex.tlist.alloc(h, (size_t)tiles * n_groups * K16_T)) return rc;
+    if (int rc = ex.tcnt.alloc(h, (size_t)tiles)) return rc;
     // (the listed screen's work items: exact_list_totals_kernel -- at most 2 tiles + 3 slots of them; + the queue's two words)
     ex.item_slots = 8 * (h->n_cus > 0 ? h->n_cus : 256);    // (more workgroups than this never fit a chip: few features, small stages)
-    if (int rc = dev_alloc(h, &ex.items, (size_t)(5 * tiles + 4 * ex.item_slots + 16))) return rc;
-    int* tmp = nullptr;
-    if (int rc = dev_alloc(h, &tmp, radix_scratch_ints(stride))) return rc;
-    ex.sk_tmp = tmp; ex.sk_tmp_bytes = radix_scratch_ints(stride) * sizeof(int);
+    if (int rc = ex.items.alloc(h, (size_t)(5 * tiles + 4 * ex.item_slots + 16))) return rc;
+    if (int rc = ex.sk_tmp.alloc(h, radix_scratch_ints(stride))) return rc;
     ex.sk_stride = stride;
     return 0;
 }
@@ -380,7 +366,7 @@ int exact_skip_sortkeys(som_handle* h, som_handle::ExactScratch::SortedRows& sr,
         exact_sortkey_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(prev, h->ex_inv, n, h->K, ex.sk_keys, ex.sk_vals);
     int bits = 1;
     while ((1L << bits) < n_groups) ++bits;
-    return radix_sort_rows(h, ex.sk_keys, n, bits, ex.sk_keys2, sr.order + s0, (int*)ex.sk_tmp);
+    return radix_sort_rows(h, ex.sk_keys, n, bits, ex.sk_keys2, sr.order + s0, ex.sk_tmp);
 }
 // ... and the operands gathered in that order (`order`: n positions -> rows of the pass) into sr at positions s0 ...
 template <class E>
@@ -503,7 +489,7 @@ int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
     exact_list_totals_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(ex.tile_counts, tiles, ex.ctr + 2 * n_groups + 3, ex.ctr + 2 * n_groups + 4,
                                                                   ex.item_queue ? (ex.screen_slots > 0 ? ex.screen_slots : ex.item_slots) : 0,
                                                                   ex.item_queue ? queue : nullptr,
-                                                                  (int*)ex.items, (int*)ex.items + 1, ex.item_len_pct);
+                                                                  (int*)ex.items.p, (int*)ex.items.p + 1, ex.item_len_pct);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -629,7 +615,7 @@ int exact_wide_plan_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
     // (... and the listed screen's work queue: the lists -- counted in 16-unit blocks, four to a group -- cut into items)
     exact_list_totals_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(ex.tile_counts, tiles, ex.ctr + 2 * n_groups + 3, ex.ctr + 2 * n_groups + 4,
                                                                   ex.item_queue ? (ex.screen_slots > 0 ? ex.screen_slots : ex.item_slots) : 0,
-                                                                  ex.item_queue ? ex.items + 8 : nullptr, (int*)ex.items, (int*)ex.items + 1,
+                                                                  ex.item_queue ? ex.items + 8 : nullptr, (int*)ex.items.p, (int*)ex.items.p + 1,
                                                                   ex.item_len_pct);
     HIPCHK(h, hipGetLastError());
     return 0;
@@ -648,7 +634,7 @@ int exact_wide_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
 }
 
 template <int KG>
-int exact_rescore_kg(som_handle* h, const float* X, int n_groups, int deint) {
+int exact_rescore_kg(som_handle* h, const float* X, unsigned long long* best64, int n_groups, int deint) {
     auto& ex = h->ex;
     auto kern = exact_rescore_mfma_kernel<KG>;
     const size_t lds = (size_t)fr_stage_bytes(KG);
@@ -657,7 +643,7 @@ int exact_rescore_kg(som_handle* h, const float* X, int n_groups, int deint) {
     // (twice the resident slots: the runs of tiles are uneven -- partial tiles, idle waves -- and finer runs balance them)
     const long grid = std::min<long>(ex.max_tiles, (long)h->ex.grid_mult * per_cu * (h->n_cus > 0 ? h->n_cus : 256));
     kern<<<dim3((unsigned)grid), dim3(256), lds, h->stream>>>(X, h->D, h->Wfst, h->K, ex.tile_tab, ex.ctr + 2 * n_groups + 1, ex.plist,
-                                                             h->best64, h->ex_perm, nullptr, h->ex_sub44 ? 1 : 0, deint);
+                                                             best64, h->ex_perm, nullptr, h->ex_sub44 ? 1 : 0, deint);
     return 0;
 }
 
@@ -670,7 +656,7 @@ int exact_refine_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
     int* n_tiles = fb_count + 1; int* overflow = fb_count + 2;
     exact_tiles_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(gcount, n_groups, ex.stride, ex.stride * ex.pairs, ex.tile_tab, n_tiles,
                                                              overflow, nullptr, nullptr, fb_count + 5);
-    uint32_t* rowmin2 = (uint32_t*)ex.rowarg;              // (round 1's scratch: unused in the one-round scheme)
+    uint32_t* rowmin2 = (uint32_t*)ex.rowarg.p;            // (round 1's scratch: unused in the one-round scheme)
     HIPCHK(h, hipMemsetAsync(rowmin2, 0xFF, (size_t)n * sizeof(uint32_t), h->stream));
     const size_t lds = (size_t)k16_stage_bytes(KS32) + (size_t)K16_T * KS32 * 1024;
     int per_cu = 1;
@@ -709,17 +695,14 @@ int exact_rescore_round(som_handle* h, const float* X, const float* xsq, unsigne
     exact_tiles_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(gcount, n_groups, ex.stride, ex.stride * ex.pairs, ex.tile_tab, n_tiles,
                                                              overflow, gstart, gstart_out,
                                                              (gstart == nullptr && gstart_out == nullptr && !ex.refine_live) ? fb_count + 5 : nullptr);
-    unsigned long long* saved = h->best64;
-    h->best64 = best64;                                   // (exact_rescore_kg reads it from the handle)
-    int rc = 0;
     if (h->wide) {
         // beyond 128 features: the float32 tile image, chunk by chunk
-        if (!h->Wfimg) { h->best64 = saved; return fail(h, "exact: no float32 tile image"); }
+        if (!h->Wfimg) return fail(h, "exact: no float32 tile image");
         const bool cosine = h->cfg.distance == SOM_DIST_COSINE;
         const void* kern = cosine ? (const void*)exact_rescore_tiled_kernel<SCORE_COSINE>
                                   : (const void*)exact_rescore_tiled_kernel<SCORE_EUCLID_PART>;
         int per_cu = 1;
-        if (int rc2 = kernel_per_cu(h, kern, 256, 0, &per_cu)) { h->best64 = saved; return rc2; }
+        if (int rc = kernel_per_cu(h, kern, 256, 0, &per_cu)) return rc;
         const long grid = std::min<long>(ex.max_tiles, (long)h->ex.grid_mult * per_cu * (h->n_cus > 0 ? h->n_cus : 256));
         if (cosine)
             exact_rescore_tiled_kernel<SCORE_COSINE><<<dim3((unsigned)grid), dim3(256), 0, h->stream>>>(
@@ -727,19 +710,16 @@ int exact_rescore_round(som_handle* h, const float* X, const float* xsq, unsigne
         else
             exact_rescore_tiled_kernel<SCORE_EUCLID_PART><<<dim3((unsigned)grid), dim3(256), 0, h->stream>>>(
                 X, h->D, xsq, h->Wfimg, h->ft_kchunks, h->K, ex.tile_tab, n_tiles, ex.plist, best64, h->ex_perm, nullptr, h->ex_sub44 ? 1 : 0);
-        h->best64 = saved;
         return 0;
     }
     switch (h->fr_kg) {
-    case 1: rc = exact_rescore_kg<1>(h, X, n_groups, deint); break;
-    case 2: rc = exact_rescore_kg<2>(h, X, n_groups, deint); break;
-    case 4: rc = exact_rescore_kg<4>(h, X, n_groups, deint); break;
-    case 8: rc = exact_rescore_kg<8>(h, X, n_groups, deint); break;
-    case 16: rc = exact_rescore_kg<16>(h, X, n_groups, deint); break;
-    default: rc = fail(h, "exact: bad k-group count");
+    case 1: return exact_rescore_kg<1>(h, X, best64, n_groups, deint);
+    case 2: return exact_rescore_kg<2>(h, X, best64, n_groups, deint);
+    case 4: return exact_rescore_kg<4>(h, X, best64, n_groups, deint);
+    case 8: return exact_rescore_kg<8>(h, X, best64, n_groups, deint);
+    case 16: return exact_rescore_kg<16>(h, X, best64, n_groups, deint);
     }
-    h->best64 = saved;
-    return rc;
+    return fail(h, "exact: bad k-group count");
 }
 
 int build_tables(som_handle* h, double sigma, double eta, int neigh_f64, hipStream_t st);
@@ -753,12 +733,7 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
     auto& ex = h->ex;
     auto& cost = ex.cost;
     if (int rc = exact_reserve(h, N)) return rc;
-    if (N > h->best64_cap) {
-        (void)hipFree(h->best64);
-        h->best64 = nullptr; h->best64_cap = 0;
-        if (int rc = dev_alloc(h, &h->best64, (size_t)round_up(N, 1024))) return rc;
-        h->best64_cap = round_up(N, 1024);
-    }
+    if (int rc = h->best64.reserve(h, (size_t)N, 1024)) return rc;
     if (!cost.have) {
         for (auto& e : cost.ev) HIPCHK(h, hipEventCreate(&e));
         cost.have = true;
@@ -882,7 +857,7 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
     if (ex.refine_live && !sr.xl_filled) {
         // the rows' second half image (a quarter of the sorted copies' bytes) exists from the first launch that refines: the
         // order is rebuilt in that launch, so that the gather fills it
-        if (sr.Xl_s == nullptr && dev_alloc(h, &sr.Xl_s, (size_t)sr.cap * h->dp) != 0) { (void)hipGetLastError(); h->err.clear(); sr.Xl_s = nullptr; ex.refine_live = false; }
+        if (sr.Xl_s == nullptr && sr.Xl_s.alloc(h, (size_t)sr.cap * h->dp) != 0) { (void)hipGetLastError(); h->err.clear(); ex.refine_live = false; }
         else resort = true;
     }
     int64_t groups_run = 0, pairs_in = 0, pairs_out = 0, scout_wins = 0;
@@ -1080,14 +1055,8 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
         if (ex.skip_live && scout && have_last) scout_wins += ex.fb_count_host[7];
         if (n_fb < 0 || n_fb > n) return fail(h, "exact: fallback counter out of range");
         if (n_fb > 0) {
-            if (n_fb > ex.fb_cap) {
-                (void)hipFree(ex.fbX); (void)hipFree(ex.fb_ids);
-                ex.fbX = nullptr; ex.fb_ids = nullptr; ex.fb_cap = 0;
-                const long cap = round_up(n_fb, 1024);
-                if (int rc = dev_alloc(h, &ex.fbX, (size_t)cap * h->D)) return rc;
-                if (int rc = dev_alloc(h, &ex.fb_ids, (size_t)cap)) return rc;
-                ex.fb_cap = cap;
-            }
+            if (int rc = ex.fbX.reserve(h, (size_t)n_fb * h->D, (size_t)1024 * h->D)) return rc;
+            if (int rc = ex.fb_ids.reserve(h, (size_t)n_fb, 1024)) return rc;
             // the float32 kernel names units by their place in its image: the units' own order for it
             if (h->wf_patch) if (int rc = refresh_codebook_operands(h, true, false)) return rc;
             exact_gather_rows_kernel<<<dim3((unsigned)cdiv((long)n_fb * h->D, 256)), dim3(256), 0, h->stream>>>(
@@ -1095,7 +1064,7 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
             // (its part merge may reuse best64[0 .. n_fb): rows this pass has already settled)
             if (h->cfg.distance == SOM_DIST_COSINE) {
                 // (|x|^2 of the gathered rows in NumPy's order, into the head of the pass's spent minima)
-                float* fsq = (float*)ex.gmin;
+                float* fsq = (float*)ex.gmin.p;
                 row_sq_f32_kernel<<<dim3((unsigned)cdiv(n_fb, 256)), dim3(256), 0, h->stream>>>(ex.fbX, n_fb, h->D, fsq);
                 if (int rc = launch_bmu_f32_any<SCORE_COSINE>(h, ex.fbX, n_fb, fsq, ex.fb_ids)) return rc;
             } else if (int rc = launch_bmu_f32_any<SCORE_EUCLID_PART>(h, ex.fbX, n_fb, nullptr, ex.fb_ids)) return rc;

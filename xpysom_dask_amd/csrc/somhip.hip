@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <string>
 #include <utility>
@@ -64,6 +65,32 @@ struct RcclApi {
 static RcclApi g_rccl;
 static std::string g_rccl_error;
 
+// Device memory the engine owns: one allocation of `cap` elements, freed by its owner's destructor (move-only; alloc and
+// reserve free what is held BEFORE they allocate, so a grown buffer never holds twice its memory).  The bytes held by every live
+// DevBuf of the process are counted (som_debug_device_bytes: the suite checks that a handle gives back what it took).
+static std::atomic<int64_t> g_dev_bytes{0};
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;          // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) { (void)hipFree(p); g_dev_bytes -= (int64_t)(cap * sizeof(T)); }
+        p = nullptr; cap = 0;
+    }
+    int alloc(som_handle* h, size_t n);   // (defined with the handle: capture refusal, graph staleness, error message)
+    int reserve(som_handle* h, size_t n, size_t round = 1) { return n <= cap ? 0 : alloc(h, (n + round - 1) / round * round); }
+    operator T*() const { return p; }
+};
+
 struct som_handle {
     som_config cfg{};
     void* comm = nullptr;        // ncclComm_t of som_comm_init (NULL: single GPU, or the host does the all-reduce)
@@ -80,27 +107,26 @@ struct som_handle {
     // proper -- fallback rows, top-2, analysis calls -- want the units' own order and rebuild it)
     bool ex_patch = false, wf_patch = false;
     bool ex_sub44 = false;                              // ... with every group an 8 x 8 patch in 4 x 4 blocks (patch_order)
-    int* ex_perm = nullptr;
-    int* ex_inv = nullptr;
-    float* Wp = nullptr;     // [K][D] codebook in patch order
-    float* wsq_p = nullptr;  // [K]   its |w|^2 (the float32 kernel's own values, permuted)
+    DevBuf<int> ex_perm;
+    DevBuf<int> ex_inv;
+    DevBuf<float> Wp;        // [K][D] codebook in patch order
+    DevBuf<float> wsq_p;     // [K]   its |w|^2 (the float32 kernel's own values, permuted)
     struct ExactScratch {
-        uint32_t* gmin = nullptr;            // [n_groups][stride] group minima of the chunk being screened (sparse: see gflags)
-        unsigned long long* gflags = nullptr;   // [stride / 64][n_groups] which rows' minima the screen stored
+        DevBuf<uint32_t> gmin;               // [n_groups][stride] group minima of the chunk being screened (sparse: see gflags)
+        DevBuf<unsigned long long> gflags;   // [stride / 64][n_groups] which rows' minima the screen stored
         long stride = 0;                     //   rows per group line (a chunk of the row set, padded)
-        int* rowcnt = nullptr;               // [stride] candidate groups of every row of the last pass (som_exact_last_counts)
-        int* rowarg = nullptr;               // [stride] the group round 1 scored for the row (-1: none)
-        float* seed = nullptr;               // [stride] exact_seed_kernel: the cap on the screen's keep threshold
+        DevBuf<int> rowcnt;                  // [stride] candidate groups of every row of the last pass (som_exact_last_counts)
+        DevBuf<int> rowarg;                  // [stride] the group round 1 scored for the row (-1: none)
+        DevBuf<float> seed;                  // [stride] exact_seed_kernel: the cap on the screen's keep threshold
         bool seed_on = true;                 // SOM_EXACT_SEED=0: no seed (A/B)
         bool seed_live = false;              // this pass's screen reads the seed
         int two_round = -1;                  // SOM_EXACT_TWO_ROUND=0|1 forces the one- / two-round re-score (default: two rounds beyond 128 features)
-        int *fb_list = nullptr, *fb_ids = nullptr;
-        int* ctr = nullptr;                  // gcount | gstart of round 2 | fb_count | n_tiles | overflow (zeroed per pass)
-        int* plist = nullptr;                // [n_groups][stride] rows bucketed by candidate group
-        int4* tile_tab = nullptr;            // re-score tiles: (group, first list entry, rows)
+        DevBuf<int> fb_list, fb_ids;
+        DevBuf<int> ctr;                     // gcount | gstart of round 2 | fb_count | n_tiles | overflow (zeroed per pass)
+        DevBuf<int> plist;                   // [n_groups][stride] rows bucketed by candidate group
+        DevBuf<int4> tile_tab;               // re-score tiles: (group, first list entry, rows)
         long max_tiles = 0;
-        float* fbX = nullptr;                // fallback rows, dense, for the float32 kernel
-        long fb_cap = 0;
+        DevBuf<float> fbX;                   // fallback rows, dense, for the float32 kernel
         int* fb_count_host = nullptr;        // pinned
         hipEvent_t fb_ready = nullptr;       // recorded behind the counter's copy
         int64_t rows_total = 0, rows_fallback = 0, chunks = 0;   // som_exact_stats
@@ -122,12 +148,12 @@ struct som_handle {
         // a TRANSIENT row set (query rows, streamed chunks: sorted by the scout of exact_skip.hpp, used once).
         struct SortedRows {
             long cap = 0;                 // positions the buffers hold (each pass padded to the tile)
-            int* order = nullptr;
-            __bf16* Xb_s = nullptr;
-            __bf16* Xl_s = nullptr;       // ... the rows' second half image (the refinement pass): allocated when it first engages
+            DevBuf<int> order;
+            DevBuf<__bf16> Xb_s;
+            DevBuf<__bf16> Xl_s;          // ... the rows' second half image (the refinement pass): allocated when it first engages
             bool xl_filled = false;       //     ... and written by a gather since
-            float *Xf_s = nullptr, *xsq_s = nullptr, *xerr_s = nullptr, *seed_s = nullptr, *sU_s = nullptr;
-            int* lastpos_s = nullptr;     // position (patch order) of every sorted row's (pseudo) last BMU
+            DevBuf<float> Xf_s, xsq_s, xerr_s, seed_s, sU_s;
+            DevBuf<int> lastpos_s;        // position (patch order) of every sorted row's (pseudo) last BMU
         } srt[2];
         bool cen_ready = false;           // both centroid levels are allocated
         long sk_stride = 0;               // rows per pass the per-pass plan buffers hold
@@ -140,8 +166,8 @@ struct som_handle {
         int res_forced = 8;               // planned epochs after which the rows are sorted in any case (doubles after a forced sort that did not pay)
         double res_share_last = 1.0;      // ... of the last planned epoch
         int64_t resorts = 0, planned = 0; // som_exact_resident_stats
-        int *sk_keys = nullptr, *sk_keys2 = nullptr, *sk_vals = nullptr;
-        void* sk_tmp = nullptr; size_t sk_tmp_bytes = 0;
+        DevBuf<int> sk_keys, sk_keys2, sk_vals;
+        DevBuf<int> sk_tmp;               // radix_sort_rows' scratch
         bool refine_on = true;            // SOM_EXACT_REFINE=0: no refinement pass (A/B)
         bool refine_live = false;
         double pairs_per_row_last = 0.0;  // candidate (row, group) pairs per row of the last planned epoch
@@ -150,8 +176,8 @@ struct som_handle {
         int grid_mult = 2;                // persistent re-score / refinement kernels: workgroups per resident slot (SOM_EXACT_GRID_MULT: A/B)
         bool scout_on = true;             // SOM_EXACT_SCOUT=0: plans only from last epoch's BMUs (A/B)
         bool scout_live = false;          // this launch runs the scout
-        int* scout_g = nullptr;           // [stride] nearest group centroid of every row of the pass
-        float* tq = nullptr;              // [stride] wide plan: the float32 score of every sorted row's last BMU under the current codebook
+        DevBuf<int> scout_g;              // [stride] nearest group centroid of every row of the pass
+        DevBuf<float> tq;                 // [stride] wide plan: the float32 score of every sorted row's last BMU under the current codebook
         double scout_est_last = 0.0;      // executed share the sample tiles forecast at the last estimate
         double scout_f_now = 0.0, scout_f_declined = 0.0; int scout_f_age = 0;   // the sampled rows' need now / when the sample tiles last declined a plan
         double scout_win_share = 0.0;     // rows of the last launch whose scout pick beat their last BMU by a tenth of the squared distance
@@ -176,14 +202,14 @@ struct som_handle {
             int since = 99;                   // planned launches since the phases were last timed
         } cost;
         // the centroid sets of the plan: [0] the 64-unit groups, [1] their 16-unit sub-blocks (exact_centroid_kernel's slot order)
-        struct Centroids { float *Cc = nullptr, *rg = nullptr, *csq = nullptr, *cmax2 = nullptr; char* Cst = nullptr;
-                           char* Cst_plain = nullptr;   // level 1 only: the scout's copy (plain initial accumulators)
+        struct Centroids { DevBuf<float> Cc, rg, csq, cmax2; DevBuf<char> Cst;
+                           DevBuf<char> Cst_plain;      // level 1 only: the scout's copy (plain initial accumulators)
                            int n_slots = 0, n_cstages = 0, n_img_stages = 0; } cen[2];
-        unsigned long long *need = nullptr, *need2 = nullptr;
-        int *glist = nullptr, *gcnt = nullptr;   // per tile: (group << 4 | sub-block mask) items: what the select kernel walks
-        int *tlist = nullptr, *tcnt = nullptr;   // per tile: the same blocks as a dense list of 16-unit tiles: what the screen walks
-        int2* tile_counts = nullptr;
-        int2* items = nullptr;            // the listed screen's work queue: [0] = (items, counter), from [8] on (tile, part | parts << 16)
+        DevBuf<unsigned long long> need, need2;
+        DevBuf<int> glist, gcnt;          // per tile: (group << 4 | sub-block mask) items: what the select kernel walks
+        DevBuf<int> tlist, tcnt;          // per tile: the same blocks as a dense list of 16-unit tiles: what the screen walks
+        DevBuf<int2> tile_counts;
+        DevBuf<int2> items;               // the listed screen's work queue: [0] = (items, counter), from [8] on (tile, part | parts << 16)
         int item_slots = 0;               // ... sized for this many resident workgroups
         int screen_slots = 0;             // ... the listed screen's last grid (what the next plan cuts its lists for)
         bool item_queue = true;           // SOM_EXACT_QUEUE=0: one workgroup per tile (and part) instead (A/B)
@@ -204,15 +230,14 @@ struct som_handle {
     hipStream_t stream = nullptr;
     bool own_stream = false;
 
-    float *W = nullptr, *wsq = nullptr, *SC = nullptr, *T = nullptr, *ACC = nullptr, *P1 = nullptr, *P2 = nullptr;
-    float* Ud = nullptr;     // the count column after stage 1 of the transform, dense [nt][X][Y]
-    char* Wst = nullptr;
-    char* Wst_lo = nullptr;  // exact mode, input_len <= 128: the units' second half image (the refinement pass, bmu_exact.hpp)
-    char* Wfst = nullptr;    // f32 parity mode, input_len <= 128: float32 stage image (bmu_f32_res.hpp)
+    DevBuf<float> W, wsq, SC, T, ACC, P1, P2;
+    DevBuf<float> Ud;        // the count column after stage 1 of the transform, dense [nt][X][Y]
+    DevBuf<char> Wst;
+    DevBuf<char> Wst_lo;     // exact mode, input_len <= 128: the units' second half image (the refinement pass, bmu_exact.hpp)
+    DevBuf<char> Wfst;       // f32 parity mode, input_len <= 128: float32 stage image (bmu_f32_res.hpp)
     int fr_kg = 0, fr_stages = 0;
-    char* Wfimg = nullptr;   // f32 parity mode, input_len > 128: float32 tile image (bmu_f32_tiled.hpp)
-    char* ftX = nullptr;     //   sample tile image of the rows being scanned (scratch, grown on demand)
-    long ftX_cap = 0;
+    DevBuf<char> Wfimg;      // f32 parity mode, input_len > 128: float32 tile image (bmu_f32_tiled.hpp)
+    DevBuf<char> ftX;        //   sample tile image of the rows being scanned (scratch, grown on demand)
     int ft_kchunks = 0, ft_ublocks = 0;
     int n_stages = 0;
     // operands derived from W, rebuilt lazily: the bf16 stage image (w_dirty), |w|^2 (wsq_dirty) and the
@@ -220,46 +245,44 @@ struct som_handle {
     bool w_dirty = true, wsq_dirty = true, wf_dirty = true, wp_dirty = true;   // (wp: the patch-order copy, exact mode)
 
     // resident training rows
-    const float* Xd = nullptr;
-    float* X_owned = nullptr;
+    const float* Xd = nullptr;   // X_owned, or the caller's device rows (som_set_data_device)
+    DevBuf<float> X_owned;
     long N = 0, Np = 0;
-    int* bmu = nullptr;
+    DevBuf<int> bmu;
     bool bmu_valid = false;  // bmu holds the ids of a completed BMU pass over the resident rows
     // precision 'exact': the update-side work that does not depend on the BMUs (the zeroed segment sums, the neighbourhood
     // tables) is queued BEFORE the pass's counter read-back, so the GPU has it to do while the host wakes up
     struct EarlyUpdate { bool armed = false, done = false; double sigma = 0, eta = 0; int neigh_f64 = 0; } early;
-    unsigned long long* best64 = nullptr;   // bf16 path: per-row (value bits | unit) merged across codebook parts
-    long best64_cap = 0;
+    DevBuf<unsigned long long> best64;   // bf16 path: per-row (value bits | unit) merged across codebook parts
     int n_cus = 0;
     // BMU-ordered view of a row set + the partial lists of the segment sum's upper levels (update.hpp)
     struct SegScratch {
-        int *iota = nullptr, *skey = nullptr, *srow = nullptr;
-        void* tmp = nullptr;
-        size_t tmp_bytes = 0;
-        int *kA = nullptr, *kB = nullptr;        // keys of the level-1 / level-2 lists (ping-pong from there on)
-        float *vA = nullptr, *vB = nullptr;      // their vectors [entries][D1p]
+        DevBuf<int> skey, srow;
+        DevBuf<int> tmp;                         // radix_sort_rows' scratch
+        DevBuf<int> kA, kB;                      // keys of the level-1 / level-2 lists (ping-pong from there on)
+        DevBuf<float> vA, vB;                    // their vectors [entries][D1p]
         long cap = 0;                            // rows this scratch serves
-        int* cs_table = nullptr;                 // counting sort (small maps): [K][blocks of 1 024 rows] counts, then [K] totals
+        DevBuf<int> cs_table;                    // counting sort (small maps): [K][blocks of 1 024 rows] counts, then [K] totals
         long cs_blocks = 0;
     };
     SegScratch seg;                              // resident rows
-    float* xsq = nullptr;
-    __bf16* Xb = nullptr;
-    float* xmax2 = nullptr;  // [0] resident rows, [1] query scratch: max_n |x~_n|^2
-    float* wn = nullptr;     // |w~_k|^2 per unit
-    float* wmax2 = nullptr;
+    DevBuf<float> xsq;
+    DevBuf<__bf16> Xb;
+    DevBuf<float> xmax2;     // [0] resident rows, [1] query scratch: max_n |x~_n|^2
+    DevBuf<float> wn;        // |w~_k|^2 per unit
+    DevBuf<float> wmax2;
 
     // scratch for som_bmu / som_quantization_error
-    float* qX = nullptr; int* qbmu = nullptr; int* qbmu2 = nullptr; float* qxsq = nullptr; __bf16* qXb = nullptr;
-    double* qX64 = nullptr; size_t qX64_cap = 0;   // som_bmu_f64: float64 query rows
-    long qcap = 0, qX_cap = 0;
-    double* dsum = nullptr;
+    DevBuf<float> qX; DevBuf<int> qbmu, qbmu2; DevBuf<float> qxsq; DevBuf<__bf16> qXb;
+    DevBuf<double> qX64;     // som_bmu_f64: float64 query rows
+    long qcap = 0;
+    DevBuf<double> dsum;
     // streamed epochs (rows that do not stay resident): per-chunk sort scratch, grown on demand
     SegScratch st_seg;
     bool streaming = false;
     // double-buffered device staging for chunks that arrive in pinned host memory
     struct Slot {
-        float* dX = nullptr; __bf16* dXb = nullptr; float* dxsq = nullptr; int* dbmu = nullptr;
+        DevBuf<float> dX; DevBuf<__bf16> dXb; DevBuf<float> dxsq; DevBuf<int> dbmu;
         long cap = 0;
         hipEvent_t copied = nullptr, consumed = nullptr;
         bool used = false;
@@ -278,15 +301,15 @@ struct som_handle {
     const void* gexec_rows = nullptr;
     long gexec_n = -1;
     int graph_warm = 0;
-    void* np_dev = nullptr;  // NeighParams read by the captured neigh_tables_kernel
-    int2* bands = nullptr;   // nonzero column ranges of the neighbourhood tables per 128-row block (update.hpp)
+    DevBuf<NeighParams> np_dev;   // read by the captured neigh_tables_kernel
+    DevBuf<int2> bands;      // nonzero column ranges of the neighbourhood tables per 128-row block (update.hpp)
     bool use_bands = true;
 
     // canary (som_set_verify / SOM_VERIFY=n): n strided rows of every BMU launch re-scored by the float32 kernel
     int verify_rows = 0;
     bool verifying = false;
-    int *vf_rows = nullptr, *vf_picks = nullptr, *vf_best = nullptr, *vf_bad = nullptr;
-    float* vf_X = nullptr;
+    DevBuf<int> vf_rows, vf_picks, vf_best, vf_bad;
+    DevBuf<float> vf_X;
     int vf_cap = 0;
     int64_t verify_launches = 0, verify_rows_checked = 0;
     bool fuse_merge_prep = true; // SOM_FUSE_MERGE=0: separate merge and operand-preparation launches (A/B)
@@ -338,15 +361,21 @@ struct DeviceGuard {
         if (e_ != hipSuccess) return fail_hip((h), #call, e_);       \
     } while (0)
 
+}  // namespace
+
 template <typename T>
-int dev_alloc(som_handle* h, T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
+int DevBuf<T>::alloc(som_handle* h, size_t n) {
+    reset();
+    if (n == 0) n = 1;
     if (h->capturing) return fail(h, "allocation during graph capture");
-    HIPCHK(h, hipMalloc((void**)p, count * sizeof(T)));
+    if (hipError_t e = hipMalloc((void**)&p, n * sizeof(T)); e != hipSuccess) { p = nullptr; return fail_hip(h, "hipMalloc", e); }
     ++h->alloc_gen;                                   // device pointers baked into a captured graph may be stale
+    cap = n;
+    g_dev_bytes += (int64_t)(n * sizeof(T));
     return 0;
 }
+
+namespace {
 
 // Host -> device copy of caller-owned (usually pageable) memory.  Blocking on purpose: the runtime stages
 // pageable sources through its own pinned buffers; the copy is complete before anything that reads `dst` is
@@ -573,12 +602,7 @@ int launch_bmu_f32_res_kg(som_handle* h, const float* X, long N, const float* xs
         kern<<<dim3((unsigned)grid), dim3(256), lds, h->stream>>>(X, N, h->D, xsq, h->Wfst, h->fr_stages, h->K, out, out2,
                                                                  nullptr);
     } else {
-        if (N > h->best64_cap) {
-            (void)hipFree(h->best64);
-            h->best64 = nullptr; h->best64_cap = 0;
-            if (int rc = dev_alloc(h, &h->best64, (size_t)round_up(N, 1024))) return rc;
-            h->best64_cap = round_up(N, 1024);
-        }
+        if (int rc = h->best64.reserve(h, (size_t)N, 1024)) return rc;
         HIPCHK(h, hipMemsetAsync(h->best64, 0xFF, (size_t)N * sizeof(unsigned long long), h->stream));
         kern<<<dim3((unsigned)grid, (unsigned)parts), dim3(256), lds, h->stream>>>(X, N, h->D, xsq, h->Wfst, h->fr_stages,
                                                                                   h->K, out, out2, h->best64);
@@ -592,12 +616,7 @@ template <int MODE, bool TOP2>
 int launch_bmu_f32_tiled(som_handle* h, const float* X, long N, const float* xsq, int* out, int* out2) {
     const long n_blocks = cdiv(N, FT_BM);
     if (n_blocks <= 0 || n_blocks > 0x7fffffffL) return fail(h, "bmu_f32: row count out of range");
-    if (n_blocks > h->ftX_cap) {
-        (void)hipFree(h->ftX);
-        h->ftX = nullptr; h->ftX_cap = 0;
-        if (int rc = dev_alloc(h, &h->ftX, (size_t)n_blocks * h->ft_kchunks * FT_TILE)) return rc;
-        h->ftX_cap = n_blocks;
-    }
+    if (int rc = h->ftX.reserve(h, (size_t)n_blocks * h->ft_kchunks * FT_TILE)) return rc;
     long total = n_blocks * h->ft_kchunks * (4 * 4 * 64);
     prep_tiles_f32_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
         X, N, h->D, h->ft_kchunks, n_blocks, FT_TILE, nullptr, h->ftX);
@@ -700,12 +719,7 @@ int launch_bmu_bf16_tiled_cfg(som_handle* h, const __bf16* Ximg, long N, int* ou
     if (h->n_ublocks >= 64 && blocks * 8 >= slots) parts = 8;
     if (h->env_bf16_parts > 0) parts = h->env_bf16_parts;
     if (parts > h->n_ublocks) parts = h->n_ublocks;
-    if (N > h->best64_cap) {
-        (void)hipFree(h->best64);
-        h->best64 = nullptr; h->best64_cap = 0;
-        if (int rc = dev_alloc(h, &h->best64, (size_t)round_up(N, 1024))) return rc;
-        h->best64_cap = round_up(N, 1024);
-    }
+    if (int rc = h->best64.reserve(h, (size_t)N, 1024)) return rc;
     HIPCHK(h, hipMemsetAsync(h->best64, 0xFF, (size_t)N * sizeof(unsigned long long), h->stream));
     const long grid = round_up(blocks, 8) * parts;
     if (grid > 0x7fffffffL) return fail(h, "bmu_bf16: grid too large");
@@ -739,12 +753,7 @@ int launch_bmu_bf16_wide(som_handle* h, const __bf16* Ximg, const float* xmax2, 
     }
     if (h->env_bf16_parts > 0) parts = h->env_bf16_parts;
     if (parts > h->n_stages) parts = h->n_stages;
-    if (N > h->best64_cap) {
-        (void)hipFree(h->best64);
-        h->best64 = nullptr; h->best64_cap = 0;
-        if (int rc = dev_alloc(h, &h->best64, (size_t)round_up(N, 1024))) return rc;
-        h->best64_cap = round_up(N, 1024);
-    }
+    if (int rc = h->best64.reserve(h, (size_t)N, 1024)) return rc;
     const long units = (long)h->n_stages * h->stage_units;
     prep_wsqh_kernel<<<dim3((unsigned)cdiv(std::max(units, N), 256)), dim3(256), 0, h->stream>>>(
         h->wn, h->K, h->wmax2, xmax2, h->Wst, h->n_stages, h->stage_bytes, h->stage_units, h->best64, N);
@@ -784,12 +793,7 @@ int launch_bmu_half(som_handle* h, const __bf16* Xb, const float* xmax2, long N,
     // the stage image's initial accumulators depend on the row set through B = xmax * wmax; the same launch
     // resets the per-row merge keys of the 16x16x32 kernel
     long units = (long)h->n_stages * h->stage_units;
-    if (N > h->best64_cap) {
-        (void)hipFree(h->best64);
-        h->best64 = nullptr; h->best64_cap = 0;
-        if (int rc = dev_alloc(h, &h->best64, (size_t)round_up(N, 1024))) return rc;
-        h->best64_cap = round_up(N, 1024);
-    }
+    if (int rc = h->best64.reserve(h, (size_t)N, 1024)) return rc;
     prep_wsqh_kernel<<<dim3((unsigned)cdiv(std::max(units, N), 256)), dim3(256), 0, h->stream>>>(
         h->wn, h->K, h->wmax2, xmax2, h->Wst, h->n_stages, h->stage_bytes, h->stage_units, h->best64, N);
     switch (h->ks32) {
@@ -923,14 +927,12 @@ int verify_bmu_launch(som_handle* h, const float* X, long N, const int* ids) {
     if (n <= 0 || h->cfg.distance > SOM_DIST_COSINE) return 0;     // (the VALU distances have one precision: nothing to cross-check)
     if (h->capturing) return fail(h, "SOM_VERIFY reads a flag back per launch: not capturable");
     if (n > h->vf_cap) {
-        void* old[] = {h->vf_rows, h->vf_picks, h->vf_best, h->vf_X};
-        for (void* p : old) if (p) (void)hipFree(p);
-        h->vf_rows = h->vf_picks = h->vf_best = nullptr; h->vf_X = nullptr; h->vf_cap = 0;
-        if (int rc = dev_alloc(h, &h->vf_rows, (size_t)n)) return rc;
-        if (int rc = dev_alloc(h, &h->vf_picks, (size_t)n)) return rc;
-        if (int rc = dev_alloc(h, &h->vf_best, (size_t)n)) return rc;
-        if (int rc = dev_alloc(h, &h->vf_X, (size_t)n * h->D)) return rc;
-        if (!h->vf_bad) if (int rc = dev_alloc(h, &h->vf_bad, 4)) return rc;
+        h->vf_rows.reset(); h->vf_picks.reset(); h->vf_best.reset(); h->vf_X.reset(); h->vf_cap = 0;
+        if (int rc = h->vf_rows.alloc(h, (size_t)n)) return rc;
+        if (int rc = h->vf_picks.alloc(h, (size_t)n)) return rc;
+        if (int rc = h->vf_best.alloc(h, (size_t)n)) return rc;
+        if (int rc = h->vf_X.alloc(h, (size_t)n * h->D)) return rc;
+        if (!h->vf_bad) if (int rc = h->vf_bad.alloc(h, 4)) return rc;
         h->vf_cap = n;
     }
     verify_pick_rows_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(N, n, ids, h->vf_rows, h->vf_picks);
@@ -1014,33 +1016,25 @@ int row_sq(som_handle* h, const float* X, long N, float* out) {
 
 // ---- update path: segment sum + separable neighbourhood transform --------------------------
 // SC[b] += sum of the rows whose BMU is b (and their count): sort by BMU, chunked register sums
-void seg_free(som_handle::SegScratch& sg) {
-    void* b[] = {sg.iota, sg.skey, sg.srow, sg.tmp, sg.kA, sg.kB, sg.vA, sg.vB, sg.cs_table};
-    for (void* p : b) if (p) (void)hipFree(p);
-    sg = som_handle::SegScratch();
-}
-
 // scratch for the segment sum of up to `rows` rows (sort buffers + the partial lists of levels 1 and 2;
 // level 3 reuses level 1's, and so on)
 int seg_reserve(som_handle* h, som_handle::SegScratch& sg, long rows) {
     if (rows <= sg.cap) return 0;
-    seg_free(sg);
+    sg = som_handle::SegScratch{};
     if (rows > 0x7fffffffL) return fail(h, "more than 2^31-1 rows per GPU in one row set");
-    if (int rc = dev_alloc(h, &sg.skey, (size_t)rows)) return rc;
-    if (int rc = dev_alloc(h, &sg.srow, (size_t)rows)) return rc;
-    const size_t bytes = radix_scratch_ints(rows) * sizeof(int);
-    if (int rc = dev_alloc(h, (char**)&sg.tmp, bytes)) return rc;
-    sg.tmp_bytes = bytes;
+    if (int rc = sg.skey.alloc(h, (size_t)rows)) return rc;
+    if (int rc = sg.srow.alloc(h, (size_t)rows)) return rc;
+    if (int rc = sg.tmp.alloc(h, radix_scratch_ints(rows))) return rc;
     const int nw = seg_waves_per_block(h->D1p);
     const long n1 = seg_next_entries(rows, SEG_CHUNK, nw), n2 = seg_next_entries(n1, SEG_CHUNK_UP, nw);
-    if (int rc = dev_alloc(h, &sg.kA, (size_t)n1)) return rc;
-    if (int rc = dev_alloc(h, &sg.vA, (size_t)n1 * h->D1p)) return rc;
-    if (int rc = dev_alloc(h, &sg.kB, (size_t)n2)) return rc;
-    if (int rc = dev_alloc(h, &sg.vB, (size_t)n2 * h->D1p)) return rc;
+    if (int rc = sg.kA.alloc(h, (size_t)n1)) return rc;
+    if (int rc = sg.vA.alloc(h, (size_t)n1 * h->D1p)) return rc;
+    if (int rc = sg.kB.alloc(h, (size_t)n2)) return rc;
+    if (int rc = sg.vB.alloc(h, (size_t)n2 * h->D1p)) return rc;
     // small maps: the counting sort's table (update.hpp); SOM_COUNTING_SORT=0 keeps rocPRIM's sort (A/B)
     const long csb = cdiv(rows, CS_BLOCK);
     if (h->counting_sort && h->K <= CS_MAX_K && rows >= 2 * CS_BLOCK && csb * h->K <= (1L << 21)) {
-        if (int rc = dev_alloc(h, &sg.cs_table, (size_t)(csb + 1) * h->K)) return rc;
+        if (int rc = sg.cs_table.alloc(h, (size_t)(csb + 1) * h->K)) return rc;
         sg.cs_blocks = csb;
     }
     sg.cap = rows;
@@ -1085,7 +1079,7 @@ int segsum_rows(som_handle* h, const float* X, const int* bmu, long N, som_handl
                                                                                     sg.srow);
             HIPCHK(h, hipGetLastError());
         } else {
-            if (int rc = radix_sort_rows(h, bmu, N, bits, sg.skey, sg.srow, (int*)sg.tmp)) return rc;
+            if (int rc = radix_sort_rows(h, bmu, N, bits, sg.skey, sg.srow, sg.tmp)) return rc;
         }
         const int acc = zero_first ? 0 : 1;
         long blocks = launch_runsum<true>(h, X, sg.skey, sg.srow, nullptr, N, acc, sg.kA, sg.vA);
@@ -1249,22 +1243,16 @@ int run_transform(som_handle* h, double sigma, double eta, int neigh_f64) {
 
 // with_rows: the caller stages host rows through qX (device rows of the caller's are read where they are)
 int ensure_query_scratch(som_handle* h, long n, bool with_rows = true) {
-    if (with_rows && n > h->qX_cap) {
-        (void)hipFree(h->qX);
-        h->qX = nullptr; h->qX_cap = 0;
-        if (int rc = dev_alloc(h, &h->qX, (size_t)round_up(n, 1024) * h->D)) return rc;
-        h->qX_cap = round_up(n, 1024);
-    }
+    if (with_rows) if (int rc = h->qX.reserve(h, (size_t)n * h->D, (size_t)1024 * h->D)) return rc;
     if (n <= h->qcap) return 0;
     long cap = round_up(n, 1024);
-    (void)hipFree(h->qbmu); (void)hipFree(h->qbmu2); (void)hipFree(h->qxsq); (void)hipFree(h->qXb);
-    h->qbmu = nullptr; h->qbmu2 = nullptr; h->qxsq = nullptr; h->qXb = nullptr; h->qcap = 0;
-    if (int rc = dev_alloc(h, &h->qbmu, (size_t)cap)) return rc;
-    if (int rc = dev_alloc(h, &h->qbmu2, (size_t)cap)) return rc;
-    if (int rc = dev_alloc(h, &h->qxsq, (size_t)cap * (h->exact ? 2 : 1))) return rc;
+    h->qbmu.reset(); h->qbmu2.reset(); h->qxsq.reset(); h->qXb.reset(); h->qcap = 0;
+    if (int rc = h->qbmu.alloc(h, (size_t)cap)) return rc;
+    if (int rc = h->qbmu2.alloc(h, (size_t)cap)) return rc;
+    if (int rc = h->qxsq.alloc(h, (size_t)cap * (h->exact ? 2 : 1))) return rc;
     if (h->cfg.precision != SOM_PREC_F32) {
         long capp = round_up(cap, ROW_PAD);
-        if (int rc = dev_alloc(h, &h->qXb, (size_t)capp * h->dp)) return rc;
+        if (int rc = h->qXb.alloc(h, (size_t)capp * h->dp)) return rc;
     }
     h->qcap = cap;
     return 0;
@@ -1424,13 +1412,13 @@ int som_create(const som_config* cfg, som_handle** out) {
         h->own_stream = true;
     }
     const size_t KD1 = (size_t)h->K * h->D1p;
-    if ((rc = dev_alloc(h, &h->W, (size_t)h->K * h->D))) return bail(rc);
-    if ((rc = dev_alloc(h, &h->wsq, (size_t)h->K))) return bail(rc);
+    if ((rc = h->W.alloc(h, (size_t)h->K * h->D))) return bail(rc);
+    if ((rc = h->wsq.alloc(h, (size_t)h->K))) return bail(rc);
     if (h->ex_patch) {
-        if ((rc = dev_alloc(h, &h->Wp, (size_t)h->K * h->D))) return bail(rc);
-        if ((rc = dev_alloc(h, &h->wsq_p, (size_t)h->K))) return bail(rc);
-        if ((rc = dev_alloc(h, &h->ex_perm, (size_t)h->K))) return bail(rc);
-        if ((rc = dev_alloc(h, &h->ex_inv, (size_t)h->K))) return bail(rc);
+        if ((rc = h->Wp.alloc(h, (size_t)h->K * h->D))) return bail(rc);
+        if ((rc = h->wsq_p.alloc(h, (size_t)h->K))) return bail(rc);
+        if ((rc = h->ex_perm.alloc(h, (size_t)h->K))) return bail(rc);
+        if ((rc = h->ex_inv.alloc(h, (size_t)h->K))) return bail(rc);
         // bands of 8 map rows, column by column: 64 consecutive positions = 8 columns of a band = an 8 x 8 patch (where
         // the sides are no multiples of 8 a group may straddle two bands or hold a narrower band's 64 / h columns: still
         // compact); then every group's units in ascending order (the first-minimum rule inside a re-score tile)
@@ -1445,17 +1433,15 @@ int som_create(const som_config* cfg, som_handle** out) {
             hipMemcpy(h->ex_inv, inv.data(), (size_t)h->K * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
             return bail(fail(h, "hipMemcpy of the patch-order tables failed"));
     }
-    if ((rc = dev_alloc(h, &h->SC, KD1 + (size_t)h->K))) return bail(rc);        // [K][D1p] sums|counts, then the counts densely [K]
-    if ((rc = dev_alloc(h, &h->Ud, (size_t)h->nt * h->K))) return bail(rc);
-    if ((rc = dev_alloc(h, &h->T, KD1 * h->nt))) return bail(rc);
-    if ((rc = dev_alloc(h, &h->ACC, KD1))) return bail(rc);
-    if ((rc = dev_alloc(h, &h->P1, (size_t)h->nt * h->Y * h->Y))) return bail(rc);
-    if ((rc = dev_alloc(h, &h->P2, (size_t)h->X * h->nt * h->X))) return bail(rc);
-    if ((rc = dev_alloc(h, &h->dsum, 1))) return bail(rc);
+    if ((rc = h->SC.alloc(h, KD1 + (size_t)h->K))) return bail(rc);        // [K][D1p] sums|counts, then the counts densely [K]
+    if ((rc = h->Ud.alloc(h, (size_t)h->nt * h->K))) return bail(rc);
+    if ((rc = h->T.alloc(h, KD1 * h->nt))) return bail(rc);
+    if ((rc = h->ACC.alloc(h, KD1))) return bail(rc);
+    if ((rc = h->P1.alloc(h, (size_t)h->nt * h->Y * h->Y))) return bail(rc);
+    if ((rc = h->P2.alloc(h, (size_t)h->X * h->nt * h->X))) return bail(rc);
+    if ((rc = h->dsum.alloc(h, 1))) return bail(rc);
     {
-        NeighParams* npd = nullptr;
-        if ((rc = dev_alloc(h, &npd, 1))) return bail(rc);
-        h->np_dev = npd;
+        if ((rc = h->np_dev.alloc(h, 1))) return bail(rc);
         if (const char* e = std::getenv("SOM_GRAPH")) h->use_graph = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_BF16_PARTS")) h->env_bf16_parts = std::atoi(e);
         h->debug = std::getenv("SOM_DEBUG") != nullptr;
@@ -1480,7 +1466,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         h->use_bands = h->X > 256 || h->Y > 256;
         if (const char* e = dev_env("SOM_NO_BANDS")) h->use_bands = std::atoi(e) == 0;
         const size_t nb = (size_t)h->nt * (cdiv(h->Y, LM_BM) + cdiv(h->X, LM_BM));
-        if ((rc = dev_alloc(h, &h->bands, nb))) return bail(rc);
+        if ((rc = h->bands.alloc(h, nb))) return bail(rc);
     }
     // (T: stage 1 of the transform writes the feature columns and the count column only; the padding columns behind
     //  them are read by a whole-row stage 2 and end up in ACC's padding, which is all-reduced: keep them defined)
@@ -1491,27 +1477,27 @@ int som_create(const som_config* cfg, som_handle** out) {
     if (h->D > 128) {
         h->ft_kchunks = (int)cdiv(h->D, FT_BK);
         h->ft_ublocks = (int)cdiv(h->K, FT_BN);
-        if ((rc = dev_alloc(h, &h->Wfimg, (size_t)h->ft_ublocks * h->ft_kchunks * FT_WTILE))) return bail(rc);
+        if ((rc = h->Wfimg.alloc(h, (size_t)h->ft_ublocks * h->ft_kchunks * FT_WTILE))) return bail(rc);
     }
     if (h->D <= 128) {
         int kg = 1;
         while (kg * 8 < h->D) kg *= 2;                      // 8, 16, 32, 64 or 128 features per row image
         h->fr_kg = kg;
         h->fr_stages = (int)cdiv(h->K, FR_STAGE_UNITS);
-        if ((rc = dev_alloc(h, &h->Wfst, (size_t)h->fr_stages * fr_stage_bytes(kg)))) return bail(rc);
+        if ((rc = h->Wfst.alloc(h, (size_t)h->fr_stages * fr_stage_bytes(kg)))) return bail(rc);
     }
     if (h->cfg.precision != SOM_PREC_F32) {
         h->n_stages = (int)cdiv(h->K, h->stage_units);
         size_t bytes = (size_t)h->n_stages * h->stage_bytes;
         if (h->tiled && !h->wide) bytes = (size_t)h->n_ublocks * h->n_kchunks * h->tl_wtile;
-        if ((rc = dev_alloc(h, &h->Wst, bytes))) return bail(rc);
+        if ((rc = h->Wst.alloc(h, bytes))) return bail(rc);
         if (h->exact && !h->tiled) {
-            if ((rc = dev_alloc(h, &h->Wst_lo, bytes))) return bail(rc);
+            if ((rc = h->Wst_lo.alloc(h, bytes))) return bail(rc);
             if (hipMemsetAsync(h->Wst_lo, 0, bytes, h->stream) != hipSuccess) return bail(fail(h, "hipMemsetAsync failed"));
         }
-        if ((rc = dev_alloc(h, &h->xmax2, 2))) return bail(rc);
-        if ((rc = dev_alloc(h, &h->wn, (size_t)h->K))) return bail(rc);
-        if ((rc = dev_alloc(h, &h->wmax2, 2))) return bail(rc);
+        if ((rc = h->xmax2.alloc(h, 2))) return bail(rc);
+        if ((rc = h->wn.alloc(h, (size_t)h->K))) return bail(rc);
+        if ((rc = h->wmax2.alloc(h, 2))) return bail(rc);
         if (hipMemsetAsync(h->Wst, 0, bytes, h->stream) != hipSuccess) return bail(fail(h, "hipMemsetAsync failed"));
     }
     if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(h, "hipStreamSynchronize failed"));
@@ -1528,46 +1514,18 @@ void som_destroy(som_handle* h) {
     if (h->ev_comm) (void)hipEventDestroy(h->ev_comm);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->gexec) (void)hipGraphExecDestroy(h->gexec);
-    if (h->np_dev) (void)hipFree(h->np_dev);
-    if (h->bands) (void)hipFree(h->bands);
     for (auto& ep : h->pending) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     for (auto& ep : h->pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
-    void* bufs[] = {h->Ud, h->W, h->wsq, h->SC, h->T, h->ACC, h->P1, h->P2, h->Wst, h->X_owned, h->bmu, h->xsq, h->Xb,
-                    h->xmax2, h->wn, h->wmax2, h->qX, h->qbmu, h->qbmu2, h->qxsq, h->qXb, h->dsum,
-                    h->best64, h->Wfst, h->Wfimg, h->ftX, h->qX64, h->Wp, h->wsq_p, h->ex_perm, h->ex_inv, h->Wst_lo};
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    seg_free(h->seg);
-    seg_free(h->st_seg);
-    {
-        void* vb[] = {h->vf_rows, h->vf_picks, h->vf_best, h->vf_bad, h->vf_X};
-        for (void* b : vb) if (b) (void)hipFree(b);
-    }
-    {
-        void* eb[] = {h->ex.gmin, h->ex.gflags, h->ex.rowcnt, h->ex.rowarg, h->ex.seed, h->ex.fb_list, h->ex.ctr, h->ex.fb_ids, h->ex.fbX, h->ex.plist, h->ex.tile_tab,
-                      h->ex.sk_keys, h->ex.sk_keys2, h->ex.sk_vals, h->ex.sk_tmp, h->ex.scout_g, h->ex.tq,
-                      h->ex.need, h->ex.need2, h->ex.glist, h->ex.gcnt, h->ex.tile_counts, h->ex.tlist, h->ex.tcnt};
-        for (void* b : eb) if (b) (void)hipFree(b);
-        for (auto& sr : h->ex.srt) {
-            void* sb[] = {sr.order, sr.Xb_s, sr.Xl_s, sr.Xf_s, sr.xsq_s, sr.xerr_s, sr.seed_s, sr.sU_s, sr.lastpos_s};
-            for (void* b : sb) if (b) (void)hipFree(b);
-        }
-        for (auto& c : h->ex.cen) {
-            void* cb[] = {c.Cc, c.rg, c.csq, c.cmax2, c.Cst, c.Cst_plain};
-            for (void* b : cb) if (b) (void)hipFree(b);
-        }
-        if (h->ex.cost.have) for (auto& e : h->ex.cost.ev) (void)hipEventDestroy(e);
-        if (h->ex.fb_count_host) (void)hipHostFree(h->ex.fb_count_host);
-        if (h->ex.fb_ready) (void)hipEventDestroy(h->ex.fb_ready);
-    }
+    if (h->ex.cost.have) for (auto& e : h->ex.cost.ev) (void)hipEventDestroy(e);
+    if (h->ex.fb_ready) (void)hipEventDestroy(h->ex.fb_ready);
     for (auto& sl : h->slot) {
-        void* sb[] = {sl.dX, sl.dXb, sl.dxsq, sl.dbmu};
-        for (void* b : sb) if (b) (void)hipFree(b);
         if (sl.copied) (void)hipEventDestroy(sl.copied);
         if (sl.consumed) (void)hipEventDestroy(sl.consumed);
     }
+    if (h->ex.fb_count_host) (void)hipHostFree(h->ex.fb_count_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;                                            // (the device buffers free themselves, on the handle's device: dev_guard)
 }
 
 int som_set_weights(som_handle* h, const float* w_host) {
@@ -1595,24 +1553,23 @@ int som_get_weights(som_handle* h, float* w_host) {
 }
 
 static int adopt_rows(som_handle* h, int64_t n_rows) {
-    (void)hipFree(h->bmu); (void)hipFree(h->xsq); (void)hipFree(h->Xb);
-    h->bmu = nullptr; h->xsq = nullptr; h->Xb = nullptr;
+    h->bmu.reset(); h->xsq.reset(); h->Xb.reset();
     h->bmu_valid = false;
     h->ex.res_valid = false;                             // (the resident sorted pass belongs to the rows it was sorted from)
-    seg_free(h->seg);
+    h->seg = som_handle::SegScratch{};
     h->N = n_rows;
     h->Np = round_up(n_rows, ROW_PAD);
     if (n_rows > 0x7fffffffL) return fail(h, "som_set_data: more than 2^31-1 rows per GPU");
-    if (int rc = dev_alloc(h, &h->bmu, (size_t)n_rows)) return rc;
+    if (int rc = h->bmu.alloc(h, (size_t)n_rows)) return rc;
     if (n_rows > 0)
         if (int rc = seg_reserve(h, h->seg, n_rows)) return rc;
     const bool bf_cos_tiled = h->cfg.precision != SOM_PREC_F32 && h->cfg.distance == SOM_DIST_COSINE && h->tiled;
     if (needs_xsq(h) || bf_cos_tiled) {
-        if (int rc = dev_alloc(h, &h->xsq, (size_t)n_rows * (h->exact ? 2 : 1))) return rc;
+        if (int rc = h->xsq.alloc(h, (size_t)n_rows * (h->exact ? 2 : 1))) return rc;
         if (needs_xsq(h)) if (int rc = row_sq(h, h->Xd, n_rows, h->xsq)) return rc;
     }
     if (h->cfg.precision != SOM_PREC_F32 && n_rows > 0) {
-        if (int rc = dev_alloc(h, &h->Xb, (size_t)h->Np * h->dp)) return rc;
+        if (int rc = h->Xb.alloc(h, (size_t)h->Np * h->dp)) return rc;
         if (int rc = prep_rows_bf16(h, h->Xd, n_rows, h->Np, h->Xb, h->xmax2, h->xsq)) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1638,9 +1595,8 @@ static int adopt_rows(som_handle* h, int64_t n_rows) {
 int som_set_data(som_handle* h, const float* x_host, int64_t n_rows) {
     DeviceGuard dev_guard(h);
     if (!h || n_rows < 0 || (!x_host && n_rows > 0)) return fail(h, "som_set_data: bad argument");
-    (void)hipFree(h->X_owned);
-    h->X_owned = nullptr; h->Xd = nullptr;
-    if (int rc = dev_alloc(h, &h->X_owned, (size_t)n_rows * h->D)) return rc;
+    h->Xd = nullptr;
+    if (int rc = h->X_owned.alloc(h, (size_t)n_rows * h->D)) return rc;
     if (n_rows > 0)
         if (int rc = h2d_blocking(h, h->X_owned, x_host, (size_t)n_rows * h->D * sizeof(float))) return rc;
     h->Xd = h->X_owned;
@@ -1650,8 +1606,7 @@ int som_set_data(som_handle* h, const float* x_host, int64_t n_rows) {
 int som_set_data_device(som_handle* h, const void* x_dev, int64_t n_rows) {
     DeviceGuard dev_guard(h);
     if (!h || n_rows < 0 || (!x_dev && n_rows > 0)) return fail(h, "som_set_data_device: bad argument");
-    (void)hipFree(h->X_owned);
-    h->X_owned = nullptr;
+    h->X_owned.reset();
     h->Xd = (const float*)x_dev;
     return adopt_rows(h, n_rows);
 }
@@ -1807,14 +1762,13 @@ static int ensure_slot(som_handle* h, som_handle::Slot& sl, long n) {
     }
     if (n <= sl.cap) return 0;
     if (sl.used) HIPCHK(h, hipEventSynchronize(sl.consumed));
-    (void)hipFree(sl.dX); (void)hipFree(sl.dXb); (void)hipFree(sl.dxsq); (void)hipFree(sl.dbmu);
-    sl.dX = nullptr; sl.dXb = nullptr; sl.dxsq = nullptr; sl.dbmu = nullptr; sl.cap = 0;
+    sl.dX.reset(); sl.dXb.reset(); sl.dxsq.reset(); sl.dbmu.reset(); sl.cap = 0;
     long cap = round_up(n, ROW_PAD);
-    if (int rc = dev_alloc(h, &sl.dX, (size_t)cap * h->D)) return rc;
-    if (int rc = dev_alloc(h, &sl.dbmu, (size_t)cap)) return rc;
-    if (int rc = dev_alloc(h, &sl.dxsq, (size_t)cap * (h->exact ? 2 : 1))) return rc;
+    if (int rc = sl.dX.alloc(h, (size_t)cap * h->D)) return rc;
+    if (int rc = sl.dbmu.alloc(h, (size_t)cap)) return rc;
+    if (int rc = sl.dxsq.alloc(h, (size_t)cap * (h->exact ? 2 : 1))) return rc;
     if (h->cfg.precision != SOM_PREC_F32)
-        if (int rc = dev_alloc(h, &sl.dXb, (size_t)cap * h->dp)) return rc;
+        if (int rc = sl.dXb.alloc(h, (size_t)cap * h->dp)) return rc;
     sl.cap = cap;
     return 0;
 }
@@ -2184,13 +2138,7 @@ int som_bmu_f64(som_handle* h, const double* x_host, int64_t n_rows, int32_t* id
     const size_t w_bytes = (size_t)PW_UNITS * h->D * sizeof(float);
     if (w_bytes > 150 * 1024) return fail(h, "som_bmu_f64: input_len too large for the LDS unit tile");
     if (int rc = ensure_query_scratch(h, n_rows)) return rc;
-    if ((size_t)n_rows * h->D > h->qX64_cap) {
-        (void)hipFree(h->qX64);
-        h->qX64 = nullptr; h->qX64_cap = 0;
-        const size_t cap = (size_t)round_up(n_rows, 1024) * h->D;
-        if (int rc = dev_alloc(h, &h->qX64, cap)) return rc;
-        h->qX64_cap = cap;
-    }
+    if (int rc = h->qX64.reserve(h, (size_t)n_rows * h->D, (size_t)1024 * h->D)) return rc;
     if (int rc = h2d_blocking(h, h->qX64, x_host, (size_t)n_rows * h->D * sizeof(double))) return rc;
     if (int rc = refresh_codebook_operands(h, true)) return rc;       // |w|^2 in NumPy's float32 order
     {
@@ -2230,19 +2178,15 @@ int som_distance_matrix(som_handle* h, const float* x_host, int64_t n_rows, int3
     if (int rc = h2d_blocking(h, h->qX, x_host, (size_t)n_rows * h->D * sizeof(float))) return rc;
     if (int rc = refresh_codebook_operands(h, true)) return rc;
     if (int rc = row_sq(h, h->qX, n_rows, h->qxsq)) return rc;
-    float* dm = nullptr;
-    if (int rc = dev_alloc(h, &dm, (size_t)n_rows * h->K)) return rc;
+    DevBuf<float> dm;
+    if (int rc = dm.alloc(h, (size_t)n_rows * h->K)) return rc;
     int rc = 0;
     if (mode == SOM_BMU_QUANTIZATION) rc = launch_dist_matrix<SCORE_EUCLID_SQRT>(h, n_rows, dm);
     else if (h->cfg.distance == SOM_DIST_EUCLIDEAN) rc = launch_dist_matrix<SCORE_EUCLID_PART>(h, n_rows, dm);
     else if (h->cfg.distance == SOM_DIST_EUCLIDEAN_NO_OPT) rc = launch_dist_matrix<SCORE_EUCLID_SQ>(h, n_rows, dm);
     else rc = launch_dist_matrix<SCORE_COSINE>(h, n_rows, dm);
-    if (!rc) {
-        rc = d2h_blocking(h, dist_out, dm, (size_t)n_rows * h->K * sizeof(float));
-    }
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(dm);
-    return rc;
+    if (rc) return rc;
+    return d2h_blocking(h, dist_out, dm, (size_t)n_rows * h->K * sizeof(float));
 }
 
 int som_quantization_error(som_handle* h, const float* x_host, int64_t n_rows, double* qe_out) {
@@ -2309,23 +2253,20 @@ int som_debug_mfma16(som_handle* h, const uint16_t* a_host, const uint16_t* b_ho
                      int32_t is_f16) {
     DeviceGuard dev_guard(h);
     if (!h || !a_host || !b_host || !c_host || !d_host) return fail(h, "som_debug_mfma16: NULL argument");
-    uint16_t *a = nullptr, *b = nullptr;
-    float *c = nullptr, *d = nullptr;
+    DevBuf<uint16_t> a, b;
+    DevBuf<float> c, d;
     int rc = 0;
-    if ((rc = dev_alloc(h, &a, 512)) || (rc = dev_alloc(h, &b, 512)) || (rc = dev_alloc(h, &c, 256)) || (rc = dev_alloc(h, &d, 256))) {
-        void* p[] = {a, b, c, d};
-        for (void* q : p) if (q) (void)hipFree(q);
-        return rc;
-    }
-    rc = h2d_blocking(h, a, a_host, 1024) || h2d_blocking(h, b, b_host, 1024) || h2d_blocking(h, c, c_host, 1024);
-    if (!rc) {
-        if (is_f16) debug_mfma16_kernel<F16><<<dim3(1), dim3(64), 0, h->stream>>>(a, b, c, d);
-        else debug_mfma16_kernel<Bf16><<<dim3(1), dim3(64), 0, h->stream>>>(a, b, c, d);
-        rc = d2h_blocking(h, d_host, d, 1024);
-    }
-    void* p[] = {a, b, c, d};
-    for (void* q : p) (void)hipFree(q);
-    return rc;
+    if ((rc = a.alloc(h, 512)) || (rc = b.alloc(h, 512)) || (rc = c.alloc(h, 256)) || (rc = d.alloc(h, 256))) return rc;
+    if (h2d_blocking(h, a, a_host, 1024) || h2d_blocking(h, b, b_host, 1024) || h2d_blocking(h, c, c_host, 1024)) return 1;
+    if (is_f16) debug_mfma16_kernel<F16><<<dim3(1), dim3(64), 0, h->stream>>>(a, b, c, d);
+    else debug_mfma16_kernel<Bf16><<<dim3(1), dim3(64), 0, h->stream>>>(a, b, c, d);
+    return d2h_blocking(h, d_host, d, 1024);
+}
+
+int som_debug_device_bytes(int64_t* out) {
+    if (!out) return 1;
+    *out = g_dev_bytes.load();
+    return 0;
 }
 
 // Diagnostic builds only (-DSOM_STAMPS): hand the BMU kernels a buffer for their in-kernel clock stamps (n_pairs
