@@ -212,7 +212,8 @@ int som_bmu(som_handle* h, const float* x_host, int64_t n_rows, int32_t mode, in
  * a fraction of the distance GEMM. */
 int som_bmu_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t mode, int32_t* ids_out);
 /* best and second-best unit per row under the full Euclidean distance (sqrt + nan_to_num):
- * what XPySom.topographic_error takes from argsort(distances)[:, :2], xpysom.py:727-734 */
+ * what XPySom.topographic_error takes from argsort(distances)[:, :2], xpysom.py:727-734.  Equal distances go to the lower
+ * id first.  A map of one unit has no second-best: both ids are then 0. */
 /* float64 query rows (XPySom.winner does not coerce its input, xpysom.py:379-396: float64 x against float32 weights is
  * computed in float64 by NumPy): the BMUs of fl64(-2 x.w + |w|^2_f32), euclidean activation distance only.  An analysis
  * call on the vector ALU; rows are staged through device memory as doubles. */
@@ -229,8 +230,10 @@ int som_distance_matrix(som_handle* h, const float* x_host, int64_t n_rows, int3
  * QUANTIZATION mode. */
 int som_quantization_error(som_handle* h, const float* x_host, int64_t n_rows, double* qe_out);
 /* ... of rows that already live in HBM (see som_bmu_device).  In EXACT precision with the 'euclidean' activation distance
- * the BMU search of both calls is the screen + float32 re-score (the float32 argmin of |w|^2 - 2 x.w: where the sqrt'd
- * distance ties two units this may name the other one -- at the same distance, which is all this call returns). */
+ * the BMU search of both calls starts with the screen + float32 re-score (the float32 argmin of |w|^2 - 2 x.w).  That is
+ * not always float32's argmin of the sqrt'd distance: where |x|^2 is large against the distances the radicand rounds or
+ * clamps to 0, units at DIFFERENT distances tie under the sqrt, and the lowest id wins.  Every row whose pick such a tie
+ * could overturn is searched again by the float32 SQRT kernel, so the ids -- and the value -- are F32 precision's. */
 int som_quantization_error_device(som_handle* h, const void* x_dev, int64_t n_rows, double* qe_out);
 
 /* The canary.  n_rows > 0: after every BMU launch (epochs, streamed chunks, som_bmu) n_rows strided rows are scored

@@ -24,6 +24,10 @@ int som_debug_mfma16(som_handle* h, const uint16_t* a_host, const uint16_t* b_ho
  * handle gives back all it took (tests/test_gpu_exact.py).  Returns non-zero for a NULL argument. */
 int som_debug_device_bytes(int64_t* out);
 
+/* precision EXACT, quantization_error: rows whose BMU the screen + re-score searched so far, and how many of them the
+ * tie-window test sent on to the float32 SQRT kernel (som_quantization_error*, include/somhip.h). */
+int som_debug_qe_stats(som_handle* h, int64_t* rows, int64_t* rows_sqrt);
+
 /* diagnostic builds only (-DSOM_STAMPS, tools/stamps.py builds one on demand): out_host == NULL attaches a buffer of n_pairs
  * (shader-clock ticks, 100 MHz ticks) pairs, one per workgroup of the next BMU launches (n_pairs == 0 detaches);
  * out_host != NULL reads n_pairs pairs back.  The product build refuses both. */

@@ -792,6 +792,35 @@ __global__ __launch_bounds__(256) void exact_scatter_ids_kernel(const int* __res
     if (i < n) out[list[i]] = ids[i];
 }
 
+// quantization_error in EXACT precision wants float32's pick under the sqrt'd distance s(q) = nan_to_num(sqrt(q + |x|^2)),
+// q = |w|^2 - 2 x.w.  The screen + re-score name u, float32's first argmin of q.  s cannot decrease as q grows (a float32
+// sum and sqrt are monotone; nan_to_num sends the negative radicands to 0, below every other value), so float32's pick under
+// s is the lowest id among the units with s(q_k) == s(q_u).  When the next float32 above q_u already has a larger s, no other
+// q can tie u's and u is that pick; every other row -- and one whose q_u is not finite -- goes to the list for the float32
+// SQRT kernel.  q_u is formed as the parity kernels form it: the k-ordered fmaf chain, then fma(-2, c, |w|^2)
+// (verify_best_kernel).  One thread per row.
+__global__ __launch_bounds__(256) void exact_qe_window_kernel(const float* __restrict__ X, long N, int D,
+                                                              const float* __restrict__ W, const float* __restrict__ wsq,
+                                                              const float* __restrict__ xsq, const int* __restrict__ ids,
+                                                              int* __restrict__ list, int* __restrict__ count) {
+    const long row = (long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= N) return;
+    const int u = ids[row];
+    const float* x = X + row * D;
+    const float* w = W + (long)u * D;
+    float c = 0.0f;
+    for (int k = 0; k < D; ++k) c = __builtin_fmaf(w[k], x[k], c);
+    const float q = __builtin_fmaf(-2.0f, c, wsq[u]);
+    const float xs = xsq[row];
+    bool settled = false;
+    if (__builtin_isfinite(q)) {
+        const uint32_t b = __float_as_uint(q);            // the next float32 above q (-0: the least positive one)
+        const float qn = __uint_as_float(b == 0x80000000u ? 1u : (b & 0x80000000u) ? b - 1u : b + 1u);
+        settled = nan_to_num_f32(__builtin_sqrtf(q + xs)) < nan_to_num_f32(__builtin_sqrtf(qn + xs));
+    }
+    if (!settled) list[atomicAdd(count, 1)] = (int)row;
+}
+
 // max_n v[n] (positive floats; NaN left out) into *out, which the caller zeroed.  Grid-stride: a few hundred workgroups hand in
 // one maximum per wave (a workgroup per 256 values put 16 384 atomics of a million-row set on one address: 0.1 ms for 4 MB)
 __global__ __launch_bounds__(256) void exact_max_kernel(const float* __restrict__ v, long n, float* __restrict__ out) {

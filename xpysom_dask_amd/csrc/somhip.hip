@@ -277,6 +277,10 @@ struct som_handle {
     DevBuf<double> qX64;     // som_bmu_f64: float64 query rows
     long qcap = 0;
     DevBuf<double> dsum;
+    // precision 'exact', value-only quantization BMUs (run_quantization_bmu): the rows whose screen pick a tie of the sqrt'd
+    // distance could overturn, gathered for the float32 SQRT kernel, and how many rows went each way (som_debug_qe_stats)
+    DevBuf<int> qe_list, qe_ids, qe_cnt; DevBuf<float> qe_X, qe_xsq;
+    int64_t qe_rows = 0, qe_rows_sqrt = 0;
     // streamed epochs (rows that do not stay resident): per-chunk sort scratch, grown on demand
     SegScratch st_seg;
     bool streaming = false;
@@ -316,6 +320,7 @@ struct som_handle {
     bool counting_sort = true;   // SOM_COUNTING_SORT=0: rocPRIM's sort on small maps too (A/B)
     // read once in som_create (experiments / A-B runs): forced part counts, launch-geometry printing
     int env_bf16_parts = 0;
+    int env_f32_parts = 0;   // SOM_F32_PARTS: the float32 resident kernel's part count (clamped to [1, fr_stages])
     bool debug = false;
     // per kernel function: the dynamic-LDS attribute is set and the occupancy queried once, not per launch
     struct KernelSlots { const void* fn; size_t lds; int per_cu; };
@@ -593,6 +598,7 @@ int launch_bmu_f32_res_kg(som_handle* h, const float* X, long N, const float* xs
     if (!TOP2) {
         const long slots = (long)per_cu * (h->n_cus > 0 ? h->n_cus : 256);
         parts = choose_parts(h, grid, slots, h->fr_stages);
+        if (h->env_f32_parts > 0) parts = h->env_f32_parts;   // (tests: the single-part and the merged paths at any size)
         if (parts > h->fr_stages) parts = h->fr_stages;
         if (h->debug)
             std::fprintf(stderr, "[somhip] bmu_f32_res: blocks=%ld per_cu=%d slots=%ld parts=%d stages=%d\n", grid, per_cu,
@@ -1444,6 +1450,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         if ((rc = h->np_dev.alloc(h, 1))) return bail(rc);
         if (const char* e = std::getenv("SOM_GRAPH")) h->use_graph = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_BF16_PARTS")) h->env_bf16_parts = std::atoi(e);
+        if (const char* e = dev_env("SOM_F32_PARTS")) h->env_f32_parts = std::atoi(e);
         h->debug = std::getenv("SOM_DEBUG") != nullptr;
         if (const char* e = std::getenv("SOM_VERIFY")) h->verify_rows = std::max(0, std::atoi(e));
         if (const char* e = dev_env("SOM_EXACT_PASS_ROWS")) h->ex.pass_rows_override = std::atol(e);
@@ -2063,14 +2070,41 @@ namespace {
 // of the n_rows rows in the query scratch.  f32 precision: the reference's sqrt'd distance, bit for bit.
 // bf16 / f16 precision with the 'euclidean' activation distance: the same argmin through the configured
 // MFMA path (the squared distance is monotone in it); the caller evaluates the distance itself exactly.
-// value_only (quantization_error): the caller evaluates the distance to the chosen unit itself and wants no id -- in EXACT
-// precision with the 'euclidean' activation distance the screen + re-score then serves (its pick is float32's argmin of the
-// squared distance's unit part; the sqrt'd distance can only tie where that one is within an ulp: the same distance).
+// value_only (quantization_error): in EXACT precision with the 'euclidean' activation distance the screen + re-score serve
+// first.  Their pick is float32's argmin of the squared distance's unit part, which is NOT always float32's pick under the
+// sqrt'd distance: where |x|^2 is large against the distances (un-centred data) the radicand rounds, or clamps to 0, so that
+// units at different distances tie under the sqrt and the lowest id wins.  exact_qe_window_kernel keeps the rows whose pick
+// no such tie can overturn; the others go through the float32 SQRT kernel, so the ids are float32's bit for bit.
 int run_quantization_bmu(som_handle* h, const float* X, long n_rows, bool value_only = false) {
     if (h->cfg.precision != SOM_PREC_F32 && h->cfg.distance == SOM_DIST_EUCLIDEAN && (!h->exact || value_only)) {
         if (h->exact) if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
         if (int rc = prep_rows_bf16(h, X, n_rows, round_up(n_rows, ROW_PAD), h->qXb, h->xmax2 + 1, h->qxsq)) return rc;
-        return run_activation_bmu(h, X, n_rows, h->qxsq, h->qXb, h->xmax2 + 1, h->qbmu);
+        if (int rc = run_activation_bmu(h, X, n_rows, h->qxsq, h->qXb, h->xmax2 + 1, h->qbmu)) return rc;
+        if (!h->exact) return 0;
+        if (int rc = h->qe_list.reserve(h, (size_t)n_rows, 1024)) return rc;
+        if (int rc = h->qe_cnt.reserve(h, 1, 1)) return rc;
+        if (int rc = refresh_codebook_operands(h, true)) return rc;       // (|w|^2; the float32 image in the units' order)
+        HIPCHK(h, hipMemsetAsync(h->qe_cnt, 0, sizeof(int), h->stream));
+        exact_qe_window_kernel<<<dim3((unsigned)cdiv(n_rows, 256)), dim3(256), 0, h->stream>>>(
+            X, n_rows, h->D, h->W, h->wsq, h->qxsq, h->qbmu, h->qe_list, h->qe_cnt);
+        HIPCHK(h, hipGetLastError());
+        int n_sq = 0;
+        if (int rc = d2h_blocking(h, &n_sq, h->qe_cnt, sizeof(int))) return rc;
+        if (n_sq < 0 || n_sq > n_rows) return fail(h, "quantization: tie-window counter out of range");
+        h->qe_rows += n_rows; h->qe_rows_sqrt += n_sq;
+        if (n_sq == 0) return 0;
+        if (int rc = h->qe_X.reserve(h, (size_t)n_sq * h->D, (size_t)1024 * h->D)) return rc;
+        if (int rc = h->qe_xsq.reserve(h, (size_t)n_sq, 1024)) return rc;
+        if (int rc = h->qe_ids.reserve(h, (size_t)n_sq, 1024)) return rc;
+        exact_gather_rows_kernel<<<dim3((unsigned)cdiv((long)n_sq * h->D, 256)), dim3(256), 0, h->stream>>>(X, h->qe_list, n_sq, h->D, h->qe_X);
+        row_sq_f32_kernel<<<dim3((unsigned)cdiv(n_sq, 256)), dim3(256), 0, h->stream>>>(h->qe_X, n_sq, h->D, h->qe_xsq);
+        {
+            Timed t(h, SOM_K_BMU);
+            if (int rc = launch_bmu_f32_any<SCORE_EUCLID_SQRT>(h, h->qe_X, n_sq, h->qe_xsq, h->qe_ids)) return rc;
+        }
+        exact_scatter_ids_kernel<<<dim3((unsigned)cdiv(n_sq, 256)), dim3(256), 0, h->stream>>>(h->qe_ids, h->qe_list, n_sq, h->qbmu);
+        HIPCHK(h, hipGetLastError());
+        return 0;
     }
     if (int rc = refresh_codebook_operands(h, true)) return rc;
     if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
@@ -2163,6 +2197,10 @@ int som_bmu_top2(som_handle* h, const float* x_host, int64_t n_rows, int32_t* id
         if (int rc = launch_bmu_top2(h, h->qX, n_rows, h->qxsq, h->qbmu, h->qbmu2)) return rc;
     }
     if (int rc = d2h_blocking(h, ids1_out, h->qbmu, (size_t)n_rows * sizeof(int))) return rc;
+    if (h->K == 1) {                                     // (one unit: it is named twice -- include/somhip.h)
+        std::memcpy(ids2_out, ids1_out, (size_t)n_rows * sizeof(int));
+        return 0;
+    }
     return d2h_blocking(h, ids2_out, h->qbmu2, (size_t)n_rows * sizeof(int));
 }
 
@@ -2266,6 +2304,13 @@ int som_debug_mfma16(som_handle* h, const uint16_t* a_host, const uint16_t* b_ho
 int som_debug_device_bytes(int64_t* out) {
     if (!out) return 1;
     *out = g_dev_bytes.load();
+    return 0;
+}
+
+int som_debug_qe_stats(som_handle* h, int64_t* rows, int64_t* rows_sqrt) {
+    if (!h || !rows || !rows_sqrt) return fail(h, "som_debug_qe_stats: NULL argument");
+    *rows = h->qe_rows;
+    *rows_sqrt = h->qe_rows_sqrt;
     return 0;
 }
 

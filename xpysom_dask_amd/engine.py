@@ -309,6 +309,13 @@ class HipEngine:
         self._check(self._lib.som_exact_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def qe_stats(self):
+        """precision 'exact': (rows quantization_error searched with the screen, rows of them sent to the float32 SQRT
+        kernel) so far."""
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self._lib.som_debug_qe_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def exact_skip_stats(self):
         """precision 'exact': (blocks the screens ran, blocks of full scans) so far -- block skipping's executed share."""
         a, b = C.c_int64(), C.c_int64()

@@ -473,6 +473,10 @@ class XPySom:
             warn('The topographic error is not defined for a 1-by-1 map.')
             return np.nan
         data = _host_rows(data, self._engine)
+        if self._weights.shape[0] * self._weights.shape[1] == 1 and len(data):
+            # one unit, input_len > 1: argsort(...)[:, :2] holds one column and its diff none -- the reference's mean over
+            # an empty axis is NaN (rectangular), its norm over one is 0 (hexagonal: 0 > 1.5 never)
+            return float('nan') if self.topology == 'rectangular' else 0.0
         eng = self._upload_weights()
         Y = self._weights.shape[1]
         bad, n = 0, 0
