@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("script,cases", [("fuzz_shapes.py", 250), ("fuzz_paths.py", 150), ("fuzz_train.py", 150), ("fuzz_infer.py", 150),
-                                          ("fuzz_exact.py", 300), ("fuzz_update.py", 80), ("fuzz_query.py", 150)])
+                                          ("fuzz_exact.py", 300), ("fuzz_update.py", 80), ("fuzz_query.py", 150), ("fuzz_half.py", 60)])
 def test_fuzz(script, cases):
     r = subprocess.run([sys.executable, os.path.join("tests", "fuzz", script), "12345", str(cases)], cwd=REPO,
                        capture_output=True, text=True, timeout=600)

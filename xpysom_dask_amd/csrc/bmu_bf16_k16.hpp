@@ -331,9 +331,11 @@ __device__ __forceinline__ void bmu_bf16_k16_body(const __bf16* __restrict__ Xb,
             const unsigned long long mask = __ballot(keep);
             if (lane == 0) gflags[ex_flag_index(wave_s0 >> 6, stage, n_stages, gm_stride)] = mask;
         }
+        // a later stage wins on smaller VALUE bits only: on equal values the key's index bits (tile << 2 | register) say
+        // nothing across stages, and the earlier stage holds the lower unit (c < (g & ~M)  <=>  (c & ~M) < (g & ~M))
 #pragma unroll
         for (int sb = 0; sb < K16_SB; ++sb) {
-            if (!GM && cbest[sb] < gbest[sb]) { gbest[sb] = cbest[sb]; gstage[sb] = stage; }   // (GM: run_min is the row minimum)
+            if (!GM && cbest[sb] < (gbest[sb] & ~IDX_MASK)) { gbest[sb] = cbest[sb]; gstage[sb] = stage; }   // (GM: run_min is the row minimum)
             cbest[sb] = 0xFFFFFFFFu;
         }
     };

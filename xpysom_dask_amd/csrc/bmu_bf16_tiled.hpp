@@ -229,7 +229,7 @@ __global__ __launch_bounds__(64 * NWR * NWC, 2) void bmu_bf16_tiled_kernel(const
                 c1 = min(min(c1, k2), k3);
             }
             const uint32_t c = min(c0, c1);
-            if (c < gbest[sb]) { gbest[sb] = c; gblock[sb] = ub; }
+            if (c < (gbest[sb] & ~IDX_MASK)) { gbest[sb] = c; gblock[sb] = ub; }   // (value bits only: see bmu_bf16_k16.hpp, fold_stage)
         }
     };
 

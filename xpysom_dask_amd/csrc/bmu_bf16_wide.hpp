@@ -409,7 +409,7 @@ __device__ __forceinline__ void bmu_bf16_wide_body(const char* __restrict__ Ximg
             c1 = min(min(c1, k2), k3);
         }
         const uint32_t c = min(c0, c1);
-        if (c < gbest[sb]) { gbest[sb] = c; gstage[sb] = s; }
+        if (c < (gbest[sb] & ~IDX_MASK)) { gbest[sb] = c; gstage[sb] = s; }     // (value bits only: see bmu_bf16_k16.hpp, fold_stage)
     }
     }
     };
