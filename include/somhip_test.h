@@ -45,6 +45,27 @@ int som_debug_stamps(som_handle* h, int64_t n_pairs, uint64_t* out_host);
  *   *out = 0 / 1; returns non-zero for an unknown `which` or a NULL argument. */
 int som_policy_eval(int32_t which, const double* costs, const double* args, int32_t* out);
 
+/* The policy's STATE MACHINE (csrc/exact_policy.hpp, policy::PlanState) on a caller-supplied script of launches -- pure host
+ * arithmetic, NO device needed.  A fresh PlanState is driven as launch_bmu_exact drives it: begin; the row sample and the
+ * sample tiles where the plan asks for them; end (tests/test_policy_cpu.py).
+ *   script[n_launches][SOM_POLICY_REPLAY_IN], per launch:
+ *     the facts    [0] resident  [1] last BMUs valid  [2] row set (an id)  [3] rows  [4] can_skip  [5] scout_ok  [6] wide
+ *                  [7] wide_can  [8] wide_scout_ok  [9] level 2's list fits in LDS  [10] the lo image exists  [11] blocks_per_row
+ *                  [12] skip_mode  [13] refine_on  [14] sub_blocks  [15] res_every
+ *     the samples  [16] the row sample's f   [17] the sample tiles' share after both levels (< 0: the pass is too short for
+ *                  sample tiles)   [18] ... after level 1
+ *     the outcome  [19..22] ms: launch, screen, level 2, sort + gather (each phase counts as timed where the plan times it)
+ *                  [23] blocks run  [24] blocks in all  [25] (tile, group) pairs level 1 kept  [26] pairs selected
+ *                  [27] pairs the refinement kept  [28] rows the scout won   (without a plan every block runs, whatever [23] says)
+ *   out[n_launches][SOM_POLICY_REPLAY_OUT], per launch:
+ *     the plan as it ran  [0] skip  [1] resort  [2] scout  [3] level 2  [4] estimate  [5] sample_tiles  [6] refine  [7] time_phases
+ *     [8] the row sample was asked  [9] the sample tiles were asked  [10] the row sample declined  [11] the sample tiles declined
+ *     the pauses after the launch  [12..14] resident: cooldown, idle, pause  [15..17] transient
+ *   returns non-zero for a NULL argument or a negative count. */
+#define SOM_POLICY_REPLAY_IN 29
+#define SOM_POLICY_REPLAY_OUT 18
+int som_policy_replay(int32_t n_launches, const double* script, double* out);
+
 #ifdef __cplusplus
 }
 #endif

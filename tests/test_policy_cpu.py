@@ -71,3 +71,185 @@ def test_unknown_decision_is_refused():
     ca, aa = (C.c_double * 9)(), (C.c_double * 4)()
     assert lib.som_policy_eval(99, ca, aa, C.byref(out)) != 0
     assert lib.som_policy_eval(0, None, aa, C.byref(out)) != 0
+
+
+# ---- the plan's STATE from launch to launch (policy::PlanState) through som_policy_replay --------------------------------------------
+# The expected sequences below are written out from the rules the library documents (csrc/exact_policy.hpp), launch by launch.
+N_ROWS = 2 ** 20
+OUT = ("skip", "resort", "scout", "level2", "estimate", "sample_tiles", "refine", "time_phases", "asked_rows", "asked_tiles",
+       "rows_declined", "tiles_declined")
+
+
+def L(**kw):
+    """One launch of a script: facts, sample answers, outcome.  Default: resident rows with last BMUs on a 256 x 256 map, default
+    mode, no scout; a plan that runs a tenth of the blocks (level 1 alone: a fifth) in 1 ms."""
+    d = dict(resident=1, have_last=1, rows=1, n=N_ROWS, can_skip=1, scout_ok=0, wide=0, wide_can=0, wide_scout_ok=0, l2_fits=1, lo=1,
+             bpr=BPR, mode=1, refine_on=1, sub_blocks=1, res_every=0, f=0.5, est=-1.0, est1=0.0,
+             t_total=1.0, t_screen=0.5, t_l2=0.05, t_sort=0.1, share=0.1, l1_share=0.2, pairs_row=1.0, pairs_out_row=1.0, win_share=0.0)
+    assert set(kw) <= set(d), set(kw) - set(d)
+    d.update(kw)
+    return d
+
+
+def replay(script):
+    lib = _lib.load()
+    flat = []
+    for d in script:
+        total = d["n"] * d["bpr"]                            # 16-unit blocks of the launch
+        flat += [d["resident"], d["have_last"], d["rows"], d["n"], d["can_skip"], d["scout_ok"], d["wide"], d["wide_can"], d["wide_scout_ok"],
+                 d["l2_fits"], d["lo"], d["bpr"], d["mode"], d["refine_on"], d["sub_blocks"], d["res_every"], d["f"], d["est"], d["est1"],
+                 d["t_total"], d["t_screen"], d["t_l2"], d["t_sort"], round(d["share"] * total), total, round(d["l1_share"] * total / 4),
+                 round(d["pairs_row"] * d["n"]), round(d["pairs_out_row"] * d["n"]), round(d["win_share"] * d["n"])]
+    n_in, n_out = 29, 18
+    assert len(flat) == n_in * len(script)
+    out = (C.c_double * (n_out * len(script)))()
+    assert lib.som_policy_replay(len(script), (C.c_double * len(flat))(*flat), out) == 0
+    res = []
+    for i in range(len(script)):
+        o = [int(v) for v in out[n_out * i:n_out * (i + 1)]]
+        r = dict(zip(OUT, o[:12]))
+        r["res_pause"], r["tr_pause"] = tuple(o[12:15]), tuple(o[15:18])   # (cooldown, idle, pause)
+        res.append(r)
+    return res
+
+
+def col(res, key):
+    return [r[key] for r in res]
+
+
+IDLE = dict(share=1.0, l1_share=1.0)         # a plan that kept every block: idle
+SCOUTED = dict(have_last=0, scout_ok=1)      # rows without last BMUs: the scout plans, the samples are asked first
+
+
+def test_pause_ladder_doubles_up_to_sixteen():
+    # plan, plan, 2 without, plan, 4 without, plan, 8 without, plan, 16 without, plan, 16 without
+    want = [1, 1] + [0] * 2 + [1] + [0] * 4 + [1] + [0] * 8 + [1] + [0] * 16 + [1] + [0] * 16 + [1]
+    res = replay([L(**IDLE) for _ in want])
+    assert col(res, "skip") == want
+    assert res[1]["res_pause"] == (2, 2, 4) and res[4]["res_pause"] == (4, 3, 8) and res[-1]["res_pause"] == (16, 7, 16)
+    assert all(r["tr_pause"] == (0, 0, 2) for r in res)
+
+
+def test_a_paying_plan_resets_the_ladder():
+    script = [L(**IDLE), L(**IDLE), L(**IDLE), L(**IDLE), L(share=0.1), L(**IDLE), L(**IDLE), L(**IDLE), L(**IDLE), L(**IDLE)]
+    res = replay(script)
+    assert col(res, "skip") == [1, 1, 0, 0, 1, 1, 1, 0, 0, 1]      # ... "two idle plans, then 2" again, not 4
+    assert res[4]["res_pause"] == (0, 0, 2) and res[6]["res_pause"] == (2, 2, 4)
+
+
+def test_a_plan_the_sample_tiles_decline_counts_as_idle():
+    # (a lower f each time: at 0.9 of the declined f or more the row sample would answer for the tiles)
+    script = [L(f=0.5, est=1.0, est1=1.0, **SCOUTED), L(f=0.4, est=1.0, est1=1.0, **SCOUTED), L(**SCOUTED), L(**SCOUTED),
+              L(f=0.3, est=1.0, est1=1.0, **SCOUTED)]
+    res = replay(script)
+    assert col(res, "skip") == [0, 0, 0, 0, 0]
+    assert col(res, "asked_tiles") == [1, 1, 0, 0, 1] and col(res, "tiles_declined") == [1, 1, 0, 0, 1]
+    assert col(res, "asked_rows") == [1, 1, 0, 0, 1]               # (a paused launch asks nothing)
+    assert [r["res_pause"] for r in res] == [(0, 1, 2), (2, 2, 4), (1, 2, 4), (0, 2, 4), (4, 3, 8)]
+
+
+def test_resident_and_transient_ladders_do_not_touch():
+    R, T = L(**IDLE), L(resident=0, rows=7, n=65536, f=0.5, **dict(IDLE, **SCOUTED))
+    res = replay([R, T, R, T, T, R, R, T])
+    assert col(res, "skip") == [1, 1, 1, 1, 0, 0, 0, 0]
+    assert [r["res_pause"] for r in res] == [(0, 1, 2), (0, 1, 2), (2, 2, 4), (2, 2, 4), (2, 2, 4), (1, 2, 4), (0, 2, 4), (0, 2, 4)]
+    assert [r["tr_pause"] for r in res] == [(0, 0, 2), (0, 1, 2), (0, 1, 2), (2, 2, 4), (1, 2, 4), (1, 2, 4), (1, 2, 4), (0, 2, 4)]
+
+
+@pytest.mark.parametrize("mode", [2, 3])
+def test_forced_modes_never_pause(mode):
+    res = replay([L(mode=mode, **IDLE) for _ in range(8)])
+    assert col(res, "skip") == [1] * 8 and all(r["res_pause"] == (0, 0, 2) for r in res)
+
+
+def sorts(res):
+    return [i + 1 for i, r in enumerate(res) if r["resort"]]     # launches, counted from 1
+
+
+def test_fresh_rows_sort():
+    res = replay([L(), L(), L(rows=2), L(rows=2), L(rows=2, n=N_ROWS // 2), L(rows=2, n=N_ROWS // 2),
+                  L(rows=2, n=N_ROWS // 2, est=-1.0, **SCOUTED), L(rows=2, n=N_ROWS // 2)])
+    assert col(res, "resort") == [1, 0, 1, 0, 1, 0, 1, 0]          # never sorted; new X; new N; no last BMUs
+
+
+def test_resort_while_a_quarter_of_the_blocks_run_then_every_eighth_epoch():
+    res = replay([L(share=0.3, l1_share=0.4), L(share=0.25, l1_share=0.4), L(share=0.1)] + [L() for _ in range(10)])
+    assert sorts(res) == [1, 2, 3, 11]                             # last share >= 0.25: sort; then 8 planned epochs after the last one
+
+
+def test_an_unpaid_sort_doubles_the_interval_up_to_64_and_a_paid_one_resets_it():
+    res = replay([L() for _ in range(190)])                        # the same share before and after every sort: none pays
+    assert sorts(res) == [1, 9, 25, 57, 121, 185]                  # 8, 16, 32, 64, 64
+    script = [L() for _ in range(60)]
+    script[24] = L(share=0.02, l1_share=0.04)                      # the sort at launch 25 (interval 16 by then) takes 0.1 -> 0.02: paid
+    for i in range(25, 60):
+        script[i] = L(share=0.02, l1_share=0.04)
+    assert sorts(replay(script)) == [1, 9, 25, 33, 49]             # ... back to 8; the next one is unpaid again: 16
+
+
+def test_a_sort_is_judged_only_between_like_epochs():
+    script = [L() for _ in range(34)]
+    script[8] = L(sub_blocks=0)                                    # the sort at launch 9 runs without level 2, the epoch before ran with it
+    assert sorts(replay(script)) == [1, 9, 17, 33]                 # not judged: still 8; launch 17's is (unpaid): 16
+    # last share >= 0.25: sorted in any case, never judged
+    res = replay([L(share=0.3, l1_share=0.4) for _ in range(12)] + [L() for _ in range(10)])
+    assert sorts(res) == list(range(1, 14)) + [21]
+
+
+def test_res_every_overrides_the_schedule():
+    res = replay([L(res_every=3, share=0.3, l1_share=0.4) for _ in range(10)])
+    assert sorts(res) == [1, 4, 7, 10]
+
+
+NO_PAY = dict(share=0.19, l1_share=0.2)      # level 2 drops a twentieth of level 1's blocks at an eighth of a block's time per group: no
+
+
+def test_level_two_is_on_until_measured_then_probed_after_four_epochs_without():
+    res = replay([L(**NO_PAY) for _ in range(12)])
+    assert col(res, "level2") == [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0]
+    assert col(replay([L() for _ in range(6)]), "level2") == [1] * 6          # where it pays it stays
+
+
+def test_level_two_is_probed_at_once_when_level_ones_share_moves_by_half():
+    assert col(replay([L(**NO_PAY), L(share=0.3, l1_share=0.31), L(share=0.3, l1_share=0.31)]), "level2") == [1, 0, 1]
+    assert col(replay([L(**NO_PAY), L(share=0.12, l1_share=0.13), L(share=0.12, l1_share=0.13)]), "level2") == [1, 0, 1]
+    assert col(replay([L(**NO_PAY), L(share=0.28, l1_share=0.29), L(share=0.28, l1_share=0.29)]), "level2") == [1, 0, 0]
+
+
+def test_level_two_is_not_probed_while_level_one_keeps_nearly_everything():
+    res = replay([L(share=0.94, l1_share=0.95, t_total=0.6) for _ in range(12)])
+    assert col(res, "skip") == [1] * 12 and col(res, "level2") == [1] + [0] * 11
+
+
+def test_a_fresh_resident_row_set_starts_level_two_over():
+    assert col(replay([L(**NO_PAY), L(**NO_PAY), L(rows=2, **NO_PAY), L(rows=2, **NO_PAY)]), "level2") == [1, 0, 1, 0]
+
+
+def test_row_sample_declines_above_nine_tenths():
+    res = replay([L(f=0.91, **SCOUTED), L(f=0.9, **SCOUTED)])
+    assert col(res, "asked_rows") == [1, 1] and col(res, "rows_declined") == [1, 0] and col(res, "skip") == [0, 1]
+    assert col(res, "asked_tiles") == [0, 0]                       # (est < 0: passes too short for sample tiles)
+    assert res[0]["res_pause"] == (0, 0, 2)                        # nearly free: not an idle plan
+
+
+def test_row_sample_remembers_a_tile_decline_for_eight_launches():
+    script = [L(f=0.5, est=1.0, est1=1.0, **SCOUTED)] + [L(f=0.46, est=1.0, est1=1.0, **SCOUTED) for _ in range(9)]
+    res = replay(script)
+    assert col(res, "asked_tiles") == [1] + [0] * 8 + [1]
+    assert col(res, "rows_declined") == [0] + [1] * 8 + [0]
+    assert [r["res_pause"] for r in res[:9]] == [(0, 1, 2)] * 9    # the remembered answers are not idle plans
+    # below 0.9 of the declined f the tiles are asked again at once
+    res = replay([L(f=0.5, est=1.0, est1=1.0, **SCOUTED), L(f=0.44, est=0.1, est1=0.2, **SCOUTED)])
+    assert col(res, "asked_tiles") == [1, 1] and col(res, "skip") == [0, 1]
+
+
+def test_refinement_from_three_pairs_a_row():
+    res = replay([L(pairs_row=3.0), L(pairs_row=2.99), L(pairs_row=5.0), L(pairs_row=5.0, lo=0), L(refine_on=0)])
+    assert col(res, "refine") == [0, 1, 0, 0, 0]
+    assert col(replay([L(mode=2, pairs_row=0.0), L(mode=3, pairs_row=0.0)]), "refine") == [1, 1]
+
+
+def test_replay_refuses_null_arguments():
+    lib = _lib.load()
+    assert lib.som_policy_replay(1, None, (C.c_double * 18)()) != 0
+    assert lib.som_policy_replay(-1, (C.c_double * 29)(), (C.c_double * 18)()) != 0

@@ -66,13 +66,26 @@ constexpr int EX_SCAN_SPLIT = 4;      // waves that share a row's groups in the 
 constexpr int EX_WERR_UNITS = 16;     // units per wave in exact_werr_kernel
 constexpr int EX_TR = 128;            // rows per re-score tile (4 waves x 32 rows against one 64-unit group)
 
-// Small per-pass counters, one allocation, zeroed by one memset before the scan:
-//   [0, n_groups)             gcount: (row, group) pairs per group = fill cursor of the group's row list
-//   [n_groups, 2 n_groups)    gstart: the lists' lengths after round 1 (two-round scheme)
-//   [2 n_groups]              fb_count: rows for the float32 fallback kernel
-//   [2 n_groups + 1]          n_tiles:  re-score tiles
-//   [2 n_groups + 2]          overflow: the pass has more pairs than the lists hold (a degenerate codebook: identical
-//                             units everywhere) -- every row goes to the float32 kernel
+// Small per-pass counters, one allocation [n_groups gcount][n_groups gstart][PassCounters], zeroed by one memset before the scan:
+//   gcount: (row, group) pairs per group = fill cursor of the group's row list
+//   gstart: the lists' lengths after round 1 (two-round scheme)
+// ... and the tail below.  A kernel receives a pointer to each slot it writes; the host reads the tail back once per pass.
+struct PassCounters {
+    int fallback;     // exact_finalize_kernel: rows for the float32 fallback kernel
+    int n_tiles;      // exact_tiles_kernel: re-score tiles
+    int overflow;     // exact_tiles_kernel: the pass has more pairs than the lists hold (a degenerate codebook: identical units
+                      // everywhere) -- every row goes to the float32 kernel
+    int blocks_run;   // exact_list_totals_kernel: 16-unit blocks on the plan's lists
+    int groups_run;   // exact_list_totals_kernel: (tile, group) pairs level 1 of the plan kept
+    int pairs_in;     // exact_tiles_kernel: candidate (row, group) pairs the select kernel found
+    int pairs_out;    // exact_select2_kernel: ... the refinement pass kept
+    int scout_wins;   // exact_plan_kernel: rows whose scout pick beat their last BMU by a tenth of the squared distance
+};
+// The row-need estimate (exact_scout_rowneed_kernel, exact_skip.hpp) runs before a launch's first pass and borrows the head of the block.
+struct RowNeed {
+    int need;         // groups the sampled rows need, summed
+    int rows;         // rows sampled
+};
 
 // (gmin [n_groups][gm_stride], gflags [gm_stride / 64][n_groups]) -> the groups' row lists plist [n_groups][gm_stride] (every
 // group owns room for a whole pass: nothing to size, nothing to prefix-sum), gcount [n_groups] and the rows' candidate

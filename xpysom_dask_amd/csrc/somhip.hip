@@ -122,12 +122,12 @@ struct som_handle {
         bool seed_live = false;              // this pass's screen reads the seed
         int two_round = -1;                  // SOM_EXACT_TWO_ROUND=0|1 forces the one- / two-round re-score (default: two rounds beyond 128 features)
         DevBuf<int> fb_list, fb_ids;
-        DevBuf<int> ctr;                     // gcount | gstart of round 2 | fb_count | n_tiles | overflow (zeroed per pass)
+        DevBuf<int> ctr;                     // [n_groups gcount][n_groups gstart of round 2][PassCounters] (bmu_exact.hpp; zeroed per pass; PassCtr names the parts)
         DevBuf<int> plist;                   // [n_groups][stride] rows bucketed by candidate group
         DevBuf<int4> tile_tab;               // re-score tiles: (group, first list entry, rows)
         long max_tiles = 0;
         DevBuf<float> fbX;                   // fallback rows, dense, for the float32 kernel
-        int* fb_count_host = nullptr;        // pinned
+        PassCounters* pass_host = nullptr;   // pinned: the pass's counter tail, read back once per pass
         hipEvent_t fb_ready = nullptr;       // recorded behind the counter's copy
         int64_t rows_total = 0, rows_fallback = 0, chunks = 0;   // som_exact_stats
         int64_t blocks_run = 0, blocks_total = 0;                // som_exact_skip_stats: (256-row tile, 16-unit block) blocks of the screens
@@ -137,14 +137,14 @@ struct som_handle {
         long pairs = 64;                  // capacity of a pass: (row, group) pairs per row on average (exact_reserve)
         // block skipping (exact_skip.hpp): resident rows from their second epoch on, input_len <= 128
         int skip_mode = 1;                // SOM_EXACT_SKIP: 0 off, 1 on for maps of >= 4096 units (default), 2 on for every map of >= 2 groups (tests), 3: plan, keep everything
-        bool skip_live = false;           // this launch plans and skips
-        int skip_cooldown = 0;            // launches to run without a plan (the last two plans kept > 97 % of the blocks)
-        int skip_idle = 0;                // plans in a row that kept > 97 % of the blocks
-        int skip_pause = 2;               // launches the next pause lasts (doubles while the plans stay idle)
+        // what a launch decides -- plan at all, re-sort, scout, level 2, refine -- and the state those decisions move from
+        // launch to launch (pause ladder, re-sort schedule, level-2 probe, measured costs): exact_policy.hpp
+        policy::PlanState plan;
+        policy::LaunchPlan lp;            // ... of the launch in flight (launch_bmu_exact)
         bool sub_blocks = true;           // SOM_EXACT_SUBBLOCKS=0: the plan stops at the groups (A/B)
         // the SORTED PASS: rows in the order of their (pseudo) last BMU's patch (position -> row: `order`), with sorted copies of
         // the half image, its second half, the float32 rows and the norms.  srt[0]: the RESIDENT rows (all passes; valid for
-        // (res_rows, res_n), re-sorted when the order has gone stale -- res_* below --, not every epoch); srt[1]: ONE pass of
+        // one row set, re-sorted when the order has gone stale -- policy::PlanState --, not every epoch); srt[1]: ONE pass of
         // a TRANSIENT row set (query rows, streamed chunks: sorted by the scout of exact_skip.hpp, used once).
         struct SortedRows {
             long cap = 0;                 // positions the buffers hold (each pass padded to the tile)
@@ -157,49 +157,24 @@ struct som_handle {
         } srt[2];
         bool cen_ready = false;           // both centroid levels are allocated
         long sk_stride = 0;               // rows per pass the per-pass plan buffers hold
-        const void* res_rows = nullptr; long res_n = -1;
-        bool res_valid = false;
         int res_every = 0;                // SOM_EXACT_RESORT=n: re-sort every n-th planned epoch (0: when the order has gone stale)
-        int res_since = 0;                // planned epochs since the last sort
-        double res_share_sort = 1.0;      // executed share of the first epoch after the last sort
-        bool res_l2_sort = false, res_l2_last = false;   // ... whether level 2 ran in that epoch / in the last one (shares compare like with like)
-        int res_forced = 8;               // planned epochs after which the rows are sorted in any case (doubles after a forced sort that did not pay)
-        double res_share_last = 1.0;      // ... of the last planned epoch
-        int64_t resorts = 0, planned = 0; // som_exact_resident_stats
         DevBuf<int> sk_keys, sk_keys2, sk_vals;
         DevBuf<int> sk_tmp;               // radix_sort_rows' scratch
         bool refine_on = true;            // SOM_EXACT_REFINE=0: no refinement pass (A/B)
-        bool refine_live = false;
-        double pairs_per_row_last = 0.0;  // candidate (row, group) pairs per row of the last planned epoch
-        int64_t pairs_refined_in = 0, pairs_refined_out = 0;   // som_exact_refine_stats
         // the SCOUT (exact_skip.hpp): pseudo last BMUs for rows that have none, or whose last BMUs say little
         int grid_mult = 2;                // persistent re-score / refinement kernels: workgroups per resident slot (SOM_EXACT_GRID_MULT: A/B)
         bool scout_on = true;             // SOM_EXACT_SCOUT=0: plans only from last epoch's BMUs (A/B)
-        bool scout_live = false;          // this launch runs the scout
         DevBuf<int> scout_g;              // [stride] nearest group centroid of every row of the pass
         DevBuf<float> tq;                 // [stride] wide plan: the float32 score of every sorted row's last BMU under the current codebook
-        double scout_est_last = 0.0;      // executed share the sample tiles forecast at the last estimate
-        double scout_f_now = 0.0, scout_f_declined = 0.0; int scout_f_age = 0;   // the sampled rows' need now / when the sample tiles last declined a plan
-        double scout_win_share = 0.0;     // rows of the last launch whose scout pick beat their last BMU by a tenth of the squared distance
-        int64_t scout_declined = 0;       // launches whose estimate said: nothing to skip, no plan
-        int64_t scouted = 0, tr_planned = 0;   // som_exact_scout_stats: launches that ran the scout; transient launches under a plan
-        double tr_share_last = 1.0;       // executed share of the last transient launch under a plan
-        double share_forecast = 1.0;      // ... of the launch about to run (the screen sizes its codebook parts by it)
-        int tr_idle = 0, tr_cooldown = 0, tr_pause = 2;   // transient launches: idle plans pause the plan as for the resident rows
-        // level 2 of the plan runs where it pays (l2_pays: measured whenever it runs), is probed again after l2_wait epochs or
-        // when level 1's share has moved by half since the last probe
-        double l1_share_last = 1.0, l1_share_probe = -1.0;
-        bool l2_live = false, l2_pays = true;
-        int l2_wait = 0;
+        double share_forecast = 1.0;      // executed share expected of the launch about to run (the screen sizes its codebook parts by it)
         // MEASURED COSTS (hipEvents on the handle's stream; per ROW, in ms, so that launches of different sizes compare): what the
         // policy decides from -- is a plan worth its launches, does level 2 pay, did a sort pay, is the plan idle.  The launch as
         // a whole is timed every time (two records); its phases under a plan -- screen, level 2, sort + gather -- in the first
         // planned launches, in every launch that sorts, and every fourth one after that (a record costs a few microseconds of
         // stream bubble: eight of them a launch would be 2 % of a 1.8 ms epoch).
-        struct Cost : policy::Costs {     // (the numbers themselves and what is decided from them: exact_policy.hpp)
+        struct Cost {                     // (the numbers themselves and what is decided from them: policy::Costs, exact_policy.hpp)
             hipEvent_t ev[8] = {};            // [0] launch / pass start, [1, 2] screen, [3, 4] level 2, [5, 6] sort + gather, [7] pass end
             bool have = false;
-            int since = 99;                   // planned launches since the phases were last timed
         } cost;
         // the centroid sets of the plan: [0] the 64-unit groups, [1] their 16-unit sub-blocks (exact_centroid_kernel's slot order)
         struct Centroids { DevBuf<float> Cc, rg, csq, cmax2; DevBuf<char> Cst;
@@ -422,6 +397,9 @@ int kernel_per_cu(som_handle* h, const void* fn, int threads, size_t lds, int* p
     return 0;
 }
 
+// resident workgroup slots of a kernel on the chip (per_cu: kernel_per_cu's answer)
+inline long resident_slots(const som_handle* h, int per_cu) { return (long)per_cu * (h->n_cus > 0 ? h->n_cus : 256); }
+
 inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 inline long round_up(long a, long b) { return cdiv(a, b) * b; }
 constexpr float HALF_MAX = 65504.0f;   // largest finite _Float16
@@ -462,6 +440,19 @@ int resolve_profile(som_handle* h) {
 // The half-precision paths are templates on the operand type's tag E (Bf16 or F16, som_common.hpp); SOM_HALF picks
 // the instance from the handle.
 #define SOM_HALF(h, fn, ...) ((h)->f16 ? fn<F16>(__VA_ARGS__) : fn<Bf16>(__VA_ARGS__))
+// ... and these the instance fn<KS32, E> for the handle's feature count: ks32 32-feature steps up to 128 features, n_kchunks
+// 64-feature chunks beyond (the wide kernel).  They return from the calling function; a count without an instance falls through.
+#define SOM_KS32_DISPATCH(fn, ...) \
+    switch (h->ks32) { \
+    case 1: return fn<1, E>(__VA_ARGS__); case 2: return fn<2, E>(__VA_ARGS__); case 3: return fn<3, E>(__VA_ARGS__); case 4: return fn<4, E>(__VA_ARGS__); }
+#define SOM_WIDE_DISPATCH(fn, ...) \
+    switch (h->n_kchunks) { \
+    case 5: return fn<5, E>(__VA_ARGS__); case 6: return fn<6, E>(__VA_ARGS__); case 7: return fn<7, E>(__VA_ARGS__); case 8: return fn<8, E>(__VA_ARGS__); \
+    case 9: return fn<9, E>(__VA_ARGS__); case 10: return fn<10, E>(__VA_ARGS__); case 11: return fn<11, E>(__VA_ARGS__); case 12: return fn<12, E>(__VA_ARGS__); \
+    case 13: return fn<13, E>(__VA_ARGS__); case 14: return fn<14, E>(__VA_ARGS__); case 15: return fn<15, E>(__VA_ARGS__); case 16: return fn<16, E>(__VA_ARGS__); \
+    case 17: return fn<17, E>(__VA_ARGS__); case 18: return fn<18, E>(__VA_ARGS__); case 19: return fn<19, E>(__VA_ARGS__); case 20: return fn<20, E>(__VA_ARGS__); \
+    case 21: return fn<21, E>(__VA_ARGS__); case 22: return fn<22, E>(__VA_ARGS__); case 23: return fn<23, E>(__VA_ARGS__); case 24: return fn<24, E>(__VA_ARGS__); \
+    case 25: return fn<25, E>(__VA_ARGS__); }
 
 void mark_codebook_changed(som_handle* h) { h->w_dirty = h->wsq_dirty = h->wf_dirty = h->wp_dirty = true; }
 
@@ -596,7 +587,7 @@ int launch_bmu_f32_res_kg(som_handle* h, const float* X, long N, const float* xs
     if (grid <= 0 || grid > 0x7fffffffL) return fail(h, "bmu_f32: row count out of range");
     int parts = 1;
     if (!TOP2) {
-        const long slots = (long)per_cu * (h->n_cus > 0 ? h->n_cus : 256);
+        const long slots = resident_slots(h, per_cu);
         parts = choose_parts(h, grid, slots, h->fr_stages);
         if (h->env_f32_parts > 0) parts = h->env_f32_parts;   // (tests: the single-part and the merged paths at any size)
         if (parts > h->fr_stages) parts = h->fr_stages;
@@ -696,7 +687,7 @@ int launch_bmu_bf16_k16(som_handle* h, const __bf16* Xb, long N, int* out) {
     long blocks = cdiv(N, K16_WG_SAMPLES);
     if (blocks <= 0 || blocks > 0x7fffffffL) return fail(h, "bmu_bf16: row count out of range");
     // split the codebook scan into `parts` so the grid fills whole rounds of resident workgroups
-    const long slots = (long)per_cu * (h->n_cus > 0 ? h->n_cus : 256);
+    const long slots = resident_slots(h, per_cu);
     int parts = choose_parts(h, blocks, slots, h->n_stages);
     if (h->env_bf16_parts > 0) parts = h->env_bf16_parts;   // experiments
     if (h->debug)
@@ -719,7 +710,7 @@ int launch_bmu_bf16_tiled_cfg(som_handle* h, const __bf16* Ximg, long N, int* ou
     if (int rc = kernel_per_cu(h, (const void*)kern, 64 * C::WAVES, lds, &per_cu)) return rc;
     long blocks = cdiv(N, C::BM);
     if (blocks <= 0 || blocks > 0x7fffffffL) return fail(h, "bmu_bf16: row count out of range");
-    const long slots = (long)per_cu * (h->n_cus > 0 ? h->n_cus : 256);
+    const long slots = resident_slots(h, per_cu);
     int parts = choose_parts(h, blocks, slots, h->n_ublocks);
     // with many unit blocks, 8 parts let one XCD's resident workgroups share sample tiles through its L2
     if (h->n_ublocks >= 64 && blocks * 8 >= slots) parts = 8;
@@ -744,7 +735,7 @@ int launch_bmu_bf16_wide(som_handle* h, const __bf16* Ximg, const float* xmax2, 
     if (int rc = kernel_per_cu(h, (const void*)kern, 64 * WD_NW, lds, &per_cu)) return rc;
     const long blocks = cdiv(N, WD_WG_SAMPLES);
     if (blocks <= 0 || blocks > 0x7fffffffL) return fail(h, "bmu_bf16: row count out of range");
-    const long slots = (long)per_cu * (h->n_cus > 0 ? h->n_cus : 256);
+    const long slots = resident_slots(h, per_cu);
     // parts: whole rounds of the resident slots (every round scans one part in step: one L2 miss per XCD and stage)
     int parts = 1;
     if (blocks < slots) {
@@ -776,14 +767,7 @@ int launch_bmu_bf16_wide(som_handle* h, const __bf16* Ximg, const float* xmax2, 
 template <class E>
 int launch_bmu_bf16_tiled(som_handle* h, const __bf16* Ximg, const float* xmax2, long N, int* out) {
     if (h->wide) {
-        switch (h->n_kchunks) {
-#define SOM_WIDE_CASE(n) case n: return launch_bmu_bf16_wide<n, E>(h, Ximg, xmax2, N, out);
-        SOM_WIDE_CASE(5) SOM_WIDE_CASE(6) SOM_WIDE_CASE(7) SOM_WIDE_CASE(8) SOM_WIDE_CASE(9) SOM_WIDE_CASE(10)
-        SOM_WIDE_CASE(11) SOM_WIDE_CASE(12) SOM_WIDE_CASE(13) SOM_WIDE_CASE(14) SOM_WIDE_CASE(15) SOM_WIDE_CASE(16)
-        SOM_WIDE_CASE(17) SOM_WIDE_CASE(18) SOM_WIDE_CASE(19) SOM_WIDE_CASE(20) SOM_WIDE_CASE(21) SOM_WIDE_CASE(22)
-        SOM_WIDE_CASE(23) SOM_WIDE_CASE(24) SOM_WIDE_CASE(25)
-#undef SOM_WIDE_CASE
-        }
+        SOM_WIDE_DISPATCH(launch_bmu_bf16_wide, h, Ximg, xmax2, N, out)
         return fail(h, "bmu_bf16_wide: no instance for this input_len");
     }
     long cin = (long)h->n_ublocks * h->n_kchunks * h->tl_bn;
@@ -802,12 +786,7 @@ int launch_bmu_half(som_handle* h, const __bf16* Xb, const float* xmax2, long N,
     if (int rc = h->best64.reserve(h, (size_t)N, 1024)) return rc;
     prep_wsqh_kernel<<<dim3((unsigned)cdiv(std::max(units, N), 256)), dim3(256), 0, h->stream>>>(
         h->wn, h->K, h->wmax2, xmax2, h->Wst, h->n_stages, h->stage_bytes, h->stage_units, h->best64, N);
-    switch (h->ks32) {
-    case 1: return launch_bmu_bf16_k16<1, E>(h, Xb, N, out);
-    case 2: return launch_bmu_bf16_k16<2, E>(h, Xb, N, out);
-    case 3: return launch_bmu_bf16_k16<3, E>(h, Xb, N, out);
-    case 4: return launch_bmu_bf16_k16<4, E>(h, Xb, N, out);
-    }
+    SOM_KS32_DISPATCH(launch_bmu_bf16_k16, h, Xb, N, out)
     return fail(h, "bf16 precision supports input_len <= 128");
 }
 
@@ -1529,7 +1508,7 @@ void som_destroy(som_handle* h) {
         if (sl.copied) (void)hipEventDestroy(sl.copied);
         if (sl.consumed) (void)hipEventDestroy(sl.consumed);
     }
-    if (h->ex.fb_count_host) (void)hipHostFree(h->ex.fb_count_host);
+    if (h->ex.pass_host) (void)hipHostFree(h->ex.pass_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;                                            // (the device buffers free themselves, on the handle's device: dev_guard)
@@ -1562,7 +1541,7 @@ int som_get_weights(som_handle* h, float* w_host) {
 static int adopt_rows(som_handle* h, int64_t n_rows) {
     h->bmu.reset(); h->xsq.reset(); h->Xb.reset();
     h->bmu_valid = false;
-    h->ex.res_valid = false;                             // (the resident sorted pass belongs to the rows it was sorted from)
+    h->ex.plan.order_lost();                             // (the resident sorted pass belongs to the rows it was sorted from)
     h->seg = som_handle::SegScratch{};
     h->N = n_rows;
     h->Np = round_up(n_rows, ROW_PAD);
@@ -1591,8 +1570,7 @@ static int adopt_rows(som_handle* h, int64_t n_rows) {
         // the rows, not inside the first epochs (gigabytes of fresh device memory can take a driver tens to hundreds of
         // milliseconds).  A refusal here is not an error: launch_bmu_exact asks again and settles it (smaller passes, no plan).
         bool ok = exact_reserve(h, n_rows) == 0;
-        const long n_groups = cdiv(h->K, EX_GROUP);
-        if (ok && h->ex.skip_mode > 0 && h->ex.seed_on && !h->wide && (h->ex.skip_mode > 1 ? n_groups >= 2 : h->K >= 4096))
+        if (ok && exact_skip_wanted(h) && !h->wide)
             ok = exact_skip_reserve(h, h->ex.srt[0], n_rows, h->ex.stride) == 0;
         if (!ok) { (void)hipGetLastError(); h->err.clear(); }
     }
@@ -2287,6 +2265,42 @@ int som_policy_eval(int32_t which, const double* costs, const double* args, int3
     return 1;
 }
 
+// TEST HOOK (no device needed): a script of launches through a fresh policy::PlanState, driven as launch_bmu_exact drives it
+// (begin; the row sample and the sample tiles where the plan asks for them; end).  Layouts: include/somhip_test.h.
+int som_policy_replay(int32_t n_launches, const double* script, double* out) {
+    if (n_launches < 0 || !script || !out) return 1;
+    policy::PlanState st;
+    for (int32_t i = 0; i < n_launches; ++i) {
+        const double* in = script + (size_t)i * SOM_POLICY_REPLAY_IN;
+        double* o = out + (size_t)i * SOM_POLICY_REPLAY_OUT;
+        policy::LaunchFacts f;
+        f.resident = in[0] != 0.0; f.have_last = in[1] != 0.0; f.rows = (const void*)(uintptr_t)in[2]; f.n_rows = (long)in[3];
+        f.can_skip = in[4] != 0.0; f.scout_ok = in[5] != 0.0; f.wide = in[6] != 0.0; f.wide_can = in[7] != 0.0; f.wide_scout_ok = in[8] != 0.0;
+        f.l2_fits_lds = in[9] != 0.0; f.have_lo_image = in[10] != 0.0; f.blocks_per_row = in[11];
+        f.skip_mode = (int)in[12]; f.refine_on = in[13] != 0.0; f.sub_blocks = in[14] != 0.0; f.res_every = (int)in[15];
+        policy::LaunchPlan p = st.begin(f);
+        const bool asked_rows = p.estimate;
+        const bool row_no = asked_rows && st.rows_sampled(in[16], p);
+        const bool asked_tiles = p.estimate && p.sample_tiles && in[17] >= 0.0;   // (in[17] < 0: a pass too short for sample tiles)
+        const bool tile_no = asked_tiles && st.tiles_sampled(in[17], in[18], f, p);
+        policy::LaunchOutcome oc;
+        oc.t_total = in[19]; oc.t_screen = in[20]; oc.t_l2 = in[21]; oc.t_sort = in[22];
+        oc.screen_timed = p.time_phases; oc.l2_timed = p.time_phases && p.skip && p.level2; oc.sort_timed = p.time_phases && p.skip && p.resort;
+        oc.blocks_total = (int64_t)in[24];
+        oc.blocks_run = p.skip ? (int64_t)in[23] : oc.blocks_total;            // (without a plan every block runs)
+        oc.groups_run = p.skip ? (int64_t)in[25] : oc.blocks_total / policy::TILES_PER_GROUP;
+        oc.pairs_in = (int64_t)in[26]; oc.pairs_out = p.refine ? (int64_t)in[27] : 0; oc.scout_wins = (p.skip && p.scout && f.have_last) ? (int64_t)in[28] : 0;
+        st.end(f, p, oc);
+        o[0] = p.skip; o[1] = p.resort; o[2] = p.scout; o[3] = p.level2; o[4] = p.estimate; o[5] = p.sample_tiles; o[6] = p.refine; o[7] = p.time_phases;
+        o[8] = asked_rows; o[9] = asked_tiles; o[10] = row_no; o[11] = tile_no;
+        for (int k = 0; k < 2; ++k) {
+            const policy::Pause& ps = st.pause(k == 0);
+            o[12 + 3 * k] = ps.cooldown; o[13 + 3 * k] = ps.idle; o[14 + 3 * k] = ps.pause;
+        }
+    }
+    return 0;
+}
+
 int som_debug_mfma16(som_handle* h, const uint16_t* a_host, const uint16_t* b_host, const float* c_host, float* d_host,
                      int32_t is_f16) {
     DeviceGuard dev_guard(h);
@@ -2366,19 +2380,19 @@ int som_exact_skip_stats(som_handle* h, int64_t* blocks_run, int64_t* blocks_tot
 
 int som_exact_resident_stats(som_handle* h, int64_t* planned_epochs, int64_t* sorts) {
     if (!h || !planned_epochs || !sorts) return 1;
-    *planned_epochs = h->ex.planned; *sorts = h->ex.resorts;
+    *planned_epochs = h->ex.plan.stats().planned; *sorts = h->ex.plan.stats().resorts;
     return 0;
 }
 
 int som_exact_scout_stats(som_handle* h, int64_t* scouted_launches, int64_t* transient_planned) {
     if (!h || !scouted_launches || !transient_planned) return 1;
-    *scouted_launches = h->ex.scouted; *transient_planned = h->ex.tr_planned;
+    *scouted_launches = h->ex.plan.stats().scouted; *transient_planned = h->ex.plan.stats().tr_planned;
     return 0;
 }
 
 int som_exact_refine_stats(som_handle* h, int64_t* pairs_in, int64_t* pairs_out) {
     if (!h || !pairs_in || !pairs_out) return 1;
-    *pairs_in = h->ex.pairs_refined_in; *pairs_out = h->ex.pairs_refined_out;
+    *pairs_in = h->ex.plan.stats().pairs_refined_in; *pairs_out = h->ex.plan.stats().pairs_refined_out;
     return 0;
 }
 
