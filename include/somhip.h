@@ -219,6 +219,14 @@ int som_bmu_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t mod
  * call on the vector ALU; rows are staged through device memory as doubles. */
 int som_bmu_f64(som_handle* h, const double* x_host, int64_t n_rows, int32_t* ids_out);
 int som_bmu_top2(som_handle* h, const float* x_host, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out);
+/* ... for rows that already live in HBM (see som_bmu_device: borrowed for the call, the same argument checks, at most
+ * 2^31-1 rows; ids1_out / ids2_out: host memory).  In EXACT precision with the 'euclidean' activation distance up to 128
+ * features both calls run the half-precision screen with its window on the SECOND-smallest group minimum, one select and the
+ * float32 re-score twice (csrc/bmu_exact.hpp, "TOP-2"); every row whose pair a tie under the sqrt could reorder, or that the
+ * screen cannot vouch for, is answered by the float32 top-2 kernel, so the ids are F32 precision's bit for bit.  Every other
+ * configuration -- cosine, more than 128 features, F32 / BF16 / F16 -- runs the float32 kernel for every row, as does a handle
+ * created with SOM_EXACT_TOP2=0 in the environment. */
+int som_bmu_top2_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out);
 /* the (n_rows, K) distance matrix itself, row-major, for the analysis calls that return it:
  * mode ACTIVATION = XPySom.activate (xpysom.py:323-354, configured GEMM-form distance),
  * mode QUANTIZATION = XPySom.distance_from_weights (xpysom.py:647-671).  Never used while training. */
@@ -254,6 +262,9 @@ int som_patch_order(int32_t x, int32_t y, int32_t* perm_out);
 
 /* precision EXACT bookkeeping: rows screened so far, rows that went to the float32 fallback kernel, screen passes */
 int som_exact_stats(som_handle* h, int64_t* rows, int64_t* rows_fallback, int64_t* passes);
+/* top-2 bookkeeping (any precision): rows the top-2 calls served so far, and how many of them the float32 top-2 kernel
+ * answered -- all of them on a handle that never takes the screen's path */
+int som_exact_top2_stats(som_handle* h, int64_t* rows, int64_t* rows_f32);
 /* precision EXACT, block skipping (csrc/exact_skip.hpp: resident rows from their second epoch on, input_len <= 128): how
  * many (256-row tile, 16-unit block) blocks the screens ran, of how many a full scan has -- the EXECUTED share of the
  * distance GEMM (launches without skipping count every block) */

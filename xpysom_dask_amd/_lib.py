@@ -65,6 +65,7 @@ SIGNATURES = {
     "som_bmu": (C.c_int, [_H, _F, C.c_int64, C.c_int32, _I]),
     "som_bmu_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, _I]),
     "som_bmu_top2": (C.c_int, [_H, _F, C.c_int64, _I, _I]),
+    "som_bmu_top2_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _I, _I]),
     "som_bmu_f64": (C.c_int, [_H, C.POINTER(C.c_double), C.c_int64, _I]),
     "som_distance_matrix": (C.c_int, [_H, _F, C.c_int64, C.c_int32, _F]),
     "som_quantization_error": (C.c_int, [_H, _F, C.c_int64, C.POINTER(C.c_double)]),
@@ -80,6 +81,7 @@ SIGNATURES = {
     "som_policy_replay": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "som_patch_order": (C.c_int, [C.c_int32, C.c_int32, _I]),
     "som_exact_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "som_exact_top2_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_exact_skip_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_exact_resident_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_exact_scout_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -218,9 +218,13 @@ __global__ __launch_bounds__(64 * KS32) void merge_prep_k16_kernel(float* __rest
 // TL (block skipping, exact_skip.hpp): the workgroup walks its tile's dense LIST of 16-unit tiles (group << 2 | sub-block)
 // instead of all stages; only the listed tiles' fragments are staged and multiplied.  With GM: the exact mode's screen
 // under a plan.  Without: the scout's pick of a pseudo last BMU among a tile's few listed groups (unit indices kept).
+// T2 (with GM, never TL: the exact mode's TOP-2 screen, bmu_exact.hpp "top-2"): the window hangs on the SECOND-smallest group
+// minimum so far -- a lane keeps the two smallest group minima of its row (two registers more), a group minimum is stored where
+// it is within E of the second one, and every part of the codebook hands back its own pair (t2min[(2 part + {0, 1}) t2pitch + row]:
+// the second-smallest of a part is never below the second-smallest of all parts; exact_select_kernel<false, true> merges them).
 // (the kernel's body for one workgroup's worth of rows: tile bx of K16_WG_SAMPLES rows, part by of ny of the codebook stages -- or,
 //  TL, of the tile's list.  The kernel below calls it once, or -- the exact mode's screen under a plan -- once per work item.)
-template <int KS32, class EL, bool GM, bool TL>
+template <int KS32, class EL, bool GM, bool TL, bool T2 = false>
 __device__ __forceinline__ void bmu_bf16_k16_body(const __bf16* __restrict__ Xb, long N,
                                                   const char* __restrict__ Wst, int n_stages, int K,
                                                   unsigned long long* __restrict__ out64,
@@ -230,7 +234,9 @@ __device__ __forceinline__ void bmu_bf16_k16_body(const __bf16* __restrict__ Xb,
                                                   const float* __restrict__ xmax2, const float* __restrict__ wmax2,
                                                   const float* __restrict__ werr2, const ExactBound& eb,
                                                   const float* __restrict__ seed, const int* __restrict__ glist,
-                                                  const int* __restrict__ gcnt, const long bx, const int by, const int ny) {
+                                                  const int* __restrict__ gcnt, const long bx, const int by, const int ny,
+                                                  float* __restrict__ t2min = nullptr, long t2pitch = 0) {
+    static_assert(!T2 || (GM && !TL), "the top-2 screen is the group-minimum instance over every stage");
     using E = typename EL::T;
     using bf16x8 = typename V8<E>::t;
     constexpr int DP = 32 * KS32;
@@ -265,6 +271,7 @@ __device__ __forceinline__ void bmu_bf16_k16_body(const __bf16* __restrict__ Xb,
     float run_min = __builtin_inff(), row_e = 0.0f;       // GM: lane l <-> row wave_s0 + l: its minimum so far, its bound E
     int run_arg = 0;                                      //     ... and the group (stage) that holds it
     float run_cap = __builtin_inff();                     //     ... and the seed's cap on what can be selected at all
+    float run_min2 = __builtin_inff();                    // T2: ... and its second-smallest group minimum so far
     if (GM) {
         const long r = wave_s0 + lane;
         row_e = r < N ? ex_row_bound(eb, ex_scales(xmax2, wmax2, werr2), xsq[r], xerr[r]) : __builtin_nanf("");
@@ -324,8 +331,10 @@ __device__ __forceinline__ void bmu_bf16_k16_body(const __bf16* __restrict__ Xb,
             auto c = __builtin_amdgcn_permlane32_swap(t01, t23, false, false);
             const uint32_t full = min(c[0], c[1]);         // quads: (v0, v1, v2, v3), each over all four quads
             const float f = __uint_as_float(full);         // (positive, or a NaN pattern: compares false, never kept)
-            const bool keep = f <= __builtin_fminf(run_min + row_e, run_cap);
+            const bool keep = f <= __builtin_fminf((T2 ? run_min2 : run_min) + row_e, run_cap);
             if (f < run_min) run_arg = stage;              // (the group that holds the row minimum: the first re-score round)
+            // (T2: the two smallest so far, a NaN pattern taking neither place: compares, not min / max)
+            if (T2) run_min2 = f < run_min ? run_min : f < run_min2 ? f : run_min2;
             run_min = __builtin_fminf(run_min, f);
             if (keep) gmin[(long)stage * gm_stride + wave_s0 + lane] = full;
             const unsigned long long mask = __ballot(keep);
@@ -486,6 +495,10 @@ __device__ __forceinline__ void bmu_bf16_k16_body(const __bf16* __restrict__ Xb,
         // bit of it, and the group that holds it (no unit indices exist here); parts merge by value, then lower group
         const long row = wave_s0 + lane;
         if (row < N) atomicMin(out64 + row, ((unsigned long long)__float_as_uint(run_min) << 32) | (uint32_t)run_arg);
+        if (T2 && row < N) {
+            t2min[(long)(2 * by) * t2pitch + row] = run_min;
+            t2min[(long)(2 * by + 1) * t2pitch + row] = run_min2;
+        }
         return;
     }
 
@@ -509,7 +522,7 @@ __device__ __forceinline__ void bmu_bf16_k16_body(const __bf16* __restrict__ Xb,
 // that held a fifth to two fifths of the launch (tools/wg_timeline.py).  exact_items_kernel cuts every list into parts of about
 // equal length (item = (tile, part | parts << 16)); a workgroup per slot of the chip takes items off one counter until none is left
 // (every workgroup reaches `it >= *n_items`: the grid drains).  A part re-reads its tile's rows: only the long lists are cut.
-template <int KS32, class EL = Bf16, bool GM = false, bool TL = false>
+template <int KS32, class EL = Bf16, bool GM = false, bool TL = false, bool T2 = false>
 __global__ __launch_bounds__(64 * K16_NW, (TL && GM) ? 3 : 2) void bmu_bf16_k16_kernel(const __bf16* __restrict__ Xb, long N,
                                                               const char* __restrict__ Wst, int n_stages, int K,
                                                               unsigned long long* __restrict__ out64,
@@ -526,7 +539,8 @@ __global__ __launch_bounds__(64 * K16_NW, (TL && GM) ? 3 : 2) void bmu_bf16_k16_
                                                               const int* __restrict__ gcnt = nullptr,
                                                               const int2* __restrict__ items = nullptr,
                                                               const int* __restrict__ n_items = nullptr,
-                                                              int* __restrict__ item_ctr = nullptr) {
+                                                              int* __restrict__ item_ctr = nullptr,
+                                                              float* __restrict__ t2min = nullptr, long t2pitch = 0) {
     if (TL && items != nullptr) {
         __shared__ int s_item;
         const int n = *n_items;
@@ -541,8 +555,8 @@ __global__ __launch_bounds__(64 * K16_NW, (TL && GM) ? 3 : 2) void bmu_bf16_k16_
                                                 seed, glist, gcnt, (long)iv.x, iv.y & 0xFFFF, iv.y >> 16);
         }
     }
-    bmu_bf16_k16_body<KS32, EL, GM, TL>(Xb, N, Wst, n_stages, K, out64, gmin, gm_stride, gflags, xsq, xerr, xmax2, wmax2, werr2, eb, seed,
-                                        glist, gcnt, (long)blockIdx.x, (int)blockIdx.y, (int)gridDim.y);
+    bmu_bf16_k16_body<KS32, EL, GM, TL, T2>(Xb, N, Wst, n_stages, K, out64, gmin, gm_stride, gflags, xsq, xerr, xmax2, wmax2, werr2, eb, seed,
+                                            glist, gcnt, (long)blockIdx.x, (int)blockIdx.y, (int)gridDim.y, t2min, t2pitch);
 }
 
 // out64 -> raveled ids (a padding unit can only win on a NaN row: numpy's argmin gives 0 there)

@@ -52,6 +52,28 @@
 //                    E32_tau + 2 (operand term + accumulation term).
 // The bound is deliberately loose (worst-case rounding everywhere it is not measured): widening E only adds candidate
 // groups, and a candidate group costs one 64-unit re-score.
+//
+// TOP-2 (som_bmu_top2 / som_bmu_top2_device, euclidean, input_len <= 128: exact_top2_host.hpp).  Wanted: float32's best unit
+// k1 = first argmin_k s(k) and its second-best k2 = first argmin_{k != k1} s(k), s the float32 score above.  The window m + E
+// finds k1 only: k2 is usually farther than E from the best.  The window hangs on m2(n) instead, the SECOND-smallest group
+// minimum of the screen, and the claim is   d'(k1) <= m2 + E  and  d'(k2) <= m2 + E.
+//   Proof.  Let g_a, g_b be the groups with the smallest and second-smallest minimum and a, b the units that hold them:
+//   d'(a) = m <= d'(b) = m2, and a != b because the groups are disjoint.  One of the two, call it c, is not k1, and
+//   d'(c) <= m2.  k2 is the first minimum of s over the units other than k1 and c is one of those: s(k2) <= s(c).  The
+//   two-unit argument above (it uses nothing of k* but s(k*) <= s(k)) turns s(k2) <= s(c) into d'(k2) <= d'(c) + E <= m2 + E.
+//   For k1: s(k1) <= s(a), so d'(k1) <= m + E <= m2 + E.  The same holds for every unit that TIES k1 or k2 in s, so the
+//   lowest id among equal scores is among the candidates too.                                                          []
+//   So far: the screen stores a group minimum f where f <= m2_so_far + E.  The second-smallest of the groups seen so far
+//   is never below the second-smallest of all groups (a minimum over fewer elements), and with the codebook cut into parts
+//   the second-smallest of a part is never below the second-smallest of the whole: what the final window needs was stored.
+//   One group (K <= 64): there is no m2; the group is every row's only candidate and holds both units.
+// The lists then go through the float32 re-score TWICE: round 1 as above gives k1; round 2 scores the same tiles with the
+// row's k1 left out of the tile's argmin (its |w|^2 replaced by +inf: exact_rescore_mfma_kernel<KG, true>) and merges into a
+// second key: the first minimum of the rest, k2.  Both are float32's own values: the instruction stream is the re-score's.
+// som_bmu_top2 is defined on the sqrt'd distance nan_to_num(sqrt(s + |x|^2)), which is monotone in s but not strictly:
+// exact_top2_settle_kernel applies the test of exact_qe_window_kernel (ex_sqrt_settled) to BOTH units; where the next float32
+// above s(k1) and the next above s(k2) each have a larger sqrt'd distance no other unit can tie either of them under the
+// sqrt, and (k1, k2) is the float32 top-2 kernel's pair.  Every other row goes to that kernel.
 #pragma once
 #include "bmu_bf16_k16.hpp"
 #include "bmu_bf16_wide.hpp"
@@ -80,6 +102,7 @@ struct PassCounters {
     int pairs_in;     // exact_tiles_kernel: candidate (row, group) pairs the select kernel found
     int pairs_out;    // exact_select2_kernel: ... the refinement pass kept
     int scout_wins;   // exact_plan_kernel: rows whose scout pick beat their last BMU by a tenth of the squared distance
+    int bad_w;        // exact_top2_settle_kernel: the codebook holds a unit whose |w|^2 is not finite
 };
 // The row-need estimate (exact_scout_rowneed_kernel, exact_skip.hpp) runs before a launch's first pass and borrows the head of the block.
 struct RowNeed {
@@ -103,7 +126,10 @@ struct RowNeed {
 // ONE-unit error E/2 of d'(t*) -- half the two-unit window m + E of the one-round scheme, from a reference point that is
 // the true minimum's rather than the screen's: 20-32 % fewer candidate pairs on smooth maps (measured).  rowarg[n] = the group
 // round 1 scored (skipped here); the lists and gcount continue behind round 1's entries; best64 is left alone.
-template <bool ROUND2>
+// TOP2 (one round, no seed, no lists): the threshold is m2 + E, m2 the second-smallest group minimum -- the two smallest of
+// the pairs (minimum, second minimum) the top-2 screen's codebook parts left in t2min (bmu_bf16_k16.hpp, T2); a map of one
+// group has no second minimum: the group is the candidate of every row the bound covers.
+template <bool ROUND2, bool TOP2 = false>
 __global__ __launch_bounds__(64 * EX_SCAN_SPLIT) void exact_select_kernel(const uint32_t* __restrict__ gmin,
                                                                          const unsigned long long* __restrict__ gflags,
                                                                          long gm_stride, int n_groups, long N,
@@ -119,7 +145,10 @@ __global__ __launch_bounds__(64 * EX_SCAN_SPLIT) void exact_select_kernel(const 
                                                                          const float* __restrict__ seed = nullptr,
                                                                          const int* __restrict__ glist = nullptr,
                                                                          const int* __restrict__ gcnt = nullptr,
-                                                                         int rows_per_list = 0) {
+                                                                         int rows_per_list = 0,
+                                                                         const float* __restrict__ t2min = nullptr,
+                                                                         int t2parts = 0, long t2pitch = 0) {
+    static_assert(!(ROUND2 && TOP2), "top-2 uses the one-round scheme");
     __shared__ int cnt_s[EX_SCAN_SPLIT][64];
     const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
     const long row0 = (long)blockIdx.x * 64;
@@ -142,6 +171,16 @@ __global__ __launch_bounds__(64 * EX_SCAN_SPLIT) void exact_select_kernel(const 
         thr_f = dp + 0.5f * e * (1.0f + 1.0f / 1024.0f) + S * sc.bmag * 0x1p-21f;
         if (k64 == ~0ull || (bits & 0x7F800000u) == 0x7F800000u) thr_f = __builtin_nanf("");   // nothing scored, or not finite
         arg = rowarg[r];
+    } else if (TOP2) {
+        float m1 = __builtin_inff(), m2 = __builtin_inff();
+        for (int p = 0; p < 2 * t2parts; ++p) {              // (every part's minimum and second minimum: the two smallest of all)
+            const float f = t2min[(long)p * t2pitch + r];
+            m2 = f < m1 ? m1 : f < m2 ? f : m2;
+            m1 = __builtin_fminf(m1, f);
+        }
+        thr_f = m2 + e;
+        // (one group: its minimum, if there is one, is below the largest finite float)
+        if (n_groups == 1 && e == e && m1 < 3.0e38f) thr_f = 2.9e38f;
     } else {
         thr_f = __uint_as_float((uint32_t)(best64[r] >> 32)) + e;
         // seed (exact_seed_kernel / the plan's prologue): an upper bound, less the float32 share, on the screen value of
@@ -545,14 +584,18 @@ __global__ __launch_bounds__(256) void exact_select2_kernel(int* __restrict__ pl
 // order-preserving 64-bit atomicMin the parity kernel's codebook parts use.  Persistent: a workgroup takes a contiguous
 // run of the tile table -- consecutive tiles mostly belong to one group, whose stage is fetched once and stays in LDS
 // -- and between two stage changes its four waves run free of each other (no barrier per tile).
-template <int KG>
+// EXCL (top-2, round 2): excl[row] = the POSITION in the image of the unit to leave out of the row's argmin (round 1's winner;
+// -1: none) -- its |w|^2 is read as +inf, so that its score is +inf (or a NaN) and neither wins nor ties; everything else is
+// the same instruction stream on the same tiles.
+template <int KG, bool EXCL = false>
 __global__ __launch_bounds__(256, 3) void exact_rescore_mfma_kernel(const float* __restrict__ X, int D,
                                                                     const char* __restrict__ Wfst, int K,
                                                                     const int4* __restrict__ tile_tab,
                                                                     const int* __restrict__ n_tiles_dev,
                                                                     const int* __restrict__ plist,
                                                                     unsigned long long* __restrict__ best64,
-        const int* __restrict__ perm, const int* __restrict__ order = nullptr, int sub44 = 0, int deint = 0) {
+        const int* __restrict__ perm, const int* __restrict__ order = nullptr, int sub44 = 0, int deint = 0,
+        const int* __restrict__ excl = nullptr) {
     constexpr int STAGE = fr_stage_bytes(KG);
     constexpr int PIECES = FR_UT * KG + 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // ONE stage: occupancy (three workgroups per CU), not a
@@ -610,6 +653,8 @@ __global__ __launch_bounds__(256, 3) void exact_rescore_mfma_kernel(const float*
                 xf[s] = (row >= 0 && k < D) ? X[(long)xrow * D + k] : 0.0f;
             }
         }
+        int ex_pos = -1;                                   // EXCL: the position this row's argmin leaves out
+        if (EXCL && row >= 0) ex_pos = excl[row];
         row_next = entry(t + 1);                           // (in flight under this tile's MFMAs)
         if (g != g_have) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the stage
@@ -638,6 +683,14 @@ __global__ __launch_bounds__(256, 3) void exact_rescore_mfma_kernel(const float*
             for (int q = 0; q < 4; ++q) wv[q] = *(const f32x4*)(wq + ut * 32 + 8 * q + 4 * half);
             const int tile = g * FR_UT + ut;
             static_assert(FR_UT == 2, "ex_rank44: a group is two 32-unit MFMA tiles");
+            if (EXCL && (ex_pos >> 5) == tile) {           // (the lane's registers hold positions 32 tile + 8 q + 4 half + j)
+                const int lp = ex_pos & 31;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (lp == 8 * q + 4 * half + j) wv[q][j] = __builtin_inff();
+            }
             if (sub44) f32_tile_argmin_ranked<SCORE_EUCLID_PART>(acc, wv, 0.0f, tile, half, best, bkey, brank);   // (whole 8 x 8 patches: no tail)
             else if ((tile + 1) * 32 > K) f32_tile_argmin<SCORE_EUCLID_PART, true>(acc, wv, 0.0f, tile, half, K, best, bkey);
             else f32_tile_argmin<SCORE_EUCLID_PART, false>(acc, wv, 0.0f, tile, half, K, best, bkey);
@@ -812,6 +865,13 @@ __global__ __launch_bounds__(256) void exact_scatter_ids_kernel(const int* __res
 // q can tie u's and u is that pick; every other row -- and one whose q_u is not finite -- goes to the list for the float32
 // SQRT kernel.  q_u is formed as the parity kernels form it: the k-ordered fmaf chain, then fma(-2, c, |w|^2)
 // (verify_best_kernel).  One thread per row.
+// is float32's sqrt'd distance strictly larger at the next float32 above q than at q?  (then no other score ties q's under the sqrt)
+__device__ __forceinline__ bool ex_sqrt_settled(float q, float xs) {
+    if (!__builtin_isfinite(q)) return false;
+    const uint32_t b = __float_as_uint(q);                // the next float32 above q (-0: the least positive one)
+    const float qn = __uint_as_float(b == 0x80000000u ? 1u : (b & 0x80000000u) ? b - 1u : b + 1u);
+    return nan_to_num_f32(__builtin_sqrtf(q + xs)) < nan_to_num_f32(__builtin_sqrtf(qn + xs));
+}
 __global__ __launch_bounds__(256) void exact_qe_window_kernel(const float* __restrict__ X, long N, int D,
                                                               const float* __restrict__ W, const float* __restrict__ wsq,
                                                               const float* __restrict__ xsq, const int* __restrict__ ids,
@@ -825,13 +885,52 @@ __global__ __launch_bounds__(256) void exact_qe_window_kernel(const float* __res
     for (int k = 0; k < D; ++k) c = __builtin_fmaf(w[k], x[k], c);
     const float q = __builtin_fmaf(-2.0f, c, wsq[u]);
     const float xs = xsq[row];
-    bool settled = false;
-    if (__builtin_isfinite(q)) {
-        const uint32_t b = __float_as_uint(q);            // the next float32 above q (-0: the least positive one)
-        const float qn = __uint_as_float(b == 0x80000000u ? 1u : (b & 0x80000000u) ? b - 1u : b + 1u);
-        settled = nan_to_num_f32(__builtin_sqrtf(q + xs)) < nan_to_num_f32(__builtin_sqrtf(qn + xs));
-    }
-    if (!settled) list[atomicAdd(count, 1)] = (int)row;
+    if (!ex_sqrt_settled(q, xs)) list[atomicAdd(count, 1)] = (int)row;
+}
+
+// ---- top-2 (header comment, "TOP-2"): between the two re-score rounds, and after them
+// round 1's merge keys -> the position (in the image's order: inv[unit], or the unit itself) round 2 leaves out; -1: nothing scored
+__global__ __launch_bounds__(256) void exact_top2_first_kernel(const unsigned long long* __restrict__ best64, long N, int K,
+                                                               const int* __restrict__ inv, int* __restrict__ excl) {
+    const long row = (long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= N) return;
+    const unsigned long long k64 = best64[row];
+    const uint32_t unit = (uint32_t)k64;
+    excl[row] = (k64 == ~0ull || unit >= (uint32_t)K) ? -1 : (inv != nullptr ? inv[unit] : (int)unit);
+}
+
+// the float32 score a merge key carries (exact_rescore_mfma_kernel's order-preserving transform, undone)
+__device__ __forceinline__ float ex_key_score(unsigned long long k64) {
+    const uint32_t key = (uint32_t)(k64 >> 32);
+    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
+
+// both rounds' merge keys -> (k1, k2), or the list for the float32 top-2 kernel: an overflowed pass, a round that scored
+// nothing, a score that is not finite, a pair a tie under the sqrt could reorder (ex_sqrt_settled on both).  The threads
+// also walk the units' |w|^2 (wsq, K values): a NaN unit scores NaN -- never a minimum of s, but 0 under nan_to_num(sqrt),
+// the smallest distance there is -- and a codebook that holds one is not served here at all (*bad_w; the host reads it).
+__global__ __launch_bounds__(256) void exact_top2_settle_kernel(const unsigned long long* __restrict__ best1,
+                                                                const unsigned long long* __restrict__ best2, long N, int K,
+                                                                const float* __restrict__ xsq, const float* __restrict__ wsq,
+                                                                const int* __restrict__ overflow, int* __restrict__ out1,
+                                                                int* __restrict__ out2, int* __restrict__ list,
+                                                                int* __restrict__ count, int* __restrict__ bad_w) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < K && !__builtin_isfinite(wsq[i])) *bad_w = 1;
+    if (i >= N) return;
+    const unsigned long long a = best1[i], b = best2[i];
+    const uint32_t u1 = (uint32_t)a, u2 = (uint32_t)b;
+    const float xs = xsq[i];
+    bool ok = !*overflow && a != ~0ull && b != ~0ull && u1 < (uint32_t)K && u2 < (uint32_t)K && u1 != u2;
+    ok = ok && ex_sqrt_settled(ex_key_score(a), xs) && ex_sqrt_settled(ex_key_score(b), xs);
+    if (ok) { out1[i] = (int)u1; out2[i] = (int)u2; }
+    else list[atomicAdd(count, 1)] = (int)i;
+}
+__global__ __launch_bounds__(256) void exact_scatter_ids2_kernel(const int* __restrict__ ids1, const int* __restrict__ ids2,
+                                                                 const int* __restrict__ list, int n, int* __restrict__ out1,
+                                                                 int* __restrict__ out2) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { out1[list[i]] = ids1[i]; out2[list[i]] = ids2[i]; }
 }
 
 // max_n v[n] (positive floats; NaN left out) into *out, which the caller zeroed.  Grid-stride: a few hundred workgroups hand in

@@ -621,7 +621,7 @@ int exact_rescore_kg(som_handle* h, const float* X, unsigned long long* best64, 
     // (twice the resident slots: the runs of tiles are uneven -- partial tiles, idle waves -- and finer runs balance them)
     const long grid = std::min<long>(ex.max_tiles, h->ex.grid_mult * resident_slots(h, per_cu));
     kern<<<dim3((unsigned)grid), dim3(256), lds, h->stream>>>(X, h->D, h->Wfst, h->K, ex.tile_tab, &pass_ctr(h).tail()->n_tiles, ex.plist,
-                                                             best64, h->ex_perm, nullptr, h->ex_sub44 ? 1 : 0, deint);
+                                                             best64, h->ex_perm, nullptr, h->ex_sub44 ? 1 : 0, deint, nullptr);
     return 0;
 }
 
@@ -658,8 +658,9 @@ int exact_refine(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long r
 // the lists' entries from gstart on -> tiles -> float32 scores merged into best64 (the pass's slice of the merge keys)
 // (sorted_copy: X is a sorted pass's float32 copy -- up to 128 features and a multiple of 8 of them: de-interleaved rows,
 //  exact_gather_sorted_kernel)
+// (count_pairs: the tiles kernel leaves the pass's pair count in the counters; the planned launch's refinement pass has counted already)
 int exact_rescore_round(som_handle* h, const float* X, const float* xsq, unsigned long long* best64, const int* gstart,
-                        int* gstart_out, bool sorted_copy = false) {
+                        int* gstart_out, bool sorted_copy, bool count_pairs) {
     auto& ex = h->ex;
     const int deint = (sorted_copy && !h->wide && (h->D & 7) == 0) ? 1 : 0;
     const PassCtr pc = pass_ctr(h);
@@ -669,7 +670,7 @@ int exact_rescore_round(som_handle* h, const float* X, const float* xsq, unsigne
     // (the pairs the select kernel found go back with the pass's counters -- unless the refinement pass has counted them already)
     exact_tiles_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(gcount, n_groups, ex.stride, ex.stride * ex.pairs, ex.tile_tab, n_tiles,
                                                              &ctr->overflow, gstart, gstart_out,
-                                                             (gstart == nullptr && gstart_out == nullptr && !ex.lp.refine) ? &ctr->pairs_in : nullptr);
+                                                             (gstart == nullptr && gstart_out == nullptr && count_pairs) ? &ctr->pairs_in : nullptr);
     if (h->wide) {
         // beyond 128 features: the float32 tile image, chunk by chunk
         if (!h->Wfimg) return fail(h, "exact: no float32 tile image");
@@ -888,18 +889,18 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
         // (under a plan -- exact_skip_wide.hpp -- rows are sorted positions: p_X, p_xsq, p_xerr; the select kernel walks the lists)
         exact_first_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(
             best, n, n_groups, ex.stride, p_xsq, h->wmax2, xmax2, eb, p_xerr, h->wmax2 + 1, ex.plist, pc.gcount(), ex.rowarg);
-        if (int rc = exact_rescore_round(h, p_X, p_xsq, best, nullptr, pc.gstart(), lp.skip)) return rc;
+        if (int rc = exact_rescore_round(h, p_X, p_xsq, best, nullptr, pc.gstart(), lp.skip, !lp.refine)) return rc;
         exact_select_kernel<true><<<sel_grid, sel_block, 0, h->stream>>>(
             ex.gmin, ex.gflags, ex.stride, n_groups, n, best, p_xsq, h->wmax2, xmax2, eb, p_xerr, h->wmax2 + 1, ex.plist,
             pc.gcount(), ex.rowcnt, ex.rowarg, nullptr, lp.skip ? ex.glist : nullptr, lp.skip ? ex.gcnt : nullptr, SK_TILE);
-        if (int rc = exact_rescore_round(h, p_X, p_xsq, best, pc.gstart(), nullptr, lp.skip)) return rc;
+        if (int rc = exact_rescore_round(h, p_X, p_xsq, best, pc.gstart(), nullptr, lp.skip, !lp.refine)) return rc;
     } else {
         exact_select_kernel<false><<<sel_grid, sel_block, 0, h->stream>>>(
             ex.gmin, ex.gflags, ex.stride, n_groups, n, best, p_xsq, h->wmax2, xmax2, eb, p_xerr, h->wmax2 + 1, ex.plist,
             pc.gcount(), ex.rowcnt, nullptr, p_seed, lp.skip ? ex.glist : nullptr, lp.skip ? ex.gcnt : nullptr, SK_TILE);
         if (lp.refine)
             if (int rc = SOM_HALF(h, exact_refine, h, sr, s0, n, xmax2, eb)) return rc;
-        if (int rc = exact_rescore_round(h, p_X, xsq + r0, best, nullptr, nullptr, lp.skip)) return rc;
+        if (int rc = exact_rescore_round(h, p_X, xsq + r0, best, nullptr, nullptr, lp.skip, !lp.refine)) return rc;
     }
     exact_finalize_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(
         best, n, h->K, &pc.tail()->overflow, out + r0, ex.fb_list, &pc.tail()->fallback, p_order);

@@ -166,6 +166,7 @@ public:
     double share_last(bool resident) const { return resident ? res_share_last : tr_share_last; }
     // the resident order no longer holds: new rows, new passes, new sorted copies
     void order_lost() { res_valid = false; }
+    bool order_valid() const { return res_valid; }   // (the top-2 launch leaves a resident order alone: exact_top2_host.hpp)
 
     // BEGIN A LAUNCH: does it plan at all, re-sort, scout, run level 2, ask the samples, refine; which phases it times.
     LaunchPlan begin(const LaunchFacts& f) {

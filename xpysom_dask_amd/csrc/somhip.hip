@@ -39,7 +39,7 @@ namespace {
 
 thread_local std::string g_create_error;
 
-// Environment switches.  Four are for users (SOM_VERIFY, SOM_DEBUG, SOM_EXACT_SKIP, SOM_GRAPH).  Everything
+// Environment switches.  Five are for users (SOM_VERIFY, SOM_DEBUG, SOM_EXACT_SKIP, SOM_EXACT_TOP2, SOM_GRAPH).  Everything
 // else -- A/B switches of kernel variants, forced pass sizes, refused allocations -- belongs to the tests and the tools and is
 // read ONLY when SOM_TEST_HOOKS=1 is set (tests/conftest.py sets it): a stray variable in a user's environment changes nothing.
 const char* dev_env(const char* name) {
@@ -256,6 +256,16 @@ struct som_handle {
     // distance could overturn, gathered for the float32 SQRT kernel, and how many rows went each way (som_debug_qe_stats)
     DevBuf<int> qe_list, qe_ids, qe_cnt; DevBuf<float> qe_X, qe_xsq;
     int64_t qe_rows = 0, qe_rows_sqrt = 0;
+    // precision 'exact', top-2 (exact_top2_host.hpp): the screen's per-part minima, the unit round 2 leaves out, the rows the
+    // float32 top-2 kernel answers (gathered), and how many rows went each way (som_exact_top2_stats)
+    struct Top2Scratch {
+        bool on = true;                   // SOM_EXACT_TOP2=0: the float32 top-2 kernel for every row
+        DevBuf<float> m;                  // [2 x codebook parts][rows of the pass, padded]: (minimum, second minimum) of every part
+        DevBuf<int> excl;                 // [rows of the pass] position of round 1's winner
+        DevBuf<float> X, xsq;
+        DevBuf<int> ids1, ids2;
+        int64_t rows = 0, rows_f32 = 0;
+    } t2;
     // streamed epochs (rows that do not stay resident): per-chunk sort scratch, grown on demand
     SegScratch st_seg;
     bool streaming = false;
@@ -1243,6 +1253,8 @@ int ensure_query_scratch(som_handle* h, long n, bool with_rows = true) {
     return 0;
 }
 
+#include "exact_top2_host.hpp"   // launch_top2_exact (precision 'exact', top-2): same translation unit
+
 template <int MODE>
 int launch_dist_matrix(som_handle* h, long N, float* out) {
     const int Dp = (int)round_up(h->D, F32_KC);
@@ -1439,6 +1451,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         if (const char* e = dev_env("SOM_EXACT_TWO_ROUND")) h->ex.two_round = std::atoi(e) != 0 ? 1 : 0;
         if (const char* e = dev_env("SOM_EXACT_SEED")) h->ex.seed_on = std::atoi(e) != 0;
         if (const char* e = std::getenv("SOM_EXACT_SKIP")) h->ex.skip_mode = std::atoi(e);
+        if (const char* e = std::getenv("SOM_EXACT_TOP2")) h->t2.on = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_EXACT_SUBBLOCKS")) h->ex.sub_blocks = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_EXACT_REFINE")) h->ex.refine_on = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_EXACT_QUEUE")) { h->ex.item_queue = std::atoi(e) != 0; if (std::atoi(e) >= 25) h->ex.item_len_pct = std::atoi(e); }
@@ -2099,6 +2112,32 @@ int run_query_bmu(som_handle* h, const float* X, long n_rows, int mode) {
     return run_activation_bmu(h, X, n_rows, h->qxsq, h->qXb, h->xmax2 + 1, h->qbmu);
 }
 
+// best and second-best unit of n device rows under the sqrt'd Euclidean distance into qbmu / qbmu2: the exact mode's screen
+// + two re-score rounds where they serve (exact_top2_fast), else -- and for every row they cannot settle -- the float32 kernel
+int run_top2(som_handle* h, const float* X, long n_rows) {
+    if (exact_top2_fast(h)) {
+        if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
+        if (int rc = prep_rows_bf16(h, X, n_rows, round_up(n_rows, ROW_PAD), h->qXb, h->xmax2 + 1, h->qxsq)) return rc;
+        if (int rc = refresh_codebook_operands(h, false, true)) return rc;
+        Timed t(h, SOM_K_BMU);
+        return launch_top2_exact(h, X, n_rows, h->qxsq, h->qXb, h->xmax2 + 1, h->qbmu, h->qbmu2);
+    }
+    if (int rc = refresh_codebook_operands(h, true)) return rc;
+    if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
+    h->t2.rows += n_rows; h->t2.rows_f32 += n_rows;
+    Timed t(h, SOM_K_BMU);
+    return launch_bmu_top2(h, X, n_rows, h->qxsq, h->qbmu, h->qbmu2);
+}
+// ... and the pair to the host (one unit: it is named twice -- include/somhip.h)
+int fetch_top2(som_handle* h, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out) {
+    if (int rc = d2h_blocking(h, ids1_out, h->qbmu, (size_t)n_rows * sizeof(int))) return rc;
+    if (h->K == 1) {
+        std::memcpy(ids2_out, ids1_out, (size_t)n_rows * sizeof(int));
+        return 0;
+    }
+    return d2h_blocking(h, ids2_out, h->qbmu2, (size_t)n_rows * sizeof(int));
+}
+
 int run_quantization_error(som_handle* h, const float* X, long n_rows, double* qe_out) {
     if (int rc = run_quantization_bmu(h, X, n_rows, true)) return rc;
     HIPCHK(h, hipMemsetAsync(h->dsum, 0, sizeof(double), h->stream));
@@ -2168,18 +2207,18 @@ int som_bmu_top2(som_handle* h, const float* x_host, int64_t n_rows, int32_t* id
     if (n_rows == 0) return 0;
     if (int rc = ensure_query_scratch(h, n_rows)) return rc;
     if (int rc = h2d_blocking(h, h->qX, x_host, (size_t)n_rows * h->D * sizeof(float))) return rc;
-    if (int rc = refresh_codebook_operands(h, true)) return rc;
-    if (int rc = row_sq(h, h->qX, n_rows, h->qxsq)) return rc;
-    {
-        Timed t(h, SOM_K_BMU);
-        if (int rc = launch_bmu_top2(h, h->qX, n_rows, h->qxsq, h->qbmu, h->qbmu2)) return rc;
-    }
-    if (int rc = d2h_blocking(h, ids1_out, h->qbmu, (size_t)n_rows * sizeof(int))) return rc;
-    if (h->K == 1) {                                     // (one unit: it is named twice -- include/somhip.h)
-        std::memcpy(ids2_out, ids1_out, (size_t)n_rows * sizeof(int));
-        return 0;
-    }
-    return d2h_blocking(h, ids2_out, h->qbmu2, (size_t)n_rows * sizeof(int));
+    if (int rc = run_top2(h, h->qX, n_rows)) return rc;
+    return fetch_top2(h, n_rows, ids1_out, ids2_out);
+}
+
+int som_bmu_top2_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || n_rows < 0 || (n_rows > 0 && (!x_dev || !ids1_out || !ids2_out))) return fail(h, "som_bmu_top2_device: bad argument");
+    if (n_rows == 0) return 0;
+    if (n_rows > 0x7fffffffL) return fail(h, "som_bmu_top2_device: more than 2^31-1 rows in one call");
+    if (int rc = ensure_query_scratch(h, n_rows, false)) return rc;
+    if (int rc = run_top2(h, (const float*)x_dev, n_rows)) return rc;
+    return fetch_top2(h, n_rows, ids1_out, ids2_out);
 }
 
 int som_distance_matrix(som_handle* h, const float* x_host, int64_t n_rows, int32_t mode, float* dist_out) {
@@ -2369,6 +2408,12 @@ int som_exact_stats(som_handle* h, int64_t* rows, int64_t* rows_fallback, int64_
     if (rows) *rows = h->ex.rows_total;
     if (rows_fallback) *rows_fallback = h->ex.rows_fallback;
     if (passes) *passes = h->ex.chunks;
+    return 0;
+}
+
+int som_exact_top2_stats(som_handle* h, int64_t* rows, int64_t* rows_f32) {
+    if (!h || !rows || !rows_f32) return fail(h, "som_exact_top2_stats: NULL argument");
+    *rows = h->t2.rows; *rows_f32 = h->t2.rows_f32;
     return 0;
 }
 

@@ -263,6 +263,13 @@ class HipEngine:
         self._check(self._lib.som_bmu_top2(self._h, self._fp(x), x.shape[0], self._ip(a), self._ip(b)))
         return a, b
 
+    def bmu_top2_device(self, dev_ptr, n_rows):
+        """(best, second-best) raveled ids of float32 rows that already live in HBM (`dev_ptr`: [n_rows][D], borrowed for the call)."""
+        a = np.empty((int(n_rows),), dtype=np.int32)
+        b = np.empty((int(n_rows),), dtype=np.int32)
+        self._check(self._lib.som_bmu_top2_device(self._h, C.c_void_p(dev_ptr), int(n_rows), self._ip(a), self._ip(b)))
+        return a, b
+
     def distance_matrix(self, x, quantization=False):
         """The (n, K) distance matrix (analysis only)."""
         x = _f32(x)
@@ -314,6 +321,12 @@ class HipEngine:
         kernel) so far."""
         a, b = C.c_int64(), C.c_int64()
         self._check(self._lib.som_debug_qe_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def exact_top2_stats(self):
+        """(rows the top-2 calls served, rows of them the float32 top-2 kernel answered) so far."""
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self._lib.som_exact_top2_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def exact_skip_stats(self):

@@ -468,20 +468,28 @@ class XPySom:
         """Share of samples whose best and second-best matching units are not adjacent on the map
         (xpysom.py:709-746, rectangular branch: |di| > 1 or |dj| > 1).  The reference sorts the whole
         (n, K) distance matrix; here a fused top-2 variant of the BMU kernel returns the pair."""
-        self._check_input_len(data)
+        # rows in HBM are searched where they are, whole (som_bmu_top2_device); host rows in n_parallel chunks
+        q = self._device_query(data)                        # (checks the feature count of device rows itself)
+        if q is None:
+            self._check_input_len(data)
         if np.prod(self._weights.shape) == 1:
             warn('The topographic error is not defined for a 1-by-1 map.')
             return np.nan
-        data = _host_rows(data, self._engine)
-        if self._weights.shape[0] * self._weights.shape[1] == 1 and len(data):
+        if q is None:
+            data = _host_rows(data, self._engine)
+        n_rows = q[2] if q is not None else len(data)
+        if self._weights.shape[0] * self._weights.shape[1] == 1 and n_rows:
             # one unit, input_len > 1: argsort(...)[:, :2] holds one column and its diff none -- the reference's mean over
             # an empty axis is NaN (rectangular), its norm over one is 0 (hexagonal: 0 > 1.5 never)
             return float('nan') if self.topology == 'rectangular' else 0.0
-        eng = self._upload_weights()
+        eng = q[0] if q is not None else self._upload_weights()   # (_device_query has uploaded the codebook)
         Y = self._weights.shape[1]
         bad, n = 0, 0
-        for s in range(0, len(data), self._n_parallel):
-            b1, b2 = eng.bmu_top2(data[s:s + self._n_parallel])
+        if q is not None:
+            pairs = [eng.bmu_top2_device(q[1], n_rows)] if n_rows else []
+        else:
+            pairs = (eng.bmu_top2(data[s:s + self._n_parallel]) for s in range(0, n_rows, self._n_parallel))
+        for b1, b2 in pairs:
             i1, j1, i2, j2 = b1 // Y, b1 % Y, b2 // Y, b2 % Y
             if self.topology == 'hexagonal':
                 # not adjacent = farther apart than 1.5 in the hexagonal coordinates (xpysom.py:739-746).  The
