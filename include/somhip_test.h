@@ -14,6 +14,13 @@ extern "C" {
  * image, bit 1: the float32 image) without marking them stale, as a lost staging copy would (tests/test_gpu_verify.py). */
 int som_debug_corrupt_operands(som_handle* h, int32_t which);
 
+/* read-only: a 64-bit FNV-1a hash of one of the codebook's operand buffers as it stands on the device right now (nothing is
+ * refreshed first).  which: 0 the 16-bit stage image, 1 its second half (exact mode), 2 the float32 stage image, 3 |w|^2 in the
+ * image order, 4 the screen's norms, 5 the {max |w|^2, max rounding error^2} pair, 6 the exact plan's centroids, radii, |c|^2 and
+ * maxima of both levels, 7 the codebook in the image order.  A buffer the handle does not hold hashes as the empty string.
+ * tests/test_gpu_exact_merge_prep.py compares the fused merge's operands with the separate kernels' through it. */
+int som_debug_operand_crc(som_handle* h, int32_t which, uint64_t* out);
+
 /* measurement hook: ONE v_mfma_f32_16x16x32 (_f16 when is_f16, else _bf16) on the caller's operands -- a [16][32] and
  * b [32][16] as 16-bit patterns, c and d [16][16] float32, row-major.  tests/test_gpu_exact.py uses it to measure the
  * rounding error the exact mode's bound charges per MFMA (the hardware's internal summation is not documented). */

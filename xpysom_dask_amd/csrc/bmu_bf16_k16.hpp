@@ -68,14 +68,18 @@ __global__ __launch_bounds__(256) void prep_w_bf16_k16_kernel(const float* __res
 // unit's error is four lanes of one wave.
 // Wst_lo (or null): the same fragments of the units' SECOND half -- lo = half(2^11 ((-w^) - hi)), so that -w^ = hi + 2^-11 lo up
 // to 2^-11 of lo's own magnitude: what the exact mode's refinement pass (bmu_exact.hpp) multiplies beside hi.
+// cm1 / cm2 (or null): the {max |c|^2, max rounding error^2} pairs of the plan's two centroid levels, reset here as
+// exact_centroids_kernel resets them when the fused merge (exact_skip.hpp) has written the centroids before the maximum was known.
 template <int KS32, class EL = Bf16>
 __global__ __launch_bounds__(256) void prep_w_exact_k16_kernel(const float* __restrict__ W, int K, int D,
                                                                char* __restrict__ Wst, int n_stages,
                                                                const float* __restrict__ scale_max2,
-                                                               float* __restrict__ werr2, char* __restrict__ Wst_lo = nullptr) {
+                                                               float* __restrict__ werr2, char* __restrict__ Wst_lo = nullptr,
+                                                               float* __restrict__ cm1 = nullptr, float* __restrict__ cm2 = nullptr) {
     using E = typename EL::T;
     using bf16x8 = typename V8<E>::t;
     const int lane = threadIdx.x & 63;
+    if (cm1 != nullptr && blockIdx.x == 0 && threadIdx.x == 0) { cm1[0] = *scale_max2; cm1[1] = 0.0f; cm2[0] = *scale_max2; cm2[1] = 0.0f; }
     const long tile = (long)blockIdx.x * 4 + (threadIdx.x >> 6);          // (stage, t16)
     if (tile >= (long)n_stages * K16_T) return;
     const long stage = tile / K16_T;

@@ -166,26 +166,29 @@ __global__ __launch_bounds__(256) void dist_matrix_f32_kernel(const float* __res
 // NumPy's and, with the k-ordered fma chain of the MFMA (== OpenBLAS' sgemm micro-kernel for
 // one K block), so is every distance and therefore every BMU, near-ties included.
 // __fmul_rn/__fadd_rn keep hipcc from contracting the square into the add.
-__device__ float np_pairwise_sq_sum(const float* __restrict__ a, int n) {
+// (the leaf, n <= 128, on any pointer type: the exact mode's fused merge runs it over a row held in LDS -- exact_skip.hpp)
+template <class P>
+__device__ __forceinline__ float np_pairwise_sq_sum_leaf(P a, int n) {
     if (n < 8) {
         float res = 0.0f;
         for (int i = 0; i < n; ++i) res = __fadd_rn(res, __fmul_rn(a[i], a[i]));
         return res;
     }
-    if (n <= 128) {
-        float r[8];
+    float r[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = __fmul_rn(a[j], a[j]);
-        int i = 8;
-        for (; i < n - (n % 8); i += 8) {
+    for (int j = 0; j < 8; ++j) r[j] = __fmul_rn(a[j], a[j]);
+    int i = 8;
+    for (; i < n - (n % 8); i += 8) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) r[j] = __fadd_rn(r[j], __fmul_rn(a[i + j], a[i + j]));
-        }
-        float res = __fadd_rn(__fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3])),
-                              __fadd_rn(__fadd_rn(r[4], r[5]), __fadd_rn(r[6], r[7])));
-        for (; i < n; ++i) res = __fadd_rn(res, __fmul_rn(a[i], a[i]));
-        return res;
+        for (int j = 0; j < 8; ++j) r[j] = __fadd_rn(r[j], __fmul_rn(a[i + j], a[i + j]));
     }
+    float res = __fadd_rn(__fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3])),
+                          __fadd_rn(__fadd_rn(r[4], r[5]), __fadd_rn(r[6], r[7])));
+    for (; i < n; ++i) res = __fadd_rn(res, __fmul_rn(a[i], a[i]));
+    return res;
+}
+__device__ float np_pairwise_sq_sum(const float* __restrict__ a, int n) {
+    if (n <= 128) return np_pairwise_sq_sum_leaf(a, n);
     int n2 = n / 2;
     n2 -= n2 % 8;
     return __fadd_rn(np_pairwise_sq_sum(a, n2), np_pairwise_sq_sum(a + n2, n - n2));

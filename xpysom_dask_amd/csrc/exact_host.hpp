@@ -342,7 +342,9 @@ int exact_skip_centroids(som_handle* h, const float* xmax2) {
     const CentroidLevel l1{c0.Cc, c0.rg, c0.csq, c0.cmax2, c0.n_slots}, l2{c1.Cc, c1.rg, c1.csq, c1.cmax2, c1.n_slots};
     // two launches for both levels: centroids + radii + |c|^2, then the stage images with their tails (the images take the
     // codebook's own power of two: a centroid is no longer than the longest unit)
-    exact_centroids_kernel<<<dim3((unsigned)(cdiv(n_groups, 4) * 4)), dim3(512), 0, h->stream>>>(Wsrc, h->K, h->D, n_groups, l1, l2, h->wmax2);
+    // (cen_fresh: the fused merge has written the first launch's outputs for this codebook -- exact_merge_prep_kernel)
+    if (!ex.cen_fresh)
+        exact_centroids_kernel<<<dim3((unsigned)(cdiv(n_groups, 4) * 4)), dim3(512), 0, h->stream>>>(Wsrc, h->K, h->D, n_groups, l1, l2, h->wmax2);
     const int nst2 = ex.lp.level2 ? c1.n_cstages : 0;
     char* plain = ex.lp.scout ? c0.Cst_plain : nullptr;
     const dim3 tgrid((unsigned)cdiv((long)(c0.n_cstages + nst2) * K16_T, 4)), block(256);

@@ -33,6 +33,7 @@
 // outwards; a row whose quantities are not finite needs every block.
 #pragma once
 #include "bmu_bf16_k16.hpp"
+#include "bmu_f32_res.hpp"
 
 namespace somhip {
 
@@ -49,27 +50,26 @@ static_assert(K16_STAGE_UNITS == 64 && K16_T == 4, "block skipping: a stage of t
 // codebook's own scale (no reduction over the centroids); the error slot is reset here and filled by the image kernel.
 struct CentroidLevel { float* C; float* rg; float* csq; float* cmax2; int n_slots; };
 // (eight waves: thread (feature d, quarter q) holds the sixteen units of sub-block q -- a group's 32 KB are in flight at once)
-__global__ __launch_bounds__(512) void exact_centroids_kernel(const float* __restrict__ W, int K, int D, int n_groups,
-                                                              CentroidLevel l1, CentroidLevel l2, const float* __restrict__ wmax2) {
-    __shared__ float qsum[4][128];                            // the sub-blocks' feature sums
-    __shared__ float part[2][64][2];                          // [feature half][unit][group / sub-block]: partial |w - c|^2
-    __shared__ float csq_s[2][5];
-    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+struct CentroidShared {
+    float qsum[4][128];                                       // the sub-blocks' feature sums
+    float part[2][64][2];                                     // [feature half][unit][group / sub-block]: partial |w - c|^2
+    float csq_s[2][5];
+};
+// The arithmetic itself, on the sixteen units a thread holds (w[k] = 0 beyond the group's units and the features): shared by
+// exact_centroids_kernel and the fused merge below, so that both write the same bits.  Every thread of the 512 calls it.
+__device__ __forceinline__ void group_centroids(const float (&w)[16], int g, int K, int D, const CentroidLevel& l1,
+                                                const CentroidLevel& l2, CentroidShared& sh) {
+    const int tid = threadIdx.x, lane = tid & 63;
     const int d = tid & 127, q = tid >> 7, fh = (tid >> 6) & 1;   // feature, sub-block, which 64 features of the 128
-    const long u0 = (long)g * 64 + 16 * q;
     const int cnt = (int)max(0L, min(64L, (long)K - (long)g * 64));
     const int cb = max(0, min(16, cnt - 16 * q));
-    if (g == 0 && tid == 0) { l1.cmax2[0] = *wmax2; l1.cmax2[1] = 0.0f; l2.cmax2[0] = *wmax2; l2.cmax2[1] = 0.0f; }
-    float w[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) w[k] = (d < D && k < cb) ? W[(u0 + k) * D + d] : 0.0f;
     float sum = 0.0f;
 #pragma unroll
     for (int k = 0; k < 16; ++k) sum += w[k];
-    qsum[q][d] = sum;
+    sh.qsum[q][d] = sum;
     __syncthreads();
     const float cs = cb > 0 ? sum / (float)cb : 0.0f;
-    const float cg = cnt > 0 ? ((qsum[0][d] + qsum[1][d]) + (qsum[2][d] + qsum[3][d])) / (float)cnt : 0.0f;
+    const float cg = cnt > 0 ? ((sh.qsum[0][d] + sh.qsum[1][d]) + (sh.qsum[2][d] + sh.qsum[3][d])) / (float)cnt : 0.0f;
     if (d < D) {
         if (q == 0 && g < l1.n_slots) l1.C[(long)g * D + d] = cg;
         const int j = 16 * (g >> 2) + 4 * (g & 3) + q;
@@ -78,8 +78,8 @@ __global__ __launch_bounds__(512) void exact_centroids_kernel(const float* __res
     // |c|^2 of the five centroids (float32, any order: the plan's margin covers it)
     {
         const float a = wave_sum(cs * cs);
-        if (lane == 0) csq_s[fh][1 + q] = a;
-        if (q == 0) { const float bq = wave_sum(cg * cg); if (lane == 0) csq_s[fh][0] = bq; }
+        if (lane == 0) sh.csq_s[fh][1 + q] = a;
+        if (q == 0) { const float bq = wave_sum(cg * cg); if (lane == 0) sh.csq_s[fh][0] = bq; }
     }
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(512) void exact_centroids_kernel(const float* __res
             const float dg = w[k] - cg, ds = w[k] - cs;
             const float qg = wave_sum(d < D ? dg * dg : 0.0f);    // (a NaN anywhere in the unit: NaN)
             const float qs = wave_sum(d < D ? ds * ds : 0.0f);
-            if (lane == 0) { part[fh][16 * q + k][0] = qg; part[fh][16 * q + k][1] = qs; }
+            if (lane == 0) { sh.part[fh][16 * q + k][0] = qg; sh.part[fh][16 * q + k][1] = qs; }
         }
     }
     __syncthreads();
@@ -97,17 +97,125 @@ __global__ __launch_bounds__(512) void exact_centroids_kernel(const float* __res
         const int k0 = tid == 0 ? 0 : 16 * b, k1 = tid == 0 ? cnt : min(cnt, 16 * b + 16);
         float m = 0.0f;
         for (int k = k0; k < k1; ++k) {
-            const float d2 = part[0][k][tid == 0 ? 0 : 1] + part[1][k][tid == 0 ? 0 : 1];
+            const float d2 = sh.part[0][k][tid == 0 ? 0 : 1] + sh.part[1][k][tid == 0 ? 0 : 1];
             m = (d2 > m || !(d2 == d2)) ? d2 : m;             // (a NaN unit: a NaN radius, the block is never skipped)
         }
         // (the sum of squares in float32, any order: relative error <= 128 * 2^-24; the margin covers it many times over)
         const float r = k1 > k0 ? __builtin_sqrtf(m) * (1.0f + 1.0f / 512.0f) + 1.0e-30f : -1.0f;
-        const float sq = csq_s[0][tid] + csq_s[1][tid];
+        const float sq = sh.csq_s[0][tid] + sh.csq_s[1][tid];
         if (tid == 0) { if (g < l1.n_slots) { l1.rg[g] = r; l1.csq[g] = sq; } }
         else {
             const int j = 16 * (g >> 2) + 4 * (g & 3) + b;
             if (j < l2.n_slots) { l2.rg[j] = r; l2.csq[j] = sq; }
         }
+    }
+}
+
+__global__ __launch_bounds__(512) void exact_centroids_kernel(const float* __restrict__ W, int K, int D, int n_groups,
+                                                              CentroidLevel l1, CentroidLevel l2, const float* __restrict__ wmax2) {
+    __shared__ CentroidShared sh;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int d = tid & 127, q = tid >> 7;
+    const long u0 = (long)g * 64 + 16 * q;
+    const int cnt = (int)max(0L, min(64L, (long)K - (long)g * 64));
+    const int cb = max(0, min(16, cnt - 16 * q));
+    if (g == 0 && tid == 0) { l1.cmax2[0] = *wmax2; l1.cmax2[1] = 0.0f; l2.cmax2[0] = *wmax2; l2.cmax2[1] = 0.0f; }
+    float w[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) w[k] = (d < D && k < cb) ? W[(u0 + k) * D + d] : 0.0f;
+    group_centroids(w, g, K, D, l1, l2, sh);
+}
+
+// THE FUSED MERGE of the exact mode (euclidean, input_len <= 128; som_epoch_merge): one read of the accumulator writes what
+// the next epoch's first launch needs of the new codebook, each bit for bit what the separate kernels write --
+//   merge_kernel            W (unit order) and Wp (patch order): den != 0 ? num / den : the old row;
+//   row_sq_f32_kernel       wsq, wsq_p: np_pairwise_sq_sum's own leaf over a padded copy of the group in LDS, a thread per unit;
+//   exact_copy_wsq_kernel   wn and the maximum of |w|^2 into wmax2[0] (the host zeroed the pair in front of this launch);
+//   prep_w_f32_res_kernel   the group's stage of the float32 image Wfst (FR_STAGE_UNITS = one group) in the image order;
+//   exact_centroids_kernel  centroids, radii, |c|^2 of both levels (l1.C != null; cmax2 waits for the final maximum: the 16-bit
+//                           image's kernel resets it, prep_w_exact_k16_kernel).
+// Workgroup g <-> group g of the IMAGE ORDER (perm[position] = unit, or null: the units' own order): thread (feature d,
+// quarter q) holds sixteen units as exact_centroids_kernel does, so every load and store of a row is one contiguous piece.
+constexpr int MPX_STRIDE = 129;       // floats between two units of the LDS copy: a thread per unit walks its row without bank conflicts
+static_assert(FR_STAGE_UNITS == 64, "the fused merge writes one float32 stage per 64-unit group");
+struct MergePrepOut {
+    float* W; float* Wp; const int* perm;
+    float* wsq; float* wsq_p; float* wn; float* wmax2;
+    char* Wfst; int fr_kg;                                     // (Wfst null: the float32 image is left to its own kernel)
+};
+__global__ __launch_bounds__(512) void exact_merge_prep_kernel(const float* __restrict__ ACC, int K, int D, int D1p, int n_groups,
+                                                               MergePrepOut o, CentroidLevel l1, CentroidLevel l2) {
+    __shared__ CentroidShared sh;
+    __shared__ float ws[64 * MPX_STRIDE];
+    __shared__ int u_s[64];
+    __shared__ float den_s[64];
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int d = tid & 127, q = tid >> 7;
+    const int cnt = (int)max(0L, min(64L, (long)K - (long)g * 64));
+    const int cb = max(0, min(16, cnt - 16 * q));
+    if (tid < cnt) {
+        const int pos = g * 64 + tid;
+        const int u = o.perm != nullptr ? o.perm[pos] : pos;
+        u_s[tid] = u;
+        den_s[tid] = ACC[(long)u * D1p + D];
+    }
+    __syncthreads();
+    // (w[] is written by selects only: a store into the array under a branch makes the compiler copy all sixteen registers)
+    float w[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {                            // every load of the thread's sixteen units first
+        const bool on = d < D && k < cb;
+        const long u = on ? u_s[16 * q + k] : 0;
+        // (no row in reach of a unit: the old weights stay; a thread without an element reads a valid address and drops it)
+        const float* src = !on ? ACC : den_s[16 * q + k] != 0.0f ? ACC + u * D1p + d : o.W + u * D + d;
+        const float v = *src;
+        w[k] = on ? v : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const bool on = d < D && k < cb;
+        const int i = 16 * q + k;
+        const float den = on ? den_s[i] : 0.0f;
+        const float v = w[k] / den;
+        w[k] = den != 0.0f ? v : w[k];
+        if (on) {
+            const long u = u_s[i];
+            if (den != 0.0f) o.W[u * D + d] = w[k];
+            if (o.Wp != nullptr) o.Wp[((long)g * 64 + i) * D + d] = w[k];
+            ws[i * MPX_STRIDE + d] = w[k];
+        }
+    }
+    if (l1.C != nullptr) group_centroids(w, g, K, D, l1, l2, sh);   // (its barriers order the LDS copy as well)
+    else __syncthreads();
+    if (g >= n_groups) return;                                // (the grid covers whole level-2 tiles: groups without units)
+    if (o.Wfst != nullptr) {
+        char* base = o.Wfst + (long)g * fr_stage_bytes(o.fr_kg);
+        for (int r = tid; r < FR_UT * o.fr_kg * 64; r += 512) {   // prep_w_f32_res_kernel's chunk r of the stage
+            const int lane = r & 63, t = r >> 6;
+            const int gk = t % o.fr_kg, i = (t / o.fr_kg) * 32 + (lane & 31);
+            f32x4 v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k = 8 * gk + 2 * j + (lane >> 5);
+                v[j] = (i < cnt && k < D) ? ws[i * MPX_STRIDE + k] : 0.0f;
+            }
+            *(f32x4*)(base + (long)r * 16) = v;
+        }
+    }
+    if (tid < 64) {                                           // a thread per unit: |w|^2 in NumPy's order
+        float qv = __builtin_inff(), m = 0.0f;
+        if (tid < cnt) {
+            const int pos = g * 64 + tid;
+            qv = np_pairwise_sq_sum_leaf((const float*)(ws + tid * MPX_STRIDE), D);
+            o.wsq[u_s[tid]] = qv;
+            if (o.wsq_p != nullptr) o.wsq_p[pos] = qv;
+            o.wn[pos] = qv;
+            m = (qv == qv) ? qv : 0.0f;
+        }
+        if (o.Wfst != nullptr) ((float*)(o.Wfst + (long)g * fr_stage_bytes(o.fr_kg) + (long)FR_UT * o.fr_kg * 1024))[tid] = qv;
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s, 64));
+        if (tid == 0) atomic_max_pos_f32(o.wmax2, m);
     }
 }
 

@@ -156,6 +156,7 @@ struct som_handle {
             DevBuf<int> lastpos_s;        // position (patch order) of every sorted row's (pseudo) last BMU
         } srt[2];
         bool cen_ready = false;           // both centroid levels are allocated
+        bool cen_fresh = false;           // ... and hold the current codebook's centroids, radii, |c|^2: the fused merge wrote them
         long sk_stride = 0;               // rows per pass the per-pass plan buffers hold
         int res_every = 0;                // SOM_EXACT_RESORT=n: re-sort every n-th planned epoch (0: when the order has gone stale)
         DevBuf<int> sk_keys, sk_keys2, sk_vals;
@@ -218,6 +219,9 @@ struct som_handle {
     // operands derived from W, rebuilt lazily: the bf16 stage image (w_dirty), |w|^2 (wsq_dirty) and the
     // float32 stage / tile images (wf_dirty).  Training in bf16 precision never touches the float32 images.
     bool w_dirty = true, wsq_dirty = true, wf_dirty = true, wp_dirty = true;   // (wp: the patch-order copy, exact mode)
+    // exact mode, input_len <= 128: the fused merge (exact_merge_prep_kernel) has left wn and wmax2[0] = max |w|^2 of the current
+    // codebook and wmax2[1] zeroed: the next prep_codebook_half goes straight to the 16-bit images (and takes the flag down)
+    bool wn_fresh = false;
 
     // resident training rows
     const float* Xd = nullptr;   // X_owned, or the caller's device rows (som_set_data_device)
@@ -464,7 +468,10 @@ int resolve_profile(som_handle* h) {
     case 21: return fn<21, E>(__VA_ARGS__); case 22: return fn<22, E>(__VA_ARGS__); case 23: return fn<23, E>(__VA_ARGS__); case 24: return fn<24, E>(__VA_ARGS__); \
     case 25: return fn<25, E>(__VA_ARGS__); }
 
-void mark_codebook_changed(som_handle* h) { h->w_dirty = h->wsq_dirty = h->wf_dirty = h->wp_dirty = true; }
+void mark_codebook_changed(som_handle* h) {
+    h->w_dirty = h->wsq_dirty = h->wf_dirty = h->wp_dirty = true;
+    h->wn_fresh = false; h->ex.cen_fresh = false;
+}
 
 // the 16-bit operand images of the codebook: stage / tile image, |w~|^2 per unit and its maximum
 template <class E>
@@ -512,14 +519,20 @@ int prep_codebook_half(som_handle* h) {
     if (h->exact) {
         // the float32 kernel's own |w|^2 (refreshed just before) and its maximum first: the units go in scaled by
         // ex_scale(max |w|^2); then the scaled stage image and the units' rounding errors in one pass
-        HIPCHK(h, hipMemsetAsync(h->wmax2, 0, 2 * sizeof(float), h->stream));     // [0]: max |w|^2, [1]: max_k |w^_k - w~_k|^2
-        exact_copy_wsq_kernel<<<dim3((unsigned)cdiv(h->K, 1024)), dim3(1024), 0, h->stream>>>(qex, h->K, h->wn, h->wmax2);
+        // (after a fused merge both are there already, and the pair was zeroed in front of it: exact_merge_prep_kernel)
+        if (!h->wn_fresh) {
+            HIPCHK(h, hipMemsetAsync(h->wmax2, 0, 2 * sizeof(float), h->stream));     // [0]: max |w|^2, [1]: max_k |w^_k - w~_k|^2
+            exact_copy_wsq_kernel<<<dim3((unsigned)cdiv(h->K, 1024)), dim3(1024), 0, h->stream>>>(qex, h->K, h->wn, h->wmax2);
+        }
+        h->wn_fresh = false;
+        // (centroids the fused merge wrote: their levels' maxima are due now that max |w|^2 is final)
+        float* cm1 = h->ex.cen_fresh ? (float*)h->ex.cen[0].cmax2 : nullptr;
+        float* cm2 = h->ex.cen_fresh ? (float*)h->ex.cen[1].cmax2 : nullptr;
         const dim3 tgrid((unsigned)cdiv((long)h->n_stages * K16_T, 4));
         switch (h->ks32) {
-        case 1: prep_w_exact_k16_kernel<1, E><<<tgrid, block, 0, h->stream>>>(Wex, h->K, h->D, h->Wst, h->n_stages, h->wmax2, h->wmax2 + 1, h->Wst_lo); break;
-        case 2: prep_w_exact_k16_kernel<2, E><<<tgrid, block, 0, h->stream>>>(Wex, h->K, h->D, h->Wst, h->n_stages, h->wmax2, h->wmax2 + 1, h->Wst_lo); break;
-        case 3: prep_w_exact_k16_kernel<3, E><<<tgrid, block, 0, h->stream>>>(Wex, h->K, h->D, h->Wst, h->n_stages, h->wmax2, h->wmax2 + 1, h->Wst_lo); break;
-        case 4: prep_w_exact_k16_kernel<4, E><<<tgrid, block, 0, h->stream>>>(Wex, h->K, h->D, h->Wst, h->n_stages, h->wmax2, h->wmax2 + 1, h->Wst_lo); break;
+#define SOM_PREPX_CASE(k) case k: prep_w_exact_k16_kernel<k, E><<<tgrid, block, 0, h->stream>>>(Wex, h->K, h->D, h->Wst, h->n_stages, h->wmax2, h->wmax2 + 1, h->Wst_lo, cm1, cm2); break;
+        SOM_PREPX_CASE(1) SOM_PREPX_CASE(2) SOM_PREPX_CASE(3) SOM_PREPX_CASE(4)
+#undef SOM_PREPX_CASE
         default: return fail(h, "the resident half-precision kernel supports input_len <= 128");
         }
         return 0;
@@ -1848,6 +1861,32 @@ int som_epoch_merge(som_handle* h) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
     Timed t(h, SOM_K_MERGE);
+    // the exact mode up to 128 features (euclidean): the merge also writes the patch-order copy, |w|^2 and its maximum, the
+    // float32 stage image and the plan's centroids -- everything of the next epoch's operands that does not wait for the
+    // maximum (exact_merge_prep_kernel); the 16-bit images follow at the head of the BMU launch (w_dirty stays set)
+    if (h->fuse_merge_prep && h->exact && !h->tiled) {
+        const int n_groups = (int)cdiv(h->K, EX_GROUP);
+        const bool cen = h->ex.cen_ready;
+        HIPCHK(h, hipMemsetAsync(h->wmax2, 0, 2 * sizeof(float), h->stream));     // [0]: max |w|^2, [1]: max_k |w^_k - w~_k|^2
+        const MergePrepOut o{h->W, h->ex_patch ? (float*)h->Wp : nullptr, h->ex_patch ? (const int*)h->ex_perm : nullptr,
+                             h->wsq, h->ex_patch ? (float*)h->wsq_p : nullptr, h->wn, h->wmax2, h->Wfst, h->fr_kg};
+        CentroidLevel l1{nullptr, nullptr, nullptr, nullptr, 0}, l2 = l1;
+        if (cen) {
+            auto& c0 = h->ex.cen[0];
+            auto& c1 = h->ex.cen[1];
+            l1 = CentroidLevel{c0.Cc, c0.rg, c0.csq, c0.cmax2, c0.n_slots};
+            l2 = CentroidLevel{c1.Cc, c1.rg, c1.csq, c1.cmax2, c1.n_slots};
+        }
+        const unsigned grid = (unsigned)(cen ? cdiv(n_groups, 4) * 4 : n_groups);
+        exact_merge_prep_kernel<<<dim3(grid), dim3(512), 0, h->stream>>>(h->ACC, h->K, h->D, h->D1p, n_groups, o, l1, l2);
+        HIPCHK(h, hipGetLastError());
+        mark_codebook_changed(h);
+        h->wsq_dirty = false; h->wp_dirty = false;
+        if (h->Wfst) { h->wf_dirty = false; h->wf_patch = h->ex_patch; }
+        h->wn_fresh = true;
+        h->ex.cen_fresh = cen;
+        return 0;
+    }
     // the half-precision paths whose operand image is a stage image (resident kernel, euclidean; wide kernel,
     // euclidean and cosine): the merge also writes the next epoch's 16-bit operands
     if (h->fuse_merge_prep && ((is_half1(h) && !h->tiled && h->cfg.distance == SOM_DIST_EUCLIDEAN) ||
@@ -2279,6 +2318,55 @@ int som_debug_corrupt_operands(som_handle* h, int32_t which) {
     }
     if ((which & 2) && h->Wfst) HIPCHK(h, hipMemsetAsync(h->Wfst, 0, (size_t)h->fr_stages * fr_stage_bytes(h->fr_kg), h->stream));
     if ((which & 2) && h->Wfimg) HIPCHK(h, hipMemsetAsync(h->Wfimg, 0, (size_t)h->ft_ublocks * h->ft_kchunks * FT_WTILE, h->stream));
+    return 0;
+}
+
+// TEST HOOK, read-only: a 64-bit FNV-1a hash of one of the codebook's operand buffers as it stands on the device (nothing is
+// refreshed).  which: 0 Wst, 1 Wst_lo, 2 Wfst, 3 |w|^2 in the image order (wsq_p, or wsq without patch order), 4 wn, 5 the wmax2
+// pair, 6 the plan's centroids, radii, |c|^2 and maxima (both levels), 7 the codebook in the image order (Wp, or W).  A buffer
+// the handle does not hold hashes as the empty string.
+int som_debug_operand_crc(som_handle* h, int32_t which, uint64_t* out) {
+    DeviceGuard dev_guard(h);
+    if (!h || !out) return 1;
+    uint64_t hash = 0xcbf29ce484222325ull;
+    std::vector<unsigned char> host;
+    auto add = [&](const void* dev, size_t bytes) -> int {
+        if (dev == nullptr || bytes == 0) return 0;
+        host.resize(bytes);
+        if (int rc = d2h_blocking(h, host.data(), dev, bytes)) return rc;
+        for (size_t i = 0; i < bytes; ++i) { hash ^= host[i]; hash *= 0x100000001b3ull; }
+        return 0;
+    };
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const bool half = h->cfg.precision != SOM_PREC_F32;
+    size_t st_bytes = (size_t)h->n_stages * h->stage_bytes;
+    if (h->tiled && !h->wide) st_bytes = (size_t)h->n_ublocks * h->n_kchunks * h->tl_wtile;
+    int rc = 0;
+    switch (which) {
+    case 0: rc = add(h->Wst, half ? st_bytes : 0); break;
+    case 1: rc = add(h->Wst_lo, st_bytes); break;
+    case 2:                                               // (a stage's fragments and its 64 norms: the rest of the last KiB is never written)
+        for (int st = 0; h->Wfst && st < h->fr_stages && rc == 0; ++st)
+            rc = add((const char*)h->Wfst + (size_t)st * fr_stage_bytes(h->fr_kg), (size_t)FR_UT * h->fr_kg * 1024 + 64 * sizeof(float));
+        break;
+    case 3: rc = add(h->ex_patch ? (const float*)h->wsq_p : (const float*)h->wsq, (size_t)h->K * sizeof(float)); break;
+    case 4: rc = add(h->wn, half ? (size_t)h->K * sizeof(float) : 0); break;
+    case 5: rc = add(h->wmax2, half ? 2 * sizeof(float) : 0); break;
+    case 6:
+        if (h->ex.cen_ready)
+            for (int lv = 0; lv < (h->wide ? 1 : 2) && rc == 0; ++lv) {
+                auto& c = h->ex.cen[lv];
+                if ((rc = add(c.Cc, (size_t)c.n_slots * h->D * sizeof(float)))) break;
+                if ((rc = add(c.rg, (size_t)c.n_slots * sizeof(float)))) break;
+                if ((rc = add(c.csq, (size_t)c.n_slots * sizeof(float)))) break;
+                rc = add(c.cmax2, 2 * sizeof(float));
+            }
+        break;
+    case 7: rc = add(h->ex_patch ? (const float*)h->Wp : (const float*)h->W, (size_t)h->K * h->D * sizeof(float)); break;
+    default: return fail(h, "som_debug_operand_crc: unknown buffer");
+    }
+    if (rc) return rc;
+    *out = hash;
     return 0;
 }
 
