@@ -35,6 +35,10 @@ int som_debug_device_bytes(int64_t* out);
  * tie-window test sent on to the float32 SQRT kernel (som_quantization_error*, include/somhip.h). */
 int som_debug_qe_stats(som_handle* h, int64_t* rows, int64_t* rows_sqrt);
 
+/* precision EXACT, planned epochs over the resident rows: how many of them took the sorted rows' last-BMU positions from
+ * the epoch before (stored by its exact_finalize_kernel) instead of gathering them with exact_lastpos_kernel. */
+int som_debug_exact_chain_stats(som_handle* h, int64_t* carried_epochs);
+
 /* diagnostic builds only (-DSOM_STAMPS, tools/stamps.py builds one on demand): out_host == NULL attaches a buffer of n_pairs
  * (shader-clock ticks, 100 MHz ticks) pairs, one per workgroup of the next BMU launches (n_pairs == 0 detaches);
  * out_host != NULL reads n_pairs pairs back.  The product build refuses both. */

@@ -121,13 +121,13 @@ __global__ __launch_bounds__(256) void prep_wnorm_kernel(const float* __restrict
 
 // initial accumulators  B + |w~|^2/2  written behind each stage's fragments; B from the two maxima
 // (+ the launch's per-row merge keys best64[0..n_rows) = all ones, when given: one launch instead of a memset and a kernel)
-__global__ __launch_bounds__(256) void prep_wsqh_kernel(const float* __restrict__ wn, int K,
-                                                        const float* __restrict__ wmax2,
-                                                        const float* __restrict__ xmax2, char* __restrict__ Wst,
-                                                        int n_stages, int stage_bytes, int stage_units,
-                                                        unsigned long long* __restrict__ best64, long n_rows,
-                                                        int scaled = 0) {
-    long u = (long)blockIdx.x * 256 + threadIdx.x;
+// (the body, for block `bid` of 256 threads: shared with exact_prep_images_kernel, exact_skip.hpp)
+__device__ __forceinline__ void prep_wsqh_body(const unsigned bid, const float* __restrict__ wn, int K,
+                                               const float* __restrict__ wmax2,
+                                               const float* __restrict__ xmax2, char* __restrict__ Wst,
+                                               int n_stages, int stage_bytes, int stage_units,
+                                               unsigned long long* __restrict__ best64, long n_rows, int scaled) {
+    long u = (long)bid * 256 + threadIdx.x;
     if (best64 != nullptr && u < n_rows) best64[u] = ~0ull;
     if (u >= (long)n_stages * stage_units) return;
     const float big = __builtin_sqrtf(*wmax2) * __builtin_sqrtf(*xmax2) * (1.0f + 1.0f / 1024.0f);
@@ -138,6 +138,14 @@ __global__ __launch_bounds__(256) void prep_wsqh_kernel(const float* __restrict_
     int within = u % stage_units;
     float* dst = (float*)(Wst + (stage + 1) * (long)stage_bytes - 1024);   // the stage's last KiB
     dst[within] = s;
+}
+__global__ __launch_bounds__(256) void prep_wsqh_kernel(const float* __restrict__ wn, int K,
+                                                        const float* __restrict__ wmax2,
+                                                        const float* __restrict__ xmax2, char* __restrict__ Wst,
+                                                        int n_stages, int stage_bytes, int stage_units,
+                                                        unsigned long long* __restrict__ best64, long n_rows,
+                                                        int scaled = 0) {
+    prep_wsqh_body(blockIdx.x, wn, K, wmax2, xmax2, Wst, n_stages, stage_bytes, stage_units, best64, n_rows, scaled);
 }
 
 // samples -> bf16 rows [Np][Dp] (zero padded) and max_n |x~_n|^2.  One wave per row.

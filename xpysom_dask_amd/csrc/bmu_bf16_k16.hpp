@@ -70,17 +70,22 @@ __global__ __launch_bounds__(256) void prep_w_bf16_k16_kernel(const float* __res
 // to 2^-11 of lo's own magnitude: what the exact mode's refinement pass (bmu_exact.hpp) multiplies beside hi.
 // cm1 / cm2 (or null): the {max |c|^2, max rounding error^2} pairs of the plan's two centroid levels, reset here as
 // exact_centroids_kernel resets them when the fused merge (exact_skip.hpp) has written the centroids before the maximum was known.
-template <int KS32, class EL = Bf16>
-__global__ __launch_bounds__(256) void prep_w_exact_k16_kernel(const float* __restrict__ W, int K, int D,
-                                                               char* __restrict__ Wst, int n_stages,
-                                                               const float* __restrict__ scale_max2,
-                                                               float* __restrict__ werr2, char* __restrict__ Wst_lo = nullptr,
-                                                               float* __restrict__ cm1 = nullptr, float* __restrict__ cm2 = nullptr) {
+// (the body, for block `bid` of 256 threads -- shared with exact_prep_images_kernel, exact_skip.hpp, whose centroid blocks are
+//  already adding to the levels' error maxima while this one runs: cm_err false leaves those words to them)
+template <int KS32, class EL>
+__device__ __forceinline__ void prep_w_exact_k16_body(const unsigned bid, const float* __restrict__ W, int K, int D,
+                                                      char* __restrict__ Wst, int n_stages,
+                                                      const float* __restrict__ scale_max2,
+                                                      float* __restrict__ werr2, char* __restrict__ Wst_lo,
+                                                      float* __restrict__ cm1, float* __restrict__ cm2, const bool cm_err) {
     using E = typename EL::T;
     using bf16x8 = typename V8<E>::t;
     const int lane = threadIdx.x & 63;
-    if (cm1 != nullptr && blockIdx.x == 0 && threadIdx.x == 0) { cm1[0] = *scale_max2; cm1[1] = 0.0f; cm2[0] = *scale_max2; cm2[1] = 0.0f; }
-    const long tile = (long)blockIdx.x * 4 + (threadIdx.x >> 6);          // (stage, t16)
+    if (cm1 != nullptr && bid == 0 && threadIdx.x == 0) {
+        cm1[0] = *scale_max2; cm2[0] = *scale_max2;
+        if (cm_err) { cm1[1] = 0.0f; cm2[1] = 0.0f; }
+    }
+    const long tile = (long)bid * 4 + (threadIdx.x >> 6);                 // (stage, t16)
     if (tile >= (long)n_stages * K16_T) return;
     const long stage = tile / K16_T;
     const int t16 = (int)(tile - stage * K16_T);
@@ -110,6 +115,14 @@ __global__ __launch_bounds__(256) void prep_w_exact_k16_kernel(const float* __re
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
     if (lane == 0) atomic_max_pos_f32(werr2, m);
+}
+template <int KS32, class EL = Bf16>
+__global__ __launch_bounds__(256) void prep_w_exact_k16_kernel(const float* __restrict__ W, int K, int D,
+                                                               char* __restrict__ Wst, int n_stages,
+                                                               const float* __restrict__ scale_max2,
+                                                               float* __restrict__ werr2, char* __restrict__ Wst_lo = nullptr,
+                                                               float* __restrict__ cm1 = nullptr, float* __restrict__ cm2 = nullptr) {
+    prep_w_exact_k16_body<KS32, EL>(blockIdx.x, W, K, D, Wst, n_stages, scale_max2, werr2, Wst_lo, cm1, cm2, true);
 }
 
 // _merge_updates (xpysom.py:446-455) fused with the NEXT epoch's operand preparation: one pass over the fused

@@ -103,6 +103,7 @@ struct PassCounters {
     int pairs_out;    // exact_select2_kernel: ... the refinement pass kept
     int scout_wins;   // exact_plan_kernel: rows whose scout pick beat their last BMU by a tenth of the squared distance
     int bad_w;        // exact_top2_settle_kernel: the codebook holds a unit whose |w|^2 is not finite
+    int lists_done;   // exact_lists_totals_kernel: its workgroups' tickets (the last one sets it back to zero)
 };
 // The row-need estimate (exact_scout_rowneed_kernel, exact_skip.hpp) runs before a launch's first pass and borrows the head of the block.
 struct RowNeed {
@@ -147,7 +148,8 @@ __global__ __launch_bounds__(64 * EX_SCAN_SPLIT) void exact_select_kernel(const 
                                                                          const int* __restrict__ gcnt = nullptr,
                                                                          int rows_per_list = 0,
                                                                          const float* __restrict__ t2min = nullptr,
-                                                                         int t2parts = 0, long t2pitch = 0) {
+                                                                         int t2parts = 0, long t2pitch = 0,
+                                                                         uint32_t* __restrict__ rowmin2_init = nullptr) {
     static_assert(!(ROUND2 && TOP2), "top-2 uses the one-round scheme");
     __shared__ int cnt_s[EX_SCAN_SPLIT][64];
     const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
@@ -266,6 +268,8 @@ __global__ __launch_bounds__(64 * EX_SCAN_SPLIT) void exact_select_kernel(const 
 #pragma unroll
         for (int p = 0; p < EX_SCAN_SPLIT; ++p) t += cnt_s[p][lane];
         rowcnt[row] = t + (ROUND2 && arg >= 0 ? 1 : 0);
+        // (a launch that refines: the row's refined minimum starts from all ones -- exact_refine_kernel's atomicMin)
+        if (rowmin2_init != nullptr) rowmin2_init[row] = 0xFFFFFFFFu;
     }
 }
 
@@ -342,7 +346,8 @@ __global__ __launch_bounds__(256) void exact_first_kernel(unsigned long long* __
 
 // gcount -> the tile table (group, first list entry of the tile in plist, its rows) and n_tiles; more pairs than
 // `capacity` (a degenerate codebook: the float32 kernel over all units costs less than re-scoring that many pairs) ->
-// overflow flag, no tiles.  One block.
+// overflow flag, no tiles.  One block -- or a handful (gridDim.x): every block repeats the scan of the counts (a few KB out of
+// L2) and writes an equal share of the table's entries; block 0 writes the scalars and gstart_out.
 // gstart (nullptr: zeros): the lists' entries before it were tiled by an earlier round; gstart_out (nullptr: none) takes
 // the lists' lengths as the next round's gstart.
 __global__ __launch_bounds__(1024) void exact_tiles_kernel(const int* __restrict__ gcount, int n_groups, long gm_stride,
@@ -380,11 +385,14 @@ __global__ __launch_bounds__(1024) void exact_tiles_kernel(const int* __restrict
         if (w < wave) tbefore += wtsum[w];
         total += wsum[w]; ttotal += wtsum[w];
     }
-    if (tid == 0 && pairs_out != nullptr) *pairs_out = (int)min(total, 0x7fffffffL);
+    const bool first_block = blockIdx.x == 0;
+    if (first_block && tid == 0 && pairs_out != nullptr) *pairs_out = (int)min(total, 0x7fffffffL);
     if (total > capacity) {
-        if (tid == 0) { *overflow = 1; *n_tiles_out = 0; }
+        if (first_block && tid == 0) { *overflow = 1; *n_tiles_out = 0; }
         return;
     }
+    // this block's share of the table: the entries [t_lo, t_hi)
+    const int t_lo = (int)((long)ttotal * blockIdx.x / gridDim.x), t_hi = (int)((long)ttotal * (blockIdx.x + 1) / gridDim.x);
     // (a group's tiles are written by its whole wave, sixty-four at a time: a popular group has a hundred and more, and one
     //  thread writing them one by one set this launch's time)
     int toff = tbefore + ti - ts;
@@ -396,17 +404,18 @@ __global__ __launch_bounds__(1024) void exact_tiles_kernel(const int* __restrict
         const int off = on ? (int)((long)g * gm_stride) + first : 0;
         const int mine = toff;
         toff += (c + EX_TR - 1) / EX_TR;
-        if (on && gstart_out) gstart_out[g] = first + c;
+        if (first_block && on && gstart_out) gstart_out[g] = first + c;
         for (int src = 0; src < 64; ++src) {
             const int c_s = __builtin_amdgcn_readlane(c, src);
             if (c_s <= 0) continue;                           // (wave-uniform)
             const int g_s = __builtin_amdgcn_readlane(g, src), off_s = __builtin_amdgcn_readlane(off, src);
             const int t_s = __builtin_amdgcn_readlane(mine, src);
-            for (int i = lane; i * EX_TR < c_s; i += 64)
+            const int i_end = min((c_s + EX_TR - 1) / EX_TR, t_hi - t_s);
+            for (int i = max(0, t_lo - t_s) + lane; i < i_end; i += 64)
                 tile_tab[t_s + i] = make_int4(g_s, off_s + i * EX_TR, min(EX_TR, c_s - i * EX_TR), 0);
         }
     }
-    if (tid == 1023) *n_tiles_out = ttotal;
+    if (first_block && tid == 1023) *n_tiles_out = ttotal;
 }
 
 // ---- REFINEMENT (resident sorted rows, input_len <= 128): the candidate (row, group) pairs once more on the half-precision
@@ -829,10 +838,13 @@ __global__ __launch_bounds__(256, 3) void exact_rescore_tiled_kernel(const float
 
 // merge key -> id; rows the scheme cannot vouch for (no candidate was scored: the key is still all ones; a best score
 // that is not finite; an overflowed pass) -> the fallback list
+// lastpos (or null): position `row` of a sorted pass also keeps inv[unit] (inv null: unit) -- a fallback row keeps nothing
 __global__ __launch_bounds__(256) void exact_finalize_kernel(const unsigned long long* __restrict__ best64, long N, int K,
                                                              const int* __restrict__ overflow, int* __restrict__ out,
                                                              int* __restrict__ fb_list, int* __restrict__ fb_count,
-                                                             const int* __restrict__ order = nullptr) {
+                                                             const int* __restrict__ order = nullptr,
+                                                             int* __restrict__ lastpos = nullptr,
+                                                             const int* __restrict__ inv = nullptr) {
     const long row = (long)blockIdx.x * 256 + threadIdx.x;
     if (row >= N) return;
     const long orow = order != nullptr ? order[row] : row;   // (sorted pass: the key at position row belongs to row order[row])
@@ -841,7 +853,11 @@ __global__ __launch_bounds__(256) void exact_finalize_kernel(const unsigned long
     const uint32_t bits = (key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key;
     const bool finite = (bits & 0x7F800000u) != 0x7F800000u;
     if (*overflow || k64 == ~0ull || !finite || unit >= (uint32_t)K) fb_list[atomicAdd(fb_count, 1)] = (int)orow;
-    else out[orow] = (int)unit;
+    else {
+        out[orow] = (int)unit;
+        // (sorted resident pass: the id's position in patch order, what exact_lastpos_kernel would gather for the next epoch's plan)
+        if (lastpos != nullptr) lastpos[row] = inv != nullptr ? inv[unit] : (int)unit;
+    }
 }
 
 // fallback rows -> a dense block for the float32 kernel, and its ids back

@@ -12,14 +12,21 @@
 // E(n) = cA |x_n| wmax + cW wmax^2 + cB Bm in d' units; derivation in bmu_exact.hpp.  KAPPA ulps are charged per MFMA.
 // the pass's counter block (ExactScratch::ctr; layout and the tail's slots: PassCounters, bmu_exact.hpp) by name
 struct PassCtr {
-    int* base; int n_groups;
+    int* base; int n_groups; bool whole_lines;
     int* gcount() const { return base; }
     int* gstart() const { return base + n_groups; }
     PassCounters* tail() const { return (PassCounters*)(gstart() + n_groups); }
     RowNeed* row_need() const { return (RowNeed*)base; }          // (before a launch's first pass: exact_scout_rowneed_kernel)
-    size_t bytes() const { return 2 * (size_t)n_groups * sizeof(int) + sizeof(PassCounters); }   // what a pass zeroes
+    // what a pass zeroes (whole_lines: up to the next multiple of 64 bytes -- the allocation has the room.  The fill of the exact
+    //  size, 8 232 bytes at 1 024 groups, shows as two fill kernels in the kernel trace, the padded one as one:
+    //  profiles/exact_chain_summary.md; SOM_EXACT_CHAIN=0: the exact size)
+    size_t bytes() const {
+        const size_t b = 2 * (size_t)n_groups * sizeof(int) + sizeof(PassCounters);
+        return whole_lines ? (size_t)round_up((long)b, 64) : b;
+    }
 };
-inline PassCtr pass_ctr(const som_handle* h) { return PassCtr{h->ex.ctr, (int)cdiv(h->K, EX_GROUP)}; }
+constexpr size_t EX_CTR_TAIL_INTS = (sizeof(PassCounters) + 64) / sizeof(int);   // (the tail and the padding of the fill above)
+inline PassCtr pass_ctr(const som_handle* h) { return PassCtr{h->ex.ctr, (int)cdiv(h->K, EX_GROUP), h->ex.chain}; }
 
 constexpr double EX_KAPPA = 6.0;     // measured through som_debug_mfma16: <= 2.4 (tests/test_gpu_exact.py holds it below 3)
 ExactBound exact_bound(const som_handle* h) {
@@ -105,7 +112,7 @@ int exact_reserve_stride(som_handle* h, long stride) {
     ex.max_tiles = cdiv(stride * ex.pairs, EX_TR) + n_groups;
     if (int rc = ex.tile_tab.alloc(h, (size_t)ex.max_tiles)) return rc;
     if (!ex.ctr) {
-        if (int rc = ex.ctr.alloc(h, (size_t)3 * n_groups + 16)) return rc;
+        if (int rc = ex.ctr.alloc(h, (size_t)3 * n_groups + EX_CTR_TAIL_INTS)) return rc;
         HIPCHK(h, hipHostMalloc((void**)&ex.pass_host, sizeof(PassCounters), hipHostMallocDefault));
     }
     ex.stride = stride;
@@ -322,7 +329,7 @@ int exact_skip_reserve(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
     if (int rc = ex.tile_counts.alloc(h, (size_t)tiles)) return rc;
     if (int rc = ex.tlist.alloc(h, (size_t)tiles * n_groups * K16_T)) return rc;
     if (int rc = ex.tcnt.alloc(h, (size_t)tiles)) return rc;
-    // (the listed screen's work items: exact_list_totals_kernel -- at most 2 tiles + 3 slots of them; + the queue's two words)
+    // (the listed screen's work items: exact_list_totals_body, exact_skip.hpp -- within 5 tiles + 4 slots of them; + the queue's two words and their padding)
     ex.item_slots = (int)resident_slots(h, 8);    // (more workgroups than this never fit a chip: few features, small stages)
     if (int rc = ex.items.alloc(h, (size_t)(5 * tiles + 4 * ex.item_slots + 16))) return rc;
     if (int rc = ex.sk_tmp.alloc(h, radix_scratch_ints(stride))) return rc;
@@ -332,8 +339,10 @@ int exact_skip_reserve(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
 
 // centroids and radii of the groups and of their sub-blocks under the current codebook, the centroids' scaled half images
 // and initial accumulators
+// (q_blocks > 0: the launch's prep_wsqh_kernel is still due as well -- best64, n_rows: its merge keys -- and rides along where the
+//  images go out in one grid; *q_done says whether it did)
 template <class E>
-int exact_skip_centroids(som_handle* h, const float* xmax2) {
+int exact_skip_centroids(som_handle* h, const float* xmax2, unsigned q_blocks, unsigned long long* best64, long n_rows, bool* q_done) {
     auto& ex = h->ex;
     const float* Wsrc = h->ex_patch ? h->Wp : h->W;
     const int n_groups = (int)cdiv(h->K, EX_GROUP);
@@ -348,6 +357,25 @@ int exact_skip_centroids(som_handle* h, const float* xmax2) {
     const int nst2 = ex.lp.level2 ? c1.n_cstages : 0;
     char* plain = ex.lp.scout ? c0.Cst_plain : nullptr;
     const dim3 tgrid((unsigned)cdiv((long)(c0.n_cstages + nst2) * K16_T, 4)), block(256);
+    if (ex.prep_w_pending) {
+        // (the codebook's own 16-bit image is still due -- refresh_codebook_operands left it to this launch: both in one grid)
+        ex.prep_w_pending = false;
+        const float* Wex = h->ex_patch ? h->Wp : h->W;
+        // (cm: centroids the fused merge wrote -- their levels' maxima are due now that max |w|^2 is final; the error maxima it zeroed)
+        float* cm1 = ex.prep_w_cm ? (float*)c0.cmax2 : nullptr;
+        float* cm2 = ex.prep_w_cm ? (float*)c1.cmax2 : nullptr;
+        const unsigned w_blocks = (unsigned)cdiv((long)h->n_stages * K16_T, 4);
+        switch (h->ks32) {
+#define SOM_PIMG_CASE(k) case k: exact_prep_images_kernel<k, E><<<dim3(w_blocks + tgrid.x + q_blocks), block, 0, h->stream>>>(w_blocks, tgrid.x, Wex, h->K, h->D, h->Wst, h->n_stages, \
+            h->wmax2 + 1, h->Wst_lo, cm1, cm2, l1, c0.Cst, c0.n_cstages, l2, c1.Cst, nst2, xmax2, h->wmax2, plain, h->wn, h->stage_units, best64, n_rows); break;
+        SOM_PIMG_CASE(1) SOM_PIMG_CASE(2) SOM_PIMG_CASE(3) SOM_PIMG_CASE(4)
+#undef SOM_PIMG_CASE
+        default: return fail(h, "exact: block skipping supports input_len <= 128");
+        }
+        HIPCHK(h, hipGetLastError());
+        *q_done = q_blocks > 0;
+        return 0;
+    }
     switch (h->ks32) {
 #define SOM_CIMG_CASE(k) case k: exact_centroid_image_kernel<k, E><<<tgrid, block, 0, h->stream>>>(l1, c0.Cst, c0.n_cstages, l2, c1.Cst, nst2, h->D, xmax2, h->wmax2, plain); break;
     SOM_CIMG_CASE(1) SOM_CIMG_CASE(2) SOM_CIMG_CASE(3) SOM_CIMG_CASE(4)
@@ -434,12 +462,32 @@ int exact_scout_pick(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lo
     return fail(h, "exact: the scout supports input_len <= 128");
 }
 
+// the need bitmaps of a pass's plan -> the tiles' lists, their totals and the screen's work queue (the lists cut into items of
+// about equal length): one launch whose last workgroup does the totals (SOM_EXACT_CHAIN=0: two launches)
+void exact_plan_lists(som_handle* h, long tiles, int n_cstages, const unsigned long long* need2) {
+    auto& ex = h->ex;
+    const int n_groups = (int)cdiv(h->K, EX_GROUP);
+    PassCounters* const ctr = pass_ctr(h).tail();
+    const int slots = ex.item_queue ? (ex.screen_slots > 0 ? ex.screen_slots : ex.item_slots) : 0;
+    int2* const queue = ex.item_queue ? ex.items + 8 : nullptr;   // (items[0] = (n_items, counter): the queue's two words)
+    int* const n_items = (int*)ex.items.p;
+    if (ex.chain) {
+        exact_lists_totals_kernel<<<dim3((unsigned)cdiv(tiles, LISTS_WG_TILES)), dim3(64 * LISTS_WG_TILES), 0, h->stream>>>(
+            ex.need, n_cstages, need2, n_groups, ex.glist, ex.gcnt, ex.tile_counts, ex.tlist, ex.tcnt, tiles, &ctr->lists_done,
+            &ctr->blocks_run, &ctr->groups_run, slots, queue, n_items, n_items + 1, ex.item_len_pct);
+        return;
+    }
+    exact_lists_kernel<<<dim3((unsigned)tiles), dim3(64), 0, h->stream>>>(ex.need, n_cstages, need2, n_groups, ex.glist, ex.gcnt,
+                                                                         ex.tile_counts, ex.tlist, ex.tcnt);
+    exact_list_totals_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(ex.tile_counts, tiles, &ctr->blocks_run, &ctr->groups_run, slots, queue,
+                                                                  n_items, n_items + 1, ex.item_len_pct);
+}
+
 // one pass's plan on the sorted rows sr[s0, s0 + n): level 1 (+ the seeds, from lastpos_s), level 2, the tiles' item lists
 template <class E>
 int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, long n, const float* xmax2, const ExactBound& eb,
                     const int* lastpos2, bool time_l2 = false) {
     auto& ex = h->ex;
-    const int n_groups = (int)cdiv(h->K, EX_GROUP);
     PassCounters* const ctr = pass_ctr(h).tail();
     const long np = round_up(n, SK_TILE);
     const long tiles = np / SK_TILE;
@@ -456,13 +504,15 @@ int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
     const bool l2 = ex.lp.level2;
     const int force = ex.skip_mode == 3 ? 1 : 0;
     const __bf16* Xs = sr.Xb_s + s0 * h->dp;
-    // (level 1 stores every word; level 2 only those of the stages it walks)
-    if (l2) HIPCHK(h, hipMemsetAsync(ex.need2, 0, (size_t)tiles * c1.n_cstages * sizeof(unsigned long long), h->stream));
+    // (level 1 stores every word; level 2 only those of the stages it walks: its words start from zero -- cleared by the level-1
+    //  workgroups, each the words of its own stages; SOM_EXACT_CHAIN=0: by a fill)
+    unsigned long long* const need2_clear = l2 && ex.chain ? ex.need2.p : nullptr;
+    if (l2 && !ex.chain) HIPCHK(h, hipMemsetAsync(ex.need2, 0, (size_t)tiles * c1.n_cstages * sizeof(unsigned long long), h->stream));
 #define SOM_PLAN_CASE(k) case k: { \
         { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_kernel<k, E, false>, 64 * K16_NW, lds1, &pc)) return rc; } \
         exact_plan_kernel<k, E, false><<<pgrid, block, lds1, h->stream>>>(Xs, n, c0.Cst, c0.n_cstages, c0.rg, c0.n_slots, \
             sr.xsq_s + s0, sr.xerr_s + s0, sr.sU_s + s0, xmax2, c0.cmax2, h->wmax2, h->wmax2 + 1, eb, ex.need, sr.lastpos_s + s0, \
-            h->Wst, sr.seed_s + s0, nullptr, 0, force, lastpos2, lastpos2 != nullptr ? &ctr->scout_wins : nullptr); \
+            h->Wst, sr.seed_s + s0, nullptr, 0, force, lastpos2, lastpos2 != nullptr ? &ctr->scout_wins : nullptr, need2_clear); \
         if (l2) { \
             if (time_l2) (void)hipEventRecord(ex.cost.ev[3], h->stream); \
             { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_kernel<k, E, true>, 64 * K16_NW, lds2, &pc)) return rc; } \
@@ -476,14 +526,7 @@ int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
     default: return fail(h, "exact: block skipping supports input_len <= 128");
     }
 #undef SOM_PLAN_CASE
-    exact_lists_kernel<<<dim3((unsigned)tiles), dim3(64), 0, h->stream>>>(ex.need, c0.n_cstages, l2 ? ex.need2 : nullptr, n_groups,
-                                                                         ex.glist, ex.gcnt, ex.tile_counts, ex.tlist, ex.tcnt);
-    // (... and the screen's work queue: the lists cut into items of about equal length)
-    int2* queue = ex.items + 8;                              // (items[0] = (n_items, counter): the queue's two words)
-    exact_list_totals_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(ex.tile_counts, tiles, &ctr->blocks_run, &ctr->groups_run,
-                                                                  ex.item_queue ? (ex.screen_slots > 0 ? ex.screen_slots : ex.item_slots) : 0,
-                                                                  ex.item_queue ? queue : nullptr,
-                                                                  (int*)ex.items.p, (int*)ex.items.p + 1, ex.item_len_pct);
+    exact_plan_lists(h, tiles, c0.n_cstages, l2 ? ex.need2.p : nullptr);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -579,8 +622,6 @@ template <int KS32, class E>
 int exact_wide_plan_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, long n, const float* xmax2, const ExactBound& eb) {
     auto& ex = h->ex;
     const auto& c0 = ex.cen[0];
-    const int n_groups = (int)cdiv(h->K, EX_GROUP);
-    PassCounters* const ctr = pass_ctr(h).tail();
     const long np = round_up(n, SK_TILE);
     const long tiles = np / SK_TILE;
     // (sr.lastpos_s holds the sorted rows' last BMUs as UNIT ids here; the seed itself is not used beyond 128 features)
@@ -598,12 +639,8 @@ int exact_wide_plan_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
     bmu_bf16_wide_kernel<KS32, E, false, false, true><<<dim3((unsigned)tiles, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
         (const char*)(sr.Xb_s + s0 * h->dp), n, c0.Cst, c0.n_img_stages, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ExactBound(),
         nullptr, nullptr, 0, sr.seed_s + s0, sr.sU_s + s0, ex.need, c0.n_cstages);
-    exact_lists_kernel<<<dim3((unsigned)tiles), dim3(64), 0, h->stream>>>(ex.need, c0.n_cstages, nullptr, n_groups, ex.glist, ex.gcnt, ex.tile_counts, ex.tlist, ex.tcnt);
-    // (... and the listed screen's work queue: the lists -- counted in 16-unit blocks, four to a group -- cut into items)
-    exact_list_totals_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(ex.tile_counts, tiles, &ctr->blocks_run, &ctr->groups_run,
-                                                                  ex.item_queue ? (ex.screen_slots > 0 ? ex.screen_slots : ex.item_slots) : 0,
-                                                                  ex.item_queue ? ex.items + 8 : nullptr, (int*)ex.items.p, (int*)ex.items.p + 1,
-                                                                  ex.item_len_pct);
+    // (the tiles' lists and the listed screen's work queue: the lists -- counted in 16-unit blocks, four to a group -- cut into items)
+    exact_plan_lists(h, tiles, c0.n_cstages, nullptr);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -627,6 +664,10 @@ int exact_rescore_kg(som_handle* h, const float* X, unsigned long long* best64, 
     return 0;
 }
 
+// workgroups of exact_tiles_kernel: each repeats the scan of the groups' counts and writes its share of the tile table (one
+// workgroup writing some tens of thousands of entries set that launch's time; SOM_EXACT_CHAIN=0: one)
+inline unsigned exact_tiles_blocks(const som_handle* h) { return h->ex.chain ? 16u : 1u; }
+
 // the refinement pass over a sorted pass's candidate pairs (bmu_exact.hpp): tiles -> refined minima -> lists compacted in place
 template <int KS32, class E>
 int exact_refine_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long r0, long n, const float* xmax2, const ExactBound& eb) {
@@ -635,10 +676,11 @@ int exact_refine_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
     const int n_groups = pc.n_groups;
     int* gcount = pc.gcount(); PassCounters* const ctr = pc.tail();
     int* n_tiles = &ctr->n_tiles;
-    exact_tiles_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(gcount, n_groups, ex.stride, ex.stride * ex.pairs, ex.tile_tab, n_tiles,
-                                                             &ctr->overflow, nullptr, nullptr, &ctr->pairs_in);
+    exact_tiles_kernel<<<dim3(exact_tiles_blocks(h)), dim3(1024), 0, h->stream>>>(gcount, n_groups, ex.stride, ex.stride * ex.pairs, ex.tile_tab, n_tiles,
+                                                                                 &ctr->overflow, nullptr, nullptr, &ctr->pairs_in);
     uint32_t* rowmin2 = (uint32_t*)ex.rowarg.p;            // (round 1's scratch: unused in the one-round scheme)
-    HIPCHK(h, hipMemsetAsync(rowmin2, 0xFF, (size_t)n * sizeof(uint32_t), h->stream));
+    // (all ones to start from: written by the select kernel, which has visited every row; SOM_EXACT_CHAIN=0: by a fill)
+    if (!ex.chain) HIPCHK(h, hipMemsetAsync(rowmin2, 0xFF, (size_t)n * sizeof(uint32_t), h->stream));
     const size_t lds = (size_t)k16_stage_bytes(KS32) + (size_t)K16_T * KS32 * 1024;
     int per_cu = 1;
     if (int rc = kernel_per_cu(h, (const void*)exact_refine_kernel<KS32, E>, 256, lds, &per_cu)) return rc;
@@ -670,9 +712,9 @@ int exact_rescore_round(som_handle* h, const float* X, const float* xsq, unsigne
     int* gcount = pc.gcount(); PassCounters* const ctr = pc.tail();
     int* n_tiles = &ctr->n_tiles;
     // (the pairs the select kernel found go back with the pass's counters -- unless the refinement pass has counted them already)
-    exact_tiles_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(gcount, n_groups, ex.stride, ex.stride * ex.pairs, ex.tile_tab, n_tiles,
-                                                             &ctr->overflow, gstart, gstart_out,
-                                                             (gstart == nullptr && gstart_out == nullptr && count_pairs) ? &ctr->pairs_in : nullptr);
+    exact_tiles_kernel<<<dim3(exact_tiles_blocks(h)), dim3(1024), 0, h->stream>>>(gcount, n_groups, ex.stride, ex.stride * ex.pairs, ex.tile_tab, n_tiles,
+                                                                                 &ctr->overflow, gstart, gstart_out,
+                                                                                 (gstart == nullptr && gstart_out == nullptr && count_pairs) ? &ctr->pairs_in : nullptr);
     if (h->wide) {
         // beyond 128 features: the float32 tile image, chunk by chunk
         if (!h->Wfimg) return fail(h, "exact: no float32 tile image");
@@ -719,6 +761,9 @@ struct ExactLaunch {
     bool two_round;
     policy::LaunchFacts f;
     policy::LaunchOutcome o;
+    bool lastpos_carried = false;    // sr.lastpos_s holds the rows' last BMUs' positions already (the last epoch's finalize): no exact_lastpos_kernel
+    long pos_kept_rows = 0;          // rows whose positions this launch's finalize has stored
+    long fallback_rows = 0;          // rows this launch handed to the float32 kernel
 };
 
 // Is there anything for the plan to skip?  The scout, the gather and the plan cost a fifth of a full scan: before the
@@ -862,7 +907,8 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
                 exact_lastpos_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(out + r0, sr.order + s0, h->ex_inv, n, h->K, ex.sk_vals);
                 lastpos2 = ex.sk_vals;
             }
-        } else {
+        } else if (!L.lastpos_carried) {
+            // (carried: the last epoch's finalize has left exactly these positions in lastpos_s -- launch_bmu_exact)
             exact_lastpos_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(out + r0, sr.order + s0, h->ex_inv, n, h->K, sr.lastpos_s + s0);
         }
         if (int rc = SOM_HALF(h, exact_skip_plan, h, sr, s0, n, xmax2, eb, lastpos2, lp.time_phases && lp.level2)) return rc;
@@ -899,13 +945,18 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
     } else {
         exact_select_kernel<false><<<sel_grid, sel_block, 0, h->stream>>>(
             ex.gmin, ex.gflags, ex.stride, n_groups, n, best, p_xsq, h->wmax2, xmax2, eb, p_xerr, h->wmax2 + 1, ex.plist,
-            pc.gcount(), ex.rowcnt, nullptr, p_seed, lp.skip ? ex.glist : nullptr, lp.skip ? ex.gcnt : nullptr, SK_TILE);
+            pc.gcount(), ex.rowcnt, nullptr, p_seed, lp.skip ? ex.glist : nullptr, lp.skip ? ex.gcnt : nullptr, SK_TILE,
+            nullptr, 0, 0, lp.refine && ex.chain ? (uint32_t*)ex.rowarg.p : nullptr);
         if (lp.refine)
             if (int rc = SOM_HALF(h, exact_refine, h, sr, s0, n, xmax2, eb)) return rc;
         if (int rc = exact_rescore_round(h, p_X, xsq + r0, best, nullptr, nullptr, lp.skip, !lp.refine)) return rc;
     }
+    // (a sorted resident pass up to 128 features: the ids' positions in patch order stay behind for the next epoch's plan)
+    const bool keep_pos = ex.chain && lp.skip && !h->wide && L.f.resident && p_order != nullptr;
     exact_finalize_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(
-        best, n, h->K, &pc.tail()->overflow, out + r0, ex.fb_list, &pc.tail()->fallback, p_order);
+        best, n, h->K, &pc.tail()->overflow, out + r0, ex.fb_list, &pc.tail()->fallback, p_order,
+        keep_pos ? sr.lastpos_s + s0 : nullptr, keep_pos && h->ex_patch ? h->ex_inv.p : nullptr);
+    if (keep_pos) L.pos_kept_rows += n;
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(ex.pass_host, pc.tail(), sizeof(PassCounters), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipEventRecord(cost.ev[7], h->stream));
@@ -939,6 +990,7 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
     L.o.pairs_in += got.pairs_in;
     if (lp.refine) L.o.pairs_out += got.pairs_out;
     if (lp.skip && lp.scout && have_last) L.o.scout_wins += got.scout_wins;
+    L.fallback_rows += n_fb;
     if (n_fb < 0 || n_fb > n) return fail(h, "exact: fallback counter out of range");
     if (n_fb > 0) return exact_fallback_rows(h, L, r0, n_fb);
     return 0;
@@ -960,9 +1012,16 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
         cost.have = true;
     }
     HIPCHK(h, hipEventRecord(cost.ev[0], h->stream));
+    // the stages' initial accumulators and the launch's merge keys: at once -- or, where the codebook's 16-bit image is still due
+    // (flush_prep_w), behind the plan's decision: a planned launch up to 128 features sends them out in one grid with the images
     const long units = (long)h->n_stages * h->stage_units;
-    prep_wsqh_kernel<<<dim3((unsigned)cdiv(std::max(units, N), 256)), dim3(256), 0, h->stream>>>(
-        h->wn, h->K, h->wmax2, xmax2, h->Wst, h->n_stages, h->stage_bytes, h->stage_units, h->best64, N, 1);
+    const unsigned wsqh_blocks = (unsigned)cdiv(std::max(units, N), 256);
+    auto launch_wsqh = [&]() {
+        prep_wsqh_kernel<<<dim3(wsqh_blocks), dim3(256), 0, h->stream>>>(
+            h->wn, h->K, h->wmax2, xmax2, h->Wst, h->n_stages, h->stage_bytes, h->stage_units, h->best64, N, 1);
+    };
+    bool wsqh_done = !ex.prep_w_pending;
+    if (wsqh_done) launch_wsqh();
     const int n_groups = (int)cdiv(h->K, EX_GROUP);
     const long chunk = std::min(exact_chunk_rows(h), ex.stride);
     ExactLaunch L{X, N, xsq, xerr, Xb, xmax2, out, exact_bound(h), n_groups, ex.two_round >= 0 ? ex.two_round != 0 : h->wide, {}, {}};
@@ -992,6 +1051,10 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
 
     lp = ex.plan.begin(f);
     auto& sr = ex.srt[f.resident ? 0 : 1];
+    // (the resident rows' carried positions: this launch's to use, and stale from here on unless its own finalize renews them;
+    //  a launch over other rows works in srt[1] and writes other ids: it leaves them alone)
+    const bool lastpos_was_valid = f.resident && sr.lastpos_valid;
+    if (f.resident) sr.lastpos_valid = false;
     const int64_t run_before = ex.blocks_run, total_before = ex.blocks_total;
     if (lp.skip && exact_skip_reserve(h, sr, f.resident ? N : std::min(N, chunk), ex.stride) != 0) {
         // no memory for the sorted pass's buffers: every block runs, from now on (the ids are the same either way)
@@ -1002,8 +1065,10 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
     }
     if (lp.skip) {
         if (h->wide) { if (int rc = SOM_HALF(h, exact_wide_centroids, h, xmax2)) return rc; }
-        else if (int rc = SOM_HALF(h, exact_skip_centroids, h, xmax2)) return rc;
+        else if (int rc = SOM_HALF(h, exact_skip_centroids, h, xmax2, wsqh_done ? 0u : wsqh_blocks, h->best64.p, N, &wsqh_done)) return rc;
     }
+    if (int rc = flush_prep_w(h)) return rc;                 // (no plan, or the wide plan: the codebook's 16-bit image on its own)
+    if (!wsqh_done) launch_wsqh();
     if (lp.estimate) {
         // the cheap question first (exact_scout_rowneed_kernel): 128 sampled rows against the group centroids (one small launch
         // and one host wait spent); policy::PlanState::rows_sampled cancels the plan where a row alone needs nearly every group
@@ -1028,8 +1093,13 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
         else lp.force_sort();
     }
 
+    // (decided here: a refused reservation, the samples or a first refinement may have changed the plan since it began)
+    L.lastpos_carried = ex.chain && lastpos_was_valid && f.have_last && lp.skip && !lp.resort && !lp.scout && !h->wide && sr.lastpos_s != nullptr;
+    if (L.lastpos_carried) ex.lastpos_carried_epochs += 1;
     for (long r0 = 0; r0 < N; r0 += chunk)
         if (int rc = exact_pass(h, L, sr, r0, std::min(chunk, N - r0))) return rc;
+    // (every pass of the epoch has stored its slice and no row went to the float32 kernel: the next epoch may skip exact_lastpos_kernel)
+    if (f.resident) sr.lastpos_valid = L.pos_kept_rows == N && L.fallback_rows == 0;
 
     L.o.blocks_run = ex.blocks_run - run_before; L.o.blocks_total = ex.blocks_total - total_before;
     const policy::LaunchReport rep = ex.plan.end(f, lp, L.o);

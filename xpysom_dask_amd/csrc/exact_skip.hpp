@@ -185,6 +185,8 @@ __global__ __launch_bounds__(512) void exact_merge_prep_kernel(const float* __re
             ws[i * MPX_STRIDE + d] = w[k];
         }
     }
+    // (the centroid levels' error maxima start from zero for the image kernel that follows: exact_prep_images_kernel)
+    if (l1.C != nullptr && g == 0 && tid == 0) { l1.cmax2[1] = 0.0f; l2.cmax2[1] = 0.0f; }
     if (l1.C != nullptr) group_centroids(w, g, K, D, l1, l2, sh);   // (its barriers order the LDS copy as well)
     else __syncthreads();
     if (g >= n_groups) return;                                // (the grid covers whole level-2 tiles: groups without units)
@@ -333,16 +335,17 @@ __device__ __forceinline__ uint32_t row16_or(uint32_t v) {
 // fragments of -c~ as prep_w_exact_k16_kernel lays out the units' (scaled by the codebook's power of two; the measured rounding
 // error's maximum into cmax2[1]), and the stage's tail: [0, 64) floats: initial accumulators S'(B' + |c|^2 / 2) - hS r^2,
 // [64, 128): -up_to_half(sw r) (an empty slot: +inf and 0: never needed; a NaN radius: NaN: always needed).
+// (the body, for block `bid` of 256 threads: shared with exact_prep_images_kernel below)
 template <int KS32, class EL>
-__global__ __launch_bounds__(256) void exact_centroid_image_kernel(CentroidLevel l1, char* __restrict__ Cst1, int n_cstages1,
-                                                                   CentroidLevel l2, char* __restrict__ Cst2, int n_cstages2, int D,
-                                                                   const float* __restrict__ xmax2, const float* __restrict__ wmax2,
-                                                                   char* __restrict__ Cst1_plain = nullptr) {
+__device__ __forceinline__ void exact_centroid_image_body(const unsigned bid, const CentroidLevel& l1, char* __restrict__ Cst1, int n_cstages1,
+                                                          const CentroidLevel& l2, char* __restrict__ Cst2, int n_cstages2, int D,
+                                                          const float* __restrict__ xmax2, const float* __restrict__ wmax2,
+                                                          char* __restrict__ Cst1_plain) {
     using E = typename EL::T;
     using bf16x8 = typename V8<E>::t;
     constexpr int STAGE = k16_stage_bytes(KS32);
     const int lane = threadIdx.x & 63;
-    long tile = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    long tile = (long)bid * 4 + (threadIdx.x >> 6);
     const long t1 = (long)n_cstages1 * K16_T;
     const bool second = tile >= t1;
     if (second) tile -= t1;
@@ -392,13 +395,43 @@ __global__ __launch_bounds__(256) void exact_centroid_image_kernel(CentroidLevel
         }
     }
 }
+template <int KS32, class EL>
+__global__ __launch_bounds__(256) void exact_centroid_image_kernel(CentroidLevel l1, char* __restrict__ Cst1, int n_cstages1,
+                                                                   CentroidLevel l2, char* __restrict__ Cst2, int n_cstages2, int D,
+                                                                   const float* __restrict__ xmax2, const float* __restrict__ wmax2,
+                                                                   char* __restrict__ Cst1_plain = nullptr) {
+    exact_centroid_image_body<KS32, EL>(blockIdx.x, l1, Cst1, n_cstages1, l2, Cst2, n_cstages2, D, xmax2, wmax2, Cst1_plain);
+}
+
+// The preparations a planned launch starts with, in ONE grid: the codebook's 16-bit stage image (prep_w_exact_k16_kernel: the
+// first w_blocks blocks), the centroid images of both levels (c_blocks blocks behind them), and the stages' initial
+// accumulators with the launch's merge keys (prep_wsqh_kernel, scaled: the blocks behind those).  All read what the merge left
+// -- the codebook, its norms and their maximum, the centroids -- and none reads what another writes (the stage image's
+// fragments and its last KiB are different bytes).  The one word two of them shared, the centroid levels' error maximum cm[1],
+// is zeroed by the fused merge that wrote the centroids (exact_merge_prep_kernel), not here: the centroid blocks add to it
+// from their first wave on.
+template <int KS32, class EL>
+__global__ __launch_bounds__(256) void exact_prep_images_kernel(unsigned w_blocks, unsigned c_blocks, const float* __restrict__ W, int K, int D,
+                                                                char* __restrict__ Wst, int n_stages, float* __restrict__ werr2,
+                                                                char* __restrict__ Wst_lo, float* __restrict__ cm1, float* __restrict__ cm2,
+                                                                CentroidLevel l1, char* __restrict__ Cst1, int n_cstages1,
+                                                                CentroidLevel l2, char* __restrict__ Cst2, int n_cstages2,
+                                                                const float* __restrict__ xmax2, const float* __restrict__ wmax2,
+                                                                char* __restrict__ Cst1_plain, const float* __restrict__ wn,
+                                                                int stage_units, unsigned long long* __restrict__ best64, long n_rows) {
+    if (blockIdx.x < w_blocks) prep_w_exact_k16_body<KS32, EL>(blockIdx.x, W, K, D, Wst, n_stages, wmax2, werr2, Wst_lo, cm1, cm2, false);
+    else if (blockIdx.x < w_blocks + c_blocks)
+        exact_centroid_image_body<KS32, EL>(blockIdx.x - w_blocks, l1, Cst1, n_cstages1, l2, Cst2, n_cstages2, D, xmax2, wmax2, Cst1_plain);
+    else prep_wsqh_body(blockIdx.x - w_blocks - c_blocks, wn, K, wmax2, xmax2, Wst, n_stages, k16_stage_bytes(KS32), stage_units, best64, n_rows, 1);
+}
 
 // The plan: which blocks does a tile of SK_TILE (sorted) rows need?  The resident kernel's MFMA loop over a centroid
 // stage image (64 centroids per stage), epilogue: need(row, j) = not (d'_c > A(row) + (S'/2) (sU(row) + r_j)^2), OR over
 // the tile's rows into need[tile][stage] (bit i <-> centroid slot 64 stage + i).
 //   LEVEL2 == false: the centroids of the groups.  The prologue also forms, per row, the screen value v_u of the row's last
 //     BMU u (vector ALU, from the row's half image and u's fragments of the screen's stage image Wst), from it the seed of
-//     the screen (seed_s) and sqrt(U) (sU_s: kept for level 2; +inf: the row needs everything).
+//     the screen (seed_s) and sqrt(U) (sU_s: kept for level 2; +inf: the row needs everything).  need2_clear (or null): level 2's
+//     bitmap [tile][4 n_cstages], whose words of this workgroup's stages are zeroed for the level-2 launch that follows.
 //   LEVEL2 == true: the centroids of the 16-unit sub-blocks, slot order as exact_centroid_kernel's (a 16-slot MFMA tile =
 //     the sub-blocks of four consecutive groups); only the tiles whose groups level 1 kept (need1) are loaded and run.
 // eb / scales: the centroid image's (cmax2 = {max |c|^2, max rounding error^2}); wmax2 / werr2: the codebook's.
@@ -415,7 +448,8 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
                                                                     float* __restrict__ seed_s,
                                                                     const unsigned long long* __restrict__ need1, int n_cstages1,
                                                                     int force_all, const int* __restrict__ lastpos2 = nullptr,
-                                                                    int* __restrict__ scout_wins = nullptr) {
+                                                                    int* __restrict__ scout_wins = nullptr,
+                                                                    unsigned long long* __restrict__ need2_clear = nullptr) {
     using E = typename EL::T;
     using bf16x8 = typename V8<E>::t;
     constexpr int DP = 32 * KS32;
@@ -650,7 +684,7 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
             if (c0 + 16 < e0) store_tail(sn, tail_n);
         }
         __syncthreads();
-        // (two parts of a tile's walk may share a stage: OR into the words the host cleared)
+        // (two parts of a tile's walk may share a stage: OR into words that start from zero -- cleared by the level-1 workgroups, or by the host's fill)
         for (int i = tid; i < n_cstages; i += 64 * K16_NW)
             if (nl[i] != 0ull) atomicOr(need + (long)blockIdx.x * n_cstages + i, nl[i]);
         return;
@@ -747,6 +781,10 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
     }
     __syncthreads();
     for (int i = s_begin + tid; i < s_end; i += 64 * K16_NW) need[(long)blockIdx.x * n_cstages + i] = nl[i - s_begin];
+    // (level 2 ORs into words that start from zero: the four level-2 words of every stage this workgroup walked are cleared
+    //  here, by the workgroup that owns them, instead of by a fill of their own in front of level 2)
+    if (need2_clear != nullptr)
+        for (int i = 4 * s_begin + tid; i < 4 * s_end; i += 64 * K16_NW) need2_clear[(long)blockIdx.x * 4 * n_cstages + i] = 0ull;
 }
 
 // need bitmaps -> per tile the ascending list of items (group << 4 | mask of the group's 16-unit sub-blocks to run), and its
@@ -754,13 +792,14 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
 // word 4 s + k holds, for the groups 64 s + 16 k .. + 15, a nibble each (bit 4 (g & 15) + sub <-> sub-block `sub` of group g).
 // ... and the same blocks as the tile's dense list of 16-unit tiles (tlist / tcnt: what the screen walks; glist / gcnt: what
 // the select kernel walks).  One wave per tile; tile_counts[tile] = (16-unit blocks listed, groups level 1 kept).
-__global__ __launch_bounds__(64) void exact_lists_kernel(const unsigned long long* __restrict__ need1, int n_cstages,
-                                                         const unsigned long long* __restrict__ need2, int n_groups,
-                                                         int* __restrict__ glist, int* __restrict__ gcnt,
-                                                         int2* __restrict__ tile_counts, int* __restrict__ tlist,
-                                                         int* __restrict__ tcnt) {
-    const long tile = blockIdx.x;
-    const int lane = threadIdx.x;
+// (PUBLISH: tile_counts[tile] leaves as one 8-byte agent-scope store, written through to memory: another workgroup of the same
+//  launch reads it -- exact_lists_totals_kernel)
+template <bool PUBLISH>
+__device__ __forceinline__ void exact_lists_tile(const long tile, const int lane, const unsigned long long* __restrict__ need1, int n_cstages,
+                                                 const unsigned long long* __restrict__ need2, int n_groups,
+                                                 int* __restrict__ glist, int* __restrict__ gcnt,
+                                                 int2* tile_counts, int* __restrict__ tlist,
+                                                 int* __restrict__ tcnt) {
     const unsigned long long below = (1ull << lane) - 1ull;
     int base = 0, blk = 0, kept = 0;
     for (int s0 = 0; s0 < n_cstages; s0 += 64) {
@@ -800,7 +839,20 @@ __global__ __launch_bounds__(64) void exact_lists_kernel(const unsigned long lon
         }
     }
     // (per tile: 4 096 waves adding into two words of one cache line took as long as the rest of this kernel)
-    if (lane == 0) { gcnt[tile] = base; tcnt[tile] = blk; tile_counts[tile] = make_int2(blk, kept); }
+    if (lane == 0) {
+        gcnt[tile] = base; tcnt[tile] = blk;
+        if (PUBLISH)
+            __hip_atomic_store((unsigned long long*)(tile_counts + tile), ((unsigned long long)(uint32_t)kept << 32) | (uint32_t)blk,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else tile_counts[tile] = make_int2(blk, kept);
+    }
+}
+__global__ __launch_bounds__(64) void exact_lists_kernel(const unsigned long long* __restrict__ need1, int n_cstages,
+                                                         const unsigned long long* __restrict__ need2, int n_groups,
+                                                         int* __restrict__ glist, int* __restrict__ gcnt,
+                                                         int2* __restrict__ tile_counts, int* __restrict__ tlist,
+                                                         int* __restrict__ tcnt) {
+    exact_lists_tile<false>(blockIdx.x, threadIdx.x, need1, n_cstages, need2, n_groups, glist, gcnt, tile_counts, tlist, tcnt);
 }
 
 // sum of the tiles' (16-unit blocks listed, groups level 1 kept) into the pass's counters.  One workgroup.
@@ -808,12 +860,11 @@ __global__ __launch_bounds__(64) void exact_lists_kernel(const unsigned long lon
 // about L blocks -- L = len_pct % of the mean list (1.25 x), or what gives every slot of the chip two items where the tiles are few; never below
 // 32 blocks (a part re-reads its tile's 64 KB of rows) --, item = (tile, part | parts << 16) in tile order; the queue's counter reset.
 // At most tiles + max(100 / len_pct tiles, 2.1 slots) items (the three cases of L): with len_pct >= 25, within 5 tiles + 4 slots.
-__global__ __launch_bounds__(1024) void exact_list_totals_kernel(const int2* __restrict__ tile_counts, long tiles, int* __restrict__ blocks_run,
-                                                                 int* __restrict__ groups_run, int slots = 0, int2* __restrict__ items = nullptr,
-                                                                 int* __restrict__ n_items = nullptr, int* __restrict__ item_ctr = nullptr,
-                                                                 int len_pct = 125) {
-    __shared__ int sb[16], sk[16];
-    __shared__ int tot_b;
+// (the body, for a workgroup of 1 024 threads; sb, sk: sixteen ints of LDS each, tot_b: one)
+__device__ __forceinline__ void exact_list_totals_body(const int2* tile_counts, long tiles, int* __restrict__ blocks_run,
+                                                       int* __restrict__ groups_run, int slots, int2* __restrict__ items,
+                                                       int* __restrict__ n_items, int* __restrict__ item_ctr, int len_pct,
+                                                       int* sb, int* sk, int& tot_b) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int b = 0, k = 0;
     for (long t = tid; t < tiles; t += 1024) { const int2 c = tile_counts[t]; b += c.x; k += c.y; }
@@ -852,6 +903,55 @@ __global__ __launch_bounds__(1024) void exact_list_totals_kernel(const int2* __r
         for (int q = 0; q < np; ++q) items[o++] = make_int2((int)t, q | (np << 16));
     }
     if (tid == 0) { *n_items = all; *item_ctr = 0; }
+}
+__global__ __launch_bounds__(1024) void exact_list_totals_kernel(const int2* __restrict__ tile_counts, long tiles, int* __restrict__ blocks_run,
+                                                                 int* __restrict__ groups_run, int slots = 0, int2* __restrict__ items = nullptr,
+                                                                 int* __restrict__ n_items = nullptr, int* __restrict__ item_ctr = nullptr,
+                                                                 int len_pct = 125) {
+    __shared__ int sb[16], sk[16];
+    __shared__ int tot_b;
+    exact_list_totals_body(tile_counts, tiles, blocks_run, groups_run, slots, items, n_items, item_ctr, len_pct, sb, sk, tot_b);
+}
+
+// Both in ONE launch: sixteen tiles a workgroup (a wave each), and the workgroup that finishes LAST does the totals and cuts the
+// items -- the single workgroup of exact_list_totals_kernel otherwise starts only when the whole lists grid has drained, and
+// costs a launch of its own.  Last is whoever draws the final ticket of `done` (the pass's counter block: zero at the pass's
+// start; the last workgroup leaves it zero again for the pass's next plan).  What crosses workgroups inside the launch is
+// tile_counts alone (the lists themselves are read by later launches): every wave writes its tile's pair through to memory
+// with one agent-scope store and waits for it, the workgroup's barrier stands between those waits and its ticket, and the last
+// workgroup acquires (agent scope) before it reads the pairs.  With a release fence per workgroup instead (__threadfence()
+// before the ticket: a write-back of all the lists the workgroup has just written) the launch measured 27.4 us against 22.5 us
+// for the two launches it replaces, this way 23.4 us: profiles/exact_chain_summary.md.  No workgroup waits for another.
+constexpr int LISTS_WG_TILES = 16;
+__global__ __launch_bounds__(64 * LISTS_WG_TILES) void exact_lists_totals_kernel(const unsigned long long* __restrict__ need1, int n_cstages,
+                                                                                const unsigned long long* __restrict__ need2, int n_groups,
+                                                                                int* __restrict__ glist, int* __restrict__ gcnt,
+                                                                                int2* tile_counts, int* __restrict__ tlist,
+                                                                                int* __restrict__ tcnt, long tiles, int* __restrict__ done,
+                                                                                int* __restrict__ blocks_run, int* __restrict__ groups_run,
+                                                                                int slots, int2* __restrict__ items, int* __restrict__ n_items,
+                                                                                int* __restrict__ item_ctr, int len_pct) {
+    static_assert(LISTS_WG_TILES == 16, "the totals' scan is written for sixteen waves");
+    __shared__ int sb[16], sk[16];
+    __shared__ int tot_b;
+    __shared__ int last;
+    const int tid = threadIdx.x;
+    const long tile = (long)blockIdx.x * LISTS_WG_TILES + (tid >> 6);
+    if (tile < tiles) exact_lists_tile<true>(tile, tid & 63, need1, n_cstages, need2, n_groups, glist, gcnt, tile_counts, tlist, tcnt);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        const int ticket = __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = ticket == (int)gridDim.x - 1 ? 1 : 0;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    if (!last) return;
+    exact_list_totals_body(tile_counts, tiles, blocks_run, groups_run, slots, items, n_items, item_ctr, len_pct, sb, sk, tot_b);
 }
 
 // ---- the SCOUT: a bound for rows WITHOUT a last BMU (query rows, streamed chunks, a row set's first epoch) and for the

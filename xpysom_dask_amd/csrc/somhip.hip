@@ -154,7 +154,20 @@ struct som_handle {
             bool xl_filled = false;       //     ... and written by a gather since
             DevBuf<float> Xf_s, xsq_s, xerr_s, seed_s, sU_s;
             DevBuf<int> lastpos_s;        // position (patch order) of every sorted row's (pseudo) last BMU
+            // lastpos_s[p] == inv[bmu[order[p]]] for every position of the resident rows: the last epoch's finalize stored them
+            // pass by pass and no row fell back.  Taken (and cleared) by the next resident launch; cleared by whatever else writes
+            // the resident ids or replaces these buffers (launch_bmu_exact, exact_pass)
+            bool lastpos_valid = false;
         } srt[2];
+        int64_t lastpos_carried_epochs = 0;   // planned resident epochs that skipped exact_lastpos_kernel (som_debug_exact_chain_stats)
+        bool chain = true;                // SOM_EXACT_CHAIN=0: the planned epoch's small launches as separate kernels and fills (A/B)
+        // the codebook's 16-bit stage image up to 128 features (prep_w_exact_k16_kernel) is due whenever the codebook has changed; a
+        // planned launch writes it in one grid with the centroid images (exact_prep_images_kernel), which only launch_bmu_exact
+        // can know: its caller lets refresh_codebook_operands leave that one kernel pending, and the launch (or, should it not
+        // get there, the next refresh) pays it
+        bool defer_prep_w = false;        // the refresh in progress may leave it pending
+        bool prep_w_pending = false;      // it is due
+        bool prep_w_cm = false;           // ... with the centroid levels' maxima to set (the fused merge wrote the centroids)
         bool cen_ready = false;           // both centroid levels are allocated
         bool cen_fresh = false;           // ... and hold the current codebook's centroids, radii, |c|^2: the fused merge wrote them
         long sk_stride = 0;               // rows per pass the per-pass plan buffers hold
@@ -473,6 +486,29 @@ void mark_codebook_changed(som_handle* h) {
     h->wn_fresh = false; h->ex.cen_fresh = false;
 }
 
+// the exact mode's 16-bit stage image up to 128 features, and the one that was left pending (som_handle::ExactScratch::prep_w_pending)
+template <class E>
+int launch_prep_w_exact(som_handle* h, bool cm) {
+    const float* Wex = h->ex_patch ? h->Wp : h->W;
+    float* cm1 = cm ? (float*)h->ex.cen[0].cmax2 : nullptr;
+    float* cm2 = cm ? (float*)h->ex.cen[1].cmax2 : nullptr;
+    const dim3 tgrid((unsigned)cdiv((long)h->n_stages * K16_T, 4)), block(256);
+    switch (h->ks32) {
+#define SOM_PREPX_CASE(k) case k: prep_w_exact_k16_kernel<k, E><<<tgrid, block, 0, h->stream>>>(Wex, h->K, h->D, h->Wst, h->n_stages, h->wmax2, h->wmax2 + 1, h->Wst_lo, cm1, cm2); break;
+    SOM_PREPX_CASE(1) SOM_PREPX_CASE(2) SOM_PREPX_CASE(3) SOM_PREPX_CASE(4)
+#undef SOM_PREPX_CASE
+    default: return fail(h, "the resident half-precision kernel supports input_len <= 128");
+    }
+    return 0;
+}
+int flush_prep_w(som_handle* h) {
+    if (!h->ex.prep_w_pending) return 0;
+    h->ex.prep_w_pending = false;
+    if (int rc = SOM_HALF(h, launch_prep_w_exact, h, h->ex.prep_w_cm)) return rc;
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 // the 16-bit operand images of the codebook: stage / tile image, |w~|^2 per unit and its maximum
 template <class E>
 int prep_codebook_half(som_handle* h) {
@@ -526,16 +562,9 @@ int prep_codebook_half(som_handle* h) {
         }
         h->wn_fresh = false;
         // (centroids the fused merge wrote: their levels' maxima are due now that max |w|^2 is final)
-        float* cm1 = h->ex.cen_fresh ? (float*)h->ex.cen[0].cmax2 : nullptr;
-        float* cm2 = h->ex.cen_fresh ? (float*)h->ex.cen[1].cmax2 : nullptr;
-        const dim3 tgrid((unsigned)cdiv((long)h->n_stages * K16_T, 4));
-        switch (h->ks32) {
-#define SOM_PREPX_CASE(k) case k: prep_w_exact_k16_kernel<k, E><<<tgrid, block, 0, h->stream>>>(Wex, h->K, h->D, h->Wst, h->n_stages, h->wmax2, h->wmax2 + 1, h->Wst_lo, cm1, cm2); break;
-        SOM_PREPX_CASE(1) SOM_PREPX_CASE(2) SOM_PREPX_CASE(3) SOM_PREPX_CASE(4)
-#undef SOM_PREPX_CASE
-        default: return fail(h, "the resident half-precision kernel supports input_len <= 128");
-        }
-        return 0;
+        if (h->ks32 < 1 || h->ks32 > 4) return fail(h, "the resident half-precision kernel supports input_len <= 128");
+        if (h->ex.defer_prep_w) { h->ex.prep_w_pending = true; h->ex.prep_w_cm = h->ex.cen_fresh; return 0; }
+        return launch_prep_w_exact<E>(h, h->ex.cen_fresh);
     }
     const float* sc = nullptr;
     switch (h->ks32) {
@@ -555,6 +584,8 @@ int prep_codebook_half(som_handle* h) {
 int refresh_codebook_operands(som_handle* h, bool need_f32, bool patch = false) {
     if (h->exact) need_f32 = true;                       // the re-score reads the float32 stage image and |w|^2
     patch = patch && h->ex_patch;
+    // (an image a BMU launch left pending and did not get to: whoever reads the operands next pays it)
+    if (!h->ex.defer_prep_w) if (int rc = flush_prep_w(h)) return rc;
     const bool bf = h->cfg.precision != SOM_PREC_F32;
     const bool do_f32 = (need_f32 || !bf) && (h->wf_dirty || h->wf_patch != patch);
     const bool do_bf = bf && h->w_dirty;
@@ -985,7 +1016,11 @@ int verify_bmu_launch(som_handle* h, const float* X, long N, const int* ids) {
 // BMU of `N` device rows with the configured activation distance (xpysom.py:410-417)
 int run_activation_bmu_launch(som_handle* h, const float* X, long N, const float* xsq, const __bf16* Xb, const float* xmax2,
                               int* out) {
-    if (int rc = refresh_codebook_operands(h, h->cfg.precision == SOM_PREC_F32, h->exact)) return rc;
+    // (exact mode up to 128 features: the launch writes the codebook's 16-bit image itself, in one grid with its plan's centroid images)
+    h->ex.defer_prep_w = h->exact && h->ex.chain;
+    const int rc_ops = refresh_codebook_operands(h, h->cfg.precision == SOM_PREC_F32, h->exact);
+    h->ex.defer_prep_w = false;
+    if (rc_ops) return rc_ops;
     Timed t(h, SOM_K_BMU);
     if (h->exact) return launch_bmu_exact(h, X, N, xsq, Xb, xmax2, out);
     if (h->cfg.precision != SOM_PREC_F32) return launch_bmu_bf16(h, Xb, xmax2, N, out);
@@ -1473,6 +1508,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         if (const char* e = dev_env("SOM_EXACT_RESORT")) h->ex.res_every = std::max(0, std::atoi(e));
         if (const char* e = dev_env("SOM_ASYNC_COPIES")) h->async_copies = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_FUSE_MERGE")) h->fuse_merge_prep = std::atoi(e) != 0;
+        if (const char* e = dev_env("SOM_EXACT_CHAIN")) h->ex.chain = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_COUNTING_SORT")) h->counting_sort = std::atoi(e) != 0;
         // a 128-row block of a table already spans most of a map side up to 256: nothing to skip there
         h->use_bands = h->X > 256 || h->Y > 256;
@@ -1568,6 +1604,7 @@ static int adopt_rows(som_handle* h, int64_t n_rows) {
     h->bmu.reset(); h->xsq.reset(); h->Xb.reset();
     h->bmu_valid = false;
     h->ex.plan.order_lost();                             // (the resident sorted pass belongs to the rows it was sorted from)
+    h->ex.srt[0].lastpos_valid = false;
     h->seg = som_handle::SegScratch{};
     h->N = n_rows;
     h->Np = round_up(n_rows, ROW_PAD);
@@ -1751,6 +1788,7 @@ int som_epoch_accumulate_forced(som_handle* h, const int32_t* bmu_host, double s
     if (!h || (!bmu_host && h->N > 0)) return fail(h, "som_epoch_accumulate_forced: bad argument");
     for (long i = 0; i < h->N; ++i)
         if (bmu_host[i] < 0 || bmu_host[i] >= h->K) return fail(h, "som_epoch_accumulate_forced: id out of range");
+    h->ex.srt[0].lastpos_valid = false;                  // (ids from outside: the sorted rows' carried positions are not theirs)
     if (h->N > 0)
         if (int rc = h2d_blocking(h, h->bmu, bmu_host, (size_t)h->N * sizeof(int))) return rc;
     return run_update(h, sigma, eta, neigh_f64);
@@ -2445,6 +2483,12 @@ int som_debug_mfma16(som_handle* h, const uint16_t* a_host, const uint16_t* b_ho
 int som_debug_device_bytes(int64_t* out) {
     if (!out) return 1;
     *out = g_dev_bytes.load();
+    return 0;
+}
+
+int som_debug_exact_chain_stats(som_handle* h, int64_t* carried_epochs) {
+    if (!h || !carried_epochs) return fail(h, "som_debug_exact_chain_stats: NULL argument");
+    *carried_epochs = h->ex.lastpos_carried_epochs;
     return 0;
 }
 

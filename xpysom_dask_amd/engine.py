@@ -329,6 +329,13 @@ class HipEngine:
         self._check(self._lib.som_exact_top2_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def exact_chain_stats(self):
+        """precision 'exact': planned resident epochs so far that took the sorted rows' last-BMU positions from the epoch
+        before instead of gathering them again."""
+        a = C.c_int64()
+        self._check(self._lib.som_debug_exact_chain_stats(self._h, C.byref(a)))
+        return a.value
+
     def exact_skip_stats(self):
         """precision 'exact': (blocks the screens ran, blocks of full scans) so far -- block skipping's executed share."""
         a, b = C.c_int64(), C.c_int64()
