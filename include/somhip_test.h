@@ -39,6 +39,11 @@ int som_debug_qe_stats(som_handle* h, int64_t* rows, int64_t* rows_sqrt);
  * the epoch before (stored by its exact_finalize_kernel) instead of gathering them with exact_lastpos_kernel. */
 int som_debug_exact_chain_stats(som_handle* h, int64_t* carried_epochs);
 
+/* precision EXACT, the candidate selection of the screen passes so far: passes whose listed screen selected in its own launch
+ * (the select tail of csrc/bmu_bf16_k16.hpp), passes that launched exact_select_kernel behind their screen, and the tiles
+ * of the former whose list was cut into parts and which the last part to arrive selected (tests/test_gpu_exact_select_fused.py). */
+int som_debug_exact_select_stats(som_handle* h, int64_t* fused_passes, int64_t* launched_passes, int64_t* ticket_tiles);
+
 /* diagnostic builds only (-DSOM_STAMPS, tools/stamps.py builds one on demand): out_host == NULL attaches a buffer of n_pairs
  * (shader-clock ticks, 100 MHz ticks) pairs, one per workgroup of the next BMU launches (n_pairs == 0 detaches);
  * out_host != NULL reads n_pairs pairs back.  The product build refuses both. */

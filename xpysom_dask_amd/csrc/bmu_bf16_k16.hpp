@@ -224,6 +224,94 @@ __global__ __launch_bounds__(64 * KS32) void merge_prep_k16_kernel(float* __rest
     }
 }
 
+// The chunk walk of the exact mode's candidate selection (bmu_exact.hpp, step 2), for ONE wave and the 64 rows of row block rb
+// (lane <-> row): the groups [g_begin, g_end) of all groups -- or, my_list != nullptr, of a tile's list (entries group << 4 | mask).
+// The wave reads the masks of 64 groups with one coalesced load (lane = group), walks the groups whose mask is not empty --
+// eight at a time, so that their value loads are in flight together --, loads only the stored rows' values (src = gmin + row)
+// and keeps the ones at or below thr (bit patterns: every d' is a positive float, a NaN pattern is above every threshold;
+// ok false: the row selects nothing).  The 64 lanes test the SAME group at the same time: a group's hits take consecutive
+// positions of its list from ONE returning atomic per wave and 64 groups (lane j adds group j's population and hands out the
+// base).  Returns the row's number of hits.  ROUND2: the group `arg` is left out (exact_select_kernel).
+// Two callers: exact_select_kernel, a launch of its own, and the listed screen's select tail below.
+template <bool ROUND2>
+__device__ __forceinline__ int ex_select_walk(const uint32_t* __restrict__ src, const unsigned long long* __restrict__ gflags,
+                                              long gm_stride, int n_groups, long rb, long row, int lane, bool ok, uint32_t thr,
+                                              int arg, const int* __restrict__ my_list, int g_begin, int g_end,
+                                              int* __restrict__ plist, int* __restrict__ gcount) {
+    const unsigned long long below = (1ull << lane) - 1;
+    int mine = 0;
+    for (int gb = g_begin; gb < g_end; gb += 64) {
+        // lane j <-> the j-th group of this chunk
+        const int gid = gb + lane < g_end ? (my_list != nullptr ? (my_list[gb + lane] >> 4) : gb + lane) : -1;
+        const unsigned long long fw = gid >= 0 ? gflags[ex_flag_index(rb, gid, n_groups, gm_stride)] : 0ull;
+        const unsigned long long any = __ballot(fw != 0ull);
+        if (any == 0) continue;
+        const uint32_t fw_lo = (uint32_t)fw, fw_hi = (uint32_t)(fw >> 32);
+        unsigned long long hits = 0;                       // bit j: the chunk's j-th group is a candidate of this lane's row
+        unsigned long long todo = any;
+        while (todo != 0) {
+            int j[8];
+            uint32_t v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                j[q] = todo != 0 ? (int)__builtin_ctzll(todo) : -1;
+                if (todo != 0) todo &= todo - 1;
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                v[q] = 0xFFFFFFFFu;
+                if (j[q] >= 0) {                           // (wave-uniform)
+                    const unsigned long long stored = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)fw_hi, j[q]) << 32) |
+                                                      (uint32_t)__builtin_amdgcn_readlane((int)fw_lo, j[q]);
+                    const int g = __builtin_amdgcn_readlane(gid, j[q]);
+                    if ((stored >> lane) & 1ull) v[q] = src[(long)g * gm_stride];   // (only the rows the screen stored)
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (j[q] >= 0) {
+                    // (ROUND2: the group round 1 scored for this row is not selected again -- by its id: under a tile list
+                    //  the chunk's j-th group is not group gb + j)
+                    const int g = __builtin_amdgcn_readlane(gid, j[q]);
+                    hits |= (unsigned long long)(v[q] <= thr && !(ROUND2 && g == arg)) << j[q];
+                }
+        }
+        if (!ok) hits = 0;
+        if (__ballot(hits != 0ull) == 0) continue;
+        int c = 0;                                         // lane j: the wave's hits in the chunk's j-th group
+        for (todo = any; todo != 0; todo &= todo - 1) {
+            const int jj = (int)__builtin_ctzll(todo);
+            const unsigned long long mk = __ballot((hits >> jj) & 1ull);
+            if (lane == jj) c = (int)__builtin_popcountll(mk);
+        }
+        int base = 0;
+        if (c > 0) base = atomicAdd(gcount + gid, c);
+        for (todo = any; todo != 0; todo &= todo - 1) {
+            const int jj = (int)__builtin_ctzll(todo);
+            const unsigned long long mk = __ballot((hits >> jj) & 1ull);
+            if (mk == 0) continue;
+            const int o = __builtin_amdgcn_readlane(base, jj);
+            const int g = __builtin_amdgcn_readlane(gid, jj);
+            if ((hits >> jj) & 1ull) plist[(long)g * gm_stride + o + (int)__builtin_popcountll(mk & below)] = (int)row;
+        }
+        mine += (int)__builtin_popcountll(hits);
+    }
+    return mine;
+}
+
+// What the listed screen's SELECT TAIL (below) walks and writes: the select kernel's inputs and outputs under a plan.
+// plist == nullptr: no tail -- the screen ends as it always did and exact_select_kernel is a launch of its own.
+struct ScreenSelect {
+    const int* glist = nullptr;       // per tile: (group << 4 | sub-block mask), the groups the plan kept ...
+    const int* gcnt = nullptr;        // ... and how many
+    int* plist = nullptr;             // [n_groups][gm_stride] the groups' row lists
+    int* gcount = nullptr;            // [n_groups] their fill cursors
+    int* rowcnt = nullptr;            // [rows] candidate groups per row
+    uint32_t* rowmin2_init = nullptr; // a launch that refines: the rows' refined minima start from all ones (or null)
+    int* tile_ticket = nullptr;       // [tiles] arrivals of a cut tile's parts; zero at the pass's start (exact_lists_tile)
+    int* ticket_tiles = nullptr;      // PassCounters::ticket_tiles
+};
+
 // GM (precision 'exact', bmu_exact.hpp): the kernel keeps VALUES only -- the row minimum (out64's upper half; no unit
 // indices exist in this instance, the float32 re-score names the unit) and, per stage (= one GROUP of 64 units) and row,
 // the group's minimum.  A lane holds its quad's minimum for each of the wave's 4 sample blocks; three v_permlane*_swap +
@@ -239,9 +327,27 @@ __global__ __launch_bounds__(64 * KS32) void merge_prep_k16_kernel(float* __rest
 // minimum so far -- a lane keeps the two smallest group minima of its row (two registers more), a group minimum is stored where
 // it is within E of the second one, and every part of the codebook hands back its own pair (t2min[(2 part + {0, 1}) t2pitch + row]:
 // the second-smallest of a part is never below the second-smallest of all parts; exact_select_kernel<false, true> merges them).
+// SEL (with GM and TL, on the work queue below; sel->plist != nullptr): the SELECT TAIL.  At the end of a tile's walk lane l holds
+// what exact_select_kernel rebuilds its threshold from -- the row's minimum, its bound E, the seed's cap -- and the masks and
+// values that kernel would walk were written a moment ago by this very wave: the wave selects for its own 64 rows here
+// (ex_select_walk over the tile's glist), in the shadow of the CU's other workgroups' MFMAs, and the launch of
+// exact_select_kernel<false> behind the screen is gone.  What is selected is bit for bit what that kernel selects: the
+// threshold is the same float expression min(m + E, seed + float32 share) with the same "finite and positive" guard.
+//   A tile with ONE item: the row minimum never leaves the registers -- no atomicMin into out64, which keeps the all-ones the
+//   re-score's merge expects.  Masks (this wave's lane 0) and values (the reading lane itself) come back from this CU: a
+//   workgroup-scope release / acquire between the walk's stores and the tail's loads.
+//   A tile CUT into parts: every part ends as before (stores, atomicMin into out64), publishes -- every storing wave drains,
+//   workgroup barrier, one lane: agent-scope release fence, an explicit wait, a relaxed agent-scope add on the tile's ticket --
+//   and the part whose add returns parts - 1 is last: it acquires (agent scope: the parts may have run on other XCDs and share
+//   128-byte lines of gflags, cut as they are at group boundaries), reads its rows' minima from out64, puts all ones back and
+//   runs the tail.  Plain stores + one release fence rather than write-through stores: the walk's stores sit in fold_stage, in
+//   the MFMA loop, which this must not touch, and a part releases once.  Nobody waits for anybody: no poll, no spin.
+//   EVERY ROW EXACTLY ONCE: exact_list_totals_body gives every tile at least one item (parts_of(0) == 1: a tile whose list is
+//   empty too) and the parts of a tile draw the tickets 0 .. parts - 1 exactly once, so exactly one workgroup per tile runs
+//   the tail -- rowcnt, rowmin2_init and the merge keys of every row of the pass are written once, as the select kernel did.
 // (the kernel's body for one workgroup's worth of rows: tile bx of K16_WG_SAMPLES rows, part by of ny of the codebook stages -- or,
 //  TL, of the tile's list.  The kernel below calls it once, or -- the exact mode's screen under a plan -- once per work item.)
-template <int KS32, class EL, bool GM, bool TL, bool T2 = false>
+template <int KS32, class EL, bool GM, bool TL, bool T2 = false, bool SEL = false>
 __device__ __forceinline__ void bmu_bf16_k16_body(const __bf16* __restrict__ Xb, long N,
                                                   const char* __restrict__ Wst, int n_stages, int K,
                                                   unsigned long long* __restrict__ out64,
@@ -252,8 +358,10 @@ __device__ __forceinline__ void bmu_bf16_k16_body(const __bf16* __restrict__ Xb,
                                                   const float* __restrict__ werr2, const ExactBound& eb,
                                                   const float* __restrict__ seed, const int* __restrict__ glist,
                                                   const int* __restrict__ gcnt, const long bx, const int by, const int ny,
-                                                  float* __restrict__ t2min = nullptr, long t2pitch = 0) {
+                                                  float* __restrict__ t2min = nullptr, long t2pitch = 0,
+                                                  const ScreenSelect* sel = nullptr, int* s_word = nullptr) {
     static_assert(!T2 || (GM && !TL), "the top-2 screen is the group-minimum instance over every stage");
+    static_assert(!SEL || (GM && TL), "the select tail belongs to the listed group-minimum screen");
     using E = typename EL::T;
     using bf16x8 = typename V8<E>::t;
     constexpr int DP = 32 * KS32;
@@ -511,6 +619,61 @@ __device__ __forceinline__ void bmu_bf16_k16_body(const __bf16* __restrict__ Xb,
         // the row minimum IS the minimum so far after the last group (lane l <-> row wave_s0 + l): the plain value, every
         // bit of it, and the group that holds it (no unit indices exist here); parts merge by value, then lower group
         const long row = wave_s0 + lane;
+        if (SEL && sel->plist != nullptr) {
+            // the SELECT TAIL (see above): this workgroup's waves select for their own 64 rows -- if the tile's minima are final here
+            // (ln: the lane again, opaque to the compiler -- what depends on the lane alone (1 << lane, its masks) is otherwise
+            //  computed once in front of the queue's loop and held in registers through every walk: this instance has none to spare)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const long row = wave_s0 + ln;
+            const bool live = row < N;
+            float m = run_min;
+            if (ny > 1) {
+                if (live) atomicMin(out64 + row, ((unsigned long long)__float_as_uint(run_min) << 32) | (uint32_t)run_arg);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every storing wave drains
+                __syncthreads();
+                if (wave == 0 && ln == 0) {                            // (not tid: a register held across the walk for this alone)
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the fence's own wait may be dropped: keep this one, in this order)
+                    const int ticket = __hip_atomic_fetch_add(sel->tile_ticket + bx, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const int last = ticket == ny - 1 ? 1 : 0;
+                    if (last) {
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        atomicAdd(sel->ticket_tiles, 1);
+                    }
+                    *s_word = last;                                      // (the queue's item word: everyone has read the item)
+                }
+                __syncthreads();
+                const int last = *s_word;
+                __syncthreads();                                         // (... before the queue's next item lands in that word)
+                if (!last) return;
+                // (agent-scope accesses: the other parts' atomics have gone to memory past every cache, and so do these)
+                const unsigned long long k64 = live ? __hip_atomic_load(out64 + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0ull;
+                if (live) __hip_atomic_store(out64 + row, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                m = __uint_as_float((uint32_t)(k64 >> 32));
+            } else {
+                // (ASSUMES the default, non-threadgroup-split mode: the waves of a workgroup share one CU and its L1, so that behind a
+                //  workgroup-scope release, a drained vmcnt and an acquire a wave's loads see what its own lanes stored.  Under
+                //  tgsplit the workgroup's waves may sit on different CUs and this pair would have to be the agent-scope one.)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            }
+            // exact_select_kernel's threshold, from the registers (run_cap is seed + ex_f32_share; a row the bound does not cover
+            // has row_e = inf here and a NaN there: neither passes the guard unless the seed's cap alone is a finite number, and
+            // then both give the cap)
+            const float thr_f = __builtin_fminf(m + row_e, run_cap);
+            const bool ok = live && thr_f > 0.0f && thr_f < 3.0e38f;
+            const uint32_t thr = ok ? __float_as_uint(thr_f) : 0u;
+            const int mine = ex_select_walk<false>(gmin + (live ? row : 0), gflags, gm_stride, n_stages, wave_s0 >> 6, row, ln, ok, thr, -1,
+                                                   sel->glist + bx * (long)n_stages, 0, sel->gcnt[bx], sel->plist, sel->gcount);
+            if (live) {
+                sel->rowcnt[row] = mine;
+                if (sel->rowmin2_init != nullptr) sel->rowmin2_init[row] = 0xFFFFFFFFu;
+            }
+            return;
+        }
         if (row < N) atomicMin(out64 + row, ((unsigned long long)__float_as_uint(run_min) << 32) | (uint32_t)run_arg);
         if (T2 && row < N) {
             t2min[(long)(2 * by) * t2pitch + row] = run_min;
@@ -557,7 +720,8 @@ __global__ __launch_bounds__(64 * K16_NW, (TL && GM) ? 3 : 2) void bmu_bf16_k16_
                                                               const int2* __restrict__ items = nullptr,
                                                               const int* __restrict__ n_items = nullptr,
                                                               int* __restrict__ item_ctr = nullptr,
-                                                              float* __restrict__ t2min = nullptr, long t2pitch = 0) {
+                                                              float* __restrict__ t2min = nullptr, long t2pitch = 0,
+                                                              ScreenSelect sel = ScreenSelect()) {
     if (TL && items != nullptr) {
         __shared__ int s_item;
         const int n = *n_items;
@@ -568,8 +732,9 @@ __global__ __launch_bounds__(64 * K16_NW, (TL && GM) ? 3 : 2) void bmu_bf16_k16_
             __syncthreads();
             if (it >= n) return;
             const int2 iv = items[it];
-            bmu_bf16_k16_body<KS32, EL, GM, TL>(Xb, N, Wst, n_stages, K, out64, gmin, gm_stride, gflags, xsq, xerr, xmax2, wmax2, werr2, eb,
-                                                seed, glist, gcnt, (long)iv.x, iv.y & 0xFFFF, iv.y >> 16);
+            bmu_bf16_k16_body<KS32, EL, GM, TL, false, GM && TL>(Xb, N, Wst, n_stages, K, out64, gmin, gm_stride, gflags, xsq, xerr, xmax2, wmax2,
+                                                                 werr2, eb, seed, glist, gcnt, (long)iv.x, iv.y & 0xFFFF, iv.y >> 16, nullptr, 0,
+                                                                 &sel, &s_item);
         }
     }
     bmu_bf16_k16_body<KS32, EL, GM, TL, T2>(Xb, N, Wst, n_stages, K, out64, gmin, gm_stride, gflags, xsq, xerr, xmax2, wmax2, werr2, eb, seed,

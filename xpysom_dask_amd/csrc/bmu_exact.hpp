@@ -104,6 +104,7 @@ struct PassCounters {
     int scout_wins;   // exact_plan_kernel: rows whose scout pick beat their last BMU by a tenth of the squared distance
     int bad_w;        // exact_top2_settle_kernel: the codebook holds a unit whose |w|^2 is not finite
     int lists_done;   // exact_lists_totals_kernel: its workgroups' tickets (the last one sets it back to zero)
+    int ticket_tiles; // the listed screen's select tail (bmu_bf16_k16.hpp): tiles cut into parts, selected by the last part to arrive
 };
 // The row-need estimate (exact_scout_rowneed_kernel, exact_skip.hpp) runs before a launch's first pass and borrows the head of the block.
 struct RowNeed {
@@ -202,65 +203,8 @@ __global__ __launch_bounds__(64 * EX_SCAN_SPLIT) void exact_select_kernel(const 
     const int* my_list = glist != nullptr ? glist + (row0 / rows_per_list) * (long)n_groups : nullptr;
     const int n_walk = my_list != nullptr ? gcnt[row0 / rows_per_list] : n_groups;
     const int g_begin = (int)((long)n_walk * part / EX_SCAN_SPLIT), g_end = (int)((long)n_walk * (part + 1) / EX_SCAN_SPLIT);
-    const uint32_t* src = gmin + r;
-    const unsigned long long below = (1ull << lane) - 1;
-    int mine = 0;
-    for (int gb = g_begin; gb < g_end; gb += 64) {
-        // lane j <-> the j-th group of this chunk
-        const int gid = gb + lane < g_end ? (my_list != nullptr ? (my_list[gb + lane] >> 4) : gb + lane) : -1;
-        const unsigned long long fw = gid >= 0 ? gflags[ex_flag_index(blockIdx.x, gid, n_groups, gm_stride)] : 0ull;
-        const unsigned long long any = __ballot(fw != 0ull);
-        if (any == 0) continue;
-        const uint32_t fw_lo = (uint32_t)fw, fw_hi = (uint32_t)(fw >> 32);
-        unsigned long long hits = 0;                       // bit j: the chunk's j-th group is a candidate of this lane's row
-        unsigned long long todo = any;
-        while (todo != 0) {
-            int j[8];
-            uint32_t v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                j[q] = todo != 0 ? (int)__builtin_ctzll(todo) : -1;
-                if (todo != 0) todo &= todo - 1;
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                v[q] = 0xFFFFFFFFu;
-                if (j[q] >= 0) {                           // (wave-uniform)
-                    const unsigned long long stored = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)fw_hi, j[q]) << 32) |
-                                                      (uint32_t)__builtin_amdgcn_readlane((int)fw_lo, j[q]);
-                    const int g = __builtin_amdgcn_readlane(gid, j[q]);
-                    if ((stored >> lane) & 1ull) v[q] = src[(long)g * gm_stride];   // (only the rows the screen stored)
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                if (j[q] >= 0) {
-                    // (ROUND2: the group round 1 scored for this row is not selected again -- by its id: under a tile list
-                    //  the chunk's j-th group is not group gb + j)
-                    const int g = __builtin_amdgcn_readlane(gid, j[q]);
-                    hits |= (unsigned long long)(v[q] <= thr && !(ROUND2 && g == arg)) << j[q];
-                }
-        }
-        if (!ok) hits = 0;
-        if (__ballot(hits != 0ull) == 0) continue;
-        int c = 0;                                         // lane j: the wave's hits in the chunk's j-th group
-        for (todo = any; todo != 0; todo &= todo - 1) {
-            const int jj = (int)__builtin_ctzll(todo);
-            const unsigned long long mk = __ballot((hits >> jj) & 1ull);
-            if (lane == jj) c = (int)__builtin_popcountll(mk);
-        }
-        int base = 0;
-        if (c > 0) base = atomicAdd(gcount + gid, c);
-        for (todo = any; todo != 0; todo &= todo - 1) {
-            const int jj = (int)__builtin_ctzll(todo);
-            const unsigned long long mk = __ballot((hits >> jj) & 1ull);
-            if (mk == 0) continue;
-            const int o = __builtin_amdgcn_readlane(base, jj);
-            const int g = __builtin_amdgcn_readlane(gid, jj);
-            if ((hits >> jj) & 1ull) plist[(long)g * gm_stride + o + (int)__builtin_popcountll(mk & below)] = (int)row;
-        }
-        mine += (int)__builtin_popcountll(hits);
-    }
+    const int mine = ex_select_walk<ROUND2>(gmin + r, gflags, gm_stride, n_groups, (long)blockIdx.x, row, lane, ok, thr, arg, my_list, g_begin,
+                                            g_end, plist, gcount);
     cnt_s[part][lane] = mine;
     __syncthreads();
     if (part == 0 && live) {

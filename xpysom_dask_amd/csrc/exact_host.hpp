@@ -121,7 +121,10 @@ int exact_reserve_stride(som_handle* h, long stride) {
 
 template <int KS32, class E>
 int exact_screen(som_handle* h, const __bf16* Xb, long n, unsigned long long* best64, const float* xsq, const float* xerr,
-                 const float* xmax2, const ExactBound& eb, const float* seed, const int* glist, const int* gcnt) {
+                 const float* xmax2, const ExactBound& eb, const float* seed, const int* glist, const int* gcnt,
+                 const ScreenSelect& sel, bool* selected) {
+    // sel: the select tail's arguments (plist null: none wanted); *selected: did this launch select -- only the work queue can
+    *selected = false;
     const int n_groups = (int)cdiv(h->K, EX_GROUP);
     // one pass on scaled half operands: a stage IS a group
     const bool tl = glist != nullptr;
@@ -147,10 +150,13 @@ int exact_screen(som_handle* h, const __bf16* Xb, long n, unsigned long long* be
     if (tl && h->ex.item_queue && glist == h->ex.tlist) {
         // (the plan's lists as a work queue: a workgroup per slot of the chip, items of about equal length -- bmu_bf16_k16.hpp;
         //  the next plan cuts its lists for this many workgroups)
+        // (sel, where the pass asks for it: the workgroup that ends a tile selects its rows' candidates too -- the select tail of
+        //  bmu_bf16_k16.hpp; *selected tells the pass that exact_select_kernel has nothing left to do)
         h->ex.screen_slots = (int)std::min<long>(slots, h->ex.item_slots);
         bmu_bf16_k16_kernel<KS32, E, true, true><<<dim3((unsigned)h->ex.screen_slots), block, lds, h->stream>>>(
             Xb, n, h->Wst, h->n_stages, h->K, best64, h->ex.gmin, h->ex.stride, h->ex.gflags, xsq, xerr, xmax2, h->wmax2, h->wmax2 + 1, eb,
-            seed, glist, gcnt, h->ex.items + 8, (const int*)h->ex.items.p, (int*)h->ex.items.p + 1);
+            seed, glist, gcnt, h->ex.items + 8, (const int*)h->ex.items.p, (int*)h->ex.items.p + 1, nullptr, 0, sel);
+        *selected = sel.plist != nullptr;
     } else if (tl)
         bmu_bf16_k16_kernel<KS32, E, true, true><<<grid, block, lds, h->stream>>>(
             Xb, n, h->Wst, h->n_stages, h->K, best64, h->ex.gmin, h->ex.stride, h->ex.gflags, xsq, xerr, xmax2, h->wmax2, h->wmax2 + 1, eb,
@@ -226,13 +232,14 @@ int exact_screen_wide(som_handle* h, const __bf16* Ximg, long n, unsigned long l
 
 template <class E>
 int exact_screen_ks(som_handle* h, const __bf16* Xb, long n, unsigned long long* best64, const float* xsq, const float* xerr,
-                    const float* xmax2, const ExactBound& eb, const float* seed, const int* glist = nullptr,
-                    const int* gcnt = nullptr) {
+                    const float* xmax2, const ExactBound& eb, const float* seed, const int* glist, const int* gcnt,
+                    const ScreenSelect& sel, bool* selected) {
+    *selected = false;
     if (h->wide) {
         SOM_WIDE_DISPATCH(exact_screen_wide, h, Xb, n, best64, xsq, xerr, xmax2, eb, glist, gcnt)
         return fail(h, "exact: no wide screen instance for this input_len");
     }
-    SOM_KS32_DISPATCH(exact_screen, h, Xb, n, best64, xsq, xerr, xmax2, eb, seed, glist, gcnt)
+    SOM_KS32_DISPATCH(exact_screen, h, Xb, n, best64, xsq, xerr, xmax2, eb, seed, glist, gcnt, sel, selected)
     return fail(h, "exact: the screen kernel supports input_len <= 128");
 }
 
@@ -313,7 +320,7 @@ int exact_skip_reserve(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
     if (stride <= ex.sk_stride) return 0;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     ex.sk_keys.reset(); ex.sk_keys2.reset(); ex.sk_vals.reset(); ex.sk_tmp.reset(); ex.need.reset(); ex.need2.reset(); ex.glist.reset(); ex.gcnt.reset();
-    ex.tile_counts.reset(); ex.tlist.reset(); ex.tcnt.reset(); ex.scout_g.reset(); ex.items.reset();
+    ex.tile_counts.reset(); ex.tlist.reset(); ex.tcnt.reset(); ex.scout_g.reset(); ex.items.reset(); ex.tile_ticket.reset();
     ex.sk_stride = 0;
     const long tiles = stride / SK_TILE;
     if (int rc = ex.sk_keys.alloc(h, (size_t)stride)) return rc;
@@ -329,6 +336,7 @@ int exact_skip_reserve(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
     if (int rc = ex.tile_counts.alloc(h, (size_t)tiles)) return rc;
     if (int rc = ex.tlist.alloc(h, (size_t)tiles * n_groups * K16_T)) return rc;
     if (int rc = ex.tcnt.alloc(h, (size_t)tiles)) return rc;
+    if (int rc = ex.tile_ticket.alloc(h, (size_t)tiles)) return rc;
     // (the listed screen's work items: exact_list_totals_body, exact_skip.hpp -- within 5 tiles + 4 slots of them; + the queue's two words and their padding)
     ex.item_slots = (int)resident_slots(h, 8);    // (more workgroups than this never fit a chip: few features, small stages)
     if (int rc = ex.items.alloc(h, (size_t)(5 * tiles + 4 * ex.item_slots + 16))) return rc;
@@ -474,11 +482,11 @@ void exact_plan_lists(som_handle* h, long tiles, int n_cstages, const unsigned l
     if (ex.chain) {
         exact_lists_totals_kernel<<<dim3((unsigned)cdiv(tiles, LISTS_WG_TILES)), dim3(64 * LISTS_WG_TILES), 0, h->stream>>>(
             ex.need, n_cstages, need2, n_groups, ex.glist, ex.gcnt, ex.tile_counts, ex.tlist, ex.tcnt, tiles, &ctr->lists_done,
-            &ctr->blocks_run, &ctr->groups_run, slots, queue, n_items, n_items + 1, ex.item_len_pct);
+            &ctr->blocks_run, &ctr->groups_run, slots, queue, n_items, n_items + 1, ex.item_len_pct, ex.tile_ticket);
         return;
     }
     exact_lists_kernel<<<dim3((unsigned)tiles), dim3(64), 0, h->stream>>>(ex.need, n_cstages, need2, n_groups, ex.glist, ex.gcnt,
-                                                                         ex.tile_counts, ex.tlist, ex.tcnt);
+                                                                         ex.tile_counts, ex.tlist, ex.tcnt, ex.tile_ticket);
     exact_list_totals_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(ex.tile_counts, tiles, &ctr->blocks_run, &ctr->groups_run, slots, queue,
                                                                   n_items, n_items + 1, ex.item_len_pct);
 }
@@ -916,15 +924,24 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
         p_xsq = sr.xsq_s + s0; p_xerr = sr.xerr_s + s0; p_seed = sr.seed_s + s0; p_Xb = sr.Xb_s + s0 * h->dp; p_order = sr.order + s0;
         p_X = sr.Xf_s + s0 * h->D;
     }
+    // the listed screen on its work queue selects the candidates in its own launch (SOM_EXACT_FUSE_SELECT=0: exact_select_kernel
+    // behind it, as on every other path): what the select kernel would get, handed to exact_screen
+    bool sel_fused = false;
+    ScreenSelect screen_sel{};
+    if (ex.fuse_select && lp.skip && !h->wide && !L.two_round && ex.item_queue)
+        screen_sel = ScreenSelect{ex.glist, ex.gcnt, ex.plist, pc.gcount(), ex.rowcnt, lp.refine && ex.chain ? (uint32_t*)ex.rowarg.p : nullptr,
+                                     ex.tile_ticket, &pc.tail()->ticket_tiles};
     {
+        // (under a plan with the select tail the bracket -- and cost.ev[1] .. ev[2], the policy's screen time -- holds the selection too)
         Timed ts(h, SOM_K_SCREEN);
         if (lp.time_phases) { HIPCHK(h, hipEventRecord(cost.ev[1], h->stream)); }
         // (the lists the screen walks: dense 16-unit tiles up to 128 features, whole groups beyond)
         if (int rc = SOM_HALF(h, exact_screen_ks, h, p_Xb, n, h->best64 + r0, p_xsq, p_xerr, xmax2, eb, p_seed,
                               lp.skip ? (h->wide ? ex.glist : ex.tlist) : nullptr,
-                              lp.skip ? (h->wide ? ex.gcnt : ex.tcnt) : nullptr)) return rc;
+                              lp.skip ? (h->wide ? ex.gcnt : ex.tcnt) : nullptr, screen_sel, &sel_fused)) return rc;
         if (lp.time_phases) { HIPCHK(h, hipEventRecord(cost.ev[2], h->stream)); L.o.screen_timed = true; }
     }
+    (sel_fused ? ex.sel_fused_passes : ex.sel_launched_passes) += 1;
     const dim3 sel_grid((unsigned)cdiv(n, 64)), sel_block(64 * EX_SCAN_SPLIT);
     unsigned long long* best = h->best64 + r0;
     // two rounds beyond 128 features, where a (row, group) pair costs 64 x D flop AND a gather of the row's D floats
@@ -943,10 +960,11 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
             pc.gcount(), ex.rowcnt, ex.rowarg, nullptr, lp.skip ? ex.glist : nullptr, lp.skip ? ex.gcnt : nullptr, SK_TILE);
         if (int rc = exact_rescore_round(h, p_X, p_xsq, best, pc.gstart(), nullptr, lp.skip, !lp.refine)) return rc;
     } else {
-        exact_select_kernel<false><<<sel_grid, sel_block, 0, h->stream>>>(
-            ex.gmin, ex.gflags, ex.stride, n_groups, n, best, p_xsq, h->wmax2, xmax2, eb, p_xerr, h->wmax2 + 1, ex.plist,
-            pc.gcount(), ex.rowcnt, nullptr, p_seed, lp.skip ? ex.glist : nullptr, lp.skip ? ex.gcnt : nullptr, SK_TILE,
-            nullptr, 0, 0, lp.refine && ex.chain ? (uint32_t*)ex.rowarg.p : nullptr);
+        if (!sel_fused)
+            exact_select_kernel<false><<<sel_grid, sel_block, 0, h->stream>>>(
+                ex.gmin, ex.gflags, ex.stride, n_groups, n, best, p_xsq, h->wmax2, xmax2, eb, p_xerr, h->wmax2 + 1, ex.plist,
+                pc.gcount(), ex.rowcnt, nullptr, p_seed, lp.skip ? ex.glist : nullptr, lp.skip ? ex.gcnt : nullptr, SK_TILE,
+                nullptr, 0, 0, lp.refine && ex.chain ? (uint32_t*)ex.rowarg.p : nullptr);
         if (lp.refine)
             if (int rc = SOM_HALF(h, exact_refine, h, sr, s0, n, xmax2, eb)) return rc;
         if (int rc = exact_rescore_round(h, p_X, xsq + r0, best, nullptr, nullptr, lp.skip, !lp.refine)) return rc;
@@ -990,6 +1008,7 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
     L.o.pairs_in += got.pairs_in;
     if (lp.refine) L.o.pairs_out += got.pairs_out;
     if (lp.skip && lp.scout && have_last) L.o.scout_wins += got.scout_wins;
+    if (sel_fused) ex.sel_ticket_tiles += got.ticket_tiles;
     L.fallback_rows += n_fb;
     if (n_fb < 0 || n_fb > n) return fail(h, "exact: fallback counter out of range");
     if (n_fb > 0) return exact_fallback_rows(h, L, r0, n_fb);

@@ -792,6 +792,8 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
 // word 4 s + k holds, for the groups 64 s + 16 k .. + 15, a nibble each (bit 4 (g & 15) + sub <-> sub-block `sub` of group g).
 // ... and the same blocks as the tile's dense list of 16-unit tiles (tlist / tcnt: what the screen walks; glist / gcnt: what
 // the select kernel walks).  One wave per tile; tile_counts[tile] = (16-unit blocks listed, groups level 1 kept).
+// tile_ticket[tile] = 0: the arrivals of the tile's parts in the listed screen's select tail (bmu_bf16_k16.hpp) start from zero in
+// every pass -- here, where every tile of the pass is visited anyway, not by a fill of their own.
 // (PUBLISH: tile_counts[tile] leaves as one 8-byte agent-scope store, written through to memory: another workgroup of the same
 //  launch reads it -- exact_lists_totals_kernel)
 template <bool PUBLISH>
@@ -799,7 +801,7 @@ __device__ __forceinline__ void exact_lists_tile(const long tile, const int lane
                                                  const unsigned long long* __restrict__ need2, int n_groups,
                                                  int* __restrict__ glist, int* __restrict__ gcnt,
                                                  int2* tile_counts, int* __restrict__ tlist,
-                                                 int* __restrict__ tcnt) {
+                                                 int* __restrict__ tcnt, int* __restrict__ tile_ticket) {
     const unsigned long long below = (1ull << lane) - 1ull;
     int base = 0, blk = 0, kept = 0;
     for (int s0 = 0; s0 < n_cstages; s0 += 64) {
@@ -841,6 +843,7 @@ __device__ __forceinline__ void exact_lists_tile(const long tile, const int lane
     // (per tile: 4 096 waves adding into two words of one cache line took as long as the rest of this kernel)
     if (lane == 0) {
         gcnt[tile] = base; tcnt[tile] = blk;
+        tile_ticket[tile] = 0;
         if (PUBLISH)
             __hip_atomic_store((unsigned long long*)(tile_counts + tile), ((unsigned long long)(uint32_t)kept << 32) | (uint32_t)blk,
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -851,8 +854,8 @@ __global__ __launch_bounds__(64) void exact_lists_kernel(const unsigned long lon
                                                          const unsigned long long* __restrict__ need2, int n_groups,
                                                          int* __restrict__ glist, int* __restrict__ gcnt,
                                                          int2* __restrict__ tile_counts, int* __restrict__ tlist,
-                                                         int* __restrict__ tcnt) {
-    exact_lists_tile<false>(blockIdx.x, threadIdx.x, need1, n_cstages, need2, n_groups, glist, gcnt, tile_counts, tlist, tcnt);
+                                                         int* __restrict__ tcnt, int* __restrict__ tile_ticket) {
+    exact_lists_tile<false>(blockIdx.x, threadIdx.x, need1, n_cstages, need2, n_groups, glist, gcnt, tile_counts, tlist, tcnt, tile_ticket);
 }
 
 // sum of the tiles' (16-unit blocks listed, groups level 1 kept) into the pass's counters.  One workgroup.
@@ -930,14 +933,15 @@ __global__ __launch_bounds__(64 * LISTS_WG_TILES) void exact_lists_totals_kernel
                                                                                 int* __restrict__ tcnt, long tiles, int* __restrict__ done,
                                                                                 int* __restrict__ blocks_run, int* __restrict__ groups_run,
                                                                                 int slots, int2* __restrict__ items, int* __restrict__ n_items,
-                                                                                int* __restrict__ item_ctr, int len_pct) {
+                                                                                int* __restrict__ item_ctr, int len_pct,
+                                                                                int* __restrict__ tile_ticket) {
     static_assert(LISTS_WG_TILES == 16, "the totals' scan is written for sixteen waves");
     __shared__ int sb[16], sk[16];
     __shared__ int tot_b;
     __shared__ int last;
     const int tid = threadIdx.x;
     const long tile = (long)blockIdx.x * LISTS_WG_TILES + (tid >> 6);
-    if (tile < tiles) exact_lists_tile<true>(tile, tid & 63, need1, n_cstages, need2, n_groups, glist, gcnt, tile_counts, tlist, tcnt);
+    if (tile < tiles) exact_lists_tile<true>(tile, tid & 63, need1, n_cstages, need2, n_groups, glist, gcnt, tile_counts, tlist, tcnt, tile_ticket);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {

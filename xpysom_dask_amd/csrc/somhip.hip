@@ -198,6 +198,10 @@ struct som_handle {
         DevBuf<int> glist, gcnt;          // per tile: (group << 4 | sub-block mask) items: what the select kernel walks
         DevBuf<int> tlist, tcnt;          // per tile: the same blocks as a dense list of 16-unit tiles: what the screen walks
         DevBuf<int2> tile_counts;
+        DevBuf<int> tile_ticket;          // per tile: arrivals of its parts in the listed screen's select tail (zeroed by the lists kernels)
+        // the listed screen's SELECT TAIL (bmu_bf16_k16.hpp): the queue's workgroups select the candidates behind their walks
+        bool fuse_select = true;          // SOM_EXACT_FUSE_SELECT=0: exact_select_kernel in a launch of its own behind the screen (A/B)
+        int64_t sel_fused_passes = 0, sel_launched_passes = 0, sel_ticket_tiles = 0;   // som_debug_exact_select_stats
         DevBuf<int2> items;               // the listed screen's work queue: [0] = (items, counter), from [8] on (tile, part | parts << 16)
         int item_slots = 0;               // ... sized for this many resident workgroups
         int screen_slots = 0;             // ... the listed screen's last grid (what the next plan cuts its lists for)
@@ -1509,6 +1513,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         if (const char* e = dev_env("SOM_ASYNC_COPIES")) h->async_copies = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_FUSE_MERGE")) h->fuse_merge_prep = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_EXACT_CHAIN")) h->ex.chain = std::atoi(e) != 0;
+        if (const char* e = dev_env("SOM_EXACT_FUSE_SELECT")) h->ex.fuse_select = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_COUNTING_SORT")) h->counting_sort = std::atoi(e) != 0;
         // a 128-row block of a table already spans most of a map side up to 256: nothing to skip there
         h->use_bands = h->X > 256 || h->Y > 256;
@@ -2489,6 +2494,14 @@ int som_debug_device_bytes(int64_t* out) {
 int som_debug_exact_chain_stats(som_handle* h, int64_t* carried_epochs) {
     if (!h || !carried_epochs) return fail(h, "som_debug_exact_chain_stats: NULL argument");
     *carried_epochs = h->ex.lastpos_carried_epochs;
+    return 0;
+}
+
+int som_debug_exact_select_stats(som_handle* h, int64_t* fused_passes, int64_t* launched_passes, int64_t* ticket_tiles) {
+    if (!h || !fused_passes || !launched_passes || !ticket_tiles) return fail(h, "som_debug_exact_select_stats: NULL argument");
+    *fused_passes = h->ex.sel_fused_passes;
+    *launched_passes = h->ex.sel_launched_passes;
+    *ticket_tiles = h->ex.sel_ticket_tiles;
     return 0;
 }
 

@@ -336,6 +336,13 @@ class HipEngine:
         self._check(self._lib.som_debug_exact_chain_stats(self._h, C.byref(a)))
         return a.value
 
+    def exact_select_stats(self):
+        """precision 'exact': (screen passes whose listed screen selected the candidates in its own launch, passes that launched
+        the select kernel behind their screen, tiles of the former that the last of their parts selected) so far."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.som_debug_exact_select_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def exact_skip_stats(self):
         """precision 'exact': (blocks the screens ran, blocks of full scans) so far -- block skipping's executed share."""
         a, b = C.c_int64(), C.c_int64()
