@@ -21,6 +21,16 @@ int som_debug_corrupt_operands(som_handle* h, int32_t which);
  * tests/test_gpu_exact_merge_prep.py compares the fused merge's operands with the separate kernels' through it. */
 int som_debug_operand_crc(som_handle* h, int32_t which, uint64_t* out);
 
+/* read-only: the exact plan's block geometry of one level as it stands on the device right now -- centroids C_out
+ * [n_slots][input_len], radii r_out [n_slots] (a slot without units: -1) and |c|^2 csq_out [n_slots].  level 0: the 64-unit groups
+ * of the patch order (som_patch_order; beyond 128 features the only level), slot g = group g; level 1: their 16-unit sub-blocks,
+ * slot 16 (g >> 2) + 4 (g & 3) + b = sub-block b of group g.  Launches nothing, refreshes nothing, changes no state: the buffers
+ * describe the codebook of the last planned launch or fused merge -- a zero return says the buffers exist, NOT that they are
+ * current: after som_set_weights and before the next planned launch they are the old codebook's.  *n_slots_out is written first; each of the three arrays may be
+ * NULL.  Returns non-zero when the handle holds no centroids (no launch has planned yet) or has no such level.
+ * tests/test_gpu_skip_bound.py compares them with a float64 computation from som_get_weights. */
+int som_debug_exact_centroids(som_handle* h, int32_t level, float* C_out, float* r_out, float* csq_out, int32_t* n_slots_out);
+
 /* measurement hook: ONE v_mfma_f32_16x16x32 (_f16 when is_f16, else _bf16) on the caller's operands -- a [16][32] and
  * b [32][16] as 16-bit patterns, c and d [16][16] float32, row-major.  tests/test_gpu_exact.py uses it to measure the
  * rounding error the exact mode's bound charges per MFMA (the hardware's internal summation is not documented). */

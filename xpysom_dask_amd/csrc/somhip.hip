@@ -2413,6 +2413,23 @@ int som_debug_operand_crc(som_handle* h, int32_t which, uint64_t* out) {
     return 0;
 }
 
+// TEST HOOK, read-only: the exact plan's centroids, radii and |c|^2 of one level as they stand on the device (nothing is launched,
+// nothing refreshed, no state changed).  level 0: the 64-unit groups (beyond 128 features the only level), level 1: the 16-unit
+// sub-blocks in exact_centroids_kernel's slot order.  Any of the three outputs may be NULL; *n_slots_out is written first.
+int som_debug_exact_centroids(som_handle* h, int32_t level, float* C_out, float* r_out, float* csq_out, int32_t* n_slots_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || !n_slots_out) return fail(h, "som_debug_exact_centroids: NULL argument");
+    if (!h->ex.cen_ready) return fail(h, "som_debug_exact_centroids: the handle holds no centroids (no launch has planned yet)");
+    if (level < 0 || level >= (h->wide ? 1 : 2)) return fail(h, "som_debug_exact_centroids: no such level");
+    const auto& c = h->ex.cen[level];
+    *n_slots_out = c.n_slots;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (C_out) if (int rc = d2h_blocking(h, C_out, c.Cc, (size_t)c.n_slots * h->D * sizeof(float))) return rc;
+    if (r_out) if (int rc = d2h_blocking(h, r_out, c.rg, (size_t)c.n_slots * sizeof(float))) return rc;
+    if (csq_out) if (int rc = d2h_blocking(h, csq_out, c.csq, (size_t)c.n_slots * sizeof(float))) return rc;
+    return 0;
+}
+
 // TEST HOOK (no device needed): the exact mode's policy functions (csrc/exact_policy.hpp) on caller-supplied numbers.
 // costs[9] = {full_total, full_screen, plan_total, plan_over, plan_over_scout, blk_ms, l2_ms_group, l2_ratio, sort_ms};
 // which / args: 0 commit_scouted_plan(share, blocks_per_row) | 1 level2_from_sample(share, share1, blocks_per_row) |

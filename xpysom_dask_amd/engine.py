@@ -299,6 +299,17 @@ class HipEngine:
         """TEST HOOK of the canary: zero the operand images behind the library's back (1: 16-bit, 2: float32)."""
         self._check(self._lib.som_debug_corrupt_operands(self._h, int(which)))
 
+    def debug_exact_centroids(self, level):
+        """Read-only: (centroids (n_slots, D), radii (n_slots,), |c|^2 (n_slots,)) of the exact plan's level 0 (64-unit groups)
+        or 1 (16-unit sub-blocks, slot 16 (g >> 2) + 4 (g & 3) + b) as the device holds them; raises where it holds none."""
+        n = C.c_int32()
+        self._check(self._lib.som_debug_exact_centroids(self._h, int(level), None, None, None, C.byref(n)))
+        cen = np.empty((n.value, self.D), dtype=np.float32)
+        rad = np.empty((n.value,), dtype=np.float32)
+        csq = np.empty((n.value,), dtype=np.float32)
+        self._check(self._lib.som_debug_exact_centroids(self._h, int(level), self._fp(cen), self._fp(rad), self._fp(csq), C.byref(n)))
+        return cen, rad, csq
+
     def debug_mfma16(self, a, b, c, f16=True):
         """Measurement hook: d = a (16x32) . b (32x16) + c (16x16) by ONE 16x16x32 MFMA; a, b float16 (or bfloat16 bit
         patterns as uint16 when f16=False), c float32."""
