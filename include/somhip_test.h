@@ -54,6 +54,16 @@ int som_debug_exact_chain_stats(som_handle* h, int64_t* carried_epochs);
  * of the former whose list was cut into parts and which the last part to arrive selected (tests/test_gpu_exact_select_fused.py). */
 int som_debug_exact_select_stats(som_handle* h, int64_t* fused_passes, int64_t* launched_passes, int64_t* ticket_tiles);
 
+/* precision EXACT up to 128 features, the plans of the screen passes so far (exact_skip_plan, csrc/exact_host.hpp): plans that
+ * ran levels 1 and 2 and the lists in ONE launch (exact_plan_fused_kernel, csrc/exact_skip.hpp), and plans that ran them as
+ * launches of their own -- every plan without level 2, with a scout, of a pass of few tiles, every plan whose level 2 the policy
+ * timed, and all of them under SOM_EXACT_FUSE_PLAN=0 (tests/test_gpu_exact_plan_fused.py). */
+int som_debug_exact_plan_stats(som_handle* h, int64_t* fused_launches, int64_t* split_launches);
+
+/* precision EXACT: the plan of the last BMU launch as it ran (policy::LaunchPlan, csrc/exact_policy.hpp):
+ *   out8 = [0] skip  [1] resort  [2] scout  [3] level 2  [4] estimate  [5] sample_tiles  [6] refine  [7] time_phases */
+int som_debug_exact_last_plan(som_handle* h, int32_t* out8);
+
 /* diagnostic builds only (-DSOM_STAMPS, tools/stamps.py builds one on demand): out_host == NULL attaches a buffer of n_pairs
  * (shader-clock ticks, 100 MHz ticks) pairs, one per workgroup of the next BMU launches (n_pairs == 0 detaches);
  * out_host != NULL reads n_pairs pairs back.  The product build refuses both. */

@@ -491,7 +491,13 @@ void exact_plan_lists(som_handle* h, long tiles, int n_cstages, const unsigned l
                                                                   n_items, n_items + 1, ex.item_len_pct);
 }
 
+// (the instances of exact_plan_fused_kernel that keep three workgroups a CU without scratch: <4, Bf16> does not -- 168 VGPRs and
+//  8 bytes of scratch a lane, bf16's conversions in the prologue -- and keeps the split pair)
+template <int KS32, class E> constexpr bool plan_fused_fits() { return !(KS32 == 4 && std::is_same<E, Bf16>::value); }
 // one pass's plan on the sorted rows sr[s0, s0 + n): level 1 (+ the seeds, from lastpos_s), level 2, the tiles' item lists
+// -- in ONE launch (exact_plan_fused_kernel) where the pass is planned with level 2, from last BMUs alone (no scout), by one
+// workgroup per tile, and the policy does not time level 2 in this launch (time_l2: the split pair keeps cost.ev[3] .. ev[4]
+// around level 2, so that policy::Costs is fed as before); SOM_EXACT_FUSE_PLAN=0 / SOM_EXACT_CHAIN=0: always the split sequence
 template <class E>
 int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, long n, const float* xmax2, const ExactBound& eb,
                     const int* lastpos2, bool time_l2 = false) {
@@ -505,13 +511,43 @@ int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
     const auto& c1 = ex.cen[1];
     // (few tiles: their centroid stages split over up to four workgroups each, so that the plan fills the chip)
     const long want = (1024 + tiles - 1) / tiles;
-    const dim3 pgrid((unsigned)tiles, (unsigned)std::max<long>(1, std::min<long>({want, 4L, (long)c0.n_cstages})));
+    // (TEST HOOK SOM_EXACT_PLAN_PARTS=n: at most n workgroups per tile -- 1 brings a small pass to the one-workgroup-per-tile grid of a large one)
+    const long parts_cap = ex.hook_plan_parts > 0 ? ex.hook_plan_parts : 4L;
+    const dim3 pgrid((unsigned)tiles, (unsigned)std::max<long>(1, std::min<long>({want, parts_cap, (long)c0.n_cstages})));
     // (two stage slots + the words the workgroup produces; level 2: + its list of active stages)
     const size_t lds1 = 2 * (size_t)h->stage_bytes + (size_t)c0.n_cstages * 8;
     const size_t lds2 = 2 * (size_t)h->stage_bytes + (size_t)c0.n_cstages * 64 * sizeof(int) + (size_t)c1.n_cstages * 8;   // (+ its list of kept groups, its words)
     const bool l2 = ex.lp.level2;
     const int force = ex.skip_mode == 3 ? 1 : 0;
     const __bf16* Xs = sr.Xb_s + s0 * h->dp;
+    // (the stage slots, the list of kept groups, level 2's and level 1's words, level 2's thresholds of the tile's rows: within the
+    //  CU's 160 KB wherever level 2's own list fits -- policy::LaunchFacts::l2_fits_lds leaves 10 KB --, checked all the same)
+    const size_t lds = lds2 + (size_t)c0.n_cstages * 8 + (size_t)SK_TILE * sizeof(float);
+    const bool fits = h->ks32 != 4 || plan_fused_fits<4, E>();
+    if (ex.fuse_plan && ex.chain && l2 && lastpos2 == nullptr && pgrid.y == 1 && !time_l2 && lds <= 160 * 1024 && fits) {
+        PlanListsOut lo;
+        lo.n_groups = (int)cdiv(h->K, EX_GROUP);
+        lo.glist = ex.glist; lo.gcnt = ex.gcnt; lo.tile_counts = ex.tile_counts; lo.tlist = ex.tlist; lo.tcnt = ex.tcnt;
+        lo.tile_ticket = ex.tile_ticket;
+        lo.done = &ctr->lists_done; lo.blocks_run = &ctr->blocks_run; lo.groups_run = &ctr->groups_run;
+        lo.slots = ex.item_queue ? (ex.screen_slots > 0 ? ex.screen_slots : ex.item_slots) : 0;
+        lo.items = ex.item_queue ? ex.items + 8 : nullptr;        // (as exact_plan_lists hands them to exact_lists_totals_kernel)
+        lo.n_items = (int*)ex.items.p; lo.item_ctr = lo.n_items + 1; lo.len_pct = ex.item_len_pct;
+#define SOM_PLAN_FUSED_CASE(k) case k: if constexpr (plan_fused_fits<k, E>()) { \
+        { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_fused_kernel<k, E>, 64 * K16_NW, lds, &pc)) return rc; } \
+        exact_plan_fused_kernel<k, E><<<dim3((unsigned)tiles), block, lds, h->stream>>>(Xs, n, c0.Cst, c0.n_cstages, c0.cmax2, c1.Cst, c1.n_slots, \
+            c1.cmax2, sr.xsq_s + s0, sr.xerr_s + s0, xmax2, h->wmax2, h->wmax2 + 1, eb, sr.lastpos_s + s0, h->Wst, sr.seed_s + s0, force, lo); \
+        } break;
+        switch (h->ks32) {
+        SOM_PLAN_FUSED_CASE(1) SOM_PLAN_FUSED_CASE(2) SOM_PLAN_FUSED_CASE(3) SOM_PLAN_FUSED_CASE(4)
+        default: return fail(h, "exact: block skipping supports input_len <= 128");
+        }
+#undef SOM_PLAN_FUSED_CASE
+        ++ex.plan_fused_launches;
+        HIPCHK(h, hipGetLastError());
+        return 0;
+    }
+    ++ex.plan_split_launches;
     // (level 1 stores every word; level 2 only those of the stages it walks: its words start from zero -- cleared by the level-1
     //  workgroups, each the words of its own stages; SOM_EXACT_CHAIN=0: by a fill)
     unsigned long long* const need2_clear = l2 && ex.chain ? ex.need2.p : nullptr;

@@ -425,12 +425,313 @@ __global__ __launch_bounds__(256) void exact_prep_images_kernel(unsigned w_block
     else prep_wsqh_body(blockIdx.x - w_blocks - c_blocks, wn, K, wmax2, xmax2, Wst, n_stages, k16_stage_bytes(KS32), stage_units, best64, n_rows, 1);
 }
 
+// The pieces below are shared by exact_plan_kernel (one level a launch) and exact_plan_fused_kernel (both levels and the lists in
+// one launch): the prologue's arithmetic, the two walks and the lists are written once, so that both paths issue the same tests
+// on the same operands.
+//
+// PROLOGUE, level 1's part for one row of the pass: the screen's value v_u of the row's last BMU on the operands the screen reads,
+// from it the screen's seed (seed_s, stored by the quad's first lanes) and sqrt(U) (returned; +inf: the row needs everything).
+template <int KS32, class EL>
+__device__ __forceinline__ float plan_row_seed(const typename V8<typename EL::T>::t (&xrow)[KS32], long row, float q, float xe,
+                                               const ExactBound& eb, const ExactScales& sw, const char* __restrict__ Wst,
+                                               const int* __restrict__ lastpos, const int* __restrict__ lastpos2,
+                                               int* __restrict__ scout_wins, float* __restrict__ seed_s, int force_all) {
+    using bf16x8 = typename V8<typename EL::T>::t;
+    constexpr int STAGE = k16_stage_bytes(KS32);
+    const int lane = threadIdx.x & 63, quad = lane >> 4;
+    // v_u: the screen's value of unit u = the row's last BMU on the operands the screen reads (-w~ fragments of
+    // the stage image, the row's x~), a float32 fma chain: every product of two halves is exact, the chain and
+    // the two cross-quad adds err by < 40 ulps of the largest accumulator magnitude (charged: e_valu)
+    // (lastpos2: a second unit per row -- the scout's pick beside the real last BMU --: the smaller value bounds as well)
+    auto value_of = [&](int pos) -> float {           // (a position below K: exact_lastpos_kernel, exact_scout_pos_kernel)
+        const char* stg = Wst + (long)(pos >> 6) * STAGE;
+        const int t16 = (pos >> 4) & 3, c = pos & 15;
+        float d = 0.0f;
+#pragma unroll
+        for (int ks = 0; ks < KS32; ++ks) {
+            const bf16x8 a = *(const bf16x8*)(stg + ((t16 * KS32 + ks) * 64 + quad * 16 + c) * 16);
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) d = __builtin_fmaf((float)a[jj], (float)xrow[ks][jj], d);
+        }
+        d += __shfl_xor(d, 16, 64);
+        d += __shfl_xor(d, 32, 64);
+        return *(const float*)(stg + K16_T * KS32 * 1024 + (t16 * 16 + c) * 4) + d;
+    };
+    float vu = value_of(lastpos[row]);
+    if (lastpos2 != nullptr) {
+        // (lastpos: the scout's pick, lastpos2: the real last BMU.  A WIN of the scout: its unit's squared distance --
+        //  |x|^2 + tau(v), tau(v) = 2 (v / S - B) -- is a tenth or more below the last BMU's: counted, so that the host
+        //  knows whether the scout is still worth its launches next epoch)
+        const float v2 = value_of(lastpos2[row]);
+        const float Sq = sw.sx * sw.sw;
+        const float ua = q + 2.0f * (vu / Sq - sw.big), ub = q + 2.0f * (v2 / Sq - sw.big);
+        const bool win = ua < 0.9f * ub;
+        const unsigned long long wm = __ballot(win && quad == 0);
+        if (scout_wins != nullptr && lane == __builtin_ctzll(__ballot(true)) && wm != 0ull) atomicAdd(scout_wins, (int)__popcll(wm));
+        vu = (v2 < vu || !(vu == vu)) ? v2 : vu;      // (a NaN value -- a NaN unit -- gives way to the other unit's)
+    }
+    const float Sw = sw.sx * sw.sw;
+    const float e = ex_row_bound(eb, sw, q, xe);          // two-unit window E of the screen (d' units)
+    const float f32s = ex_f32_share(eb, sw, q);           // its float32 share (two evaluations)
+    const float e_valu = 48.0f * 0x1p-24f * Sw * sw.bmag;
+    // seed: whatever beats u in the float32 kernel has a screen value of at most v_u + E + e_valu = seed + f32s
+    const float sd = vu + (e - f32s) * (1.0f + 1.0f / 1024.0f) + e_valu + Sw * sw.bmag * 0x1p-21f;
+    if (quad == 0) seed_s[row] = (sd > 0.0f && sd < 3.0e38f) ? sd : __builtin_inff();
+    // tau_up >= u's real score: d'_real(u) <= v_u + (one-unit screen error) + e_valu,  tau = 2 (d' / S - B)
+    const float e_one = 0.5f * (e - f32s) * (1.0f + 1.0f / 1024.0f) + e_valu;
+    const float tau_up = 2.0f * (((vu + e_one) - Sw * sw.big) / Sw) + 0x1p-20f * (sw.big + __builtin_fabsf(vu) / Sw);
+    const float xn = __builtin_sqrtf(q) * (1.0f + 1.0f / 1024.0f);
+    const float share = 2.0f * (eb.cA * xn * sw.wm + eb.cW * sw.wm * sw.wm);      // tau units, one float32 window
+    // (no fmax here: it would swallow the NaN of a row whose last BMU is a NaN unit, and bound that row by zero)
+    const float U0 = q * (1.0f + 1.0f / 1024.0f) + tau_up + share * (1.0f + 1.0f / 1024.0f) + 0x1p-18f * (q + __builtin_fabsf(tau_up));
+    const float U = U0 < 0.0f ? 0.0f : U0;
+    float su = __builtin_sqrtf(U) * (1.0f + 1.0f / 1024.0f);
+    if (force_all || !(su == su) || !(su < 3.0e38f) || !(e == e)) su = __builtin_inff();
+    return su;
+}
+
+// PROLOGUE, one level's part for one row: the right-hand side P of the level's test and the rows' side bx of the extra feature
+// step, from |x|^2, the row's rounding error, sqrt(U) and the level's scales (sc: ex_scales on the level's centroid image).
+// in_pass == false (a row behind the pass) needs nothing: P = -inf; a row whose numbers are not finite needs everything: P = +inf.
+template <int KS32>
+__device__ __forceinline__ void plan_row_threshold(const ExactBound& eb, const ExactScales& sc, bool in_pass, float q, float xe, float su,
+                                                   float& P, float& bx) {
+    const float S = sc.sx * sc.sw;
+    float A = -__builtin_inff(), sU = 0.0f;
+    if (in_pass) {
+        const float ec = 0.5f * ex_row_bound(eb, sc, q, xe) * (1.0f + 1.0f / 1024.0f);
+        sU = su;
+        // d'_c > S' (B' + ((sU + r)^2 - |x|^2_lo) / 2) + e_c   <=>   skip
+        // (+ margins: the float32 rounding of this line, and |c|^2 as float32 summed it against the real |c|^2)
+        A = S * sc.big + ec - 0.5f * S * q * (1.0f - 1.0f / 1024.0f) + 0x1p-12f * S * (sc.big + q) + 0x1p-16f * S * sc.wm * sc.wm;
+        if (!(A == A) || !(A < 3.0e38f) || !(su < 3.0e38f)) {
+            A = __builtin_inff(); sU = 0.0f;                                                 // need everything
+        }
+    }
+    // P = A + hS sU^2 (+ the extra feature step's and the larger accumulators' share of the MFMA rounding: the cross term
+    // can double the accumulator's magnitude, and there is one more MFMA in the chain: 4 (KS32 + 1) x 6 ulps of S' Bm')
+    bx = up_to_half(sc.sx * sU * (1.0f + 1.0f / 1024.0f));
+    P = A + 0.5f * S * (1.0f + 1.0f / 1024.0f) * sU * sU * (1.0f + 0x1p-20f) + (float)(24 * (KS32 + 1)) * 0x1p-23f * S * sc.bmag;
+    if (!(bx < 3.0e38f) || !(P == P)) P = __builtin_inff();                                  // (sU beyond the half range: need everything)
+    if (A == -__builtin_inff()) P = -__builtin_inff();                                       // (rows behind the pass)
+}
+// the rows' operand of the extra feature step: slot 0 of the first quad = bx, else 0
+template <class EL>
+__device__ __forceinline__ typename V8<typename EL::T>::t plan_extra_step(float bx) {
+    using E = typename EL::T;
+    typename V8<E>::t v;
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) v[jj] = (E)0.0f;
+    if (((threadIdx.x & 63) >> 4) == 0 && bx < 3.0e38f) v[0] = (E)bx;
+    return v;
+}
+
+// MFMAs + test of one 16-centroid tile (either level; its operands in (a, wv, rneg): the KS32 fragments, the initial
+// accumulators, the centroids' side of the extra step, slot 0 = -up_to_half(sw r)): lane (quad, col) sets bit 4 j + r of
+// lane_bits where one of its rows needs the centroid behind accumulator register r of tile j.
+template <int KS32, class EL>
+__device__ __forceinline__ void plan_run_tile(int j, const typename V8<typename EL::T>::t (&a)[KS32], const f32x4& wv, float rneg,
+                                              const typename V8<typename EL::T>::t (&xf)[K16_SB][KS32],
+                                              const typename V8<typename EL::T>::t (&xe)[K16_SB], const float (&P)[K16_SB],
+                                              uint32_t& lane_bits) {
+    using E = typename EL::T;
+    using bf16x8 = typename V8<E>::t;
+    bf16x8 ae;
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) ae[jj] = (E)0.0f;
+    if (((threadIdx.x & 63) >> 4) == 0) ae[0] = (E)rneg;
+    f32x4 acc[K16_SB];
+#pragma unroll
+    for (int sb = 0; sb < K16_SB; ++sb) acc[sb] = wv;
+#pragma unroll
+    for (int ks = 0; ks < KS32; ++ks)
+#pragma unroll
+        for (int sb = 0; sb < K16_SB; ++sb) acc[sb] = mfma16(a[ks], xf[sb][ks], acc[sb]);
+#pragma unroll
+    for (int sb = 0; sb < K16_SB; ++sb) acc[sb] = mfma16(ae, xe[sb], acc[sb]);
+    // (gathered over the rows once per stage / chunk by the caller -- a ballot and four scalar tests per accumulator register
+    //  kept the scalar unit busier than the matrix pipe)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        bool nd = false;
+#pragma unroll
+        for (int sb = 0; sb < K16_SB; ++sb) nd = nd || !(acc[sb][r] > P[sb]);
+        lane_bits |= nd ? (1u << (4 * j + r)) : 0u;
+    }
+}
+// a tile's operands out of its stage slot in LDS (st; wq: the slot's tail)
+template <int KS32, class EL>
+__device__ __forceinline__ void plan_load_tile(const char* st, int t, typename V8<typename EL::T>::t (&a)[KS32], f32x4& wv, float& rneg) {
+    using bf16x8 = typename V8<typename EL::T>::t;
+    const int lane = threadIdx.x & 63;
+    const float* wq = (const float*)(st + K16_T * KS32 * 1024);
+#pragma unroll
+    for (int ks = 0; ks < KS32; ++ks) a[ks] = *(const bf16x8*)(st + ((t * KS32 + ks) * 64 + lane) * 16);
+    wv = *(const f32x4*)(wq + t * 16 + 4 * (lane >> 4));
+    rneg = wq[64 + t * 16 + (lane & 15)];
+}
+
+// LEVEL 1's WALK over the centroid stages [s_begin, s_end) of Cst, double-buffered in the two stage slots at smem: word
+// nl[s - s_begin] (LDS, zero on entry -- the first barrier of the walk orders the clearing) collects the tile's need bits of stage s
+// (bit i <-> centroid slot 64 s + i).  The caller's barrier behind the walk completes the words.
+template <int KS32, class EL>
+__device__ __forceinline__ void plan_walk_level1(const char* __restrict__ Cst, int s_begin, int s_end, char* smem, unsigned long long* nl,
+                                                 const typename V8<typename EL::T>::t (&xf)[K16_SB][KS32],
+                                                 const typename V8<typename EL::T>::t (&xe)[K16_SB], const float (&P)[K16_SB]) {
+    using bf16x8 = typename V8<typename EL::T>::t;
+    constexpr int STAGE = k16_stage_bytes(KS32);
+    constexpr int PIECES = K16_T * KS32 + 1;
+    const int lane = threadIdx.x & 63, quad = lane >> 4, col = lane & 15;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    auto dma_stage = [&](int s, char* dst) {
+        const char* src = Cst + (long)s * STAGE;
+        for (int p = wave; p < PIECES; p += K16_NW) lds_dma_16(src + (long)p * 1024 + lane * 16, dst + p * 1024);
+    };
+    if (s_begin < s_end) dma_stage(s_begin, smem);
+    for (int i = s_begin; i < s_end; ++i) {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (i + 1 < s_end) dma_stage(i + 1, smem + ((i + 1 - s_begin) & 1) * STAGE);
+        const char* st = smem + ((i - s_begin) & 1) * STAGE;
+        uint32_t lane_bits = 0u;                              // (the word's bit 16 t16 + 4 quad + r <-> centroid slot of that place in the stage)
+        // the stage's four tiles, their operands alternating between two register sets (no copies): the next tile's are read
+        // under this tile's MFMAs and test
+        bf16x8 aA[KS32], aB[KS32];
+        f32x4 wvA, wvB;
+        float rnA, rnB;
+        plan_load_tile<KS32, EL>(st, 0, aA, wvA, rnA);
+        plan_load_tile<KS32, EL>(st, 1, aB, wvB, rnB);
+        plan_run_tile<KS32, EL>(0, aA, wvA, rnA, xf, xe, P, lane_bits);
+        plan_load_tile<KS32, EL>(st, 2, aA, wvA, rnA);
+        plan_run_tile<KS32, EL>(1, aB, wvB, rnB, xf, xe, P, lane_bits);
+        plan_load_tile<KS32, EL>(st, 3, aB, wvB, rnB);
+        plan_run_tile<KS32, EL>(2, aA, wvA, rnA, xf, xe, P, lane_bits);
+        plan_run_tile<KS32, EL>(3, aB, wvB, rnB, xf, xe, P, lane_bits);
+        // OR over the sixteen rows of every quad; the quad's first lane spreads its four nibbles (one per tile) to their places
+        const uint32_t any_row = row16_or(lane_bits);
+        if (col == 0 && any_row != 0u) {
+            const uint32_t lo = ((any_row & 15u) | (((any_row >> 4) & 15u) << 16)) << (4 * quad);
+            const uint32_t hi = (((any_row >> 8) & 15u) | (((any_row >> 12) & 15u) << 16)) << (4 * quad);
+            atomicOr(nl + (i - s_begin), ((unsigned long long)hi << 32) | lo);
+        }
+    }
+}
+
+// LEVEL 2's LIST: the groups level 1 kept for this tile (need1: the tile's n_cstages1 level-1 words, in LDS or in memory), dense and
+// ascending in act[]; their number in *act_n.  Called by one wave; the caller's barrier publishes the list.
+// (n_slots2: the slots of the level-2 image -- a group behind them has no sub-blocks to test)
+__device__ __forceinline__ void plan_level2_list(const unsigned long long* need1, int n_cstages1, int n_slots2, int* act, int* act_n) {
+    const int lane = threadIdx.x & 63;
+    int cnt = 0;
+    for (int s1 = 0; s1 < n_cstages1; ++s1) {
+        const unsigned long long w = need1[s1];
+        const int g = s1 * 64 + lane;
+        const bool on = ((w >> lane) & 1ull) && 4 * (g >> 2) * 4 < n_slots2;
+        const unsigned long long mk = __ballot(on);
+        if (on) act[cnt + __popcll(mk & ((1ull << lane) - 1ull))] = g;
+        cnt += __popcll(mk);
+    }
+    if (lane == 0) *act_n = cnt;
+}
+
+// LEVEL 2's WALK over the entries [b0, e0) of the DENSE list act[] of kept groups, sixteen to a barrier: four MFMA tiles of four
+// groups' sub-blocks each, GATHERED -- late in a schedule a quarter of the groups is kept, spread so evenly that nearly every tile
+// of four consecutive groups holds one: walking image tiles ran four times level 1's work to test a quarter of it.
+// A tile's fragments come by LDS-DMA with per-lane addresses (lane (quad, c) <-> sub-block c & 3 of the tile's
+// (c >> 2)-th group), its initial accumulators and radii by plain loads one chunk ahead (a wave per tile), written
+// into the slot's tail (laid out like a stage's) before the next barrier.
+// nl (LDS, zero on entry, ordered by a barrier of the caller's): word g >> 4 collects a nibble per group (bit 4 (g & 15) + sub <->
+// sub-block `sub` of group g), filed by LDS atomics.  The caller's barrier behind the walk completes the words.
+template <int KS32, class EL>
+__device__ __forceinline__ void plan_walk_level2(const char* __restrict__ Cst, const int* act, int b0, int e0, char* smem,
+                                                 unsigned long long* nl, const typename V8<typename EL::T>::t (&xf)[K16_SB][KS32],
+                                                 const typename V8<typename EL::T>::t (&xe)[K16_SB], const float (&P)[K16_SB]) {
+    using bf16x8 = typename V8<typename EL::T>::t;
+    constexpr int STAGE = k16_stage_bytes(KS32);
+    static_assert(K16_NW == 4, "a wave per tile fills the slot's tail");
+    const int lane = threadIdx.x & 63, quad = lane >> 4, col = lane & 15;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int TQ = K16_T * KS32 * 1024;              // the slot's tail: [0, 64) initial accumulators, [64, 128) -up_to_half(sw r)
+    // where sub-block `sub` of group g sits in the level-2 image: stage g >> 4, tile (g >> 2) & 3, row 4 (g & 3) + sub
+    auto frag_of = [&](int g, int sub, int ks, int q) -> const char* {
+        return Cst + (long)(g >> 4) * STAGE + (((((g >> 2) & 3) * KS32 + ks) * 64 + q * 16 + 4 * (g & 3) + sub) * 16);
+    };
+    auto dma_chunk = [&](int c0, char* dst) {
+        for (int p = wave; p < K16_T * KS32; p += K16_NW) {
+            const int j = p / KS32, ks = p - j * KS32;
+            if (c0 + 4 * j < e0) {                        // (wave-uniform)
+                const int gi = c0 + 4 * j + (col >> 2);
+                const int g = gi < e0 ? act[gi] : act[c0 + 4 * j];   // (a slot behind the list: any valid address; its bits are dropped)
+                lds_dma_16(frag_of(g, col & 3, ks, quad), dst + p * 1024);
+            }
+        }
+    };
+    // wave w <-> the chunk's tile w: lanes 0..15 its initial accumulators, lanes 16..31 its radii (row i <-> sub-block i & 3 of
+    // the tile's (i >> 2)-th group)
+    auto load_tail = [&](int c0) -> float {
+        const int i = lane & 15, gi = c0 + 4 * wave + (i >> 2);
+        if (lane >= 32 || gi >= e0) return lane < 16 ? __builtin_inff() : 0.0f;     // (an empty slot: never needed)
+        const int g = act[gi];
+        return *(const float*)(Cst + (long)(g >> 4) * STAGE + TQ + (((lane >> 4) * 64) + ((g >> 2) & 3) * 16 + 4 * (g & 3) + (i & 3)) * 4);
+    };
+    auto store_tail = [&](char* dst, float v) {
+        if (lane < 32) *(float*)(dst + TQ + (((lane >> 4) * 64) + wave * 16 + (lane & 15)) * 4) = v;
+    };
+    if (b0 < e0) { dma_chunk(b0, smem); store_tail(smem, load_tail(b0)); }
+    int k = 0;
+    for (int c0 = b0; c0 < e0; c0 += 16, ++k) {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        char* sn = smem + ((k + 1) & 1) * STAGE;
+        float tail_n = 0.0f;
+        if (c0 + 16 < e0) { dma_chunk(c0 + 16, sn); tail_n = load_tail(c0 + 16); }
+        const char* st = smem + (k & 1) * STAGE;
+        uint32_t lane_bits = 0u;                           // bit 4 j + r: tile j of the chunk, accumulator register r
+        // (lane (quad, col): bit r <-> its row needs sub-block r of the tile's quad-th group; gathered over the rows
+        //  once per chunk, below)
+        bf16x8 aA[KS32], aB[KS32];
+        f32x4 wvA, wvB;
+        float rnA, rnB;
+        const bool h1 = c0 + 4 < e0, h2 = c0 + 8 < e0, h3 = c0 + 12 < e0;
+        plan_load_tile<KS32, EL>(st, 0, aA, wvA, rnA);
+        if (h1) plan_load_tile<KS32, EL>(st, 1, aB, wvB, rnB);
+        plan_run_tile<KS32, EL>(0, aA, wvA, rnA, xf, xe, P, lane_bits);
+        if (h1) {
+            if (h2) plan_load_tile<KS32, EL>(st, 2, aA, wvA, rnA);
+            plan_run_tile<KS32, EL>(1, aB, wvB, rnB, xf, xe, P, lane_bits);
+            if (h2) {
+                if (h3) plan_load_tile<KS32, EL>(st, 3, aB, wvB, rnB);
+                plan_run_tile<KS32, EL>(2, aA, wvA, rnA, xf, xe, P, lane_bits);
+                if (h3) plan_run_tile<KS32, EL>(3, aB, wvB, rnB, xf, xe, P, lane_bits);
+            }
+        }
+        // the chunk's sixteen groups: OR over the sixteen rows of every quad (lanes of one DPP row), then the quad's first lane
+        // files tile j's nibble under the tile's quad-th group
+        const uint32_t any_row = row16_or(lane_bits);
+        if (col == 0 && any_row != 0u) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t nib = (any_row >> (4 * j)) & 15u;
+                const int gi = c0 + 4 * j + quad;
+                if (nib != 0u && gi < e0) {
+                    const int g = act[gi];
+                    atomicOr(nl + (g >> 4), (unsigned long long)nib << (4 * (g & 15)));
+                }
+            }
+        }
+        if (c0 + 16 < e0) store_tail(sn, tail_n);
+    }
+}
+
 // The plan: which blocks does a tile of SK_TILE (sorted) rows need?  The resident kernel's MFMA loop over a centroid
 // stage image (64 centroids per stage), epilogue: need(row, j) = not (d'_c > A(row) + (S'/2) (sU(row) + r_j)^2), OR over
 // the tile's rows into need[tile][stage] (bit i <-> centroid slot 64 stage + i).
 //   LEVEL2 == false: the centroids of the groups.  The prologue also forms, per row, the screen value v_u of the row's last
 //     BMU u (vector ALU, from the row's half image and u's fragments of the screen's stage image Wst), from it the seed of
-//     the screen (seed_s) and sqrt(U) (sU_s: kept for level 2; +inf: the row needs everything).  need2_clear (or null): level 2's
+//     the screen (seed_s) and sqrt(U) (sU_s: kept for the level-2 LAUNCH -- exact_plan_fused_kernel keeps it in registers and writes
+//     no sU_s --; +inf: the row needs everything).  need2_clear (or null): level 2's
 //     bitmap [tile][4 n_cstages], whose words of this workgroup's stages are zeroed for the level-2 launch that follows.
 //   LEVEL2 == true: the centroids of the 16-unit sub-blocks, slot order as exact_centroid_kernel's (a 16-slot MFMA tile =
 //     the sub-blocks of four consecutive groups); only the tiles whose groups level 1 kept (need1) are loaded and run.
@@ -450,11 +751,9 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
                                                                     int force_all, const int* __restrict__ lastpos2 = nullptr,
                                                                     int* __restrict__ scout_wins = nullptr,
                                                                     unsigned long long* __restrict__ need2_clear = nullptr) {
-    using E = typename EL::T;
-    using bf16x8 = typename V8<E>::t;
+    using bf16x8 = typename V8<typename EL::T>::t;
     constexpr int DP = 32 * KS32;
     constexpr int STAGE = k16_stage_bytes(KS32);
-    constexpr int PIECES = K16_T * KS32 + 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int act_n;
 
@@ -465,91 +764,28 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
 
     bf16x8 xf[K16_SB][KS32];
     bf16x8 xe[K16_SB];                                       // the extra feature step: slot 0 = up_to_half(sx sU (1 + 2^-10)), else 0
-    float A[K16_SB], sU[K16_SB], P[K16_SB];
+    float P[K16_SB];
     const ExactScales sc = ex_scales(xmax2, cmax2, cmax2 + 1);
     const ExactScales sw = ex_scales(xmax2, wmax2, werr2);
-    const float S = sc.sx * sc.sw;
 #pragma unroll
     for (int sb = 0; sb < K16_SB; ++sb) {
         const long row = wave_s0 + sb * 16 + col;
 #pragma unroll
         for (int ks = 0; ks < KS32; ++ks) xf[sb][ks] = *(const bf16x8*)(Xb + row * DP + ks * 32 + quad * 8);
         // rows behind the pass need nothing (A = -inf: d' > rhs always); a row whose numbers are not finite needs everything
-        A[sb] = -__builtin_inff(); sU[sb] = 0.0f;
+        float q = 0.0f, xer = 0.0f, su = 0.0f;
         if (row < N) {
-            const float q = xsq[row], xe = xerr[row];
-            float su;
-            if (!LEVEL2) {
-                // v_u: the screen's value of unit u = the row's last BMU on the operands the screen reads (-w~ fragments of
-                // the stage image, the row's x~), a float32 fma chain: every product of two halves is exact, the chain and
-                // the two cross-quad adds err by < 40 ulps of the largest accumulator magnitude (charged: e_valu)
-                // (lastpos2: a second unit per row -- the scout's pick beside the real last BMU --: the smaller value bounds as well)
-                auto value_of = [&](int pos) -> float {           // (a position below K: exact_lastpos_kernel, exact_scout_pos_kernel)
-                    const char* stg = Wst + (long)(pos >> 6) * STAGE;
-                    const int t16 = (pos >> 4) & 3, c = pos & 15;
-                    float d = 0.0f;
-#pragma unroll
-                    for (int ks = 0; ks < KS32; ++ks) {
-                        const bf16x8 a = *(const bf16x8*)(stg + ((t16 * KS32 + ks) * 64 + quad * 16 + c) * 16);
-#pragma unroll
-                        for (int jj = 0; jj < 8; ++jj) d = __builtin_fmaf((float)a[jj], (float)xf[sb][ks][jj], d);
-                    }
-                    d += __shfl_xor(d, 16, 64);
-                    d += __shfl_xor(d, 32, 64);
-                    return *(const float*)(stg + K16_T * KS32 * 1024 + (t16 * 16 + c) * 4) + d;
-                };
-                float vu = value_of(lastpos[row]);
-                if (lastpos2 != nullptr) {
-                    // (lastpos: the scout's pick, lastpos2: the real last BMU.  A WIN of the scout: its unit's squared distance --
-                    //  |x|^2 + tau(v), tau(v) = 2 (v / S - B) -- is a tenth or more below the last BMU's: counted, so that the host
-                    //  knows whether the scout is still worth its launches next epoch)
-                    const float v2 = value_of(lastpos2[row]);
-                    const float Sq = sw.sx * sw.sw;
-                    const float ua = q + 2.0f * (vu / Sq - sw.big), ub = q + 2.0f * (v2 / Sq - sw.big);
-                    const bool win = ua < 0.9f * ub;
-                    const unsigned long long wm = __ballot(win && quad == 0);
-                    if (scout_wins != nullptr && lane == __builtin_ctzll(__ballot(true)) && wm != 0ull) atomicAdd(scout_wins, (int)__popcll(wm));
-                    vu = (v2 < vu || !(vu == vu)) ? v2 : vu;      // (a NaN value -- a NaN unit -- gives way to the other unit's)
-                }
-                const float Sw = sw.sx * sw.sw;
-                const float e = ex_row_bound(eb, sw, q, xe);          // two-unit window E of the screen (d' units)
-                const float f32s = ex_f32_share(eb, sw, q);           // its float32 share (two evaluations)
-                const float e_valu = 48.0f * 0x1p-24f * Sw * sw.bmag;
-                // seed: whatever beats u in the float32 kernel has a screen value of at most v_u + E + e_valu = seed + f32s
-                const float sd = vu + (e - f32s) * (1.0f + 1.0f / 1024.0f) + e_valu + Sw * sw.bmag * 0x1p-21f;
-                if (quad == 0) seed_s[row] = (sd > 0.0f && sd < 3.0e38f) ? sd : __builtin_inff();
-                // tau_up >= u's real score: d'_real(u) <= v_u + (one-unit screen error) + e_valu,  tau = 2 (d' / S - B)
-                const float e_one = 0.5f * (e - f32s) * (1.0f + 1.0f / 1024.0f) + e_valu;
-                const float tau_up = 2.0f * (((vu + e_one) - Sw * sw.big) / Sw) + 0x1p-20f * (sw.big + __builtin_fabsf(vu) / Sw);
-                const float xn = __builtin_sqrtf(q) * (1.0f + 1.0f / 1024.0f);
-                const float share = 2.0f * (eb.cA * xn * sw.wm + eb.cW * sw.wm * sw.wm);      // tau units, one float32 window
-                // (no fmax here: it would swallow the NaN of a row whose last BMU is a NaN unit, and bound that row by zero)
-                const float U0 = q * (1.0f + 1.0f / 1024.0f) + tau_up + share * (1.0f + 1.0f / 1024.0f) + 0x1p-18f * (q + __builtin_fabsf(tau_up));
-                const float U = U0 < 0.0f ? 0.0f : U0;
-                su = __builtin_sqrtf(U) * (1.0f + 1.0f / 1024.0f);
-                if (force_all || !(su == su) || !(su < 3.0e38f) || !(e == e)) su = __builtin_inff();
+            q = xsq[row]; xer = xerr[row];
+            if constexpr (!LEVEL2) {
+                su = plan_row_seed<KS32, EL>(xf[sb], row, q, xer, eb, sw, Wst, lastpos, lastpos2, scout_wins, seed_s, force_all);
                 if (quad == 0) sU_s[row] = su;
             } else {
                 su = sU_s[row];
             }
-            const float ec = 0.5f * ex_row_bound(eb, sc, q, xe) * (1.0f + 1.0f / 1024.0f);
-            sU[sb] = su;
-            // d'_c > S' (B' + ((sU + r)^2 - |x|^2_lo) / 2) + e_c   <=>   skip
-            // (+ margins: the float32 rounding of this line, and |c|^2 as float32 summed it against the real |c|^2)
-            A[sb] = S * sc.big + ec - 0.5f * S * q * (1.0f - 1.0f / 1024.0f) + 0x1p-12f * S * (sc.big + q) + 0x1p-16f * S * sc.wm * sc.wm;
-            if (!(A[sb] == A[sb]) || !(A[sb] < 3.0e38f) || !(su < 3.0e38f)) {
-                A[sb] = __builtin_inff(); sU[sb] = 0.0f;                                         // need everything
-            }
         }
-        // P = A + hS sU^2 (+ the extra feature step's and the larger accumulators' share of the MFMA rounding: the cross term
-        // can double the accumulator's magnitude, and there is one more MFMA in the chain: 4 (KS32 + 1) x 6 ulps of S' Bm')
-        const float bx = up_to_half(sc.sx * sU[sb] * (1.0f + 1.0f / 1024.0f));
-        P[sb] = A[sb] + 0.5f * S * (1.0f + 1.0f / 1024.0f) * sU[sb] * sU[sb] * (1.0f + 0x1p-20f) + (float)(24 * (KS32 + 1)) * 0x1p-23f * S * sc.bmag;
-        if (!(bx < 3.0e38f) || !(P[sb] == P[sb])) P[sb] = __builtin_inff();                      // (sU beyond the half range: need everything)
-        if (A[sb] == -__builtin_inff()) P[sb] = -__builtin_inff();                               // (rows behind the pass)
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) xe[sb][jj] = (E)0.0f;
-        if (quad == 0 && bx < 3.0e38f) xe[sb][0] = (E)bx;
+        float bx;
+        plan_row_threshold<KS32>(eb, sc, row < N, q, xer, su, P[sb], bx);
+        xe[sb] = plan_extra_step<EL>(bx);
     }
 
     // the words this workgroup produces (one per stage), gathered in LDS with LDS atomics (a global atomic per wave and stage
@@ -558,227 +794,24 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
     unsigned long long* nl = (unsigned long long*)(smem + 2 * STAGE + (LEVEL2 ? (size_t)n_cstages1 * 64 * sizeof(int) : 0));
     for (int i = tid; i < n_cstages; i += 64 * K16_NW) nl[i] = 0ull;
     if constexpr (LEVEL2) {
-        // LEVEL 2 walks a DENSE list of the groups level 1 kept, sixteen to a barrier: four MFMA tiles of four groups' sub-blocks
-        // each, GATHERED -- late in a schedule a quarter of the groups is kept, spread so evenly that nearly every tile of
-        // four consecutive groups holds one: walking image tiles ran four times level 1's work to test a quarter of it.
-        // A tile's fragments come by LDS-DMA with per-lane addresses (lane (quad, c) <-> sub-block c & 3 of the tile's
-        // (c >> 2)-th group), its initial accumulators and radii by plain loads one chunk ahead (a wave per tile), written
-        // into the slot's tail (laid out like a stage's) before the next barrier.
-        static_assert(K16_NW == 4, "a wave per tile fills the slot's tail");
-        if (wave == 0) {
-            int cnt = 0;
-            for (int s1 = 0; s1 < n_cstages1; ++s1) {
-                const unsigned long long w = need1[(long)blockIdx.x * n_cstages1 + s1];
-                const int g = s1 * 64 + lane;
-                const bool on = ((w >> lane) & 1ull) && 4 * (g >> 2) * 4 < n_slots;
-                const unsigned long long mk = __ballot(on);
-                if (on) act[cnt + __popcll(mk & ((1ull << lane) - 1ull))] = g;
-                cnt += __popcll(mk);
-            }
-            if (lane == 0) act_n = cnt;
-        }
+        if (wave == 0) plan_level2_list(need1 + (long)blockIdx.x * n_cstages1, n_cstages1, n_slots, act, &act_n);
         __syncthreads();
         const int n_act = act_n;
         const int c_all = (n_act + 15) / 16;
         const int b0 = 16 * (int)((long)c_all * blockIdx.y / gridDim.y);
         const int e0 = min(n_act, 16 * (int)((long)c_all * (blockIdx.y + 1) / gridDim.y));
-        constexpr int TQ = K16_T * KS32 * 1024;              // the slot's tail: [0, 64) initial accumulators, [64, 128) -up_to_half(sw r)
-        // where sub-block `sub` of group g sits in the level-2 image: stage g >> 4, tile (g >> 2) & 3, row 4 (g & 3) + sub
-        auto frag_of = [&](int g, int sub, int ks, int q) -> const char* {
-            return Cst + (long)(g >> 4) * STAGE + (((((g >> 2) & 3) * KS32 + ks) * 64 + q * 16 + 4 * (g & 3) + sub) * 16);
-        };
-        auto dma_chunk = [&](int c0, char* dst) {
-            for (int p = wave; p < K16_T * KS32; p += K16_NW) {
-                const int j = p / KS32, ks = p - j * KS32;
-                if (c0 + 4 * j < e0) {                        // (wave-uniform)
-                    const int gi = c0 + 4 * j + (col >> 2);
-                    const int g = gi < e0 ? act[gi] : act[c0 + 4 * j];   // (a slot behind the list: any valid address; its bits are dropped)
-                    lds_dma_16(frag_of(g, col & 3, ks, quad), dst + p * 1024);
-                }
-            }
-        };
-        // wave w <-> the chunk's tile w: lanes 0..15 its initial accumulators, lanes 16..31 its radii (row i <-> sub-block i & 3 of
-        // the tile's (i >> 2)-th group)
-        auto load_tail = [&](int c0) -> float {
-            const int i = lane & 15, gi = c0 + 4 * wave + (i >> 2);
-            if (lane >= 32 || gi >= e0) return lane < 16 ? __builtin_inff() : 0.0f;     // (an empty slot: never needed)
-            const int g = act[gi];
-            return *(const float*)(Cst + (long)(g >> 4) * STAGE + TQ + (((lane >> 4) * 64) + ((g >> 2) & 3) * 16 + 4 * (g & 3) + (i & 3)) * 4);
-        };
-        auto store_tail = [&](char* dst, float v) {
-            if (lane < 32) *(float*)(dst + TQ + (((lane >> 4) * 64) + wave * 16 + (lane & 15)) * 4) = v;
-        };
-        if (b0 < e0) { dma_chunk(b0, smem); store_tail(smem, load_tail(b0)); }
-        int k = 0;
-        for (int c0 = b0; c0 < e0; c0 += 16, ++k) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            char* sn = smem + ((k + 1) & 1) * STAGE;
-            float tail_n = 0.0f;
-            if (c0 + 16 < e0) { dma_chunk(c0 + 16, sn); tail_n = load_tail(c0 + 16); }
-            const char* st = smem + (k & 1) * STAGE;
-            const float* wq = (const float*)(st + TQ);
-            auto load_tile = [&](int j, bf16x8 (&a)[KS32], f32x4& wv, float& rneg) {
-#pragma unroll
-                for (int ks = 0; ks < KS32; ++ks) a[ks] = *(const bf16x8*)(st + ((j * KS32 + ks) * 64 + lane) * 16);
-                wv = *(const f32x4*)(wq + j * 16 + 4 * quad);
-                rneg = wq[64 + j * 16 + col];
-            };
-            uint32_t lane_bits = 0u;                           // bit 4 j + r: tile j of the chunk, accumulator register r
-            auto run_tile = [&](int j, const bf16x8 (&a)[KS32], const f32x4& wv, float rneg) {
-                bf16x8 ae;
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) ae[jj] = (E)0.0f;
-                if (quad == 0) ae[0] = (E)rneg;
-                f32x4 acc[K16_SB];
-#pragma unroll
-                for (int sb = 0; sb < K16_SB; ++sb) acc[sb] = wv;
-#pragma unroll
-                for (int ks = 0; ks < KS32; ++ks)
-#pragma unroll
-                    for (int sb = 0; sb < K16_SB; ++sb) acc[sb] = mfma16(a[ks], xf[sb][ks], acc[sb]);
-#pragma unroll
-                for (int sb = 0; sb < K16_SB; ++sb) acc[sb] = mfma16(ae, xe[sb], acc[sb]);
-                // (lane (quad, col): bit r <-> its row needs sub-block r of the tile's quad-th group; gathered over the rows
-                //  once per chunk, below -- a ballot and four scalar tests per accumulator register kept the scalar unit busier
-                //  than the matrix pipe)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    bool nd = false;
-#pragma unroll
-                    for (int sb = 0; sb < K16_SB; ++sb) nd = nd || !(acc[sb][r] > P[sb]);
-                    lane_bits |= nd ? (1u << (4 * j + r)) : 0u;
-                }
-            };
-            bf16x8 aA[KS32], aB[KS32];
-            f32x4 wvA, wvB;
-            float rnA, rnB;
-            const bool h1 = c0 + 4 < e0, h2 = c0 + 8 < e0, h3 = c0 + 12 < e0;
-            load_tile(0, aA, wvA, rnA);
-            if (h1) load_tile(1, aB, wvB, rnB);
-            run_tile(0, aA, wvA, rnA);
-            if (h1) {
-                if (h2) load_tile(2, aA, wvA, rnA);
-                run_tile(1, aB, wvB, rnB);
-                if (h2) {
-                    if (h3) load_tile(3, aB, wvB, rnB);
-                    run_tile(2, aA, wvA, rnA);
-                    if (h3) run_tile(3, aB, wvB, rnB);
-                }
-            }
-            // the chunk's sixteen groups: OR over the sixteen rows of every quad (lanes of one DPP row), then the quad's first lane
-            // files tile j's nibble under the tile's quad-th group
-            const uint32_t any_row = row16_or(lane_bits);
-            if (col == 0 && any_row != 0u) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t nib = (any_row >> (4 * j)) & 15u;
-                    const int gi = c0 + 4 * j + quad;
-                    if (nib != 0u && gi < e0) {
-                        const int g = act[gi];
-                        atomicOr(nl + (g >> 4), (unsigned long long)nib << (4 * (g & 15)));
-                    }
-                }
-            }
-            if (c0 + 16 < e0) store_tail(sn, tail_n);
-        }
+        plan_walk_level2<KS32, EL>(Cst, act, b0, e0, smem, nl, xf, xe, P);
         __syncthreads();
         // (two parts of a tile's walk may share a stage: OR into words that start from zero -- cleared by the level-1 workgroups, or by the host's fill)
         for (int i = tid; i < n_cstages; i += 64 * K16_NW)
             if (nl[i] != 0ull) atomicOr(need + (long)blockIdx.x * n_cstages + i, nl[i]);
         return;
     }
-    const int n_walk = n_cstages;
     // (gridDim.y workgroups share a tile's centroid stages: few tiles -- a batch of 65 536 rows is 256 -- would otherwise be
     //  one workgroup per CU walking all the stages alone)
-    const int s_begin = (int)((long)n_walk * blockIdx.y / gridDim.y);
-    const int s_end = (int)((long)n_walk * (blockIdx.y + 1) / gridDim.y);
-    auto item_of = [&](int i) -> int { return (i << 4) | 15; };
-    auto dma_stage = [&](int s, uint32_t tm, char* dst) {
-        const char* src = Cst + (long)s * STAGE;
-        for (int p = wave; p < PIECES; p += K16_NW)
-            if (p == PIECES - 1 || ((tm >> (p / KS32)) & 1u)) lds_dma_16(src + (long)p * 1024 + lane * 16, dst + p * 1024);
-    };
-    int st_cur = 0, st_next = 0;
-    uint32_t tm_cur = 0, tm_next = 0;
-    if (s_begin < s_end) {
-        const int it = item_of(s_begin);
-        st_cur = it >> 4; tm_cur = (uint32_t)it & 15u;
-        dma_stage(st_cur, tm_cur, smem);
-    }
-    for (int i = s_begin; i < s_end; ++i) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (i + 1 < s_end) {
-            const int it = item_of(i + 1);
-            st_next = it >> 4; tm_next = (uint32_t)it & 15u;
-            dma_stage(st_next, tm_next, smem + ((i + 1 - s_begin) & 1) * STAGE);
-        }
-        const char* st = smem + ((i - s_begin) & 1) * STAGE;
-        const float* wq = (const float*)(st + K16_T * KS32 * 1024);
-        uint32_t lane_bits = 0u;                              // (the word's bit 16 t16 + 4 quad + r <-> centroid slot of that place in the stage)
-        // a tile's operands: its KS32 fragments, its initial accumulators, the centroids' side of the extra step (slot 0 =
-        // -up_to_half(sw r)); the NEXT tile's are read under this tile's MFMAs and epilogue
-        auto load_tile = [&](int t, bf16x8 (&a)[KS32], f32x4& wv, float& rneg) {
-#pragma unroll
-            for (int ks = 0; ks < KS32; ++ks) a[ks] = *(const bf16x8*)(st + ((t * KS32 + ks) * 64 + lane) * 16);
-            wv = *(const f32x4*)(wq + t * 16 + 4 * quad);
-            rneg = wq[64 + t * 16 + col];
-        };
-        // MFMAs + test of one tile; its operands in (a, wv, rneg)
-        auto run_tile = [&](int t16, const bf16x8 (&a)[KS32], const f32x4& wv, float rneg) {
-            bf16x8 ae;
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) ae[jj] = (E)0.0f;
-            if (quad == 0) ae[0] = (E)rneg;
-            f32x4 acc[K16_SB];
-#pragma unroll
-            for (int sb = 0; sb < K16_SB; ++sb) acc[sb] = wv;
-#pragma unroll
-            for (int ks = 0; ks < KS32; ++ks)
-#pragma unroll
-                for (int sb = 0; sb < K16_SB; ++sb) acc[sb] = mfma16(a[ks], xf[sb][ks], acc[sb]);
-#pragma unroll
-            for (int sb = 0; sb < K16_SB; ++sb) acc[sb] = mfma16(ae, xe[sb], acc[sb]);
-            // lane (quad, col): bit 4 t16 + r <-> its row needs centroid 4 quad + r of tile t16 (gathered over the rows once per stage)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                bool nd = false;
-#pragma unroll
-                for (int sb = 0; sb < K16_SB; ++sb) nd = nd || !(acc[sb][r] > P[sb]);
-                lane_bits |= nd ? (1u << (4 * t16 + r)) : 0u;
-            }
-        };
-        // up to four tiles, their operands alternating between two register sets (no copies): the next tile's are read
-        // under this tile's MFMAs and test
-        const uint32_t m0 = 15u, m1 = m0 & (m0 - 1u), m2 = m1 & (m1 - 1u), m3 = m2 & (m2 - 1u);
-        const int t0 = __builtin_ctz(m0), t1 = m1 ? __builtin_ctz(m1) : -1, t2 = m2 ? __builtin_ctz(m2) : -1, t3 = m3 ? __builtin_ctz(m3) : -1;
-        bf16x8 aA[KS32], aB[KS32];
-        f32x4 wvA, wvB;
-        float rnA, rnB;
-        load_tile(t0, aA, wvA, rnA);
-        if (t1 >= 0) load_tile(t1, aB, wvB, rnB);
-        run_tile(t0, aA, wvA, rnA);
-        if (t1 >= 0) {
-            if (t2 >= 0) load_tile(t2, aA, wvA, rnA);
-            run_tile(t1, aB, wvB, rnB);
-            if (t2 >= 0) {
-                if (t3 >= 0) load_tile(t3, aB, wvB, rnB);
-                run_tile(t2, aA, wvA, rnA);
-                if (t3 >= 0) run_tile(t3, aB, wvB, rnB);
-            }
-        }
-        // OR over the sixteen rows of every quad; the quad's first lane spreads its four nibbles (one per tile) to their places
-        const uint32_t any_row = row16_or(lane_bits);
-        if (col == 0 && any_row != 0u) {
-            const uint32_t lo = ((any_row & 15u) | (((any_row >> 4) & 15u) << 16)) << (4 * quad);
-            const uint32_t hi = (((any_row >> 8) & 15u) | (((any_row >> 12) & 15u) << 16)) << (4 * quad);
-            atomicOr(nl + (i - s_begin), ((unsigned long long)hi << 32) | lo);
-        }
-        st_cur = st_next; tm_cur = tm_next;
-    }
+    const int s_begin = (int)((long)n_cstages * blockIdx.y / gridDim.y);
+    const int s_end = (int)((long)n_cstages * (blockIdx.y + 1) / gridDim.y);
+    plan_walk_level1<KS32, EL>(Cst, s_begin, s_end, smem, nl, xf, xe, P);
     __syncthreads();
     for (int i = s_begin + tid; i < s_end; i += 64 * K16_NW) need[(long)blockIdx.x * n_cstages + i] = nl[i - s_begin];
     // (level 2 ORs into words that start from zero: the four level-2 words of every stage this workgroup walked are cleared
@@ -798,7 +831,7 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
 //  launch reads it -- exact_lists_totals_kernel)
 template <bool PUBLISH>
 __device__ __forceinline__ void exact_lists_tile(const long tile, const int lane, const unsigned long long* __restrict__ need1, int n_cstages,
-                                                 const unsigned long long* __restrict__ need2, int n_groups,
+                                                 const unsigned long long* __restrict__ need2, int n_groups,   // (the TILE's own words, in memory or in LDS)
                                                  int* __restrict__ glist, int* __restrict__ gcnt,
                                                  int2* tile_counts, int* __restrict__ tlist,
                                                  int* __restrict__ tcnt, int* __restrict__ tile_ticket) {
@@ -806,7 +839,7 @@ __device__ __forceinline__ void exact_lists_tile(const long tile, const int lane
     int base = 0, blk = 0, kept = 0;
     for (int s0 = 0; s0 < n_cstages; s0 += 64) {
         // (the tile's level-1 words in one load, lane <-> stage; then stage by stage out of registers)
-        const unsigned long long mine = s0 + lane < n_cstages ? need1[tile * n_cstages + s0 + lane] : 0ull;
+        const unsigned long long mine = s0 + lane < n_cstages ? need1[s0 + lane] : 0ull;
         const uint32_t lo = (uint32_t)mine, hi = (uint32_t)(mine >> 32);
         unsigned long long todo = __ballot(mine != 0ull);
         for (; todo != 0ull; todo &= todo - 1ull) {
@@ -814,7 +847,7 @@ __device__ __forceinline__ void exact_lists_tile(const long tile, const int lane
             const unsigned long long w = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)hi, sl) << 32) |
                                          (uint32_t)__builtin_amdgcn_readlane((int)lo, sl);
             uint32_t nib = 15u;
-            if (need2 != nullptr) nib = (uint32_t)(need2[tile * 4 * n_cstages + 4 * s + (lane >> 4)] >> (4 * (lane & 15))) & 15u;
+            if (need2 != nullptr) nib = (uint32_t)(need2[4 * s + (lane >> 4)] >> (4 * (lane & 15))) & 15u;
             const int g = s * 64 + lane;
             const bool l1 = ((w >> lane) & 1ull) && g < n_groups;
             const bool on = l1 && nib != 0u;
@@ -855,7 +888,8 @@ __global__ __launch_bounds__(64) void exact_lists_kernel(const unsigned long lon
                                                          int* __restrict__ glist, int* __restrict__ gcnt,
                                                          int2* __restrict__ tile_counts, int* __restrict__ tlist,
                                                          int* __restrict__ tcnt, int* __restrict__ tile_ticket) {
-    exact_lists_tile<false>(blockIdx.x, threadIdx.x, need1, n_cstages, need2, n_groups, glist, gcnt, tile_counts, tlist, tcnt, tile_ticket);
+    exact_lists_tile<false>(blockIdx.x, threadIdx.x, need1 + (long)blockIdx.x * n_cstages, n_cstages,
+                            need2 != nullptr ? need2 + (long)blockIdx.x * 4 * n_cstages : nullptr, n_groups, glist, gcnt, tile_counts, tlist, tcnt, tile_ticket);
 }
 
 // sum of the tiles' (16-unit blocks listed, groups level 1 kept) into the pass's counters.  One workgroup.
@@ -863,21 +897,23 @@ __global__ __launch_bounds__(64) void exact_lists_kernel(const unsigned long lon
 // about L blocks -- L = len_pct % of the mean list (1.25 x), or what gives every slot of the chip two items where the tiles are few; never below
 // 32 blocks (a part re-reads its tile's 64 KB of rows) --, item = (tile, part | parts << 16) in tile order; the queue's counter reset.
 // At most tiles + max(100 / len_pct tiles, 2.1 slots) items (the three cases of L): with len_pct >= 25, within 5 tiles + 4 slots.
-// (the body, for a workgroup of 1 024 threads; sb, sk: sixteen ints of LDS each, tot_b: one)
+// (the body, for a workgroup of NT threads -- what it writes does not depend on NT: integer sums, and items in tile order --;
+//  sb, sk: NT / 64 ints of LDS each, tot_b: one)
+template <int NT>
 __device__ __forceinline__ void exact_list_totals_body(const int2* tile_counts, long tiles, int* __restrict__ blocks_run,
                                                        int* __restrict__ groups_run, int slots, int2* __restrict__ items,
                                                        int* __restrict__ n_items, int* __restrict__ item_ctr, int len_pct,
                                                        int* sb, int* sk, int& tot_b) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int b = 0, k = 0;
-    for (long t = tid; t < tiles; t += 1024) { const int2 c = tile_counts[t]; b += c.x; k += c.y; }
+    for (long t = tid; t < tiles; t += NT) { const int2 c = tile_counts[t]; b += c.x; k += c.y; }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { b += __shfl_xor(b, o, 64); k += __shfl_xor(k, o, 64); }
     if (lane == 0) { sb[wave] = b; sk[wave] = k; }
     __syncthreads();
     if (tid == 0) {
         b = 0; k = 0;
-        for (int w = 0; w < 16; ++w) { b += sb[w]; k += sk[w]; }
+        for (int w = 0; w < NT / 64; ++w) { b += sb[w]; k += sk[w]; }
         *blocks_run = b; *groups_run = k;
         tot_b = b;
     }
@@ -887,8 +923,8 @@ __device__ __forceinline__ void exact_list_totals_body(const int2* tile_counts, 
     const long by_mean = (len_pct * total) / (100 * (tiles > 0 ? tiles : 1)) + 1, by_slots = total / (2 * (long)(slots > 0 ? slots : 1));
     const int L = (int)max(32L, min(by_mean, by_slots));
     auto parts_of = [&](int cnt) -> int { return cnt <= L ? 1 : (cnt + L - 1) / L; };
-    // a contiguous run of tiles per thread; exclusive scan of the runs' item counts over the 1 024 threads
-    const long per = (tiles + 1023) / 1024, t_b = min((long)tid * per, tiles), t_e = min(t_b + per, tiles);
+    // a contiguous run of tiles per thread; exclusive scan of the runs' item counts over the NT threads
+    const long per = (tiles + NT - 1) / NT, t_b = min((long)tid * per, tiles), t_e = min(t_b + per, tiles);
     int mine = 0;
     for (long t = t_b; t < t_e; ++t) mine += parts_of(tile_counts[t].x);
     int incl = mine;
@@ -899,7 +935,7 @@ __device__ __forceinline__ void exact_list_totals_body(const int2* tile_counts, 
     __syncthreads();
     int before = 0, all = 0;
 #pragma unroll
-    for (int w = 0; w < 16; ++w) { if (w < wave) before += sb[w]; all += sb[w]; }
+    for (int w = 0; w < NT / 64; ++w) { if (w < wave) before += sb[w]; all += sb[w]; }
     int o = before + incl - mine;
     for (long t = t_b; t < t_e; ++t) {
         const int np = parts_of(tile_counts[t].x);
@@ -913,7 +949,7 @@ __global__ __launch_bounds__(1024) void exact_list_totals_kernel(const int2* __r
                                                                  int len_pct = 125) {
     __shared__ int sb[16], sk[16];
     __shared__ int tot_b;
-    exact_list_totals_body(tile_counts, tiles, blocks_run, groups_run, slots, items, n_items, item_ctr, len_pct, sb, sk, tot_b);
+    exact_list_totals_body<1024>(tile_counts, tiles, blocks_run, groups_run, slots, items, n_items, item_ctr, len_pct, sb, sk, tot_b);
 }
 
 // Both in ONE launch: sixteen tiles a workgroup (a wave each), and the workgroup that finishes LAST does the totals and cuts the
@@ -926,6 +962,29 @@ __global__ __launch_bounds__(1024) void exact_list_totals_kernel(const int2* __r
 // before the ticket: a write-back of all the lists the workgroup has just written) the launch measured 27.4 us against 22.5 us
 // for the two launches it replaces, this way 23.4 us: profiles/exact_chain_summary.md.  No workgroup waits for another.
 constexpr int LISTS_WG_TILES = 16;
+// the ticket: every thread of the workgroup calls it behind its tiles' lists; true in the workgroup that arrives last (*last_s: LDS)
+__device__ __forceinline__ bool exact_lists_last(int* __restrict__ done, int* last_s) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int ticket = __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *last_s = ticket == (int)gridDim.x - 1 ? 1 : 0;
+        if (*last_s) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    return *last_s != 0;
+}
+// where the lists, the counts and the work items of a pass go (exact_plan_fused_kernel: the arguments of exact_lists_totals_kernel)
+struct PlanListsOut {
+    int n_groups;
+    int* glist; int* gcnt; int2* tile_counts; int* tlist; int* tcnt; int* tile_ticket;
+    int* done; int* blocks_run; int* groups_run;
+    int slots; int2* items; int* n_items; int* item_ctr; int len_pct;
+};
 __global__ __launch_bounds__(64 * LISTS_WG_TILES) void exact_lists_totals_kernel(const unsigned long long* __restrict__ need1, int n_cstages,
                                                                                 const unsigned long long* __restrict__ need2, int n_groups,
                                                                                 int* __restrict__ glist, int* __restrict__ gcnt,
@@ -941,21 +1000,97 @@ __global__ __launch_bounds__(64 * LISTS_WG_TILES) void exact_lists_totals_kernel
     __shared__ int last;
     const int tid = threadIdx.x;
     const long tile = (long)blockIdx.x * LISTS_WG_TILES + (tid >> 6);
-    if (tile < tiles) exact_lists_tile<true>(tile, tid & 63, need1, n_cstages, need2, n_groups, glist, gcnt, tile_counts, tlist, tcnt, tile_ticket);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        const int ticket = __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = ticket == (int)gridDim.x - 1 ? 1 : 0;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tile < tiles)
+        exact_lists_tile<true>(tile, tid & 63, need1 + tile * n_cstages, n_cstages, need2 != nullptr ? need2 + tile * 4 * n_cstages : nullptr, n_groups,
+                               glist, gcnt, tile_counts, tlist, tcnt, tile_ticket);
+    if (!exact_lists_last(done, &last)) return;
+    exact_list_totals_body<64 * LISTS_WG_TILES>(tile_counts, tiles, blocks_run, groups_run, slots, items, n_items, item_ctr, len_pct, sb, sk, tot_b);
+}
+
+// BOTH LEVELS AND THE LISTS IN ONE LAUNCH, one workgroup per 256-row tile (a pass of many tiles: the split kernels' gridDim.y == 1),
+// three phases on the tile's rows, which stay in registers throughout:
+//   A  level 1 as exact_plan_kernel<.., false> runs it: prologue, walk over all centroid stages, the need words in LDS (nl1);
+//   B  level 2 as exact_plan_kernel<.., true> runs it: the dense list of the groups kept, from nl1; the gathered walk; the nibbles
+//      filed into the workgroup's own words in LDS (nl2: no global atomics, nothing to clear);
+//   C  exact_lists_tile from the two sets of LDS words (one wave), then exact_lists_totals_kernel's ticket: the workgroup that
+//      finishes last sums the tiles' counts and cuts the screen's work items.
+// Nothing but the lists, the counts and seed_s leaves the workgroup: the need bitmaps and sqrt(U) (sU_s) have no other reader.
+// The two levels' thresholds differ (the centroid images' measured rounding errors: ec in plan_row_threshold): both are formed in
+// the prologue, level 2's waits in LDS (p2s) while level 1 walks.  The extra step's row operand bx is sx sqrt(U) rounded up in both
+// levels unless the level's A is not finite, where it is up_to_half(0) and P = +inf: every test of that level then says "needed"
+// whatever the accumulator holds, so one operand serves both levels -- level 1's, or level 2's where level 1's P is +inf.
+template <int KS32, class EL>
+__global__ __launch_bounds__(64 * K16_NW, 3) void exact_plan_fused_kernel(const __bf16* __restrict__ Xb, long N,
+                                                                    const char* __restrict__ Cst1, int n_cstages1, const float* __restrict__ cmax2_1,
+                                                                    const char* __restrict__ Cst2, int n_slots2, const float* __restrict__ cmax2_2,
+                                                                    const float* __restrict__ xsq, const float* __restrict__ xerr,
+                                                                    const float* __restrict__ xmax2,
+                                                                    const float* __restrict__ wmax2, const float* __restrict__ werr2,
+                                                                    ExactBound eb, const int* __restrict__ lastpos, const char* __restrict__ Wst,
+                                                                    float* __restrict__ seed_s, int force_all, PlanListsOut lo) {
+    using bf16x8 = typename V8<typename EL::T>::t;
+    constexpr int DP = 32 * KS32;
+    constexpr int STAGE = k16_stage_bytes(KS32);
+    constexpr int NT = 64 * K16_NW;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int act_n;
+    __shared__ int sb_s[NT / 64], sk_s[NT / 64];
+    __shared__ int tot_b;
+    __shared__ int last;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int quad = lane >> 4, col = lane & 15;
+    const long wave_s0 = (long)blockIdx.x * K16_WG_SAMPLES + wave * (16 * K16_SB);
+    // LDS behind the two stage slots: the list of kept groups, level 2's words, level 1's words, level 2's thresholds
+    const int n_cstages2 = 4 * n_cstages1;
+    int* act = (int*)(smem + 2 * STAGE);
+    unsigned long long* nl2 = (unsigned long long*)(smem + 2 * STAGE + (size_t)n_cstages1 * 64 * sizeof(int));
+    unsigned long long* nl1 = nl2 + n_cstages2;
+    float* p2s = (float*)(nl1 + n_cstages1);
+
+    bf16x8 xf[K16_SB][KS32];
+    bf16x8 xe[K16_SB];
+    float P[K16_SB];
+    {
+        const ExactScales sc1 = ex_scales(xmax2, cmax2_1, cmax2_1 + 1);
+        const ExactScales sc2 = ex_scales(xmax2, cmax2_2, cmax2_2 + 1);
+        const ExactScales sw = ex_scales(xmax2, wmax2, werr2);
+#pragma unroll
+        for (int sb = 0; sb < K16_SB; ++sb) {
+            const long row = wave_s0 + sb * 16 + col;
+#pragma unroll
+            for (int ks = 0; ks < KS32; ++ks) xf[sb][ks] = *(const bf16x8*)(Xb + row * DP + ks * 32 + quad * 8);
+            float q = 0.0f, xer = 0.0f, su = 0.0f;
+            if (row < N) {
+                q = xsq[row]; xer = xerr[row];
+                su = plan_row_seed<KS32, EL>(xf[sb], row, q, xer, eb, sw, Wst, lastpos, nullptr, nullptr, seed_s, force_all);
+            }
+            float bx1, bx2, P2;
+            plan_row_threshold<KS32>(eb, sc1, row < N, q, xer, su, P[sb], bx1);
+            plan_row_threshold<KS32>(eb, sc2, row < N, q, xer, su, P2, bx2);
+            xe[sb] = plan_extra_step<EL>(P[sb] == __builtin_inff() ? bx2 : bx1);
+            if (quad == 0) p2s[wave * (16 * K16_SB) + sb * 16 + col] = P2;
         }
     }
+    for (int i = tid; i < n_cstages1 + n_cstages2; i += NT) nl2[i] = 0ull;   // (nl2, then nl1: one run of words)
+
+    // A
+    plan_walk_level1<KS32, EL>(Cst1, 0, n_cstages1, smem, nl1, xf, xe, P);
     __syncthreads();
-    if (!last) return;
-    exact_list_totals_body(tile_counts, tiles, blocks_run, groups_run, slots, items, n_items, item_ctr, len_pct, sb, sk, tot_b);
+    // B
+    if (wave == 0) plan_level2_list(nl1, n_cstages1, n_slots2, act, &act_n);
+#pragma unroll
+    for (int sb = 0; sb < K16_SB; ++sb) P[sb] = p2s[wave * (16 * K16_SB) + sb * 16 + col];
+    __syncthreads();
+    plan_walk_level2<KS32, EL>(Cst2, act, 0, act_n, smem, nl2, xf, xe, P);
+    __syncthreads();
+    // C
+    if (wave == 0)
+        exact_lists_tile<true>(blockIdx.x, lane, nl1, n_cstages1, nl2, lo.n_groups, lo.glist, lo.gcnt, lo.tile_counts, lo.tlist, lo.tcnt, lo.tile_ticket);
+    if (!exact_lists_last(lo.done, &last)) return;
+    exact_list_totals_body<NT>(lo.tile_counts, gridDim.x, lo.blocks_run, lo.groups_run, lo.slots, lo.items, lo.n_items, lo.item_ctr, lo.len_pct,
+                               sb_s, sk_s, tot_b);
 }
 
 // ---- the SCOUT: a bound for rows WITHOUT a last BMU (query rows, streamed chunks, a row set's first epoch) and for the

@@ -202,6 +202,10 @@ struct som_handle {
         // the listed screen's SELECT TAIL (bmu_bf16_k16.hpp): the queue's workgroups select the candidates behind their walks
         bool fuse_select = true;          // SOM_EXACT_FUSE_SELECT=0: exact_select_kernel in a launch of its own behind the screen (A/B)
         int64_t sel_fused_passes = 0, sel_launched_passes = 0, sel_ticket_tiles = 0;   // som_debug_exact_select_stats
+        // a pass's PLAN (exact_skip_plan): levels 1 and 2 and the lists in one launch (exact_plan_fused_kernel) where the launch allows it
+        bool fuse_plan = true;            // SOM_EXACT_FUSE_PLAN=0: always level 1, level 2 and the lists as launches of their own (A/B)
+        int hook_plan_parts = 0;          // SOM_EXACT_PLAN_PARTS=n: at most n workgroups per tile in the plan's grids (0: four)
+        int64_t plan_fused_launches = 0, plan_split_launches = 0;   // som_debug_exact_plan_stats
         DevBuf<int2> items;               // the listed screen's work queue: [0] = (items, counter), from [8] on (tile, part | parts << 16)
         int item_slots = 0;               // ... sized for this many resident workgroups
         int screen_slots = 0;             // ... the listed screen's last grid (what the next plan cuts its lists for)
@@ -1514,6 +1518,8 @@ int som_create(const som_config* cfg, som_handle** out) {
         if (const char* e = dev_env("SOM_FUSE_MERGE")) h->fuse_merge_prep = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_EXACT_CHAIN")) h->ex.chain = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_EXACT_FUSE_SELECT")) h->ex.fuse_select = std::atoi(e) != 0;
+        if (const char* e = dev_env("SOM_EXACT_FUSE_PLAN")) h->ex.fuse_plan = std::atoi(e) != 0;
+        if (const char* e = dev_env("SOM_EXACT_PLAN_PARTS")) h->ex.hook_plan_parts = std::max(0, std::atoi(e));
         if (const char* e = dev_env("SOM_COUNTING_SORT")) h->counting_sort = std::atoi(e) != 0;
         // a 128-row block of a table already spans most of a map side up to 256: nothing to skip there
         h->use_bands = h->X > 256 || h->Y > 256;
@@ -2519,6 +2525,21 @@ int som_debug_exact_select_stats(som_handle* h, int64_t* fused_passes, int64_t* 
     *fused_passes = h->ex.sel_fused_passes;
     *launched_passes = h->ex.sel_launched_passes;
     *ticket_tiles = h->ex.sel_ticket_tiles;
+    return 0;
+}
+
+int som_debug_exact_plan_stats(som_handle* h, int64_t* fused_launches, int64_t* split_launches) {
+    if (!h || !fused_launches || !split_launches) return fail(h, "som_debug_exact_plan_stats: NULL argument");
+    *fused_launches = h->ex.plan_fused_launches;
+    *split_launches = h->ex.plan_split_launches;
+    return 0;
+}
+
+int som_debug_exact_last_plan(som_handle* h, int32_t* out8) {
+    if (!h || !out8) return fail(h, "som_debug_exact_last_plan: NULL argument");
+    const policy::LaunchPlan& p = h->ex.lp;
+    out8[0] = p.skip; out8[1] = p.resort; out8[2] = p.scout; out8[3] = p.level2; out8[4] = p.estimate; out8[5] = p.sample_tiles;
+    out8[6] = p.refine; out8[7] = p.time_phases;
     return 0;
 }
 

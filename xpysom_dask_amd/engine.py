@@ -354,6 +354,19 @@ class HipEngine:
         self._check(self._lib.som_debug_exact_select_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def exact_plan_stats(self):
+        """precision 'exact': (plans of a screen pass that ran both levels and the lists in one launch, plans that ran them as
+        launches of their own) so far."""
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self._lib.som_debug_exact_plan_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def exact_last_plan(self):
+        """precision 'exact': the plan of the last BMU launch as it ran, a dict of the policy's eight decisions."""
+        out = (C.c_int32 * 8)()
+        self._check(self._lib.som_debug_exact_last_plan(self._h, out))
+        return dict(zip(("skip", "resort", "scout", "level2", "estimate", "sample_tiles", "refine", "time_phases"), (bool(v) for v in out)))
+
     def exact_skip_stats(self):
         """precision 'exact': (blocks the screens ran, blocks of full scans) so far -- block skipping's executed share."""
         a, b = C.c_int64(), C.c_int64()
