@@ -102,6 +102,30 @@ int som_policy_eval(int32_t which, const double* costs, const double* args, int3
 #define SOM_POLICY_REPLAY_OUT 18
 int som_policy_replay(int32_t n_launches, const double* script, double* out);
 
+/* The codebook operands' STATE (csrc/codebook_operands.hpp, operands::State: which of |w|^2, the patch-order copy, the float32
+ * image and its order, the 16-bit image with its norms, the plan's centroids are current) on a caller-supplied script of events
+ * -- pure host code, NO device needed.  A fresh State (everything stale) is moved as the host code moves the handle's
+ * (tests/test_operands_cpu.py).
+ *   config[6] = {half, exact, patch order, cosine, resident (exact, <= 128 features), a float32 stage image exists}
+ *   script[n_events][SOM_OPERANDS_REPLAY_IN] = {event, request, flag}
+ *     event   0 codebook replaced   1 plain merge   2 half-fused merge   3 exact fused merge (flag: it wrote the centroids)
+ *             4 a request (flag: the caller may defer the 16-bit image to its launch), decided and committed
+ *             5 the pending 16-bit image is taken (by the planned launch, or flushed)
+ *             6 a captured graph replayed (its request)   7 the canary's |w|^2
+ *     request 0 the configured search   1 a float32 kernel in the units' own order   2 the exact screen's patch-order operands
+ *   out[n_events][SOM_OPERANDS_REPLAY_OUT], per event:
+ *     the rebuilds the decision listed (events 4 and 7; else 0)
+ *             [0] |w|^2  [1] permute  [2] float32 image  [3] ... in patch order  [4] 16-bit image  [5] ... its norms step skipped
+ *             [6] ... its image kernel deferred  [7] ... which also sets the centroid levels' maxima (cm)
+ *     [8] a pending image was flushed (event 4) or taken (event 5)  [9] ... with cm
+ *     the accessors afterwards  [10] the float32 image is in patch order  [11] an image is pending  [12] the centroids are fresh
+ *             [13] the patch-order copy is in step with the codebook
+ *   returns non-zero for a NULL argument, a negative count, an inconsistent config, an unknown event or request, or an event the
+ *   config has no path for (2 without a plain half mode, 3 and a deferring request without the resident exact path, 6 in exact mode). */
+#define SOM_OPERANDS_REPLAY_IN 3
+#define SOM_OPERANDS_REPLAY_OUT 14
+int som_operands_replay(const int32_t* config, int32_t n_events, const int32_t* script, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -359,19 +359,19 @@ int exact_skip_centroids(som_handle* h, const float* xmax2, unsigned q_blocks, u
     const CentroidLevel l1{c0.Cc, c0.rg, c0.csq, c0.cmax2, c0.n_slots}, l2{c1.Cc, c1.rg, c1.csq, c1.cmax2, c1.n_slots};
     // two launches for both levels: centroids + radii + |c|^2, then the stage images with their tails (the images take the
     // codebook's own power of two: a centroid is no longer than the longest unit)
-    // (cen_fresh: the fused merge has written the first launch's outputs for this codebook -- exact_merge_prep_kernel)
-    if (!ex.cen_fresh)
+    // (fresh centroids: the fused merge has written the first launch's outputs for this codebook -- exact_merge_prep_kernel)
+    if (!h->ops.centroids_fresh())
         exact_centroids_kernel<<<dim3((unsigned)(cdiv(n_groups, 4) * 4)), dim3(512), 0, h->stream>>>(Wsrc, h->K, h->D, n_groups, l1, l2, h->wmax2);
     const int nst2 = ex.lp.level2 ? c1.n_cstages : 0;
     char* plain = ex.lp.scout ? c0.Cst_plain : nullptr;
     const dim3 tgrid((unsigned)cdiv((long)(c0.n_cstages + nst2) * K16_T, 4)), block(256);
-    if (ex.prep_w_pending) {
+    bool cm = false;
+    if (h->ops.take_pending_image(&cm)) {
         // (the codebook's own 16-bit image is still due -- refresh_codebook_operands left it to this launch: both in one grid)
-        ex.prep_w_pending = false;
         const float* Wex = h->ex_patch ? h->Wp : h->W;
         // (cm: centroids the fused merge wrote -- their levels' maxima are due now that max |w|^2 is final; the error maxima it zeroed)
-        float* cm1 = ex.prep_w_cm ? (float*)c0.cmax2 : nullptr;
-        float* cm2 = ex.prep_w_cm ? (float*)c1.cmax2 : nullptr;
+        float* cm1 = cm ? (float*)c0.cmax2 : nullptr;
+        float* cm2 = cm ? (float*)c1.cmax2 : nullptr;
         const unsigned w_blocks = (unsigned)cdiv((long)h->n_stages * K16_T, 4);
         switch (h->ks32) {
 #define SOM_PIMG_CASE(k) case k: exact_prep_images_kernel<k, E><<<dim3(w_blocks + tgrid.x + q_blocks), block, 0, h->stream>>>(w_blocks, tgrid.x, Wex, h->K, h->D, h->Wst, h->n_stages, \
@@ -862,7 +862,7 @@ int exact_fallback_rows(som_handle* h, const ExactLaunch& L, long r0, int n_fb) 
     if (int rc = ex.fbX.reserve(h, (size_t)n_fb * h->D, (size_t)1024 * h->D)) return rc;
     if (int rc = ex.fb_ids.reserve(h, (size_t)n_fb, 1024)) return rc;
     // the float32 kernel names units by their place in its image: the units' own order for it
-    if (h->wf_patch) if (int rc = refresh_codebook_operands(h, true, false)) return rc;
+    if (h->ops.f32_in_patch_order()) if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
     exact_gather_rows_kernel<<<dim3((unsigned)cdiv((long)n_fb * h->D, 256)), dim3(256), 0, h->stream>>>(
         L.X + r0 * h->D, ex.fb_list, n_fb, h->D, ex.fbX);
     // (its part merge may reuse best64[0 .. n_fb): rows this pass has already settled)
@@ -894,7 +894,7 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
     const long s0 = L.f.resident ? r0 : 0;               // where the pass sits in the sorted copies
     if (r0 > 0) HIPCHK(h, hipEventRecord(cost.ev[0], h->stream));
     // (a pass behind one whose fallback rows went through the float32 kernel: its image back in patch order)
-    if (h->wf_patch != h->ex_patch) if (int rc = refresh_codebook_operands(h, true, true)) return rc;
+    if (h->ops.f32_in_patch_order() != h->ex_patch) if (int rc = refresh_codebook_operands(h, operands::Request::ExactScreen)) return rc;
     HIPCHK(h, hipMemsetAsync(pc.base, 0, pc.bytes(), h->stream));
     // (sorted pass: the screen, the select kernel and the merge keys work on positions of the sorted order)
     const float* p_xsq = xsq + r0; const float* p_xerr = xerr + r0; const float* p_seed = nullptr;
@@ -1075,7 +1075,7 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
         prep_wsqh_kernel<<<dim3(wsqh_blocks), dim3(256), 0, h->stream>>>(
             h->wn, h->K, h->wmax2, xmax2, h->Wst, h->n_stages, h->stage_bytes, h->stage_units, h->best64, N, 1);
     };
-    bool wsqh_done = !ex.prep_w_pending;
+    bool wsqh_done = !h->ops.image_pending();
     if (wsqh_done) launch_wsqh();
     const int n_groups = (int)cdiv(h->K, EX_GROUP);
     const long chunk = std::min(exact_chunk_rows(h), ex.stride);

@@ -74,7 +74,7 @@ int exact_top2_list_rows(som_handle* h, const float* X, const int* list, int n_l
     if (int rc = t2.ids1.reserve(h, (size_t)n_list, 1024)) return rc;
     if (int rc = t2.ids2.reserve(h, (size_t)n_list, 1024)) return rc;
     // the float32 kernel names units by their place in its image: the units' own order for it
-    if (int rc = refresh_codebook_operands(h, true, false)) return rc;
+    if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
     exact_gather_rows_kernel<<<dim3((unsigned)cdiv((long)n_list * h->D, 256)), dim3(256), 0, h->stream>>>(X, list, n_list, h->D, t2.X);
     row_sq_f32_kernel<<<dim3((unsigned)cdiv(n_list, 256)), dim3(256), 0, h->stream>>>(t2.X, n_list, h->D, t2.xsq);
     if (int rc = launch_bmu_top2(h, t2.X, n_list, t2.xsq, t2.ids1, t2.ids2)) return rc;
@@ -92,7 +92,7 @@ int exact_top2_pass(som_handle* h, const float* X, const float* xsq, const float
     const PassCtr pc = pass_ctr(h);
     const int n_groups = pc.n_groups;
     // (a pass behind one whose listed rows went through the float32 kernel: its image back in patch order)
-    if (h->wf_patch != h->ex_patch) if (int rc = refresh_codebook_operands(h, true, true)) return rc;
+    if (h->ops.f32_in_patch_order() != h->ex_patch) if (int rc = refresh_codebook_operands(h, operands::Request::ExactScreen)) return rc;
     HIPCHK(h, hipMemsetAsync(pc.base, 0, pc.bytes(), h->stream));
     int parts = 1;
     long pitch = 0;
@@ -153,7 +153,7 @@ int launch_top2_exact(som_handle* h, const float* X, long N, const float* xsq, c
         if (bad_w) {
             // a unit with a NaN or infinite norm: the float32 kernel for every row of the call
             h->t2.rows_f32 = f32_before + N;
-            if (int rc = refresh_codebook_operands(h, true, false)) return rc;
+            if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
             return launch_bmu_top2(h, X, N, xsq, out1, out2);
         }
     }

@@ -26,6 +26,7 @@
 #include "bmu_exact.hpp"
 #include "exact_skip.hpp"
 #include "exact_policy.hpp"
+#include "codebook_operands.hpp"
 #include "exact_skip_wide.hpp"
 #include "bmu_f32.hpp"
 #include "bmu_f32_res.hpp"
@@ -103,9 +104,9 @@ struct som_handle {
     bool f16 = false;        // precision f16: _Float16 operands instead of __bf16 (the same kernels, som_common.hpp)
     bool exact = false;      // precision 'exact': MFMA screen + float32 re-score of the candidates (bmu_exact.hpp)
     // exact mode: the operand images in PATCH ORDER (som_common.hpp; ex_perm[position] = unit, ex_inv[unit] = position) -- prepared
-    // from a permuted copy of the codebook; wf_patch: the order the float32 image is in right now (the float32 kernels
-    // proper -- fallback rows, top-2, analysis calls -- want the units' own order and rebuild it)
-    bool ex_patch = false, wf_patch = false;
+    // from a permuted copy of the codebook (the float32 kernels proper -- fallback rows, top-2, analysis calls -- want the
+    // float32 image in the units' own order and rebuild it: operands::Request::F32Units)
+    bool ex_patch = false;
     bool ex_sub44 = false;                              // ... with every group an 8 x 8 patch in 4 x 4 blocks (patch_order)
     DevBuf<int> ex_perm;
     DevBuf<int> ex_inv;
@@ -161,15 +162,7 @@ struct som_handle {
         } srt[2];
         int64_t lastpos_carried_epochs = 0;   // planned resident epochs that skipped exact_lastpos_kernel (som_debug_exact_chain_stats)
         bool chain = true;                // SOM_EXACT_CHAIN=0: the planned epoch's small launches as separate kernels and fills (A/B)
-        // the codebook's 16-bit stage image up to 128 features (prep_w_exact_k16_kernel) is due whenever the codebook has changed; a
-        // planned launch writes it in one grid with the centroid images (exact_prep_images_kernel), which only launch_bmu_exact
-        // can know: its caller lets refresh_codebook_operands leave that one kernel pending, and the launch (or, should it not
-        // get there, the next refresh) pays it
-        bool defer_prep_w = false;        // the refresh in progress may leave it pending
-        bool prep_w_pending = false;      // it is due
-        bool prep_w_cm = false;           // ... with the centroid levels' maxima to set (the fused merge wrote the centroids)
         bool cen_ready = false;           // both centroid levels are allocated
-        bool cen_fresh = false;           // ... and hold the current codebook's centroids, radii, |c|^2: the fused merge wrote them
         long sk_stride = 0;               // rows per pass the per-pass plan buffers hold
         int res_every = 0;                // SOM_EXACT_RESORT=n: re-sort every n-th planned epoch (0: when the order has gone stale)
         DevBuf<int> sk_keys, sk_keys2, sk_vals;
@@ -237,12 +230,8 @@ struct som_handle {
     DevBuf<char> ftX;        //   sample tile image of the rows being scanned (scratch, grown on demand)
     int ft_kchunks = 0, ft_ublocks = 0;
     int n_stages = 0;
-    // operands derived from W, rebuilt lazily: the bf16 stage image (w_dirty), |w|^2 (wsq_dirty) and the
-    // float32 stage / tile images (wf_dirty).  Training in bf16 precision never touches the float32 images.
-    bool w_dirty = true, wsq_dirty = true, wf_dirty = true, wp_dirty = true;   // (wp: the patch-order copy, exact mode)
-    // exact mode, input_len <= 128: the fused merge (exact_merge_prep_kernel) has left wn and wmax2[0] = max |w|^2 of the current
-    // codebook and wmax2[1] zeroed: the next prep_codebook_half goes straight to the 16-bit images (and takes the flag down)
-    bool wn_fresh = false;
+    // which of the operands derived from W are current (rebuilt lazily: refresh_codebook_operands): codebook_operands.hpp
+    operands::State ops;
 
     // resident training rows
     const float* Xd = nullptr;   // X_owned, or the caller's device rows (som_set_data_device)
@@ -489,12 +478,10 @@ int resolve_profile(som_handle* h) {
     case 21: return fn<21, E>(__VA_ARGS__); case 22: return fn<22, E>(__VA_ARGS__); case 23: return fn<23, E>(__VA_ARGS__); case 24: return fn<24, E>(__VA_ARGS__); \
     case 25: return fn<25, E>(__VA_ARGS__); }
 
-void mark_codebook_changed(som_handle* h) {
-    h->w_dirty = h->wsq_dirty = h->wf_dirty = h->wp_dirty = true;
-    h->wn_fresh = false; h->ex.cen_fresh = false;
-}
-
-// the exact mode's 16-bit stage image up to 128 features, and the one that was left pending (som_handle::ExactScratch::prep_w_pending)
+// the exact mode's 16-bit stage image up to 128 features (cm: with the centroid levels' maxima -- the fused merge wrote the
+// centroids).  It is due whenever the codebook has changed; a planned launch writes it in one grid with its centroid images
+// (exact_prep_images_kernel), which only launch_bmu_exact can know: its caller lets the refresh leave this one kernel pending
+// (operands::State), and the launch -- or, should it not get there, the next refresh -- pays it
 template <class E>
 int launch_prep_w_exact(som_handle* h, bool cm) {
     const float* Wex = h->ex_patch ? h->Wp : h->W;
@@ -510,16 +497,17 @@ int launch_prep_w_exact(som_handle* h, bool cm) {
     return 0;
 }
 int flush_prep_w(som_handle* h) {
-    if (!h->ex.prep_w_pending) return 0;
-    h->ex.prep_w_pending = false;
-    if (int rc = SOM_HALF(h, launch_prep_w_exact, h, h->ex.prep_w_cm)) return rc;
+    bool cm = false;
+    if (!h->ops.take_pending_image(&cm)) return 0;
+    if (int rc = SOM_HALF(h, launch_prep_w_exact, h, cm)) return rc;
     HIPCHK(h, hipGetLastError());
     return 0;
 }
 
 // the 16-bit operand images of the codebook: stage / tile image, |w~|^2 per unit and its maximum
+// (r: the refresh's decision -- exact mode up to 128 features skips the norms step behind a fused merge and may leave the image kernel pending)
 template <class E>
-int prep_codebook_half(som_handle* h) {
+int prep_codebook_half(som_handle* h, const operands::Rebuilds& r) {
     const float* unit = h->cfg.distance == SOM_DIST_COSINE ? h->wsq : nullptr;
     // exact mode in patch order: the screen's image from the permuted codebook (refresh_codebook_operands wrote it)
     const float* Wex = h->ex_patch ? h->Wp : h->W;
@@ -564,15 +552,14 @@ int prep_codebook_half(som_handle* h) {
         // the float32 kernel's own |w|^2 (refreshed just before) and its maximum first: the units go in scaled by
         // ex_scale(max |w|^2); then the scaled stage image and the units' rounding errors in one pass
         // (after a fused merge both are there already, and the pair was zeroed in front of it: exact_merge_prep_kernel)
-        if (!h->wn_fresh) {
+        if (!r.skip_norms) {
             HIPCHK(h, hipMemsetAsync(h->wmax2, 0, 2 * sizeof(float), h->stream));     // [0]: max |w|^2, [1]: max_k |w^_k - w~_k|^2
             exact_copy_wsq_kernel<<<dim3((unsigned)cdiv(h->K, 1024)), dim3(1024), 0, h->stream>>>(qex, h->K, h->wn, h->wmax2);
         }
-        h->wn_fresh = false;
-        // (centroids the fused merge wrote: their levels' maxima are due now that max |w|^2 is final)
+        // (r.cm: centroids the fused merge wrote: their levels' maxima are due now that max |w|^2 is final)
         if (h->ks32 < 1 || h->ks32 > 4) return fail(h, "the resident half-precision kernel supports input_len <= 128");
-        if (h->ex.defer_prep_w) { h->ex.prep_w_pending = true; h->ex.prep_w_cm = h->ex.cen_fresh; return 0; }
-        return launch_prep_w_exact<E>(h, h->ex.cen_fresh);
+        if (r.deferred) return 0;
+        return launch_prep_w_exact<E>(h, r.cm);
     }
     const float* sc = nullptr;
     switch (h->ks32) {
@@ -587,52 +574,46 @@ int prep_codebook_half(som_handle* h) {
     return 0;
 }
 
-// need_f32: the caller is about to run a float32 kernel (parity-mode BMU, top-2, distance matrix).
-// patch: the caller is the exact mode's screen + re-score (float32 image in patch order, where the handle uses one).
-int refresh_codebook_operands(som_handle* h, bool need_f32, bool patch = false) {
-    if (h->exact) need_f32 = true;                       // the re-score reads the float32 stage image and |w|^2
-    patch = patch && h->ex_patch;
+// |w|^2 in NumPy's order (the parity kernels' own; with a patch order also permuted into wsq_p)
+void launch_codebook_wsq(som_handle* h) {
+    row_sq_f32_kernel<<<dim3((unsigned)cdiv(h->K, 256)), dim3(256), 0, h->stream>>>(h->W, h->K, h->D, h->wsq, h->wsq_p, h->ex_inv);
+}
+
+// the operands `rq`'s reader needs, rebuilt where they are stale: decide, launch what the decision lists, commit
+// (may_defer: operands::State::decide)
+int refresh_codebook_operands(som_handle* h, operands::Request rq, bool may_defer = false) {
+    const operands::Rebuilds r = h->ops.decide(rq, may_defer);
     // (an image a BMU launch left pending and did not get to: whoever reads the operands next pays it)
-    if (!h->ex.defer_prep_w) if (int rc = flush_prep_w(h)) return rc;
-    const bool bf = h->cfg.precision != SOM_PREC_F32;
-    const bool do_f32 = (need_f32 || !bf) && (h->wf_dirty || h->wf_patch != patch);
-    const bool do_bf = bf && h->w_dirty;
-    // (cosine scales the 16-bit images by 1/|w|: |w|^2 is wanted whenever they are rebuilt)
-    const bool do_wsq = h->wsq_dirty && (need_f32 || !bf || (do_bf && h->cfg.distance == SOM_DIST_COSINE));
-    if (!do_f32 && !do_wsq && !do_bf) return 0;
-    Timed t(h, SOM_K_PREP);
-    if (do_wsq) {
-        row_sq_f32_kernel<<<dim3((unsigned)cdiv(h->K, 256)), dim3(256), 0, h->stream>>>(h->W, h->K, h->D, h->wsq, h->wsq_p,
-                                                                                        h->ex_inv);
-        h->wsq_dirty = false;
+    if (r.flush) {
+        if (int rc = SOM_HALF(h, launch_prep_w_exact, h, r.flush_cm)) return rc;
+        HIPCHK(h, hipGetLastError());
     }
-    if (h->ex_patch && h->wp_dirty && ((do_f32 && patch) || do_bf)) {
-        const long total = (long)h->K * ((h->D & 3) == 0 ? h->D / 4 : h->D);
-        exact_permute_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(h->W, h->wsq, h->K, h->D, h->ex_perm, h->Wp,
-                                                                                           h->wsq_p);
-        h->wp_dirty = false;
-    }
-    if (do_f32) {
-        const float* Wsrc = patch ? h->Wp : h->W;
-        const float* qsrc = patch ? h->wsq_p : h->wsq;
-        if (h->Wfimg) {
-            long total = (long)h->ft_ublocks * h->ft_kchunks * (4 * 4 * 64 + 128);
-            prep_tiles_f32_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
-                Wsrc, h->K, h->D, h->ft_kchunks, h->ft_ublocks, FT_WTILE, qsrc, h->Wfimg);
+    if (r.any()) {
+        Timed t(h, SOM_K_PREP);
+        if (r.wsq) launch_codebook_wsq(h);
+        if (r.permute) {
+            const long total = (long)h->K * ((h->D & 3) == 0 ? h->D / 4 : h->D);
+            exact_permute_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(h->W, h->wsq, h->K, h->D, h->ex_perm, h->Wp,
+                                                                                               h->wsq_p);
         }
-        if (h->Wfst) {
-            long total = (long)h->fr_stages * ((long)FR_UT * h->fr_kg * 64 + 64);
-            prep_w_f32_res_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
-                Wsrc, qsrc, h->K, h->D, h->fr_kg, h->Wfst, h->fr_stages);
+        if (r.f32) {
+            const float* Wsrc = r.f32_patch ? h->Wp : h->W;
+            const float* qsrc = r.f32_patch ? h->wsq_p : h->wsq;
+            if (h->Wfimg) {
+                long total = (long)h->ft_ublocks * h->ft_kchunks * (4 * 4 * 64 + 128);
+                prep_tiles_f32_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
+                    Wsrc, h->K, h->D, h->ft_kchunks, h->ft_ublocks, FT_WTILE, qsrc, h->Wfimg);
+            }
+            if (h->Wfst) {
+                long total = (long)h->fr_stages * ((long)FR_UT * h->fr_kg * 64 + 64);
+                prep_w_f32_res_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
+                    Wsrc, qsrc, h->K, h->D, h->fr_kg, h->Wfst, h->fr_stages);
+            }
         }
-        h->wf_dirty = false;
-        h->wf_patch = patch;
+        if (r.half) if (int rc = SOM_HALF(h, prep_codebook_half, h, r)) return rc;
+        HIPCHK(h, hipGetLastError());
     }
-    if (do_bf) {
-        if (int rc = SOM_HALF(h, prep_codebook_half, h)) return rc;
-        h->w_dirty = false;
-    }
-    HIPCHK(h, hipGetLastError());
+    h->ops.commit(r);
     return 0;
 }
 
@@ -985,10 +966,9 @@ int verify_bmu_launch(som_handle* h, const float* X, long N, const int* ids) {
     verify_pick_rows_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(N, n, ids, h->vf_rows, h->vf_picks);
     exact_gather_rows_kernel<<<dim3((unsigned)cdiv((long)n * h->D, 256)), dim3(256), 0, h->stream>>>(X, h->vf_rows, n, h->D, h->vf_X);
     HIPCHK(h, hipMemsetAsync(h->vf_bad, 0, 4 * sizeof(int), h->stream));
-    if (h->wsq_dirty) {                                            // |w|^2 in NumPy's order (the parity kernels' own)
-        row_sq_f32_kernel<<<dim3((unsigned)cdiv(h->K, 256)), dim3(256), 0, h->stream>>>(h->W, h->K, h->D, h->wsq, h->wsq_p,
-                                                                                        h->ex_inv);
-        h->wsq_dirty = false;
+    if (const operands::Rebuilds r = h->ops.decide_wsq(); r.wsq) {
+        launch_codebook_wsq(h);
+        h->ops.commit(r);
     }
     const dim3 grid((unsigned)n), block(256);
     const size_t lds = (size_t)h->D * sizeof(float);
@@ -1025,10 +1005,7 @@ int verify_bmu_launch(som_handle* h, const float* X, long N, const int* ids) {
 int run_activation_bmu_launch(som_handle* h, const float* X, long N, const float* xsq, const __bf16* Xb, const float* xmax2,
                               int* out) {
     // (exact mode up to 128 features: the launch writes the codebook's 16-bit image itself, in one grid with its plan's centroid images)
-    h->ex.defer_prep_w = h->exact && h->ex.chain;
-    const int rc_ops = refresh_codebook_operands(h, h->cfg.precision == SOM_PREC_F32, h->exact);
-    h->ex.defer_prep_w = false;
-    if (rc_ops) return rc_ops;
+    if (int rc = refresh_codebook_operands(h, operands::Request::Search, h->exact && h->ex.chain)) return rc;
     Timed t(h, SOM_K_BMU);
     if (h->exact) return launch_bmu_exact(h, X, N, xsq, Xb, xmax2, out);
     if (h->cfg.precision != SOM_PREC_F32) return launch_bmu_bf16(h, Xb, xmax2, N, out);
@@ -1439,6 +1416,8 @@ int som_create(const som_config* cfg, som_handle** out) {
     }
     h->ex_patch = h->exact && h->K >= 2 * EX_GROUP;      // (a map of one group has nothing to order)
     if (const char* e = dev_env("SOM_EXACT_PATCH")) if (std::atoi(e) == 0) h->ex_patch = false;   // A/B: groups = strips of a map row
+    h->ops = operands::State(operands::Config{h->cfg.precision != SOM_PREC_F32, h->exact, h->ex_patch, h->cfg.distance == SOM_DIST_COSINE,
+                                              h->exact && !h->tiled, h->D <= 128});
     h->dp = h->tiled ? TL_BK * h->n_kchunks : 32 * h->ks32;
     h->stage_bytes = h->wide ? wd_stage_bytes(h->n_kchunks) : k16_stage_bytes(h->ks32);
     h->stage_units = h->wide ? WD_STAGE_UNITS : K16_STAGE_UNITS;
@@ -1601,7 +1580,7 @@ int som_set_weights(som_handle* h, const float* w_host) {
     }
     if (int rc = h2d_blocking(h, h->W, w_host, (size_t)h->K * h->D * sizeof(float))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    mark_codebook_changed(h);
+    h->ops.codebook_replaced();
     return 0;
 }
 
@@ -1720,7 +1699,7 @@ int capture_epoch_graph(som_handle* h) {
         return 0;
     }
     h->capturing = true;
-    mark_codebook_changed(h);                           // the replayed epoch always rebuilds the operands its BMU kernel needs
+    h->ops.codebook_replaced();                         // the replayed epoch always rebuilds the operands its BMU kernel needs
     const std::string saved_err = h->err;
     int rc = epoch_accumulate_eager(h, 1.0, 1.0, 1);
     h->capturing = false;
@@ -1732,7 +1711,7 @@ int capture_epoch_graph(som_handle* h) {
         h->gexec = nullptr;
         h->use_graph = false;                           // this handle stays on the eager path
         h->err = saved_err;
-        mark_codebook_changed(h);
+        h->ops.codebook_replaced();
         if (h->debug) std::fprintf(stderr, "[somhip] epoch graph capture failed; eager launches\n");
         return 0;
     }
@@ -1765,11 +1744,7 @@ int som_epoch_accumulate(som_handle* h, double sigma, double eta, int neigh_f64)
             const NeighParams p = make_neigh_params(h, sigma, eta, neigh_f64);
             store_params_kernel<<<dim3(1), dim3(64), 0, h->stream>>>(p, (NeighParams*)h->np_dev);
             HIPCHK(h, hipGraphLaunch(h->gexec, h->stream));
-            // what the captured refresh_codebook_operands(h, precision == F32) rebuilt
-            const bool bf = h->cfg.precision != SOM_PREC_F32;
-            h->w_dirty = false;
-            if (!bf) h->wf_dirty = false;
-            if (!bf || h->cfg.distance == SOM_DIST_COSINE) h->wsq_dirty = false;
+            h->ops.graph_replayed(operands::Request::Search);   // (the captured epoch's own refresh: run_activation_bmu_launch)
             return 0;
         }
     }
@@ -1809,7 +1784,7 @@ int som_epoch_accumulate_forced(som_handle* h, const int32_t* bmu_host, double s
 int som_stream_begin(som_handle* h) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
-    if (int rc = refresh_codebook_operands(h, h->cfg.precision == SOM_PREC_F32, h->exact)) return rc;
+    if (int rc = refresh_codebook_operands(h, operands::Request::Search)) return rc;
     HIPCHK(h, hipMemsetAsync(h->SC, 0, (size_t)h->K * (h->D1p + 1) * sizeof(float), h->stream));
     h->streaming = true;
     return 0;
@@ -1912,7 +1887,7 @@ int som_epoch_merge(som_handle* h) {
     Timed t(h, SOM_K_MERGE);
     // the exact mode up to 128 features (euclidean): the merge also writes the patch-order copy, |w|^2 and its maximum, the
     // float32 stage image and the plan's centroids -- everything of the next epoch's operands that does not wait for the
-    // maximum (exact_merge_prep_kernel); the 16-bit images follow at the head of the BMU launch (w_dirty stays set)
+    // maximum (exact_merge_prep_kernel); the 16-bit images follow at the head of the BMU launch (they stay owed)
     if (h->fuse_merge_prep && h->exact && !h->tiled) {
         const int n_groups = (int)cdiv(h->K, EX_GROUP);
         const bool cen = h->ex.cen_ready;
@@ -1929,11 +1904,7 @@ int som_epoch_merge(som_handle* h) {
         const unsigned grid = (unsigned)(cen ? cdiv(n_groups, 4) * 4 : n_groups);
         exact_merge_prep_kernel<<<dim3(grid), dim3(512), 0, h->stream>>>(h->ACC, h->K, h->D, h->D1p, n_groups, o, l1, l2);
         HIPCHK(h, hipGetLastError());
-        mark_codebook_changed(h);
-        h->wsq_dirty = false; h->wp_dirty = false;
-        if (h->Wfst) { h->wf_dirty = false; h->wf_patch = h->ex_patch; }
-        h->wn_fresh = true;
-        h->ex.cen_fresh = cen;
+        h->ops.merged_exact_fused(cen);
         return 0;
     }
     // the half-precision paths whose operand image is a stage image (resident kernel, euclidean; wide kernel,
@@ -1942,18 +1913,16 @@ int som_epoch_merge(som_handle* h) {
                                (h->wide && !h->exact && h->n_kchunks <= 4 * WD_MP_ITERS))) {
         if (int rc = SOM_HALF(h, merge_prep_half, h)) return rc;
         HIPCHK(h, hipGetLastError());
-        mark_codebook_changed(h);
-        h->w_dirty = false;                              // the stage image and |w~|^2 are already the new codebook's
+        h->ops.merged_half_fused();                      // the stage image and |w~|^2 are already the new codebook's
         return 0;
     }
     long total = (long)h->K * h->D;
     // (exact mode in patch order: a copy that was in step with the codebook stays in step -- the merge writes both)
-    const bool keep_wp = h->ex_patch && !h->wp_dirty;
+    const bool keep_wp = h->ops.patch_copy_in_step();
     merge_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(h->W, h->ACC, h->K, h->D, h->D1p,
                                                                                 keep_wp ? h->Wp : nullptr, h->ex_inv);
     HIPCHK(h, hipGetLastError());
-    mark_codebook_changed(h);
-    if (keep_wp) h->wp_dirty = false;
+    h->ops.merged_plain();
     return 0;
 }
 
@@ -2162,7 +2131,7 @@ int run_quantization_bmu(som_handle* h, const float* X, long n_rows, bool value_
         if (!h->exact) return 0;
         if (int rc = h->qe_list.reserve(h, (size_t)n_rows, 1024)) return rc;
         if (int rc = h->qe_cnt.reserve(h, 1, 1)) return rc;
-        if (int rc = refresh_codebook_operands(h, true)) return rc;       // (|w|^2; the float32 image in the units' order)
+        if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;       // (|w|^2; the float32 image in the units' order)
         HIPCHK(h, hipMemsetAsync(h->qe_cnt, 0, sizeof(int), h->stream));
         exact_qe_window_kernel<<<dim3((unsigned)cdiv(n_rows, 256)), dim3(256), 0, h->stream>>>(
             X, n_rows, h->D, h->W, h->wsq, h->qxsq, h->qbmu, h->qe_list, h->qe_cnt);
@@ -2185,7 +2154,7 @@ int run_quantization_bmu(som_handle* h, const float* X, long n_rows, bool value_
         HIPCHK(h, hipGetLastError());
         return 0;
     }
-    if (int rc = refresh_codebook_operands(h, true)) return rc;
+    if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
     if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
     Timed t(h, SOM_K_BMU);
     return launch_bmu_f32_any<SCORE_EUCLID_SQRT>(h, X, n_rows, h->qxsq, h->qbmu);
@@ -2206,11 +2175,11 @@ int run_top2(som_handle* h, const float* X, long n_rows) {
     if (exact_top2_fast(h)) {
         if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
         if (int rc = prep_rows_bf16(h, X, n_rows, round_up(n_rows, ROW_PAD), h->qXb, h->xmax2 + 1, h->qxsq)) return rc;
-        if (int rc = refresh_codebook_operands(h, false, true)) return rc;
+        if (int rc = refresh_codebook_operands(h, operands::Request::ExactScreen)) return rc;
         Timed t(h, SOM_K_BMU);
         return launch_top2_exact(h, X, n_rows, h->qxsq, h->qXb, h->xmax2 + 1, h->qbmu, h->qbmu2);
     }
-    if (int rc = refresh_codebook_operands(h, true)) return rc;
+    if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
     if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
     h->t2.rows += n_rows; h->t2.rows_f32 += n_rows;
     Timed t(h, SOM_K_BMU);
@@ -2279,7 +2248,7 @@ int som_bmu_f64(som_handle* h, const double* x_host, int64_t n_rows, int32_t* id
     if (int rc = ensure_query_scratch(h, n_rows)) return rc;
     if (int rc = h->qX64.reserve(h, (size_t)n_rows * h->D, (size_t)1024 * h->D)) return rc;
     if (int rc = h2d_blocking(h, h->qX64, x_host, (size_t)n_rows * h->D * sizeof(double))) return rc;
-    if (int rc = refresh_codebook_operands(h, true)) return rc;       // |w|^2 in NumPy's float32 order
+    if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;       // |w|^2 in NumPy's float32 order
     {
         Timed t(h, SOM_K_BMU);
         bmu_f64_kernel<<<dim3((unsigned)cdiv(n_rows, PW_SAMPLES)), dim3(PW_SAMPLES), w_bytes, h->stream>>>(
@@ -2319,7 +2288,7 @@ int som_distance_matrix(som_handle* h, const float* x_host, int64_t n_rows, int3
     if ((double)n_rows * h->K > 2.0e9) return fail(h, "som_distance_matrix: n_rows * K too large (analysis call, chunk it)");
     if (int rc = ensure_query_scratch(h, n_rows)) return rc;
     if (int rc = h2d_blocking(h, h->qX, x_host, (size_t)n_rows * h->D * sizeof(float))) return rc;
-    if (int rc = refresh_codebook_operands(h, true)) return rc;
+    if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
     if (int rc = row_sq(h, h->qX, n_rows, h->qxsq)) return rc;
     DevBuf<float> dm;
     if (int rc = dm.alloc(h, (size_t)n_rows * h->K)) return rc;
@@ -2359,7 +2328,8 @@ int som_verify_stats(som_handle* h, int64_t* launches, int64_t* rows_checked) {
 int som_debug_corrupt_operands(som_handle* h, int32_t which) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
-    if (int rc = refresh_codebook_operands(h, true, h->exact)) return rc;   // (in the order the next BMU launch wants: no rebuild there)
+    // (every image, the float32 one in the order the next BMU launch wants: no rebuild there)
+    if (int rc = refresh_codebook_operands(h, h->exact ? operands::Request::ExactScreen : operands::Request::F32Units)) return rc;
     if ((which & 1) && h->Wst) {
         size_t bytes = (size_t)h->n_stages * h->stage_bytes;
         if (h->tiled && !h->wide) bytes = (size_t)h->n_ublocks * h->n_kchunks * h->tl_wtile;
@@ -2490,6 +2460,37 @@ int som_policy_replay(int32_t n_launches, const double* script, double* out) {
             const policy::Pause& ps = st.pause(k == 0);
             o[12 + 3 * k] = ps.cooldown; o[13 + 3 * k] = ps.idle; o[14 + 3 * k] = ps.pause;
         }
+    }
+    return 0;
+}
+
+// TEST HOOK (no device needed): a script of events through a fresh operands::State (csrc/codebook_operands.hpp), moved as the
+// host code moves the handle's.  Layouts: include/somhip_test.h.
+int som_operands_replay(const int32_t* config, int32_t n_events, const int32_t* script, int32_t* out) {
+    if (!config || n_events < 0 || !script || !out) return 1;
+    const operands::Config cfg{config[0] != 0, config[1] != 0, config[2] != 0, config[3] != 0, config[4] != 0, config[5] != 0};
+    if (!cfg.valid()) return 1;
+    operands::State st(cfg);
+    for (int32_t i = 0; i < n_events; ++i) {
+        const int32_t* in = script + (size_t)i * SOM_OPERANDS_REPLAY_IN;
+        int32_t* o = out + (size_t)i * SOM_OPERANDS_REPLAY_OUT;
+        if (in[1] < 0 || in[1] > 2) return 1;
+        const operands::Request rq = in[1] == 0 ? operands::Request::Search : in[1] == 1 ? operands::Request::F32Units : operands::Request::ExactScreen;
+        operands::Rebuilds r;
+        switch (in[0]) {
+        case 0: st.codebook_replaced(); break;
+        case 1: st.merged_plain(); break;
+        case 2: if (!cfg.half || cfg.exact) return 1; st.merged_half_fused(); break;
+        case 3: if (!cfg.resident) return 1; st.merged_exact_fused(in[2] != 0); break;
+        case 4: if (in[2] != 0 && !cfg.resident) return 1; r = st.decide(rq, in[2] != 0); st.commit(r); break;
+        case 5: r.flush = st.take_pending_image(&r.flush_cm); break;
+        case 6: if (cfg.exact) return 1; st.graph_replayed(rq); break;
+        case 7: r = st.decide_wsq(); st.commit(r); break;
+        default: return 1;
+        }
+        o[0] = r.wsq; o[1] = r.permute; o[2] = r.f32; o[3] = r.f32_patch; o[4] = r.half; o[5] = r.skip_norms; o[6] = r.deferred; o[7] = r.cm;
+        o[8] = r.flush; o[9] = r.flush_cm;
+        o[10] = st.f32_in_patch_order(); o[11] = st.image_pending(); o[12] = st.centroids_fresh(); o[13] = st.patch_copy_in_step();
     }
     return 0;
 }

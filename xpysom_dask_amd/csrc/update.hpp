@@ -47,11 +47,6 @@ constexpr int SEG_CHUNK_UP = 16;   // partial entries per wave, upper levels: at
                                    // latency chain), up to 64 when that lets ONE workgroup finish the list (seg_chunk_up)
 constexpr int SEG_MAX_WAVES = 16;  // waves per workgroup (fewer when 2 * waves * D1p floats would not fit in LDS)
 
-__global__ __launch_bounds__(256) void iota_kernel(int* __restrict__ v, long n) {
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) v[i] = (int)i;
-}
-
 // ---- stable LSD radix sort of (key, value) pairs, 8 bits a pass: the rows by BMU for the segment sum (maps too large for the
 // counting sort below), the rows by their last BMU's patch for the exact mode's resident order (exact_skip.hpp).  Hand-written
 // for these two jobs (keys of 10 .. 20 bits, values = row indices, 10^5 .. 10^7 items): per pass
