@@ -60,6 +60,17 @@ int som_debug_exact_select_stats(som_handle* h, int64_t* fused_passes, int64_t* 
  * timed, and all of them under SOM_EXACT_FUSE_PLAN=0 (tests/test_gpu_exact_plan_fused.py). */
 int som_debug_exact_plan_stats(som_handle* h, int64_t* fused_launches, int64_t* split_launches);
 
+/* precision EXACT up to 128 features, the plans of the screen passes so far by the form of their test: plans whose kernels took
+ * the row threshold P into the extra MFMA step and tested a sign (the default), and plans that compared every accumulator with P
+ * (SOM_EXACT_PLAN_FOLD=0) -- fused or split alike (tests/test_gpu_exact_plan_fold.py). */
+int som_debug_exact_plan_fold_stats(som_handle* h, int64_t* folded, int64_t* compared);
+
+/* The folded plan's split of a threshold (plan_fold_scale, plan_split_threshold, csrc/exact_skip.hpp) on caller-supplied numbers --
+ * the host side of the __host__ __device__ functions the plan kernels call, NO device needed (tests/test_plan_fold_cpu.py).
+ *   bf16: 0 = IEEE half operands, else bfloat16.  Per item i: the level's scale c from s_bmag[i] (= S'Bm'), then P[i] split:
+ *   out4[4 i ..] = {c, p1, p2, p3}, c (p1 + p2 + p3) >= P[i].  Returns non-zero for a NULL argument or a negative count. */
+int som_debug_plan_split(int32_t bf16, int64_t n, const float* P, const float* s_bmag, float* out4);
+
 /* precision EXACT: the plan of the last BMU launch as it ran (policy::LaunchPlan, csrc/exact_policy.hpp):
  *   out8 = [0] skip  [1] resort  [2] scout  [3] level 2  [4] estimate  [5] sample_tiles  [6] refine  [7] time_phases */
 int som_debug_exact_last_plan(som_handle* h, int32_t* out8);

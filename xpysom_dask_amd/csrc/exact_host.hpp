@@ -491,9 +491,12 @@ void exact_plan_lists(som_handle* h, long tiles, int n_cstages, const unsigned l
                                                                   n_items, n_items + 1, ex.item_len_pct);
 }
 
-// (the instances of exact_plan_fused_kernel that keep three workgroups a CU without scratch: <4, Bf16> does not -- 168 VGPRs and
-//  8 bytes of scratch a lane, bf16's conversions in the prologue -- and keeps the split pair)
-template <int KS32, class E> constexpr bool plan_fused_fits() { return !(KS32 == 4 && std::is_same<E, Bf16>::value); }
+// (the instances of exact_plan_fused_kernel that keep three workgroups a CU without scratch: <4, Bf16> comparing against P does
+//  not -- 168 VGPRs and 8 bytes of scratch a lane, bf16's conversions in the prologue -- and is not built: see plan_folds)
+template <int KS32, class E> constexpr bool plan_fused_fits() { return true; }
+// SOM_EXACT_PLAN_FOLD=0 (the plan kernels compare against P as before) is built for the F16 instances -- the operands of every
+// exact handle today --; a Bf16 instance always folds.
+template <class E> bool plan_folds(bool asked) { return asked || !std::is_same<E, F16>::value; }
 // one pass's plan on the sorted rows sr[s0, s0 + n): level 1 (+ the seeds, from lastpos_s), level 2, the tiles' item lists
 // -- in ONE launch (exact_plan_fused_kernel) where the pass is planned with level 2, from last BMUs alone (no scout), by one
 // workgroup per tile, and the policy does not time level 2 in this launch (time_l2: the split pair keeps cost.ev[3] .. ev[4]
@@ -522,8 +525,9 @@ int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
     const __bf16* Xs = sr.Xb_s + s0 * h->dp;
     // (the stage slots, the list of kept groups, level 2's and level 1's words, level 2's thresholds of the tile's rows: within the
     //  CU's 160 KB wherever level 2's own list fits -- policy::LaunchFacts::l2_fits_lds leaves 10 KB --, checked all the same)
-    const size_t lds = lds2 + (size_t)c0.n_cstages * 8 + (size_t)SK_TILE * sizeof(float);
+    const size_t lds = lds2 + (size_t)c0.n_cstages * 8 + (size_t)SK_TILE * 8;   // (8 bytes a row: level 2's threshold as MFMA operands, exact_plan_fused_kernel)
     const bool fits = h->ks32 != 4 || plan_fused_fits<4, E>();
+    const bool fold = plan_folds<E>(ex.plan_fold);
     if (ex.fuse_plan && ex.chain && l2 && lastpos2 == nullptr && pgrid.y == 1 && !time_l2 && lds <= 160 * 1024 && fits) {
         PlanListsOut lo;
         lo.n_groups = (int)cdiv(h->K, EX_GROUP);
@@ -533,43 +537,50 @@ int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
         lo.slots = ex.item_queue ? (ex.screen_slots > 0 ? ex.screen_slots : ex.item_slots) : 0;
         lo.items = ex.item_queue ? ex.items + 8 : nullptr;        // (as exact_plan_lists hands them to exact_lists_totals_kernel)
         lo.n_items = (int*)ex.items.p; lo.item_ctr = lo.n_items + 1; lo.len_pct = ex.item_len_pct;
+#define SOM_PLAN_FUSED_RUN(k, F) { \
+        { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_fused_kernel<k, E, F>, 64 * K16_NW, lds, &pc)) return rc; } \
+        exact_plan_fused_kernel<k, E, F><<<dim3((unsigned)tiles), block, lds, h->stream>>>(Xs, n, c0.Cst, c0.n_cstages, c0.cmax2, c1.Cst, c1.n_slots, \
+            c1.cmax2, sr.xsq_s + s0, sr.xerr_s + s0, xmax2, h->wmax2, h->wmax2 + 1, eb, sr.lastpos_s + s0, h->Wst, sr.seed_s + s0, force, lo); }
 #define SOM_PLAN_FUSED_CASE(k) case k: if constexpr (plan_fused_fits<k, E>()) { \
-        { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_fused_kernel<k, E>, 64 * K16_NW, lds, &pc)) return rc; } \
-        exact_plan_fused_kernel<k, E><<<dim3((unsigned)tiles), block, lds, h->stream>>>(Xs, n, c0.Cst, c0.n_cstages, c0.cmax2, c1.Cst, c1.n_slots, \
-            c1.cmax2, sr.xsq_s + s0, sr.xerr_s + s0, xmax2, h->wmax2, h->wmax2 + 1, eb, sr.lastpos_s + s0, h->Wst, sr.seed_s + s0, force, lo); \
+        if (fold) SOM_PLAN_FUSED_RUN(k, true) else if constexpr (std::is_same<E, F16>::value) SOM_PLAN_FUSED_RUN(k, false) \
         } break;
         switch (h->ks32) {
         SOM_PLAN_FUSED_CASE(1) SOM_PLAN_FUSED_CASE(2) SOM_PLAN_FUSED_CASE(3) SOM_PLAN_FUSED_CASE(4)
         default: return fail(h, "exact: block skipping supports input_len <= 128");
         }
 #undef SOM_PLAN_FUSED_CASE
+#undef SOM_PLAN_FUSED_RUN
         ++ex.plan_fused_launches;
+        ++(fold ? ex.plan_folded : ex.plan_compared);
         HIPCHK(h, hipGetLastError());
         return 0;
     }
     ++ex.plan_split_launches;
+    ++(fold ? ex.plan_folded : ex.plan_compared);
     // (level 1 stores every word; level 2 only those of the stages it walks: its words start from zero -- cleared by the level-1
     //  workgroups, each the words of its own stages; SOM_EXACT_CHAIN=0: by a fill)
     unsigned long long* const need2_clear = l2 && ex.chain ? ex.need2.p : nullptr;
     if (l2 && !ex.chain) HIPCHK(h, hipMemsetAsync(ex.need2, 0, (size_t)tiles * c1.n_cstages * sizeof(unsigned long long), h->stream));
-#define SOM_PLAN_CASE(k) case k: { \
-        { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_kernel<k, E, false>, 64 * K16_NW, lds1, &pc)) return rc; } \
-        exact_plan_kernel<k, E, false><<<pgrid, block, lds1, h->stream>>>(Xs, n, c0.Cst, c0.n_cstages, c0.rg, c0.n_slots, \
+#define SOM_PLAN_RUN(k, F) { \
+        { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_kernel<k, E, false, F>, 64 * K16_NW, lds1, &pc)) return rc; } \
+        exact_plan_kernel<k, E, false, F><<<pgrid, block, lds1, h->stream>>>(Xs, n, c0.Cst, c0.n_cstages, c0.rg, c0.n_slots, \
             sr.xsq_s + s0, sr.xerr_s + s0, sr.sU_s + s0, xmax2, c0.cmax2, h->wmax2, h->wmax2 + 1, eb, ex.need, sr.lastpos_s + s0, \
             h->Wst, sr.seed_s + s0, nullptr, 0, force, lastpos2, lastpos2 != nullptr ? &ctr->scout_wins : nullptr, need2_clear); \
         if (l2) { \
             if (time_l2) (void)hipEventRecord(ex.cost.ev[3], h->stream); \
-            { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_kernel<k, E, true>, 64 * K16_NW, lds2, &pc)) return rc; } \
-            exact_plan_kernel<k, E, true><<<dim3((unsigned)tiles, pgrid.y), block, lds2, h->stream>>>(Xs, n, c1.Cst, c1.n_cstages, c1.rg, c1.n_slots, \
+            { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_kernel<k, E, true, F>, 64 * K16_NW, lds2, &pc)) return rc; } \
+            exact_plan_kernel<k, E, true, F><<<dim3((unsigned)tiles, pgrid.y), block, lds2, h->stream>>>(Xs, n, c1.Cst, c1.n_cstages, c1.rg, c1.n_slots, \
                 sr.xsq_s + s0, sr.xerr_s + s0, sr.sU_s + s0, xmax2, c1.cmax2, h->wmax2, h->wmax2 + 1, eb, ex.need2, nullptr, \
                 nullptr, nullptr, ex.need, c0.n_cstages, force); \
             if (time_l2) (void)hipEventRecord(ex.cost.ev[4], h->stream); \
-        } } break;
+        } }
+#define SOM_PLAN_CASE(k) case k: if (fold) SOM_PLAN_RUN(k, true) else if constexpr (std::is_same<E, F16>::value) SOM_PLAN_RUN(k, false) break;
     switch (h->ks32) {
     SOM_PLAN_CASE(1) SOM_PLAN_CASE(2) SOM_PLAN_CASE(3) SOM_PLAN_CASE(4)
     default: return fail(h, "exact: block skipping supports input_len <= 128");
     }
 #undef SOM_PLAN_CASE
+#undef SOM_PLAN_RUN
     exact_plan_lists(h, tiles, c0.n_cstages, l2 ? ex.need2.p : nullptr);
     HIPCHK(h, hipGetLastError());
     return 0;

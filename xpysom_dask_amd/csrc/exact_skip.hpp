@@ -315,6 +315,83 @@ __device__ __forceinline__ float up_to_half(float v) {
     return f;
 }
 
+// ---- the plan's threshold P as three MFMA operands (SOM_EXACT_PLAN_FOLD) -----------------------------------------------------
+// The rows' side of the extra feature step carries P beside bx: three values p1, p2, p3 of the operand type and ONE power of two c
+// per launch and level on the centroids' side (-c in three slots), so that the step subtracts P~ = c (p1 + p2 + p3) from every
+// accumulator and the tile's test is the SIGN of what is left.  Each product -c p_i is exact (c a power of two), and
+//   P~ >= nextup(P) > P   in real arithmetic:  t = nextup(P) / c exactly, p1 = rn(t), p2 = rn(t - p1), p3 = up(t - p1 - p2)
+// (both differences are exact: a float32 less its rounding to fewer bits), a part that would be subnormal in the operand type is
+// left out of its rounding step and the LAST part rounds the whole remainder UP -- to the smallest normal value where that
+// remainder is positive and below it (an MFMA that flushes subnormal operands would read 0).  P~ <= P + |P| 2^-19 + c MINN.
+// nextup: an accumulator EQUAL to P reads "needed" in the test against P (!(acc > P)); acc - P~ is then negative.
+// P = +inf (the row needs everything) and a NaN: p1 = +inf; P = -inf (a row behind the pass): p1 = -inf; t beyond the operand
+// type's range: p1 = +inf above it (see plan_fold_scale: such a P is above every accumulator), the largest negative value below.
+struct PlanParts { float p1, p2, p3; };
+template <class EL> struct PlanPartFmt;
+template <> struct PlanPartFmt<F16> {                       // IEEE half: 11 significant bits, normal from 2^-14, c within its normal powers of two
+    static constexpr int M = 10, CMIN = -14, CMAX = 15;
+    static constexpr float MINN = 0x1p-14f, MAXV = 65504.0f;
+};
+template <> struct PlanPartFmt<Bf16> {                      // bfloat16: 8 significant bits, float32's exponents
+    static constexpr int M = 7, CMIN = -100, CMAX = 100;
+    static constexpr float MINN = 0x1p-126f, MAXV = 0x1.FEp127f;
+};
+// a float32 rounded to M + 1 significant bits: to nearest even, or UP (towards +inf); v normal in the narrower type or zero
+__host__ __device__ inline float plan_part_round(float v, int M, bool up) {
+    uint32_t b = __builtin_bit_cast(uint32_t, v);
+    const int sh = 23 - M;
+    const uint32_t low = (1u << sh) - 1u;
+    if (up) { if ((b >> 31) == 0u) b += low; }               // (a negative value is cut towards zero: up)
+    else b += (low >> 1) + ((b >> sh) & 1u);
+    b &= ~low;
+    return __builtin_bit_cast(float, b);
+}
+// c, once per launch and level, from the level's scales: the power of two with 65504 c >= 1.01 S'Bm' (< 2.02 S'Bm'; clamped to the
+// operand type's powers of two).  Every accumulator is at most S'Bm' (d'_c <= S'(2 B' + |c|^2 / 2), less positive terms), so a finite P
+// beyond 65504 c keeps every block whatever it is compared with: +inf says the same.  ANY power of two is safe (P~ >= P).
+template <class EL>
+__host__ __device__ inline float plan_fold_scale(float s_bmag) {
+    using F = PlanPartFmt<EL>;
+    const float m = s_bmag * (1.01f / 65504.0f);
+    if (!(m > 0.0f) || !(m < 3.0e38f)) return 1.0f;
+    const uint32_t b = __builtin_bit_cast(uint32_t, m);
+    int e = (int)(b >> 23) - 127 + ((b & 0x7FFFFFu) != 0u ? 1 : 0);
+    e = e > F::CMAX ? F::CMAX : e < F::CMIN ? F::CMIN : e;
+    return __builtin_bit_cast(float, (uint32_t)(e + 127) << 23);
+}
+template <class EL>
+__host__ __device__ inline PlanParts plan_split_threshold(float P, float c) {
+    using F = PlanPartFmt<EL>;
+    const float inf = __builtin_inff();
+    if (!(P == P) || P == inf) return PlanParts{inf, 0.0f, 0.0f};
+    if (P == -inf) return PlanParts{-inf, 0.0f, 0.0f};
+    {                                                        // one float32 step up
+        uint32_t b = __builtin_bit_cast(uint32_t, P);
+        if ((b << 1) == 0u) b = 1u; else b = (b >> 31) == 0u ? b + 1u : b - 1u;
+        P = __builtin_bit_cast(float, b);
+        if (P == inf) return PlanParts{inf, 0.0f, 0.0f};
+    }
+    const float rc = __builtin_bit_cast(float, (uint32_t)(254 - (int)(__builtin_bit_cast(uint32_t, c) >> 23)) << 23);   // 1 / c
+    const float t = P * rc;                                  // (exact unless it leaves float32's normal range: the two lines below)
+    if (P > 0.0f && !(t >= F::MINN)) return PlanParts{0.0f, 0.0f, F::MINN};
+    if (P <= 0.0f && !(t <= -F::MINN)) return PlanParts{0.0f, 0.0f, 0.0f};
+    if (!(t < 3.0e38f)) return PlanParts{inf, 0.0f, 0.0f};
+    PlanParts o;
+    o.p1 = plan_part_round(t, F::M, false);
+    if (o.p1 > F::MAXV) return PlanParts{inf, 0.0f, 0.0f};
+    if (o.p1 < -F::MAXV) return PlanParts{-F::MAXV, 0.0f, 0.0f};
+    const float r1 = t - o.p1;
+    o.p2 = plan_part_round(r1, F::M, false);
+    if (__builtin_fabsf(o.p2) < F::MINN) o.p2 = 0.0f;
+    const float r2 = r1 - o.p2;
+    if (r2 > 0.0f) o.p3 = r2 < F::MINN ? F::MINN : plan_part_round(r2, F::M, true);
+    else {
+        o.p3 = plan_part_round(r2, F::M, true);
+        if (__builtin_fabsf(o.p3) < F::MINN) o.p3 = 0.0f;
+    }
+    return o;
+}
+
 // OR of a value over the sixteen lanes of its DPP row (a quad of the MFMA layout: lanes 16 q .. 16 q + 15), in every lane of the
 // row: four rotations inside the row, no LDS, no scalar unit
 __device__ __forceinline__ uint32_t row16_or(uint32_t v) {
@@ -493,7 +570,10 @@ __device__ __forceinline__ float plan_row_seed(const typename V8<typename EL::T>
 // PROLOGUE, one level's part for one row: the right-hand side P of the level's test and the rows' side bx of the extra feature
 // step, from |x|^2, the row's rounding error, sqrt(U) and the level's scales (sc: ex_scales on the level's centroid image).
 // in_pass == false (a row behind the pass) needs nothing: P = -inf; a row whose numbers are not finite needs everything: P = +inf.
-template <int KS32>
+// FOLD: P enters the accumulator in the extra step (plan_extra_step, plan_run_tile): that step's sum then reaches 2 S'Bm' + |P~|,
+// |P~| <= 65504 c < 2.02 S'Bm' for every P that can decide a test (plan_fold_scale), 2.01 times what the charge below assumes for
+// ONE of the KS32 + 1 MFMAs (24 ulps of S'Bm' each): + 24.3 ulps, rounded up to + 28.
+template <int KS32, bool FOLD>
 __device__ __forceinline__ void plan_row_threshold(const ExactBound& eb, const ExactScales& sc, bool in_pass, float q, float xe, float su,
                                                    float& P, float& bx) {
     const float S = sc.sx * sc.sw;
@@ -511,35 +591,59 @@ __device__ __forceinline__ void plan_row_threshold(const ExactBound& eb, const E
     // P = A + hS sU^2 (+ the extra feature step's and the larger accumulators' share of the MFMA rounding: the cross term
     // can double the accumulator's magnitude, and there is one more MFMA in the chain: 4 (KS32 + 1) x 6 ulps of S' Bm')
     bx = up_to_half(sc.sx * sU * (1.0f + 1.0f / 1024.0f));
-    P = A + 0.5f * S * (1.0f + 1.0f / 1024.0f) * sU * sU * (1.0f + 0x1p-20f) + (float)(24 * (KS32 + 1)) * 0x1p-23f * S * sc.bmag;
+    P = A + 0.5f * S * (1.0f + 1.0f / 1024.0f) * sU * sU * (1.0f + 0x1p-20f) + (float)(24 * (KS32 + 1) + (FOLD ? 28 : 0)) * 0x1p-23f * S * sc.bmag;
     if (!(bx < 3.0e38f) || !(P == P)) P = __builtin_inff();                                  // (sU beyond the half range: need everything)
     if (A == -__builtin_inff()) P = -__builtin_inff();                                       // (rows behind the pass)
 }
-// the rows' operand of the extra feature step: slot 0 of the first quad = bx, else 0
-template <class EL>
-__device__ __forceinline__ typename V8<typename EL::T>::t plan_extra_step(float bx) {
+// the rows' operand of the extra feature step: slot 0 of the first quad = bx, FOLD: its slots 1..3 = the parts of P under the
+// level's scale c (plan_split_threshold), else 0
+template <class EL, bool FOLD>
+__device__ __forceinline__ typename V8<typename EL::T>::t plan_extra_step(float bx, float P, float c) {
     using E = typename EL::T;
     typename V8<E>::t v;
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) v[jj] = (E)0.0f;
-    if (((threadIdx.x & 63) >> 4) == 0 && bx < 3.0e38f) v[0] = (E)bx;
+    if (((threadIdx.x & 63) >> 4) == 0) {
+        if (bx < 3.0e38f) v[0] = (E)bx;
+        if constexpr (FOLD) {
+            const PlanParts pp = plan_split_threshold<EL>(P, c);
+            v[1] = (E)pp.p1; v[2] = (E)pp.p2; v[3] = (E)pp.p3;      // (exact: the parts are values of the operand type)
+        }
+    }
     return v;
 }
+// what the walks hand every tile beside its operands: the thresholds of the wave's four sample blocks (FOLD: unused, the
+// registers are free) and -c of the level (FOLD: the centroids' side of slots 1..3)
+template <class EL>
+struct PlanTest {
+    float P[K16_SB];
+    typename EL::T negc;
+};
 
 // MFMAs + test of one 16-centroid tile (either level; its operands in (a, wv, rneg): the KS32 fragments, the initial
 // accumulators, the centroids' side of the extra step, slot 0 = -up_to_half(sw r)): lane (quad, col) sets bit 4 j + r of
 // lane_bits where one of its rows needs the centroid behind accumulator register r of tile j.
-template <int KS32, class EL>
+// FOLD: the extra step also subtracts P~ >= P (the rows' slots 1..3 times -c), and a row needs the centroid iff what is left is
+// not above zero: negative, or a NaN (a NaN centroid, a row that needs everything and an empty slot: +inf - inf).  Read on the
+// accumulators' BIT PATTERNS, as unsigned integers: exactly the patterns above +inf's -- every value with the sign bit set and
+// every positive NaN -- say "needed", so one unsigned maximum over the four sample blocks (v_max3_u32 + v_max_u32) and one
+// compare serve a register, with no NaN rule of a floating-point minimum to rely on (and none of the canonicalising
+// instructions the compiler puts in front of one).  +0 (acc == P~ > P) is not needed; -0 would read "needed": the safe side.
+template <int KS32, class EL, bool FOLD>
 __device__ __forceinline__ void plan_run_tile(int j, const typename V8<typename EL::T>::t (&a)[KS32], const f32x4& wv, float rneg,
                                               const typename V8<typename EL::T>::t (&xf)[K16_SB][KS32],
-                                              const typename V8<typename EL::T>::t (&xe)[K16_SB], const float (&P)[K16_SB],
+                                              const typename V8<typename EL::T>::t (&xe)[K16_SB], const PlanTest<EL>& pt,
                                               uint32_t& lane_bits) {
     using E = typename EL::T;
     using bf16x8 = typename V8<E>::t;
+    const float (&P)[K16_SB] = pt.P;
     bf16x8 ae;
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) ae[jj] = (E)0.0f;
-    if (((threadIdx.x & 63) >> 4) == 0) ae[0] = (E)rneg;
+    if (((threadIdx.x & 63) >> 4) == 0) {
+        ae[0] = (E)rneg;
+        if constexpr (FOLD) { ae[1] = pt.negc; ae[2] = pt.negc; ae[3] = pt.negc; }
+    }
     f32x4 acc[K16_SB];
 #pragma unroll
     for (int sb = 0; sb < K16_SB; ++sb) acc[sb] = wv;
@@ -553,10 +657,18 @@ __device__ __forceinline__ void plan_run_tile(int j, const typename V8<typename 
     //  kept the scalar unit busier than the matrix pipe)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        bool nd = false;
+        if constexpr (FOLD) {
+            // (__float_as_uint takes the element BY VALUE: a bit cast of the vector element expression itself read element 0)
+            uint32_t m = __float_as_uint(acc[0][r]);
 #pragma unroll
-        for (int sb = 0; sb < K16_SB; ++sb) nd = nd || !(acc[sb][r] > P[sb]);
-        lane_bits |= nd ? (1u << (4 * j + r)) : 0u;
+            for (int sb = 1; sb < K16_SB; ++sb) { const uint32_t u = __float_as_uint(acc[sb][r]); m = u > m ? u : m; }
+            lane_bits |= m > 0x7F800000u ? (1u << (4 * j + r)) : 0u;
+        } else {
+            bool nd = false;
+#pragma unroll
+            for (int sb = 0; sb < K16_SB; ++sb) nd = nd || !(acc[sb][r] > P[sb]);
+            lane_bits |= nd ? (1u << (4 * j + r)) : 0u;
+        }
     }
 }
 // a tile's operands out of its stage slot in LDS (st; wq: the slot's tail)
@@ -574,10 +686,10 @@ __device__ __forceinline__ void plan_load_tile(const char* st, int t, typename V
 // LEVEL 1's WALK over the centroid stages [s_begin, s_end) of Cst, double-buffered in the two stage slots at smem: word
 // nl[s - s_begin] (LDS, zero on entry -- the first barrier of the walk orders the clearing) collects the tile's need bits of stage s
 // (bit i <-> centroid slot 64 s + i).  The caller's barrier behind the walk completes the words.
-template <int KS32, class EL>
+template <int KS32, class EL, bool FOLD>
 __device__ __forceinline__ void plan_walk_level1(const char* __restrict__ Cst, int s_begin, int s_end, char* smem, unsigned long long* nl,
                                                  const typename V8<typename EL::T>::t (&xf)[K16_SB][KS32],
-                                                 const typename V8<typename EL::T>::t (&xe)[K16_SB], const float (&P)[K16_SB]) {
+                                                 const typename V8<typename EL::T>::t (&xe)[K16_SB], const PlanTest<EL>& P) {
     using bf16x8 = typename V8<typename EL::T>::t;
     constexpr int STAGE = k16_stage_bytes(KS32);
     constexpr int PIECES = K16_T * KS32 + 1;
@@ -602,12 +714,12 @@ __device__ __forceinline__ void plan_walk_level1(const char* __restrict__ Cst, i
         float rnA, rnB;
         plan_load_tile<KS32, EL>(st, 0, aA, wvA, rnA);
         plan_load_tile<KS32, EL>(st, 1, aB, wvB, rnB);
-        plan_run_tile<KS32, EL>(0, aA, wvA, rnA, xf, xe, P, lane_bits);
+        plan_run_tile<KS32, EL, FOLD>(0, aA, wvA, rnA, xf, xe, P, lane_bits);
         plan_load_tile<KS32, EL>(st, 2, aA, wvA, rnA);
-        plan_run_tile<KS32, EL>(1, aB, wvB, rnB, xf, xe, P, lane_bits);
+        plan_run_tile<KS32, EL, FOLD>(1, aB, wvB, rnB, xf, xe, P, lane_bits);
         plan_load_tile<KS32, EL>(st, 3, aB, wvB, rnB);
-        plan_run_tile<KS32, EL>(2, aA, wvA, rnA, xf, xe, P, lane_bits);
-        plan_run_tile<KS32, EL>(3, aB, wvB, rnB, xf, xe, P, lane_bits);
+        plan_run_tile<KS32, EL, FOLD>(2, aA, wvA, rnA, xf, xe, P, lane_bits);
+        plan_run_tile<KS32, EL, FOLD>(3, aB, wvB, rnB, xf, xe, P, lane_bits);
         // OR over the sixteen rows of every quad; the quad's first lane spreads its four nibbles (one per tile) to their places
         const uint32_t any_row = row16_or(lane_bits);
         if (col == 0 && any_row != 0u) {
@@ -643,10 +755,10 @@ __device__ __forceinline__ void plan_level2_list(const unsigned long long* need1
 // into the slot's tail (laid out like a stage's) before the next barrier.
 // nl (LDS, zero on entry, ordered by a barrier of the caller's): word g >> 4 collects a nibble per group (bit 4 (g & 15) + sub <->
 // sub-block `sub` of group g), filed by LDS atomics.  The caller's barrier behind the walk completes the words.
-template <int KS32, class EL>
+template <int KS32, class EL, bool FOLD>
 __device__ __forceinline__ void plan_walk_level2(const char* __restrict__ Cst, const int* act, int b0, int e0, char* smem,
                                                  unsigned long long* nl, const typename V8<typename EL::T>::t (&xf)[K16_SB][KS32],
-                                                 const typename V8<typename EL::T>::t (&xe)[K16_SB], const float (&P)[K16_SB]) {
+                                                 const typename V8<typename EL::T>::t (&xe)[K16_SB], const PlanTest<EL>& P) {
     using bf16x8 = typename V8<typename EL::T>::t;
     constexpr int STAGE = k16_stage_bytes(KS32);
     static_assert(K16_NW == 4, "a wave per tile fills the slot's tail");
@@ -697,14 +809,14 @@ __device__ __forceinline__ void plan_walk_level2(const char* __restrict__ Cst, c
         const bool h1 = c0 + 4 < e0, h2 = c0 + 8 < e0, h3 = c0 + 12 < e0;
         plan_load_tile<KS32, EL>(st, 0, aA, wvA, rnA);
         if (h1) plan_load_tile<KS32, EL>(st, 1, aB, wvB, rnB);
-        plan_run_tile<KS32, EL>(0, aA, wvA, rnA, xf, xe, P, lane_bits);
+        plan_run_tile<KS32, EL, FOLD>(0, aA, wvA, rnA, xf, xe, P, lane_bits);
         if (h1) {
             if (h2) plan_load_tile<KS32, EL>(st, 2, aA, wvA, rnA);
-            plan_run_tile<KS32, EL>(1, aB, wvB, rnB, xf, xe, P, lane_bits);
+            plan_run_tile<KS32, EL, FOLD>(1, aB, wvB, rnB, xf, xe, P, lane_bits);
             if (h2) {
                 if (h3) plan_load_tile<KS32, EL>(st, 3, aB, wvB, rnB);
-                plan_run_tile<KS32, EL>(2, aA, wvA, rnA, xf, xe, P, lane_bits);
-                if (h3) plan_run_tile<KS32, EL>(3, aB, wvB, rnB, xf, xe, P, lane_bits);
+                plan_run_tile<KS32, EL, FOLD>(2, aA, wvA, rnA, xf, xe, P, lane_bits);
+                if (h3) plan_run_tile<KS32, EL, FOLD>(3, aB, wvB, rnB, xf, xe, P, lane_bits);
             }
         }
         // the chunk's sixteen groups: OR over the sixteen rows of every quad (lanes of one DPP row), then the quad's first lane
@@ -736,7 +848,9 @@ __device__ __forceinline__ void plan_walk_level2(const char* __restrict__ Cst, c
 //   LEVEL2 == true: the centroids of the 16-unit sub-blocks, slot order as exact_centroid_kernel's (a 16-slot MFMA tile =
 //     the sub-blocks of four consecutive groups); only the tiles whose groups level 1 kept (need1) are loaded and run.
 // eb / scales: the centroid image's (cmax2 = {max |c|^2, max rounding error^2}); wmax2 / werr2: the codebook's.
-template <int KS32, class EL, bool LEVEL2>
+// FOLD (SOM_EXACT_PLAN_FOLD, default): the threshold rides in the extra MFMA step and the test is a sign (plan_run_tile); false:
+// the compare against P of before, for A/B runs on the same data.
+template <int KS32, class EL, bool LEVEL2, bool FOLD>
 __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel(const __bf16* __restrict__ Xb, long N,
                                                                     const char* __restrict__ Cst, int n_cstages,
                                                                     const float* __restrict__ rg, int n_slots,
@@ -763,10 +877,12 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
     const long wave_s0 = (long)blockIdx.x * K16_WG_SAMPLES + wave * (16 * K16_SB);
 
     bf16x8 xf[K16_SB][KS32];
-    bf16x8 xe[K16_SB];                                       // the extra feature step: slot 0 = up_to_half(sx sU (1 + 2^-10)), else 0
-    float P[K16_SB];
+    bf16x8 xe[K16_SB];                                       // the extra feature step: slot 0 = up_to_half(sx sU (1 + 2^-10)), FOLD: 1..3 = P's parts, else 0
+    PlanTest<EL> pt;
     const ExactScales sc = ex_scales(xmax2, cmax2, cmax2 + 1);
     const ExactScales sw = ex_scales(xmax2, wmax2, werr2);
+    const float cf = plan_fold_scale<EL>(sc.sx * sc.sw * sc.bmag);
+    pt.negc = (typename EL::T)(-cf);
 #pragma unroll
     for (int sb = 0; sb < K16_SB; ++sb) {
         const long row = wave_s0 + sb * 16 + col;
@@ -784,8 +900,8 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
             }
         }
         float bx;
-        plan_row_threshold<KS32>(eb, sc, row < N, q, xer, su, P[sb], bx);
-        xe[sb] = plan_extra_step<EL>(bx);
+        plan_row_threshold<KS32, FOLD>(eb, sc, row < N, q, xer, su, pt.P[sb], bx);
+        xe[sb] = plan_extra_step<EL, FOLD>(bx, pt.P[sb], cf);
     }
 
     // the words this workgroup produces (one per stage), gathered in LDS with LDS atomics (a global atomic per wave and stage
@@ -800,7 +916,7 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
         const int c_all = (n_act + 15) / 16;
         const int b0 = 16 * (int)((long)c_all * blockIdx.y / gridDim.y);
         const int e0 = min(n_act, 16 * (int)((long)c_all * (blockIdx.y + 1) / gridDim.y));
-        plan_walk_level2<KS32, EL>(Cst, act, b0, e0, smem, nl, xf, xe, P);
+        plan_walk_level2<KS32, EL, FOLD>(Cst, act, b0, e0, smem, nl, xf, xe, pt);
         __syncthreads();
         // (two parts of a tile's walk may share a stage: OR into words that start from zero -- cleared by the level-1 workgroups, or by the host's fill)
         for (int i = tid; i < n_cstages; i += 64 * K16_NW)
@@ -811,7 +927,7 @@ __global__ __launch_bounds__(64 * K16_NW, LEVEL2 ? 3 : 2) void exact_plan_kernel
     //  one workgroup per CU walking all the stages alone)
     const int s_begin = (int)((long)n_cstages * blockIdx.y / gridDim.y);
     const int s_end = (int)((long)n_cstages * (blockIdx.y + 1) / gridDim.y);
-    plan_walk_level1<KS32, EL>(Cst, s_begin, s_end, smem, nl, xf, xe, P);
+    plan_walk_level1<KS32, EL, FOLD>(Cst, s_begin, s_end, smem, nl, xf, xe, pt);
     __syncthreads();
     for (int i = s_begin + tid; i < s_end; i += 64 * K16_NW) need[(long)blockIdx.x * n_cstages + i] = nl[i - s_begin];
     // (level 2 ORs into words that start from zero: the four level-2 words of every stage this workgroup walked are cleared
@@ -1019,7 +1135,9 @@ __global__ __launch_bounds__(64 * LISTS_WG_TILES) void exact_lists_totals_kernel
 // the prologue, level 2's waits in LDS (p2s) while level 1 walks.  The extra step's row operand bx is sx sqrt(U) rounded up in both
 // levels unless the level's A is not finite, where it is up_to_half(0) and P = +inf: every test of that level then says "needed"
 // whatever the accumulator holds, so one operand serves both levels -- level 1's, or level 2's where level 1's P is +inf.
-template <int KS32, class EL>
+// FOLD: a level's threshold is part of the rows' extra-step operand, so level 2's parts (under level 2's scale c) wait in LDS
+// instead of its P, four operand values a row, and replace level 1's in xe between the walks.
+template <int KS32, class EL, bool FOLD>
 __global__ __launch_bounds__(64 * K16_NW, 3) void exact_plan_fused_kernel(const __bf16* __restrict__ Xb, long N,
                                                                     const char* __restrict__ Cst1, int n_cstages1, const float* __restrict__ cmax2_1,
                                                                     const char* __restrict__ Cst2, int n_slots2, const float* __restrict__ cmax2_2,
@@ -1028,7 +1146,8 @@ __global__ __launch_bounds__(64 * K16_NW, 3) void exact_plan_fused_kernel(const 
                                                                     const float* __restrict__ wmax2, const float* __restrict__ werr2,
                                                                     ExactBound eb, const int* __restrict__ lastpos, const char* __restrict__ Wst,
                                                                     float* __restrict__ seed_s, int force_all, PlanListsOut lo) {
-    using bf16x8 = typename V8<typename EL::T>::t;
+    using E = typename EL::T;
+    using bf16x8 = typename V8<E>::t;
     constexpr int DP = 32 * KS32;
     constexpr int STAGE = k16_stage_bytes(KS32);
     constexpr int NT = 64 * K16_NW;
@@ -1047,15 +1166,21 @@ __global__ __launch_bounds__(64 * K16_NW, 3) void exact_plan_fused_kernel(const 
     int* act = (int*)(smem + 2 * STAGE);
     unsigned long long* nl2 = (unsigned long long*)(smem + 2 * STAGE + (size_t)n_cstages1 * 64 * sizeof(int));
     unsigned long long* nl1 = nl2 + n_cstages2;
-    float* p2s = (float*)(nl1 + n_cstages1);
+    float* p2s = (float*)(nl1 + n_cstages1);               // (8 bytes a row: FOLD: (-, p1, p2, p3) of the operand type, else P as a float)
+    E* p2e = (E*)p2s;
 
     bf16x8 xf[K16_SB][KS32];
     bf16x8 xe[K16_SB];
-    float P[K16_SB];
+    PlanTest<EL> pt;
+    float (&P)[K16_SB] = pt.P;
+    E negc2;
     {
         const ExactScales sc1 = ex_scales(xmax2, cmax2_1, cmax2_1 + 1);
         const ExactScales sc2 = ex_scales(xmax2, cmax2_2, cmax2_2 + 1);
         const ExactScales sw = ex_scales(xmax2, wmax2, werr2);
+        const float cf1 = plan_fold_scale<EL>(sc1.sx * sc1.sw * sc1.bmag), cf2 = plan_fold_scale<EL>(sc2.sx * sc2.sw * sc2.bmag);
+        pt.negc = (E)(-cf1);
+        negc2 = (E)(-cf2);
 #pragma unroll
         for (int sb = 0; sb < K16_SB; ++sb) {
             const long row = wave_s0 + sb * 16 + col;
@@ -1067,23 +1192,35 @@ __global__ __launch_bounds__(64 * K16_NW, 3) void exact_plan_fused_kernel(const 
                 su = plan_row_seed<KS32, EL>(xf[sb], row, q, xer, eb, sw, Wst, lastpos, nullptr, nullptr, seed_s, force_all);
             }
             float bx1, bx2, P2;
-            plan_row_threshold<KS32>(eb, sc1, row < N, q, xer, su, P[sb], bx1);
-            plan_row_threshold<KS32>(eb, sc2, row < N, q, xer, su, P2, bx2);
-            xe[sb] = plan_extra_step<EL>(P[sb] == __builtin_inff() ? bx2 : bx1);
-            if (quad == 0) p2s[wave * (16 * K16_SB) + sb * 16 + col] = P2;
+            plan_row_threshold<KS32, FOLD>(eb, sc1, row < N, q, xer, su, P[sb], bx1);
+            plan_row_threshold<KS32, FOLD>(eb, sc2, row < N, q, xer, su, P2, bx2);
+            xe[sb] = plan_extra_step<EL, FOLD>(P[sb] == __builtin_inff() ? bx2 : bx1, P[sb], cf1);
+            if (quad == 0) {
+                const int at = wave * (16 * K16_SB) + sb * 16 + col;
+                if constexpr (FOLD) {
+                    const PlanParts pp = plan_split_threshold<EL>(P2, cf2);
+                    p2e[4 * at + 1] = (E)pp.p1; p2e[4 * at + 2] = (E)pp.p2; p2e[4 * at + 3] = (E)pp.p3;
+                } else p2s[2 * at] = P2;
+            }
         }
     }
     for (int i = tid; i < n_cstages1 + n_cstages2; i += NT) nl2[i] = 0ull;   // (nl2, then nl1: one run of words)
 
     // A
-    plan_walk_level1<KS32, EL>(Cst1, 0, n_cstages1, smem, nl1, xf, xe, P);
+    plan_walk_level1<KS32, EL, FOLD>(Cst1, 0, n_cstages1, smem, nl1, xf, xe, pt);
     __syncthreads();
     // B
     if (wave == 0) plan_level2_list(nl1, n_cstages1, n_slots2, act, &act_n);
 #pragma unroll
-    for (int sb = 0; sb < K16_SB; ++sb) P[sb] = p2s[wave * (16 * K16_SB) + sb * 16 + col];
+    for (int sb = 0; sb < K16_SB; ++sb) {
+        const int at = wave * (16 * K16_SB) + sb * 16 + col;
+        if constexpr (FOLD) {
+            if (quad == 0) { xe[sb][1] = p2e[4 * at + 1]; xe[sb][2] = p2e[4 * at + 2]; xe[sb][3] = p2e[4 * at + 3]; }
+        } else P[sb] = p2s[2 * at];
+    }
+    pt.negc = negc2;
     __syncthreads();
-    plan_walk_level2<KS32, EL>(Cst2, act, 0, act_n, smem, nl2, xf, xe, P);
+    plan_walk_level2<KS32, EL, FOLD>(Cst2, act, 0, act_n, smem, nl2, xf, xe, pt);
     __syncthreads();
     // C
     if (wave == 0)

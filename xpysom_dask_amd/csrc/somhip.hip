@@ -199,6 +199,8 @@ struct som_handle {
         bool fuse_plan = true;            // SOM_EXACT_FUSE_PLAN=0: always level 1, level 2 and the lists as launches of their own (A/B)
         int hook_plan_parts = 0;          // SOM_EXACT_PLAN_PARTS=n: at most n workgroups per tile in the plan's grids (0: four)
         int64_t plan_fused_launches = 0, plan_split_launches = 0;   // som_debug_exact_plan_stats
+        bool plan_fold = true;            // SOM_EXACT_PLAN_FOLD=0: the plan kernels compare against P as before instead of folding it into the extra MFMA step (A/B)
+        int64_t plan_folded = 0, plan_compared = 0;                 // som_debug_exact_plan_fold_stats
         DevBuf<int2> items;               // the listed screen's work queue: [0] = (items, counter), from [8] on (tile, part | parts << 16)
         int item_slots = 0;               // ... sized for this many resident workgroups
         int screen_slots = 0;             // ... the listed screen's last grid (what the next plan cuts its lists for)
@@ -1498,6 +1500,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         if (const char* e = dev_env("SOM_EXACT_CHAIN")) h->ex.chain = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_EXACT_FUSE_SELECT")) h->ex.fuse_select = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_EXACT_FUSE_PLAN")) h->ex.fuse_plan = std::atoi(e) != 0;
+        if (const char* e = dev_env("SOM_EXACT_PLAN_FOLD")) h->ex.plan_fold = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_EXACT_PLAN_PARTS")) h->ex.hook_plan_parts = std::max(0, std::atoi(e));
         if (const char* e = dev_env("SOM_COUNTING_SORT")) h->counting_sort = std::atoi(e) != 0;
         // a 128-row block of a table already spans most of a map side up to 256: nothing to skip there
@@ -2533,6 +2536,23 @@ int som_debug_exact_plan_stats(som_handle* h, int64_t* fused_launches, int64_t* 
     if (!h || !fused_launches || !split_launches) return fail(h, "som_debug_exact_plan_stats: NULL argument");
     *fused_launches = h->ex.plan_fused_launches;
     *split_launches = h->ex.plan_split_launches;
+    return 0;
+}
+
+int som_debug_exact_plan_fold_stats(som_handle* h, int64_t* folded, int64_t* compared) {
+    if (!h || !folded || !compared) return fail(h, "som_debug_exact_plan_fold_stats: NULL argument");
+    *folded = h->ex.plan_folded;
+    *compared = h->ex.plan_compared;
+    return 0;
+}
+
+int som_debug_plan_split(int32_t bf16, int64_t n, const float* P, const float* s_bmag, float* out4) {
+    if (n < 0 || (n > 0 && (!P || !s_bmag || !out4))) return 1;
+    for (int64_t i = 0; i < n; ++i) {
+        const float c = bf16 ? plan_fold_scale<Bf16>(s_bmag[i]) : plan_fold_scale<F16>(s_bmag[i]);
+        const PlanParts pp = bf16 ? plan_split_threshold<Bf16>(P[i], c) : plan_split_threshold<F16>(P[i], c);
+        out4[4 * i] = c; out4[4 * i + 1] = pp.p1; out4[4 * i + 2] = pp.p2; out4[4 * i + 3] = pp.p3;
+    }
     return 0;
 }
 

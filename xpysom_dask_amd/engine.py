@@ -361,6 +361,13 @@ class HipEngine:
         self._check(self._lib.som_debug_exact_plan_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def exact_plan_fold_stats(self):
+        """precision 'exact': (plans whose kernels folded the row threshold into the extra MFMA step, plans that compared against
+        it -- SOM_EXACT_PLAN_FOLD=0) so far."""
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self._lib.som_debug_exact_plan_fold_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def exact_last_plan(self):
         """precision 'exact': the plan of the last BMU launch as it ran, a dict of the policy's eight decisions."""
         out = (C.c_int32 * 8)()
