@@ -71,6 +71,25 @@ int som_debug_exact_plan_fold_stats(som_handle* h, int64_t* folded, int64_t* com
  *   out4[4 i ..] = {c, p1, p2, p3}, c (p1 + p2 + p3) >= P[i].  Returns non-zero for a NULL argument or a negative count. */
 int som_debug_plan_split(int32_t bf16, int64_t n, const float* P, const float* s_bmag, float* out4);
 
+/* The transform's band arithmetic (band_entry_with, band_tile_range, band_union, csrc/update.hpp) on a caller-supplied table --
+ * the host side of the __host__ __device__ functions the kernels call, NO device needed (tests/test_transform_bands_cpu.py).
+ *   H [rows][nseg * segw] float32, row-major; wg_rows: 64 or 128, the rows of H a workgroup of the GEMM owns.
+ *   tiles_out [ceil(rows / 32)][nseg][2] = {tlo, thi}: the columns, in segment coordinates, in which a wave issues the 32-row
+ *     tile's MFMA steps (rounded outwards to the skipping granularity; {0, 0}: none).
+ *   wg_out [ceil(rows / wg_rows)][3] = {lo, hi, chunks}: the workgroup stages columns [lo, lo + 32 chunks) of every segment, those
+ *     from hi on as zeros.
+ * Returns non-zero for a NULL or non-positive argument. */
+int som_debug_band_walk(const float* H, int32_t rows, int32_t nseg, int32_t segw, int32_t wg_rows, int32_t* tiles_out,
+                        int32_t* wg_out);
+
+/* read-only: the neighbourhood tables of the last build and the band ranges recorded with them, as they stand on the device
+ * (csrc/update.hpp, "ranges").  info4 = {the bands are on, nt = segments, range entries per buffer, the buffer the last build
+ * filled}; entries_out [entries][2] = {segw - first nonzero column, last nonzero column + 1} per 32-row tile and segment -- stage 1
+ * entry t * ceil(Y / 32) + tile, then stage 2 entry nt * ceil(Y / 32) + tile * nt + t; P1_out [nt][Y][Y], P2_out [X][nt * X].  Each
+ * array may be NULL.  Without bands the entries are whatever the buffer holds (zeros).  tests/test_gpu_transform_bands.py compares
+ * the entries with the tables' own nonzeros. */
+int som_debug_band_tables(som_handle* h, int32_t* info4, int32_t* entries_out, float* P1_out, float* P2_out);
+
 /* precision EXACT: the plan of the last BMU launch as it ran (policy::LaunchPlan, csrc/exact_policy.hpp):
  *   out8 = [0] skip  [1] resort  [2] scout  [3] level 2  [4] estimate  [5] sample_tiles  [6] refine  [7] time_phases */
 int som_debug_exact_last_plan(som_handle* h, int32_t* out8);

@@ -84,6 +84,8 @@ SIGNATURES = {
     "som_debug_exact_plan_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_debug_exact_plan_fold_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_debug_plan_split": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "som_debug_band_tables": (C.c_int, [_H, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "som_debug_band_walk": (C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, _I]),
     "som_debug_exact_last_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "som_policy_eval": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "som_policy_replay": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

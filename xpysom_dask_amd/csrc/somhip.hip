@@ -307,8 +307,10 @@ struct som_handle {
     long gexec_n = -1;
     int graph_warm = 0;
     DevBuf<NeighParams> np_dev;   // read by the captured neigh_tables_kernel
-    DevBuf<int2> bands;      // nonzero column ranges of the neighbourhood tables per 128-row block (update.hpp)
+    DevBuf<int2> bands;      // nonzero column ranges of the neighbourhood tables per 32-row tile: two buffers (update.hpp, "ranges")
     bool use_bands = true;
+    int band_sel = 0;        // the buffer the last build of the tables filled; the next build fills the other one
+    int lm_rows = 0;         // SOM_LM_ROWS: rows of H per leftmul workgroup, 64 or 128 (0: launch_leftmul's own choice)
 
     // canary (som_set_verify / SOM_VERIFY=n): n strided rows of every BMU launch re-scored by the float32 kernel
     int verify_rows = 0;
@@ -1148,32 +1150,35 @@ int run_update(som_handle* h, double sigma, double eta, int neigh_f64) {
 }
 
 // [num|den] = sum_t (Px_t (x) Py_t) [S|c]
-// the factor tables of this epoch's neighbourhood (+ their nonzero bands)
+// the factor tables of this epoch's neighbourhood, and (in the same launch) their nonzero bands: the kernel fills one
+// of the two range buffers and zeroes the other, and the buffers change roles from build to build.  A captured launch
+// reads the role from np_dev, where som_epoch_accumulate puts the next one before every replay.
 int build_tables(som_handle* h, double sigma, double eta, int neigh_f64, hipStream_t st) {
-    const NeighParams p = make_neigh_params(h, sigma, eta, neigh_f64);
-    long ntab = (long)h->nt * h->Y * h->Y + (long)h->X * h->nt * h->X;
-    neigh_tables_kernel<<<dim3((unsigned)cdiv(ntab, 256)), dim3(256), 0, st>>>(
-        p, h->capturing ? (const NeighParams*)h->np_dev : nullptr, h->P1, h->P2);
+    NeighParams p = make_neigh_params(h, sigma, eta, neigh_f64);
+    if (!h->capturing) h->band_sel ^= 1;
+    p.rsel = h->band_sel;
+    // (late epochs: most of Px, Py is exact zeros; SOM_NO_BANDS=1 records nothing and walks everything)
+    neigh_tables_kernel<<<dim3((unsigned)neigh_tables_grid(h->X, h->Y, h->nt, p.swapped)), dim3(NT_THREADS), 0, st>>>(
+        p, h->capturing ? (const NeighParams*)h->np_dev : nullptr, h->P1, h->P2, h->use_bands ? (int2*)h->bands : nullptr);
     HIPCHK(h, hipGetLastError());
-    // nonzero bands of the tables (late epochs: most of Px, Py is exact zeros); SOM_NO_BANDS=1 walks everything
-    const int nyb = (int)cdiv(h->Y, LM_BM), nxb = (int)cdiv(h->X, LM_BM);
-    if (h->use_bands) {
-        int2* bands1 = h->bands;                             // [nt][nyb]
-        int2* bands2 = h->bands + (long)h->nt * nyb;         // [nxb][nt]
-        HIPCHK(h, hipMemsetAsync(h->bands, 0, (size_t)h->nt * (nyb + nxb) * sizeof(int2), st));
-        band_ranges_kernel<<<dim3((unsigned)nyb, (unsigned)cdiv(h->Y, 64), (unsigned)h->nt), dim3(256), 0, st>>>(
-            h->P1, h->Y, h->Y, 1, h->Y, bands1, (long)h->Y * h->Y, nyb);
-        band_ranges_kernel<<<dim3((unsigned)nxb, (unsigned)(h->nt * cdiv(h->X, 64)), 1), dim3(256), 0, st>>>(
-            h->P2, h->X, h->nt * h->X, h->nt, h->X, bands2, 0, 0);
-        HIPCHK(h, hipGetLastError());
-    }
     return 0;
 }
 
+// the ranges of the tables' last build from entry `first` on (update.hpp: band_entry_stage1 / band_entry_stage2)
+BandRanges band_ranges_from(const som_handle* h, long first) {
+    BandRanges br{};
+    if (!h->use_bands || h->swapped) return br;
+    br.base = (const int2*)h->bands + first;
+    br.p_dev = h->capturing ? (const NeighParams*)h->np_dev : nullptr;
+    br.stride = band_entries(h->X, h->Y, h->nt);
+    br.sel = h->band_sel;
+    return br;
+}
+
 // OUT = H * M over C columns (rows of M / OUT ld floats apart): 128-wide MFMA tiles, and a VALU kernel for a last
-// tile of <= LM_NARROW columns
+// tile of <= LM_NARROW columns.  row_blocks: the 128-row blocks of H.
 void launch_leftmul(som_handle* h, const float* H, int Ro, int Ri, const float* M, long mstride, float* OUT, long ostride,
-                    long C, long ld, int row_blocks, int batch, const int2* ranges, int nseg, int segw, long ldo = 0) {
+                    long C, long ld, int row_blocks, int batch, const BandRanges& ranges, int nseg, int segw, long ldo = 0) {
     if (ldo == 0) ldo = ld;                              // rows of OUT as far apart as rows of M unless told otherwise
     long wide = cdiv(C, LM_BN);
     const long rem = C - (C / LM_BN) * LM_BN;
@@ -1184,9 +1189,12 @@ void launch_leftmul(som_handle* h, const float* H, int Ro, int Ri, const float* 
         else leftmul_narrow_f32_kernel<4><<<g, b, 0, h->stream>>>(H, Ro, Ri, M, mstride, OUT, ostride, C, ld, ldo, C - rem, ranges, nseg, segw);
     }
     if (wide <= 0) return;
-    // 64-row tiles where 128-row ones would be half empty (64 x 64 x 32: transform 34.6 -> 26.6 us); on grids that leave
-    // two or three 128-row workgroups per CU (256 x 256 x 128: 528 on 256 CUs) they were measured neutral (109 vs 110 us)
-    if (Ro <= 64)
+    // 64-row tiles where 128-row ones would be half empty (64 x 64 x 32: transform 34.6 -> 26.6 us), and wherever the
+    // launch walks bands: a 64-row workgroup stages the union of two 32-row tiles' ranges, not of four, so staging and
+    // barriers shrink with the band as the MFMAs do (256 x 256 x 128, sigma 1.2: 21 us a launch against 25; on dense
+    // tables the two were measured neutral at that shape, 49 us both).  Without ranges: the 128-row tile as before.
+    const bool rows64 = h->lm_rows == 64 || (h->lm_rows == 0 && (Ro <= 64 || ranges.base != nullptr));
+    if (rows64)
         leftmul_f32_kernel<64><<<dim3((unsigned)wide, (unsigned)cdiv(Ro, 64), (unsigned)batch), dim3(256), 0, h->stream>>>(
             H, Ro, Ri, M, mstride, OUT, ostride, C, ld, ldo, ranges, nseg, segw);
     else
@@ -1202,7 +1210,6 @@ int run_transform_stage1(som_handle* h, double sigma, double eta, int neigh_f64)
     if (!h->early.done)                                  // (exact mode: built before the pass's read-back)
         if (int rc = build_tables(h, sigma, eta, neigh_f64, h->stream)) return rc;
     const int nyb = (int)cdiv(h->Y, LM_BM);
-    const int2* bands1 = h->use_bands ? h->bands : nullptr;             // [nt][nyb]
     const long slab = (long)h->Y * h->D1p;
     if (h->swapped) {
         // mexican_hat + compact_support, rectangular (X == Y): the row stage first, V_t = Fx_t (X x X) * SC (X x Y*D1p),
@@ -1211,7 +1218,7 @@ int run_transform_stage1(som_handle* h, double sigma, double eta, int neigh_f64)
         const int nxb = (int)cdiv(h->X, LM_BM);
         for (int t1 = 0; t1 < h->nt; ++t1)
             launch_leftmul(h, h->P1 + (long)t1 * h->X * h->X, h->X, h->X, h->SC, 0, h->T + (long)t1 * slab, 0, slab, slab, nxb,
-                           1, nullptr, 1, h->X, (long)h->nt * slab);
+                           1, BandRanges{}, 1, h->X, (long)h->nt * slab);
         const NeighParams p = make_neigh_params(h, sigma, eta, neigh_f64);
         const long total = (long)h->X * h->nt * slab;
         mask_rows_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
@@ -1221,7 +1228,7 @@ int run_transform_stage1(som_handle* h, double sigma, double eta, int neigh_f64)
     }
     for (int t1 = 0; t1 < h->nt; ++t1)
         launch_leftmul(h, h->P1 + (long)t1 * h->Y * h->Y, h->Y, h->Y, h->SC, slab, h->T + (long)t1 * h->X * slab, slab,
-                       h->D, h->D1p, nyb, h->X, bands1 ? bands1 + (long)t1 * nyb : nullptr, 1, h->Y);
+                       h->D, h->D1p, nyb, h->X, band_ranges_from(h, band_entry_stage1(t1, 0, h->Y)), 1, h->Y);
     // U_t[a][j] = sum_b C[a][b] Py_t[j][b] from the dense counts; stage 2 reads it densely (Ud) when it batches over
     // the map columns, or finds it where stage 1 would have put it, T_t[a][j][D], when it runs over whole rows
     const bool per_column = h->D % LM_BN == 0;
@@ -1239,19 +1246,18 @@ int run_transform_stage1(som_handle* h, double sigma, double eta, int neigh_f64)
 int run_transform_stage2(som_handle* h, int b0, int b1) {
     const int nyb = (int)cdiv(h->Y, LM_BM), nxb = (int)cdiv(h->X, LM_BM);
     if (b0 < 0 || b1 > nxb || b0 >= b1) return fail(h, "transform: map-row block out of range");
-    const int2* bands2 = h->use_bands ? h->bands + (long)h->nt * nyb : nullptr;   // [nxb][nt]
     const long slab = (long)h->Y * h->D1p;
     const long i0 = (long)b0 * LM_BM;
     const int rows = (int)std::min<long>((long)b1 * LM_BM, h->X) - (int)i0;
     if (h->swapped) {
         // the column stage, batched over the block's map rows: ACC[i] = [Gy_0 | Gy_1 ...] (Y x nt*Y) * T[i] (nt*Y x D1p)
         launch_leftmul(h, h->P2, h->Y, h->nt * h->Y, h->T + i0 * h->nt * slab, (long)h->nt * slab, h->ACC + i0 * slab, slab,
-                       h->D1p, h->D1p, nyb, rows, nullptr, 1, h->nt * h->Y);
+                       h->D1p, h->D1p, nyb, rows, BandRanges{}, 1, h->nt * h->Y);
         HIPCHK(h, hipGetLastError());
         return 0;
     }
     const float* H = h->P2 + i0 * h->nt * h->X;
-    const int2* ranges = bands2 ? bands2 + (long)b0 * h->nt : nullptr;
+    const BandRanges ranges = band_ranges_from(h, band_entry_stage2((int)i0, 0, h->Y, h->nt));   // the block's first 32-row tile
     if (h->D % LM_BN == 0) {
         launch_leftmul(h, H, rows, h->nt * h->X, h->T, h->D1p, h->ACC + i0 * slab, h->D1p, h->D, slab, b1 - b0, h->Y, ranges,
                        h->nt, h->X);
@@ -1503,11 +1509,14 @@ int som_create(const som_config* cfg, som_handle** out) {
         if (const char* e = dev_env("SOM_EXACT_PLAN_FOLD")) h->ex.plan_fold = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_EXACT_PLAN_PARTS")) h->ex.hook_plan_parts = std::max(0, std::atoi(e));
         if (const char* e = dev_env("SOM_COUNTING_SORT")) h->counting_sort = std::atoi(e) != 0;
-        // a 128-row block of a table already spans most of a map side up to 256: nothing to skip there
-        h->use_bands = h->X > 256 || h->Y > 256;
+        // the ranges are kept per 32-row tile of a table (update.hpp): a tile can have a zero column, and an MFMA step to
+        // skip, as soon as the table has more columns than the tile has rows -- a map side above 32.  They cost no launch.
+        h->use_bands = h->X > LM_TILE || h->Y > LM_TILE;
         if (const char* e = dev_env("SOM_NO_BANDS")) h->use_bands = std::atoi(e) == 0;
-        const size_t nb = (size_t)h->nt * (cdiv(h->Y, LM_BM) + cdiv(h->X, LM_BM));
+        if (const char* e = dev_env("SOM_LM_ROWS")) h->lm_rows = std::atoi(e) == 64 ? 64 : std::atoi(e) == 128 ? 128 : 0;
+        const size_t nb = (size_t)2 * band_entries(h->X, h->Y, h->nt);   // two buffers, both empty
         if ((rc = h->bands.alloc(h, nb))) return bail(rc);
+        if (hipMemsetAsync(h->bands, 0, nb * sizeof(int2), h->stream) != hipSuccess) return bail(fail(h, "hipMemsetAsync failed"));
     }
     // (T: stage 1 of the transform writes the feature columns and the count column only; the padding columns behind
     //  them are read by a whole-row stage 2 and end up in ACC's padding, which is all-reduced: keep them defined)
@@ -1744,7 +1753,9 @@ int som_epoch_accumulate(som_handle* h, double sigma, double eta, int neigh_f64)
             if (int rc = capture_epoch_graph(h)) return rc;
         }
         if (h->gexec) {
-            const NeighParams p = make_neigh_params(h, sigma, eta, neigh_f64);
+            NeighParams p = make_neigh_params(h, sigma, eta, neigh_f64);
+            h->band_sel ^= 1;                           // the replayed build of the tables fills the other range buffer
+            p.rsel = h->band_sel;
             store_params_kernel<<<dim3(1), dim3(64), 0, h->stream>>>(p, (NeighParams*)h->np_dev);
             HIPCHK(h, hipGraphLaunch(h->gexec, h->stream));
             h->ops.graph_replayed(operands::Request::Search);   // (the captured epoch's own refresh: run_activation_bmu_launch)
@@ -2552,6 +2563,45 @@ int som_debug_plan_split(int32_t bf16, int64_t n, const float* P, const float* s
         const float c = bf16 ? plan_fold_scale<Bf16>(s_bmag[i]) : plan_fold_scale<F16>(s_bmag[i]);
         const PlanParts pp = bf16 ? plan_split_threshold<Bf16>(P[i], c) : plan_split_threshold<F16>(P[i], c);
         out4[4 * i] = c; out4[4 * i + 1] = pp.p1; out4[4 * i + 2] = pp.p2; out4[4 * i + 3] = pp.p3;
+    }
+    return 0;
+}
+
+int som_debug_band_tables(som_handle* h, int32_t* info4, int32_t* entries_out, float* P1_out, float* P2_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || !info4) return fail(h, "som_debug_band_tables: NULL argument");
+    const long nb = band_entries(h->X, h->Y, h->nt);
+    info4[0] = h->use_bands && !h->swapped; info4[1] = h->nt; info4[2] = (int32_t)nb; info4[3] = h->band_sel;
+    if (entries_out)
+        if (int rc = d2h_blocking(h, entries_out, (const int2*)h->bands + (long)h->band_sel * nb, (size_t)nb * sizeof(int2))) return rc;
+    if (P1_out)
+        if (int rc = d2h_blocking(h, P1_out, h->P1, (size_t)h->nt * h->Y * h->Y * sizeof(float))) return rc;
+    if (P2_out)
+        if (int rc = d2h_blocking(h, P2_out, h->P2, (size_t)h->X * h->nt * h->X * sizeof(float))) return rc;
+    return 0;
+}
+
+int som_debug_band_walk(const float* H, int32_t rows, int32_t nseg, int32_t segw, int32_t wg_rows, int32_t* tiles_out,
+                        int32_t* wg_out) {
+    if (!H || !tiles_out || !wg_out || rows <= 0 || nseg <= 0 || segw <= 0 || (wg_rows != 64 && wg_rows != 128)) return 1;
+    const int nt = band_tiles(rows), per_wg = wg_rows / LM_TILE;
+    std::vector<int2> e((size_t)nt * nseg, make_int2(0, 0));
+    for (int i = 0; i < rows; ++i)
+        for (int sg = 0; sg < nseg; ++sg)
+            for (int k = 0; k < segw; ++k)
+                if (H[((size_t)i * nseg + sg) * segw + k] != 0.0f) {
+                    int2& v = e[(size_t)(i / LM_TILE) * nseg + sg];
+                    v = band_entry_with(v, k, segw);
+                }
+    for (size_t i = 0; i < e.size(); ++i) {
+        int lo, hi;
+        band_tile_range(e[i], segw, lo, hi);
+        tiles_out[2 * i] = lo; tiles_out[2 * i + 1] = hi;
+    }
+    for (int w = 0; w * wg_rows < rows; ++w) {
+        int lo, hi;
+        band_union(e.data() + (size_t)w * per_wg * nseg, std::min(per_wg, band_tiles(rows - w * wg_rows)), nseg, segw, LM_BK, lo, hi);
+        wg_out[3 * w] = lo; wg_out[3 * w + 1] = hi; wg_out[3 * w + 2] = (hi - lo + LM_BK - 1) / LM_BK;
     }
     return 0;
 }

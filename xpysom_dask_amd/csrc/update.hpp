@@ -20,6 +20,7 @@
 //     [num|den](i,j,:) = sum_t sum_a Px_t[i,a] sum_b Py_t[j,b] [S|c](a,b,:)   (two small exact-f32 MFMA GEMMs)
 // which replaces the 2*N*K*D-flop GEMM of xpysom.py:437-438 by 2*K*(X+Y)*(D+1) flops.
 #pragma once
+#include <type_traits>
 #include "som_common.hpp"
 
 namespace somhip {
@@ -422,6 +423,7 @@ struct NeighParams {
     int kind, compact, wide, X, Y, nt;
     int hex, base_nt, ncls; // hexagonal topology: nt = ncls * base_nt, one copy of the terms per parity class
     int swapped;            // mexican_hat + compact_support on the rectangular topology: row stage first (see below)
+    int rsel;               // which of the two band-range buffers this build of the tables fills (BandRanges, below)
 };
 
 __device__ __forceinline__ double neigh_exp(double delta2, const NeighParams& p) {
@@ -496,15 +498,95 @@ __global__ void store_params_kernel(NeighParams p, NeighParams* __restrict__ dst
     if (threadIdx.x == 0 && blockIdx.x == 0) *dst = p;
 }
 
-__global__ __launch_bounds__(256) void neigh_tables_kernel(NeighParams p_val, const NeighParams* __restrict__ p_dev,
-                                                           float* __restrict__ P1, float* __restrict__ P2) {
+// ---- nonzero column ranges of the tables ("bands"; the GEMMs that walk them: leftmul_f32_kernel below) -------------
+// Per 32-row tile of a table (the rows of one v_mfma_f32_32x32x2_f32 A operand) and per column segment (one per
+// neighbourhood term) an entry {segw - first nonzero column, last nonzero column + 1} in segment coordinates; both
+// fields only grow (atomicMax from {0, 0} = the tile holds no nonzero).  Layout of one buffer:
+//   stage 1 (P1, [nt][Y][Y], one segment of Y columns per table):  entry t * ty + j / 32,         ty = ceil(Y / 32)
+//   stage 2 (P2, [X][nt * X], nt segments of X columns):           nt * ty + (i / 32) * nt + t
+// neigh_tables_kernel fills them from the float32 values it STORES (never from a formula for where the zeros ought to
+// be), so a range contains every nonzero of its tile: that is the whole correctness argument of the skipping.  There
+// are two buffers: a build of the tables fills buffer rsel and zeroes the other one, whose last readers (the GEMMs of
+// the build before) are done; the host alternates rsel from build to build, so no launch is spent on clearing.
+constexpr int LM_TILE = 32;     // rows of H per range entry
+constexpr int LM_KG = 8;        // columns per skipping decision: four MFMA k steps (a tile's range is rounded outwards to it)
+
+__host__ __device__ inline int band_tiles(int rows) { return (rows + LM_TILE - 1) / LM_TILE; }
+__host__ __device__ inline long band_entries(int X, int Y, int nt) { return (long)nt * (band_tiles(Y) + band_tiles(X)); }
+__host__ __device__ inline long band_entry_stage1(int t, int j, int Y) { return (long)t * band_tiles(Y) + j / LM_TILE; }
+__host__ __device__ inline long band_entry_stage2(int i, int t, int Y, int nt) {
+    return (long)nt * band_tiles(Y) + (long)(i / LM_TILE) * nt + t;
+}
+// what the GEMMs make of the entries (host-callable: tests/test_transform_bands_cpu.py runs them against a NumPy model)
+// a tile's range of one segment, rounded outwards to LM_KG columns: [tlo, thi), empty = {0, 0}
+__host__ __device__ inline void band_tile_range(int2 v, int segw, int& tlo, int& thi) {
+    tlo = 0; thi = 0;
+    if (v.y > 0) {
+        const int hi = v.y < segw ? v.y : segw;
+        tlo = ((segw - v.x) / LM_KG) * LM_KG;
+        thi = ((hi + LM_KG - 1) / LM_KG) * LM_KG;
+    }
+}
+// are the LM_KG columns from k0 on (a multiple of LM_KG) inside [tlo, thi)?
+__host__ __device__ inline bool band_group_on(int k0, int tlo, int thi) { return k0 < thi && k0 + LM_KG > tlo; }
+// the columns a workgroup stages: the union over its ntiles tiles (entries tiles[t * nseg + sg]) and all segments, the
+// lower end rounded down to a chunk; every segment is walked over the same [lo, hi).  Nothing nonzero: lo = hi = 0.
+__host__ __device__ inline void band_union(const int2* tiles, int ntiles, int nseg, int segw, int chunk, int& lo, int& hi) {
+    lo = segw; hi = 0;
+    for (int i = 0; i < ntiles * nseg; ++i) {
+        const int2 v = tiles[i];
+        if (v.y > 0) {
+            const int l = ((segw - v.x) / chunk) * chunk, u = v.y < segw ? v.y : segw;
+            lo = l < lo ? l : lo;
+            hi = u > hi ? u : hi;
+        }
+    }
+    if (hi <= lo) lo = hi = 0;
+}
+
+// an entry after one more nonzero at column `col` (what neigh_tables_kernel's atomicMax pairs leave; the CPU test's hook builds entries with it)
+__host__ __device__ inline int2 band_entry_with(int2 v, int col, int segw) {
+    v.x = v.x > segw - col ? v.x : segw - col;
+    v.y = v.y > col + 1 ? v.y : col + 1;
+    return v;
+}
+
+// the ranges as a launch gets them: base == nullptr: none (walk everything); else buffer (p_dev ? p_dev->rsel : sel),
+// `stride` entries apart, `base` already advanced to the launch's first tile (a captured launch reads rsel where
+// store_params_kernel puts it before every replay)
+struct BandRanges {
+    const int2* base;
+    const NeighParams* p_dev;
+    long stride;
+    int sel;
+};
+__device__ __forceinline__ const int2* band_ranges_of(const BandRanges& b) {
+    if (b.base == nullptr) return nullptr;
+    return b.base + (long)(b.p_dev ? b.p_dev->rsel : b.sel) * b.stride;
+}
+
+// Workgroup = 16 waves = one 32-row tile of a table x 64 of its columns (wave w: rows 2 w, 2 w + 1 of the tile; lane: a
+// column): blocks [0, nt ty cy) are stage 1's (term, tile, column chunk), the rest stage 2's (tile, term, column chunk),
+// cy = ceil(Y / 64).  A workgroup's nonzeros belong to ONE range entry, so the waves' ballots are combined in LDS and the
+// entry gets one pair of atomicMax per workgroup: side / 64 pairs per entry (all entries of a map share a cache line or
+// two, where atomics are served one after the other).  neigh_tables_grid() is the grid.
+// bands != nullptr: two buffers of band_entries() each (see above); this launch fills buffer p.rsel, zeroes the other.
+constexpr int NT_THREADS = 1024, NT_COLS = 64;
+__host__ __device__ inline long neigh_tables_grid(int X, int Y, int nt, int swapped) {
+    if (swapped) return ((long)nt * Y * Y + (long)X * nt * X + NT_THREADS - 1) / NT_THREADS;   // one thread per entry
+    return (long)nt * (band_tiles(Y) * ((Y + NT_COLS - 1) / NT_COLS) + band_tiles(X) * ((X + NT_COLS - 1) / NT_COLS));
+}
+
+__global__ __launch_bounds__(NT_THREADS) void neigh_tables_kernel(NeighParams p_val, const NeighParams* __restrict__ p_dev,
+                                                                  float* __restrict__ P1, float* __restrict__ P2,
+                                                                  int2* __restrict__ bands) {
     const NeighParams p = p_dev ? *p_dev : p_val;
-    long id = (long)blockIdx.x * 256 + threadIdx.x;
-    const long n1 = (long)p.nt * p.Y * p.Y;
-    const long n2 = (long)p.X * p.nt * p.X;
+    const long id = (long)blockIdx.x * NT_THREADS + threadIdx.x;
     if (p.swapped) {
         // row stage first (X == Y): P1 = the row factors [nt][X][X] (Fx_t[i][a], with eta), P2 = the column factors
-        // [Y][nt*Y] (Gy_t[j][b] at column t*Y + b)
+        // [Y][nt*Y] (Gy_t[j][b] at column t*Y + b)   (this pipeline walks whole tables: no ranges, one thread per entry)
+        const long n1 = (long)p.nt * p.Y * p.Y;
+        const long n2 = (long)p.X * p.nt * p.X;
         if (id < n1) {
             int a = id % p.X;
             long r = id / p.X;
@@ -521,34 +603,63 @@ __global__ __launch_bounds__(256) void neigh_tables_kernel(NeighParams p_val, co
         }
         return;
     }
-    if (id < n1) {
-        int b = id % p.Y;
-        long r = id / p.Y;
-        int j = r % p.Y;
-        int t = r / p.Y;
-        double v = neigh_factor(1, t % p.base_nt, (double)j, (double)b, p);
-        if (p.hex) {                                   // class indicator on (s(j), s(cj)): s = the row is shifted by -0.5
-            const int cls = t / p.base_nt;
-            const int sj = ((p.Y - 1 - j) & 1) == 0, sb = ((p.Y - 1 - b) & 1) == 0;
-            bool in;
-            if (p.ncls == 3) in = cls == 0 ? sj == sb : cls == 1 ? (sj == 0 && sb == 1) : (sj == 1 && sb == 0);
-            else in = cls == 0 ? (sj == 0 && sb == 0) : cls == 1 ? (sj == 0 && sb == 1) : cls == 2 ? (sj == 1 && sb == 0)
-                                                                                                  : (sj == 1 && sb == 1);
-            if (!in) v = 0.0;
+    __shared__ int s_first[NT_THREADS / 64], s_end[NT_THREADS / 64];
+    const long nb = band_entries(p.X, p.Y, p.nt);
+    if (bands != nullptr && id < nb) bands[(p.rsel ? 0 : nb) + id] = make_int2(0, 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ty = band_tiles(p.Y), cy = (p.Y + NT_COLS - 1) / NT_COLS, cx = (p.X + NT_COLS - 1) / NT_COLS;
+    int blk = blockIdx.x;
+    const bool stage1 = blk < p.nt * ty * cy;
+    int t, tile, chunk;
+    if (stage1) { chunk = blk % cy; tile = (blk / cy) % ty; t = blk / (cy * ty); }
+    else { blk -= p.nt * ty * cy; chunk = blk % cx; t = (blk / cx) % p.nt; tile = blk / (cx * p.nt); }
+    const int side = stage1 ? p.Y : p.X;
+    const int c = chunk * NT_COLS + lane;               // the BMU coordinate: b (stage 1) or a (stage 2)
+    const int cls = t / p.base_nt;
+    unsigned long long nz = 0;                          // the columns of this chunk in which the wave STORED a nonzero
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int r = tile * LM_TILE + wave * 2 + q;    // the unit coordinate: j (stage 1) or i (stage 2)
+        const bool in = r < side && c < side;
+        float stored = 0.0f;
+        if (in && stage1) {
+            double v = neigh_factor(1, t % p.base_nt, (double)r, (double)c, p);
+            if (p.hex) {                               // class indicator on (s(j), s(cj)): s = the row is shifted by -0.5
+                const int sj = ((p.Y - 1 - r) & 1) == 0, sb = ((p.Y - 1 - c) & 1) == 0;
+                bool on;
+                if (p.ncls == 3) on = cls == 0 ? sj == sb : cls == 1 ? (sj == 0 && sb == 1) : (sj == 1 && sb == 0);
+                else on = cls == 0 ? (sj == 0 && sb == 0) : cls == 1 ? (sj == 0 && sb == 1) : cls == 2 ? (sj == 1 && sb == 0)
+                                                                                                      : (sj == 1 && sb == 1);
+                if (!on) v = 0.0;
+            }
+            stored = (float)v;
+            P1[((long)t * p.Y + r) * p.Y + c] = stored;
+        } else if (in) {
+            // x coordinates of the class: unit rows of classes 2, 3 and BMU rows of classes 1, 3 are shifted by -0.5
+            // (three classes: only the difference matters, the both-shifted rows share class 0 with the unshifted ones)
+            const double off_n = p.hex && (cls == 2 || cls == 3) ? -0.5 : 0.0;
+            const double off_c = p.hex && (cls == 1 || cls == 3) ? -0.5 : 0.0;
+            double v = neigh_factor(0, t % p.base_nt, (double)r + off_n, (double)c + off_c, p);
+            stored = p.wide ? (float)(v * p.eta) : (float)v * (float)p.eta;
+            P2[((long)r * p.nt + t) * p.X + c] = stored;
         }
-        P1[id] = (float)v;
-    } else if (id < n1 + n2) {
-        long q = id - n1;
-        int col = q % ((long)p.nt * p.X);
-        int i = q / ((long)p.nt * p.X);
-        int t = col / p.X, a = col % p.X;
-        const int cls = t / p.base_nt;
-        // x coordinates of the class: unit rows of classes 2, 3 and BMU rows of classes 1, 3 are shifted by -0.5
-        // (three classes: only the difference matters, the both-shifted rows share class 0 with the unshifted ones)
-        const double off_n = p.hex && (cls == 2 || cls == 3) ? -0.5 : 0.0;
-        const double off_c = p.hex && (cls == 1 || cls == 3) ? -0.5 : 0.0;
-        double v = neigh_factor(0, t % p.base_nt, (double)i + off_n, (double)a + off_c, p);
-        P2[q] = p.wide ? (float)(v * p.eta) : (float)v * (float)p.eta;
+        nz |= __ballot(in && stored != 0.0f);
+    }
+    if (bands == nullptr) return;
+    if (lane == 0) {
+        s_first[wave] = nz != 0 ? chunk * NT_COLS + (int)__builtin_ctzll(nz) : side;
+        s_end[wave] = nz != 0 ? chunk * NT_COLS + 64 - (int)__builtin_clzll(nz) : 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int first = side, end = 0;
+        for (int w = 0; w < NT_THREADS / 64; ++w) { first = min(first, s_first[w]); end = max(end, s_end[w]); }
+        if (end > 0) {
+            const long e = stage1 ? band_entry_stage1(t, tile * LM_TILE, p.Y) : band_entry_stage2(tile * LM_TILE, t, p.Y, p.nt);
+            int* r = (int*)(bands + (p.rsel ? nb : 0) + e);
+            atomicMax(r, side - first);
+            atomicMax(r + 1, end);
+        }
     }
 }
 
@@ -578,54 +689,29 @@ __global__ __launch_bounds__(256) void mask_rows_kernel(NeighParams p_val, const
 //
 // Bands.  Late in training sigma is small and the neighbourhood tables underflow to EXACT float32 zeros
 // away from the diagonal (exp(-dx^2/d) < 2^-150 for |dx| > ~7 sigma at std_coeff 0.5; bubble / triangle
-// are compact by definition).  band_ranges_kernel records, per 128-row block of H and per column
-// segment (one per neighbourhood term), the smallest range of 32-column chunks that holds every nonzero;
-// the GEMM then walks only those chunks.  Skipped chunks would have added 0 * m = 0 to the accumulators,
-// so the result is bit-identical for finite data.
+// are compact by definition).  neigh_tables_kernel records, per 32-row tile of H and per column segment
+// (one per neighbourhood term), the column range that holds every nonzero (above).  A workgroup stages
+// 32-column chunks over the union of its tiles' ranges only, and a wave issues the MFMAs of an a-tile only
+// for the LM_KG-column groups inside that tile's own range (a wave-uniform test; the k order of the steps that
+// remain is the ascending one of the full walk).  A skipped step would have added 0 * m = +0 to a float32
+// accumulator, so the result is bit-identical for finite data.
 constexpr int LM_BM = 128, LM_BN = 128, LM_BK = 32;
 constexpr int LM_NARROW = 8;    // a last column tile this narrow goes to leftmul_narrow_f32_kernel (VALU) instead of a
                                 // mostly empty 128-wide MFMA tile (64x64x32: 32 columns as a partial MFMA tile 11 us, as VALU 14)
 
-// ranges[rb * nseg + s] = {segw - lo, hi}: columns [s*segw + lo, s*segw + hi) of rows [128 rb, 128 rb + 128) hold
-// every nonzero of that segment; both fields only grow (atomicMax from a zeroed buffer: {0, 0} = all zero).
-// One workgroup scans 128 rows x 64 columns (wave w: rows 32 w .. 32 w + 31, lane: one column); grid =
-// (row blocks, segments * column chunks, batch), batch z: H + z * hz, ranges + z * rz.
-__global__ __launch_bounds__(256) void band_ranges_kernel(const float* __restrict__ H, int Ro, int Ri, int nseg,
-                                                          int segw, int2* __restrict__ ranges, long hz, long rz) {
-    const int rb = blockIdx.x;
-    const int cchunks = (segw + 63) / 64;
-    const int seg = blockIdx.y / cchunks, cc = blockIdx.y - seg * cchunks;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* Hb = H + (long)blockIdx.z * hz;
-    const int k = cc * 64 + lane;                      // column inside the segment
-    const int r_begin = rb * LM_BM + wave * 32;
-    bool nz = false;
-    if (k < segw) {
-#pragma unroll 8
-        for (int i = 0; i < 32; ++i) {
-            const int r = r_begin + i;
-            if (r < Ro) nz |= Hb[(long)r * Ri + seg * segw + k] != 0.0f;
-        }
-    }
-    const unsigned long long m = __ballot(nz);
-    if (m != 0 && lane == 0) {
-        const int first = cc * 64 + __builtin_ctzll(m), last = cc * 64 + 63 - __builtin_clzll(m);
-        int* r = (int*)(ranges + (long)blockIdx.z * rz + (long)rb * nseg + seg);
-        atomicMax(r, segw - first);
-        atomicMax(r + 1, last + 1);
-    }
-}
-
-// ranges == nullptr: the whole of H (one segment [0, Ri)).  C columns are computed; rows of M are ld, rows of OUT ldo floats apart.
+// No ranges (br.base == nullptr): the whole of H (one segment [0, Ri)); else br.base is the entry of the launch's first
+// 32-row tile, segment 0.  C columns are computed; rows of M are ld, rows of OUT ldo floats apart.
 // BM = rows of H per workgroup: 128 (waves 2 x 2, each 64 rows x 64 columns) or 64 (waves 1 x 4, each 64 rows x 32
-// columns) for maps of at most 64 rows, whose 128-row tiles would be half empty.
+// columns; launch_leftmul in somhip.hip chooses).
+template <int A> using a_is = std::integral_constant<int, A>;
 template <int BM>
-__global__ __launch_bounds__(256) void leftmul_f32_kernel(const float* __restrict__ H, int Ro, int Ri,
+__global__ __launch_bounds__(256, BM == 128 ? 3 : 5) void leftmul_f32_kernel(const float* __restrict__ H, int Ro, int Ri,
                                                           const float* __restrict__ M, long m_batch_stride,
                                                           float* __restrict__ OUT, long o_batch_stride, long C,
-                                                          long ld, long ldo, const int2* __restrict__ ranges, int nseg,
-                                                          int segw) {
+                                                          long ld, long ldo, BandRanges br, int nseg, int segw) {
     static_assert(BM == 128 || BM == 64, "leftmul: 128- or 64-row tiles");
+    static_assert(LM_BK % LM_KG == 0 && LM_KG % 2 == 0, "leftmul: whole MFMA steps per skipping group, whole groups per chunk");
+    constexpr int NT = BM / LM_TILE;                     // range entries (32-row tiles) per workgroup
     constexpr int TC = BM / 64;                          // 32-column tiles per wave: 2 (64 columns) or 1 (32 columns)
     constexpr int HQ = BM / 32;                          // 4-float pieces of the H tile per thread
     __shared__ float Hs[BM][LM_BK + 1];
@@ -636,6 +722,7 @@ __global__ __launch_bounds__(256) void leftmul_f32_kernel(const float* __restric
     const int wcol = BM == 128 ? (wave & 1) * 64 : wave * 32;   // ... and its first column inside the 128-column tile
     const long c0 = (long)blockIdx.x * LM_BN;
     const int i0 = blockIdx.y * BM;
+    const int2* __restrict__ ranges = band_ranges_of(br);
     const float* Mb = M + (long)blockIdx.z * m_batch_stride;
     float* Ob = OUT + (long)blockIdx.z * o_batch_stride;
 
@@ -653,7 +740,7 @@ __global__ __launch_bounds__(256) void leftmul_f32_kernel(const float* __restric
     // 16-byte aligned is ONE global_load_dwordx4 (the common case: 8 loads per thread and chunk where the scalar
     // form needed 32 loads with their 64-bit address arithmetic); otherwise its four floats are loaded one by one.
     f32x4 hreg[HQ], mreg[4];
-    auto fetch = [&](int r0, int kend) {               // chunk [r0, r0 + 32) clipped to columns < kend
+    auto fetch = [&](int r0, int kend) __attribute__((always_inline)) {               // chunk [r0, r0 + 32) clipped to columns < kend
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int idx = tid + q * 256;
@@ -676,7 +763,7 @@ __global__ __launch_bounds__(256) void leftmul_f32_kernel(const float* __restric
             }
         }
     };
-    auto stash = [&]() {
+    auto stash = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int idx = tid + q * 256;
@@ -689,55 +776,106 @@ __global__ __launch_bounds__(256) void leftmul_f32_kernel(const float* __restric
         }
     };
 
-    // the chunks to walk (uniform over the workgroup): every segment is walked over the union [lo, hi) of
-    // the segments' nonzero ranges, LM_BK columns at a time, clipped to hi
+    // the chunks to walk (uniform over the workgroup): every segment is walked over the union [lo, hi) of the
+    // nonzero ranges of the workgroup's tiles and segments, LM_BK columns at a time, clipped to hi
     int lo = 0, hi = Ri, ns = 1, sw = Ri;
+    const int my_tiles = min(NT, band_tiles(Ro - i0));   // (the entries of tiles past the last row do not exist)
+    bool dense = true;                                   // every tile of the workgroup covers [lo, hi) in every segment
     if (ranges != nullptr) {
-        ns = nseg; sw = segw; lo = segw; hi = 0;
-        for (int sg = 0; sg < nseg; ++sg) {
-            const int2 v = ranges[(blockIdx.y * BM / LM_BM) * nseg + sg];   // {segw - first nonzero, last nonzero + 1} of the 128-row block
-            if (v.y > 0) { lo = min(lo, ((segw - v.x) / LM_BK) * LM_BK); hi = max(hi, min(v.y, segw)); }
+        ns = nseg; sw = segw;
+        const int2* mine = ranges + (long)blockIdx.y * NT * nseg;
+        band_union(mine, my_tiles, nseg, segw, LM_BK, lo, hi);
+        dense = my_tiles == NT;
+        for (int i = 0; i < my_tiles * nseg; ++i) {
+            int l, u;
+            band_tile_range(mine[i], segw, l, u);
+            dense = dense && l <= lo && u >= hi;
         }
-        if (hi <= lo) lo = hi = 0;
     }
     const int per = (hi - lo + LM_BK - 1) / LM_BK;     // chunks per segment
     const int total = per * ns;
-    auto chunk_at = [&](int c, int& r0, int& kend) {
-        const int sg = c / per, j = c - sg * per;
+    auto chunk_at = [&](int c, int& sg, int& j, int& r0, int& kend) __attribute__((always_inline)) {
+        sg = c / per; j = c - sg * per;
         r0 = sg * sw + lo + j * LM_BK;
         kend = sg * sw + hi;
     };
-    if (total > 0) { int r0, kend; chunk_at(0, r0, kend); fetch(r0, kend); }
-    for (int c = 0; c < total; ++c) {
-        __syncthreads();                                // everyone is done reading the previous chunk
-        stash();
-        __syncthreads();
-        if (c + 1 < total) { int r0, kend; chunk_at(c + 1, r0, kend); fetch(r0, kend); }   // in flight under the MFMAs below
+    // this wave's two a-tiles: their own ranges in the segment being walked (wave-uniform; no ranges: everything)
+    const int wtile = __builtin_amdgcn_readfirstlane(wr) * 2;
+    int tlo[2] = {0, 0}, thi[2] = {0, 0};
+    // the MFMA steps of columns [g LM_KG, g LM_KG + LM_KG) of the staged chunk for a-tiles [a0, a1)
+    auto steps = [&](int g, auto first, auto end) __attribute__((always_inline)) {
+        constexpr int a0 = decltype(first)::value, a1 = decltype(end)::value;
 #pragma unroll
-        for (int k = 0; k < LM_BK; k += 2) {
+        for (int kk = 0; kk < LM_KG; kk += 2) {
+            const int k = g * LM_KG + kk;
             float av[2], bv[TC];
 #pragma unroll
-            for (int a = 0; a < 2; ++a) av[a] = Hs[wr * 64 + a * 32 + col][k + half];
+            for (int a = 0; a < 2; ++a) if (a >= a0 && a < a1) av[a] = Hs[wr * 64 + a * 32 + col][k + half];
 #pragma unroll
             for (int t = 0; t < TC; ++t) bv[t] = Ms[k + half][wcol + t * 32 + col];
 #pragma unroll
             for (int a = 0; a < 2; ++a)
+                if (a >= a0 && a < a1)
 #pragma unroll
-                for (int t = 0; t < TC; ++t)
-                    acc[a][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[t], acc[a][t], 0, 0, 0);
+                    for (int t = 0; t < TC; ++t)
+                        acc[a][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[t], acc[a][t], 0, 0, 0);
         }
-    }
+    };
+    auto store = [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+        for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int t = 0; t < TC; ++t) {
-            long c = c0 + wcol + t * 32 + col;
+            for (int t = 0; t < TC; ++t) {
+                long c = c0 + wcol + t * 32 + col;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int i = i0 + wr * 64 + a * 32 + mfma32_row(r, half);
-                if (i < Ro && c < C) Ob[(long)i * ldo + c] = acc[a][t][r];
+                for (int r = 0; r < 16; ++r) {
+                    int i = i0 + wr * 64 + a * 32 + mfma32_row(r, half);
+                    if (i < Ro && c < C) Ob[(long)i * ldo + c] = acc[a][t][r];
+                }
+            }
+    };
+    // The walk, in two forms that share nothing after the prologue (one loop with both forms inside makes the compiler
+    // keep the accumulators twice: 128 AGPRs, a workgroup per CU less).  DENSE: every tile of the workgroup is nonzero
+    // over the whole of [lo, hi) in every segment, or there are no ranges -- 16 MFMA steps per chunk and a-tile in one
+    // straight run.  Otherwise each a-tile runs the LM_KG-column groups of its own range, ascending.
+    auto walk = [&](auto dense_form) __attribute__((always_inline)) {
+        constexpr bool DENSE = decltype(dense_form)::value;
+        int sg = 0, j = 0;
+        if (total > 0) { int r0, kend; chunk_at(0, sg, j, r0, kend); fetch(r0, kend); }
+        for (int c = 0; c < total; ++c) {
+            __syncthreads();                            // everyone is done reading the previous chunk
+            stash();
+            __syncthreads();
+            const int kc = lo + j * LM_BK;              // the staged chunk's first column, in segment coordinates
+            if (!DENSE && j == 0) {                     // a new segment: this wave's tiles' ranges in it
+#pragma unroll
+                for (int a = 0; a < 2; ++a) {
+                    int2 v = make_int2(0, 0);
+                    if (wtile + a < my_tiles) v = ranges[((long)blockIdx.y * NT + wtile + a) * nseg + sg];
+                    int l, u;
+                    band_tile_range(v, segw, l, u);
+                    tlo[a] = __builtin_amdgcn_readfirstlane(l);
+                    thi[a] = __builtin_amdgcn_readfirstlane(u);
+                }
+            }
+            if (c + 1 < total) { int r0, kend; chunk_at(c + 1, sg, j, r0, kend); fetch(r0, kend); }   // in flight under the MFMAs below
+            if (DENSE) {
+#pragma unroll
+                for (int g = 0; g < LM_BK / LM_KG; ++g) steps(g, a_is<0>(), a_is<2>());
+            } else {
+                int g0[2], g1[2];                       // (tlo, thi: multiples of LM_KG)
+#pragma unroll
+                for (int a = 0; a < 2; ++a) { g0[a] = max(tlo[a] - kc, 0) / LM_KG; g1[a] = min((thi[a] - kc) / LM_KG, LM_BK / LM_KG); }
+#pragma unroll 1
+                for (int g = g0[0]; g < g1[0]; ++g) steps(g, a_is<0>(), a_is<1>());
+#pragma unroll 1
+                for (int g = g0[1]; g < g1[1]; ++g) steps(g, a_is<1>(), a_is<2>());
             }
         }
+        store();
+    };
+    if (dense) walk(std::integral_constant<bool, true>());
+    else walk(std::integral_constant<bool, false>());
 }
 
 // The columns [c_begin, C) of the same product when they are too few for a 128-wide MFMA tile (the count
@@ -749,8 +887,8 @@ template <int NQ>                                       // columns handled per t
 __global__ __launch_bounds__(256) void leftmul_narrow_f32_kernel(const float* __restrict__ H, int Ro, int Ri,
                                                                  const float* __restrict__ M, long m_batch_stride,
                                                                  float* __restrict__ OUT, long o_batch_stride, long C,
-                                                                 long ld, long ldo, long c_begin,
-                                                                 const int2* __restrict__ ranges, int nseg, int segw) {
+                                                                 long ld, long ldo, long c_begin, BandRanges br, int nseg,
+                                                                 int segw) {
     __shared__ float Hs[LM_BM][LM_BK + 1];
     __shared__ float Ms[LM_BK][2 * NQ];
     const int tid = threadIdx.x;
@@ -763,14 +901,13 @@ __global__ __launch_bounds__(256) void leftmul_narrow_f32_kernel(const float* __
 #pragma unroll
     for (int q = 0; q < NQ; ++q) acc[q] = 0.0f;
 
+    // the union of the block's four tiles and all segments (the chunks the MFMA kernel's 128-row workgroup stages)
+    const int2* __restrict__ ranges = band_ranges_of(br);
     int lo = 0, hi = Ri, ns = 1, sw = Ri;
     if (ranges != nullptr) {
-        ns = nseg; sw = segw; lo = segw; hi = 0;
-        for (int sg = 0; sg < nseg; ++sg) {
-            const int2 v = ranges[blockIdx.y * nseg + sg];
-            if (v.y > 0) { lo = min(lo, ((segw - v.x) / LM_BK) * LM_BK); hi = max(hi, min(v.y, segw)); }
-        }
-        if (hi <= lo) lo = hi = 0;
+        ns = nseg; sw = segw;
+        constexpr int NT = LM_BM / LM_TILE;
+        band_union(ranges + (long)blockIdx.y * NT * nseg, min(NT, band_tiles(Ro - i0)), nseg, segw, LM_BK, lo, hi);
     }
     const int per = (hi - lo + LM_BK - 1) / LM_BK;
     const int total = per * ns;
