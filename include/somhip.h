@@ -115,6 +115,23 @@ int som_get_weights(som_handle* h, float* w_host);
  * must outlive the handle's use of them). */
 int som_set_data(som_handle* h, const float* x_host, int64_t n_rows);
 int som_set_data_device(som_handle* h, const void* x_dev, int64_t n_rows);
+/* Per-row sample weights of the resident rows, w_n >= 0 (scikit-style sample_weight):
+ *     num[k] = sum_n w_n h(bmu_n -> k) x_n,   den[k] = sum_n w_n h(bmu_n -> k),   W[k] = num[k] / den[k] where den[k] != 0.
+ * The BMUs are those of the unweighted call; the weights enter at one place, level 0 of the segment sum (csrc/update.hpp), where
+ * a row adds w_n x_n to its BMU's sum and w_n to its count.  Weights of 1.0 give the unweighted epoch bit for bit; an integer
+ * weight m counts the row m times; a row of weight 0 is not read at all (NaN / infinite features in it harm nothing); two
+ * weighted epochs from the same state are bitwise equal.  Applies to som_epoch_accumulate, som_epoch, the staged form and
+ * som_epoch_accumulate_forced; som_epoch_accumulate_faithful refuses to run while weights are set.
+ *   som_set_sample_weights          float32 [n_rows] in host memory, copied to a buffer the library owns.  n_rows must be the
+ *                                   resident row count; every value finite and >= 0 (checked on the host: the error names the first
+ *                                   offending index).  w_host == NULL or n_rows == 0 clears the weights.
+ *   som_set_sample_weights_device   float32 [n_rows] already in HBM, BORROWED like the rows of som_set_data_device (it must outlive
+ *                                   the handle's use of it; order the engine behind its producer with som_sync_producer).  The
+ *                                   CONTENTS ARE THE CALLER'S RESPONSIBILITY: nothing checks them, a negative, NaN or infinite
+ *                                   weight goes into the sums as it is.  NULL / 0 clears.
+ * som_set_data and som_set_data_device clear any weights: they belong to the rows they were set for. */
+int som_set_sample_weights(som_handle* h, const float* w_host, int64_t n_rows);
+int som_set_sample_weights_device(som_handle* h, const void* w_dev, int64_t n_rows);
 /* ... whose producer may still be running: wait for it first.  `stream` is the producer's stream as the
  * __cuda_array_interface__ protocol names it (1 = legacy default, 2 = per-thread default, otherwise a
  * hipStream_t); has_stream == 0 = unknown producer, wait for the whole device.  (The reference's CuPy arrays
@@ -170,6 +187,10 @@ int som_pinned_alloc(uint64_t bytes, void** out);
 int som_pinned_free(void* p);
 int som_stream_begin(som_handle* h);
 int som_stream_rows(som_handle* h, const float* x_host, int64_t n_rows);
+/* a chunk with its sample weights (w_host: float32 [n_rows], finite and >= 0, checked on the host; see som_set_sample_weights).
+ * They travel the way the rows do: with a pinned x_host on the copy stream into the device slot, else synchronously.  Weighted
+ * and unweighted chunks may follow each other; an unweighted chunk's rows count 1 each. */
+int som_stream_rows_weighted(som_handle* h, const float* x_host, const float* w_host, int64_t n_rows);
 int som_stream_end(som_handle* h, double sigma, double eta, int neigh_f64);
 
 /* The exchange step inside the library: one process per GPU, RCCL (bound at run time with dlopen -- the copy a host

@@ -39,6 +39,8 @@ SIGNATURES = {
     "som_get_weights": (C.c_int, [_H, _F]),
     "som_set_data": (C.c_int, [_H, _F, C.c_int64]),
     "som_set_data_device": (C.c_int, [_H, C.c_void_p, C.c_int64]),
+    "som_set_sample_weights": (C.c_int, [_H, _F, C.c_int64]),
+    "som_set_sample_weights_device": (C.c_int, [_H, C.c_void_p, C.c_int64]),
     "som_sync_producer": (C.c_int, [_H, C.c_uint64, C.c_int32]),
     "som_copy_to_host": (C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_void_p]),
     "som_epoch_accumulate": (C.c_int, [_H, C.c_double, C.c_double, C.c_int]),
@@ -57,6 +59,7 @@ SIGNATURES = {
     "som_pinned_free": (C.c_int, [C.c_void_p]),
     "som_stream_begin": (C.c_int, [_H]),
     "som_stream_rows": (C.c_int, [_H, _F, C.c_int64]),
+    "som_stream_rows_weighted": (C.c_int, [_H, _F, _F, C.c_int64]),
     "som_stream_end": (C.c_int, [_H, C.c_double, C.c_double, C.c_int]),
     "som_accum_device_ptr": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "som_get_stream": (C.c_int, [_H, C.POINTER(C.c_void_p)]),

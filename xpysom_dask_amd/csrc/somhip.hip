@@ -239,6 +239,10 @@ struct som_handle {
     const float* Xd = nullptr;   // X_owned, or the caller's device rows (som_set_data_device)
     DevBuf<float> X_owned;
     long N = 0, Np = 0;
+    // per-row sample weights of the resident rows (som_set_sample_weights*): float32 [N], finite, >= 0; nullptr = every row counts 1.
+    // They enter at level 0 of the run sum and nowhere else (update.hpp, runsum_kernel<.., WEIGHTED>)
+    const float* wgt = nullptr;  // wgt_owned, or the caller's device array (som_set_sample_weights_device)
+    DevBuf<float> wgt_owned;
     DevBuf<int> bmu;
     bool bmu_valid = false;  // bmu holds the ids of a completed BMU pass over the resident rows
     // precision 'exact': the update-side work that does not depend on the BMUs (the zeroed segment sums, the neighbourhood
@@ -265,6 +269,7 @@ struct som_handle {
 
     // scratch for som_bmu / som_quantization_error
     DevBuf<float> qX; DevBuf<int> qbmu, qbmu2; DevBuf<float> qxsq; DevBuf<__bf16> qXb;
+    DevBuf<float> qw;        // som_stream_rows_weighted, pageable chunk: its weights
     DevBuf<double> qX64;     // som_bmu_f64: float64 query rows
     long qcap = 0;
     DevBuf<double> dsum;
@@ -288,6 +293,7 @@ struct som_handle {
     // double-buffered device staging for chunks that arrive in pinned host memory
     struct Slot {
         DevBuf<float> dX; DevBuf<__bf16> dXb; DevBuf<float> dxsq; DevBuf<int> dbmu;
+        DevBuf<float> dw;                        // the chunk's sample weights (som_stream_rows_weighted), allocated on first use
         long cap = 0;
         hipEvent_t copied = nullptr, consumed = nullptr;
         bool used = false;
@@ -1076,12 +1082,21 @@ int seg_reserve(som_handle* h, som_handle::SegScratch& sg, long rows) {
 // one level of the run sum over n entries; returns the number of workgroups it used
 template <bool LEVEL0>
 long launch_runsum(som_handle* h, const float* X, const int* keys, const int* srow, const float* vin, long n,
-                   int accumulate, int* kout, float* vout) {
+                   int accumulate, int* kout, float* vout, const float* wgt = nullptr) {
     const int nw = seg_waves_per_block(h->D1p);
     const int chunk = LEVEL0 ? SEG_CHUNK : seg_chunk_up(n, nw);
     const long blocks = cdiv(n, (long)nw * chunk);
     const dim3 grid((unsigned)blocks), block(64 * nw);
     const size_t lds = nw > 1 ? (size_t)2 * nw * (h->D1p + 1) * sizeof(float) : 0;
+    if constexpr (LEVEL0) {
+        if (wgt != nullptr) {                            // sample weights: the weighted instances of level 0
+            if ((h->D & 1) == 0)
+                runsum_kernel<true, true, true><<<grid, block, lds, h->stream>>>(X, keys, srow, vin, n, chunk, h->D, h->D1p, accumulate, h->SC, h->SC + (size_t)h->K * h->D1p, kout, vout, wgt);
+            else
+                runsum_kernel<true, false, true><<<grid, block, lds, h->stream>>>(X, keys, srow, vin, n, chunk, h->D, h->D1p, accumulate, h->SC, h->SC + (size_t)h->K * h->D1p, kout, vout, wgt);
+            return blocks;
+        }
+    }
     if ((h->D & 1) == 0)
         runsum_kernel<LEVEL0, true><<<grid, block, lds, h->stream>>>(X, keys, srow, vin, n, chunk, h->D, h->D1p, accumulate, h->SC, h->SC + (size_t)h->K * h->D1p, kout, vout);
     else
@@ -1092,7 +1107,9 @@ long launch_runsum(som_handle* h, const float* X, const int* keys, const int* sr
 // SC[b] += sum of the rows whose BMU is b (and their count): sort by BMU, then the levels of update.hpp's
 // run sum (rows -> partial lists) until one workgroup holds the whole list.  zero_first: SC starts from zero and
 // every unit is written once (plain stores); otherwise the chunk's sums are added to what SC holds.
-int segsum_rows(som_handle* h, const float* X, const int* bmu, long N, som_handle::SegScratch& sg, bool zero_first) {
+// wgt != nullptr: the sample weights of these N rows (device, indexed like X's rows): SC[b] = sum of w_n x_n, count = sum of w_n.
+int segsum_rows(som_handle* h, const float* X, const int* bmu, long N, som_handle::SegScratch& sg, bool zero_first,
+                const float* wgt = nullptr) {
     Timed t(h, SOM_K_SEGSUM);
     if (zero_first && !(h->early.done && X == h->Xd))   // (exact mode: already zeroed before the pass's read-back)
         HIPCHK(h, hipMemsetAsync(h->SC, 0, (size_t)h->K * (h->D1p + 1) * sizeof(float), h->stream));
@@ -1114,7 +1131,7 @@ int segsum_rows(som_handle* h, const float* X, const int* bmu, long N, som_handl
             if (int rc = radix_sort_rows(h, bmu, N, bits, sg.skey, sg.srow, sg.tmp)) return rc;
         }
         const int acc = zero_first ? 0 : 1;
-        long blocks = launch_runsum<true>(h, X, sg.skey, sg.srow, nullptr, N, acc, sg.kA, sg.vA);
+        long blocks = launch_runsum<true>(h, X, sg.skey, sg.srow, nullptr, N, acc, sg.kA, sg.vA, wgt);
         int *kin = sg.kA, *kout = sg.kB;
         float *vin = sg.vA, *vout = sg.vB;
         while (blocks > 1) {                             // 2 * blocks entries are waiting in (kin, vin)
@@ -1145,7 +1162,7 @@ NeighParams make_neigh_params(const som_handle* h, double sigma, double eta, int
 }
 
 int run_update(som_handle* h, double sigma, double eta, int neigh_f64) {
-    if (int rc = segsum_rows(h, h->Xd, h->bmu, h->N, h->seg, true)) return rc;
+    if (int rc = segsum_rows(h, h->Xd, h->bmu, h->N, h->seg, true, h->wgt)) return rc;
     return run_transform(h, sigma, eta, neigh_f64);
 }
 
@@ -1602,7 +1619,20 @@ int som_get_weights(som_handle* h, float* w_host) {
     return d2h_blocking(h, w_host, h->W, (size_t)h->K * h->D * sizeof(float));
 }
 
+namespace { void drop_graph(som_handle* h); }
+
+// no sample weights from here on; a captured epoch graph has the weighted or the unweighted instance of the segment sum baked in,
+// so it goes, and its warm-up epoch runs again
+static void clear_sample_weights(som_handle* h) {
+    if (h->wgt == nullptr) return;
+    h->wgt = nullptr;
+    h->wgt_owned.reset();
+    drop_graph(h);
+    h->graph_warm = 0;
+}
+
 static int adopt_rows(som_handle* h, int64_t n_rows) {
+    clear_sample_weights(h);                             // (weights belong to the rows they were set for)
     h->bmu.reset(); h->xsq.reset(); h->Xb.reset();
     h->bmu_valid = false;
     h->ex.plan.order_lost();                             // (the resident sorted pass belongs to the rows it was sorted from)
@@ -1772,6 +1802,8 @@ int som_epoch_accumulate_faithful(som_handle* h, double sigma, double eta, int n
     if (!h->Xd && h->N > 0) return fail(h, "som_epoch_accumulate_faithful: no resident data (call som_set_data)");
     if (h->swapped) return fail(h, "som_epoch_accumulate_faithful: mexican_hat with compact_support on the rectangular "
                                    "topology is not a sum of row factor x column factor terms");
+    if (h->wgt) return fail(h, "som_epoch_accumulate_faithful: sample weights are set; the faithful form is the cross-check of the "
+                               "unweighted update (clear them with som_set_sample_weights(h, NULL, 0))");
     if (int rc = run_activation_bmu(h, h->Xd, h->N, h->xsq, h->Xb, h->xmax2, h->bmu)) return rc;
     Timed t(h, SOM_K_KRON);
     if (int rc = build_tables(h, sigma, eta, neigh_f64, h->stream)) return rc;
@@ -1794,6 +1826,47 @@ int som_epoch_accumulate_forced(som_handle* h, const int32_t* bmu_host, double s
     return run_update(h, sigma, eta, neigh_f64);
 }
 
+// ---- per-row sample weights (include/somhip.h) ------------------------------------------------
+// index of the first weight that is not finite or is negative, -1 = none
+static int64_t first_bad_weight(const float* w, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!(std::isfinite(w[i]) && w[i] >= 0.0f)) return i;
+    return -1;
+}
+static int fail_bad_weight(som_handle* h, const char* who, const float* w, int64_t i) {
+    char msg[160];
+    std::snprintf(msg, sizeof(msg), "%s: weight %lld is %g: sample weights must be finite and >= 0", who, (long long)i, (double)w[i]);
+    return fail(h, msg);
+}
+
+int som_set_sample_weights(som_handle* h, const float* w_host, int64_t n_rows) {
+    DeviceGuard dev_guard(h);
+    if (!h || n_rows < 0) return fail(h, "som_set_sample_weights: bad argument");
+    if (!w_host || n_rows == 0) { clear_sample_weights(h); return 0; }
+    if (n_rows != h->N) return fail(h, "som_set_sample_weights: one weight per resident row (set the rows first: som_set_data)");
+    if (const int64_t bad = first_bad_weight(w_host, n_rows); bad >= 0) return fail_bad_weight(h, "som_set_sample_weights", w_host, bad);
+    clear_sample_weights(h);
+    if (int rc = h->wgt_owned.alloc(h, (size_t)n_rows)) return rc;
+    if (int rc = h2d_blocking(h, h->wgt_owned, w_host, (size_t)n_rows * sizeof(float))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->wgt = h->wgt_owned;
+    drop_graph(h);
+    h->graph_warm = 0;
+    return 0;
+}
+
+int som_set_sample_weights_device(som_handle* h, const void* w_dev, int64_t n_rows) {
+    DeviceGuard dev_guard(h);
+    if (!h || n_rows < 0) return fail(h, "som_set_sample_weights_device: bad argument");
+    if (!w_dev || n_rows == 0) { clear_sample_weights(h); return 0; }
+    if (n_rows != h->N) return fail(h, "som_set_sample_weights_device: one weight per resident row (set the rows first: som_set_data)");
+    clear_sample_weights(h);
+    h->wgt = (const float*)w_dev;
+    drop_graph(h);
+    h->graph_warm = 0;
+    return 0;
+}
+
 // ---- streamed epoch: rows pass through HBM chunk by chunk (out-of-core data) ------------------
 int som_stream_begin(som_handle* h) {
     DeviceGuard dev_guard(h);
@@ -1811,7 +1884,7 @@ static int ensure_slot(som_handle* h, som_handle::Slot& sl, long n) {
     }
     if (n <= sl.cap) return 0;
     if (sl.used) HIPCHK(h, hipEventSynchronize(sl.consumed));
-    sl.dX.reset(); sl.dXb.reset(); sl.dxsq.reset(); sl.dbmu.reset(); sl.cap = 0;
+    sl.dX.reset(); sl.dXb.reset(); sl.dxsq.reset(); sl.dbmu.reset(); sl.dw.reset(); sl.cap = 0;
     long cap = round_up(n, ROW_PAD);
     if (int rc = sl.dX.alloc(h, (size_t)cap * h->D)) return rc;
     if (int rc = sl.dbmu.alloc(h, (size_t)cap)) return rc;
@@ -1828,9 +1901,8 @@ static bool is_pinned_host(const void* p) {
     return attr.type == hipMemoryTypeHost;
 }
 
-int som_stream_rows(som_handle* h, const float* x_host, int64_t n_rows) {
-    DeviceGuard dev_guard(h);
-    if (!h || n_rows < 0 || (n_rows > 0 && !x_host)) return fail(h, "som_stream_rows: bad argument");
+// one streamed chunk; w_host != nullptr: with its sample weights (checked by the caller)
+static int stream_rows(som_handle* h, const float* x_host, const float* w_host, int64_t n_rows) {
     if (!h->streaming) return fail(h, "som_stream_rows: call som_stream_begin first");
     if (n_rows == 0) return 0;
     if (n_rows > 0x7fffffffL) return fail(h, "som_stream_rows: more than 2^31-1 rows in one chunk");
@@ -1852,6 +1924,10 @@ int som_stream_rows(som_handle* h, const float* x_host, int64_t n_rows) {
         h->slot_idx ^= 1;
         if (int rc = ensure_slot(h, sl, n_rows)) return rc;
         if (sl.used) HIPCHK(h, hipEventSynchronize(sl.consumed));     // the kernels that read this slot are done
+        if (w_host) {                                    // the weights travel with the rows, on the copy stream, into the slot
+            if (int rc = sl.dw.reserve(h, (size_t)sl.cap)) return rc;
+            HIPCHK(h, hipMemcpyAsync(sl.dw, w_host, (size_t)n_rows * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
+        }
         HIPCHK(h, hipMemcpyAsync(sl.dX, x_host, bytes, hipMemcpyHostToDevice, h->copy_stream));
         HIPCHK(h, hipEventRecord(sl.copied, h->copy_stream));
         HIPCHK(h, hipStreamWaitEvent(h->stream, sl.copied, 0));
@@ -1859,20 +1935,37 @@ int som_stream_rows(som_handle* h, const float* x_host, int64_t n_rows) {
         if (h->cfg.precision != SOM_PREC_F32)
             if (int rc = prep_rows_bf16(h, sl.dX, n_rows, round_up(n_rows, ROW_PAD), sl.dXb, h->xmax2 + 1, sl.dxsq)) return rc;
         if (int rc = run_activation_bmu(h, sl.dX, n_rows, sl.dxsq, sl.dXb, h->xmax2 + 1, sl.dbmu)) return rc;
-        if (int rc = segsum_rows(h, sl.dX, sl.dbmu, n_rows, h->st_seg, false)) return rc;
+        if (int rc = segsum_rows(h, sl.dX, sl.dbmu, n_rows, h->st_seg, false, w_host ? (const float*)sl.dw : nullptr)) return rc;
         HIPCHK(h, hipEventRecord(sl.consumed, h->stream));
         sl.used = true;
         return 0;
     }
     // pageable chunk: staged by the runtime, synchronous; the caller's buffer is free on return
     if (int rc = h2d_blocking(h, h->qX, x_host, bytes)) return rc;
+    if (w_host) {                                        // (the stream is drained: nothing reads the old qw)
+        if (int rc = h->qw.reserve(h, (size_t)n_rows, 1024)) return rc;
+        if (int rc = h2d_blocking(h, h->qw, w_host, (size_t)n_rows * sizeof(float))) return rc;
+    }
     if (needs_xsq(h)) if (int rc = row_sq(h, h->qX, n_rows, h->qxsq)) return rc;
     if (h->cfg.precision != SOM_PREC_F32)
         if (int rc = prep_rows_bf16(h, h->qX, n_rows, round_up(n_rows, ROW_PAD), h->qXb, h->xmax2 + 1, h->qxsq)) return rc;
     if (int rc = run_activation_bmu(h, h->qX, n_rows, h->qxsq, h->qXb, h->xmax2 + 1, h->qbmu)) return rc;
-    if (int rc = segsum_rows(h, h->qX, h->qbmu, n_rows, h->st_seg, false)) return rc;
+    if (int rc = segsum_rows(h, h->qX, h->qbmu, n_rows, h->st_seg, false, w_host ? (const float*)h->qw : nullptr)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return 0;
+}
+
+int som_stream_rows(som_handle* h, const float* x_host, int64_t n_rows) {
+    DeviceGuard dev_guard(h);
+    if (!h || n_rows < 0 || (n_rows > 0 && !x_host)) return fail(h, "som_stream_rows: bad argument");
+    return stream_rows(h, x_host, nullptr, n_rows);
+}
+
+int som_stream_rows_weighted(som_handle* h, const float* x_host, const float* w_host, int64_t n_rows) {
+    DeviceGuard dev_guard(h);
+    if (!h || n_rows < 0 || (n_rows > 0 && (!x_host || !w_host))) return fail(h, "som_stream_rows_weighted: bad argument");
+    if (const int64_t bad = first_bad_weight(w_host, n_rows); bad >= 0) return fail_bad_weight(h, "som_stream_rows_weighted", w_host, bad);
+    return stream_rows(h, x_host, w_host, n_rows);
 }
 
 int som_pinned_alloc(uint64_t bytes, void** out) {
@@ -2068,7 +2161,7 @@ int som_epoch_accumulate_begin(som_handle* h, double sigma, double eta, int neig
     if (!h) return 1;
     if (!h->Xd && h->N > 0) return fail(h, "som_epoch_accumulate_begin: no resident data (call som_set_data)");
     if (int rc = run_activation_bmu(h, h->Xd, h->N, h->xsq, h->Xb, h->xmax2, h->bmu)) return rc;
-    if (int rc = segsum_rows(h, h->Xd, h->bmu, h->N, h->seg, true)) return rc;
+    if (int rc = segsum_rows(h, h->Xd, h->bmu, h->N, h->seg, true, h->wgt)) return rc;
     Timed t(h, SOM_K_KRON);
     if (int rc = run_transform_stage1(h, sigma, eta, neigh_f64)) return rc;
     h->staged_blocks_done = 0;

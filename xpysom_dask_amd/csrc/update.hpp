@@ -249,7 +249,11 @@ __host__ __device__ inline long seg_next_entries(long n, int c, int nw) { return
 // One chunk walk.  Entry i (< cnt <= 64) has key readlane(my_key, i), count readlane(my_cnt, i) and its vector at
 // ROWS ? X + readlane(my_row, i) * D : list + i * D1p.  Complete runs go to SC, the two possible partials to
 // slot0 / slot1 (rows of D1p floats); key0 / key1 return the slots' keys (-1 = unused).
-template <bool ROWS, bool VEC2>
+// WEIGHTED (with ROWS only): my_cnt holds the rows' sample weights w >= 0 instead of 1.0f.  A row enters the sum as
+// fmaf(w, x, acc) at the place and in the order the unweighted walk forms acc + x (fmaf(1, x, acc) rounds like acc + x:
+// weights of 1.0 give the unweighted sums bit for bit), and the count column carries the sum of the weights.  A row of
+// weight 0 is not loaded at all -- it is absent, not multiplied by 0, so its NaN / infinite features stay out of its unit.
+template <bool ROWS, bool VEC2, bool WEIGHTED = false>
 __device__ __forceinline__ void seg_walk(const float* __restrict__ X, const float* list, int my_key, int my_row,
                                          float my_cnt, int cnt, bool open_left, bool open_right, int D, int D1p,
                                          int accumulate, float* __restrict__ SC, float* __restrict__ cnt_dense,
@@ -311,7 +315,8 @@ __device__ __forceinline__ void seg_walk(const float* __restrict__ X, const floa
             for (int u = 0; u < 8; ++u) {
                 const int i = i0 + u;
                 const int ii = i < cnt ? i : 0;
-                const bool live = i < cnt && __builtin_amdgcn_readlane(my_key, ii) >= 0;
+                bool live = i < cnt && __builtin_amdgcn_readlane(my_key, ii) >= 0;
+                if (ROWS && WEIGHTED) live = live && __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_cnt), ii)) != 0.0f;
                 const float* x = ROWS ? X + (long)__builtin_amdgcn_readlane(my_row, ii) * D : list + (long)ii * D1p;
                 if (VEC2) {
 #pragma unroll
@@ -335,9 +340,10 @@ __device__ __forceinline__ void seg_walk(const float* __restrict__ X, const floa
                 if (i < cnt) {
                     const int b = __builtin_amdgcn_readlane(my_key, i);
                     if (b != cur) { flush(i); cur = b; run_begin = i; }
+                    const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_cnt), i));
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] += v[u][j];
-                    run += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_cnt), i));
+                    for (int j = 0; j < 4; ++j) acc[j] = (ROWS && WEIGHTED) ? __builtin_fmaf(w, v[u][j], acc[j]) : acc[j] + v[u][j];
+                    run += w;
                 }
             }
         }
@@ -353,18 +359,22 @@ __device__ __forceinline__ void seg_walk(const float* __restrict__ X, const floa
 
 // LEVEL0: keys = sorted BMUs, srow = sorted row ids, rows gathered from X (count 1 each).
 // !LEVEL0: keys / vin = the previous level's partial list ([n] keys, [n][D1p] vectors, count in column D).
+// WEIGHTED (LEVEL0 only): wgt[row id] is the row's sample weight (float32, finite, >= 0) -- the count 1 of the row becomes
+// its weight, its features enter the sum times the weight (seg_walk); the upper levels do not know the difference.
 // VEC2 (D even): a lane owns feature pairs (8-byte accesses, one instruction per 128 features of a row).
 // accumulate == 0: SC was zeroed and every unit is written at most once in the whole pass: plain stores.
 // Dynamic LDS: blockDim.x / 64 > 1 ? 2 * waves * (D1p + 1) floats : none (a one-wave block writes its slots
 // straight to the next list).
-template <bool LEVEL0, bool VEC2>
+template <bool LEVEL0, bool VEC2, bool WEIGHTED = false>
 __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void runsum_kernel(const float* __restrict__ X,
                                                                    const int* __restrict__ keys,
                                                                    const int* __restrict__ srow,
                                                                    const float* __restrict__ vin, long n, int chunk,
                                                                    int D, int D1p, int accumulate, float* __restrict__ SC,
                                                                    float* __restrict__ cnt_dense, int* __restrict__ kout,
-                                                                   float* __restrict__ vout) {
+                                                                   float* __restrict__ vout,
+                                                                   const float* __restrict__ wgt = nullptr) {
+    static_assert(LEVEL0 || !WEIGHTED, "run sum: only level 0 reads rows, so only level 0 is weighted");
     extern __shared__ __attribute__((aligned(16))) float seg_lds[];
     const int C = LEVEL0 ? SEG_CHUNK : chunk;             // <= 64: lane i holds entry i
     const int lane = threadIdx.x & 63;
@@ -380,7 +390,8 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void runsum_kernel(const float*
         // lane i < cnt holds the i-th (key, row, count) of the chunk
         const int my_key = lane < cnt ? keys[p0 + lane] : -1;
         const int my_row = (LEVEL0 && lane < cnt) ? srow[p0 + lane] : 0;
-        const float my_cnt = LEVEL0 ? 1.0f : ((lane < cnt && my_key >= 0) ? vin[(p0 + lane) * D1p + D] : 0.0f);
+        const float my_cnt = LEVEL0 ? (WEIGHTED ? (lane < cnt ? wgt[my_row] : 0.0f) : 1.0f)
+                                    : ((lane < cnt && my_key >= 0) ? vin[(p0 + lane) * D1p + D] : 0.0f);
         const int first_key = __builtin_amdgcn_readfirstlane(my_key);
         const int last_key = __builtin_amdgcn_readlane(my_key, cnt - 1);
         const int prev_key = p0 > 0 ? keys[p0 - 1] : -2;
@@ -389,7 +400,7 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void runsum_kernel(const float*
         const bool open_right = last_key >= 0 && __builtin_amdgcn_readfirstlane(next_key) == last_key;
         float* s0 = direct ? vout + (2 * blk) * (long)D1p : slots + (long)(2 * wave) * D1p;
         float* s1 = direct ? vout + (2 * blk + 1) * (long)D1p : slots + (long)(2 * wave + 1) * D1p;
-        seg_walk<LEVEL0, VEC2>(X, LEVEL0 ? nullptr : vin + p0 * (long)D1p, my_key, my_row, my_cnt, cnt, open_left,
+        seg_walk<LEVEL0, VEC2, WEIGHTED>(X, LEVEL0 ? nullptr : vin + p0 * (long)D1p, my_key, my_row, my_cnt, cnt, open_left,
                                open_right, D, D1p, accumulate, SC, cnt_dense, s0, s1, k0, k1);
     }
     if (direct) {

@@ -29,6 +29,7 @@ class HipEngine:
         self.x, self.y = int(x), int(y)
         self.n_rows = 0
         self._keepalive = None
+        self._weights_keepalive = None
         cfg = _lib.SomConfig(int(x), int(y), int(input_len), _lib.SOM_DIST[distance],
                              _lib.SOM_NEIGH[neighborhood], int(bool(compact_support)),
                              _lib.SOM_PREC[precision], int(device), float(std_coeff),
@@ -82,12 +83,30 @@ class HipEngine:
         self._check(self._lib.som_set_data(self._h, self._fp(data), data.shape[0]))
         self.n_rows = data.shape[0]
         self._keepalive = None
+        self._weights_keepalive = None        # (new rows: the library has dropped the old rows' weights)
 
     def set_data_device(self, dev_ptr, n_rows, keepalive=None):
         """Rows already resident in HBM (float32 [n][D]); `keepalive` is whatever owns them."""
         self._check(self._lib.som_set_data_device(self._h, C.c_void_p(dev_ptr), int(n_rows)))
         self.n_rows = int(n_rows)
         self._keepalive = keepalive
+        self._weights_keepalive = None
+
+    def set_sample_weights(self, w):
+        """Per-row weights of the resident rows (a host array of n_rows finite values >= 0); None clears them."""
+        if w is None:
+            self._check(self._lib.som_set_sample_weights(self._h, None, 0))
+        else:
+            w = _f32(w)
+            if w.shape != (self.n_rows,):
+                raise ValueError("sample weights must have one value per resident row")
+            self._check(self._lib.som_set_sample_weights(self._h, self._fp(w), w.shape[0]))
+        self._weights_keepalive = None
+
+    def set_sample_weights_device(self, dev_ptr, n_rows, keepalive=None):
+        """Weights already resident in HBM (float32 [n_rows], borrowed; contents unchecked); `keepalive` is whatever owns them."""
+        self._check(self._lib.som_set_sample_weights_device(self._h, C.c_void_p(dev_ptr), int(n_rows)))
+        self._weights_keepalive = keepalive
 
     def sync_producer(self, stream=None):
         """Wait for the producer of device rows: its `__cuda_array_interface__` stream, or (None) the device."""
@@ -181,13 +200,30 @@ class HipEngine:
         return arr
 
     def stream_epoch_accumulate(self, chunks, sigma, eta, neigh_f64):
-        """epoch_accumulate for rows handed over chunk by chunk (an iterable of (n_i, D) arrays)."""
+        """epoch_accumulate for rows handed over chunk by chunk: an iterable of (n_i, D) arrays, or of (rows, weights)
+        pairs with one sample weight per row -- one form or the other for the whole epoch."""
         self._check(self._lib.som_stream_begin(self._h))
+        weighted = None
         for chunk in chunks:
+            w = None
+            if isinstance(chunk, tuple):
+                if len(chunk) != 2:
+                    raise ValueError("a weighted chunk is a (rows, weights) pair")
+                chunk, w = chunk
+            if weighted is None:
+                weighted = w is not None
+            elif weighted != (w is not None):
+                raise ValueError("an epoch's chunks are all rows or all (rows, weights) pairs, not a mix")
             chunk = _f32(chunk)
             if chunk.ndim != 2 or chunk.shape[1] != self.D:
                 raise ValueError("chunk must be (n, %d), got %r" % (self.D, chunk.shape))
-            self._check(self._lib.som_stream_rows(self._h, self._fp(chunk), chunk.shape[0]))
+            if w is None:
+                self._check(self._lib.som_stream_rows(self._h, self._fp(chunk), chunk.shape[0]))
+            else:
+                w = _f32(w)
+                if w.shape != (chunk.shape[0],):
+                    raise ValueError("a chunk's weights must have one value per row, got %r for %d rows" % (w.shape, chunk.shape[0]))
+                self._check(self._lib.som_stream_rows_weighted(self._h, self._fp(chunk), self._fp(w), chunk.shape[0]))
         self._check(self._lib.som_stream_end(self._h, float(sigma), float(eta), int(bool(neigh_f64))))
         self.sync()                       # pinned chunks are copied asynchronously: their buffers are free now
 

@@ -53,6 +53,73 @@ def _device_rows(data):
     return None
 
 
+def _n_rows(data):
+    """Row count of host or device data without touching it."""
+    shape = getattr(data, "shape", None)
+    if shape is None:
+        cai = getattr(data, "__cuda_array_interface__", None)
+        shape = cai["shape"] if cai is not None else None
+    return int(shape[0]) if shape is not None and len(shape) > 0 else len(data)
+
+
+def _is_device_array(a):
+    if type(a).__module__.split(".")[0] == "torch":
+        return bool(getattr(a, "is_cuda", False))
+    return getattr(a, "__cuda_array_interface__", None) is not None
+
+
+def _check_sample_weight(sample_weight, n_rows, device_rows):
+    """``train``'s ``sample_weight`` validated against ``n_rows`` rows, before any engine exists (``ValueError`` otherwise):
+    one dimension, one value per row, a real dtype, every value finite and >= 0.  Returns a float32 host array -- or, for
+    weights that live in HBM next to device rows, the device array itself (a 1-D torch CUDA tensor or
+    ``__cuda_array_interface__`` object; its shape and dtype are checked here, its contents are the caller's business)."""
+    if _is_device_array(sample_weight):
+        if type(sample_weight).__module__.split(".")[0] == "torch":
+            shape, real = tuple(sample_weight.shape), not (sample_weight.is_complex() or sample_weight.dtype == __import__("torch").bool)
+        else:
+            cai = sample_weight.__cuda_array_interface__
+            shape, real = tuple(cai["shape"]), cai["typestr"] == "<f4" and cai.get("strides") is None
+            if not real:
+                raise ValueError('device sample_weight must be a C-contiguous float32 array')
+        if len(shape) != 1:
+            raise ValueError('sample_weight must be 1-dimensional, got shape %r' % (shape,))
+        if shape[0] != n_rows:
+            raise ValueError('sample_weight has %d values for %d rows of data' % (shape[0], n_rows))
+        if not real:
+            raise ValueError('sample_weight must have a real dtype, got %s' % (sample_weight.dtype,))
+        if device_rows:
+            return sample_weight
+        if not hasattr(sample_weight, "cpu"):
+            raise ValueError('sample_weight in device memory needs data in device memory')
+        sample_weight = sample_weight.detach().cpu().numpy()       # host rows: the weights join them on the host
+    w = np.asarray(sample_weight)
+    if w.ndim != 1:
+        raise ValueError('sample_weight must be 1-dimensional, got shape %r' % (w.shape,))
+    if len(w) != n_rows:
+        raise ValueError('sample_weight has %d values for %d rows of data' % (len(w), n_rows))
+    if w.dtype == np.bool_ or not (np.issubdtype(w.dtype, np.integer) or np.issubdtype(w.dtype, np.floating)):
+        raise ValueError('sample_weight must have a real dtype, got %s' % (w.dtype,))
+    with np.errstate(over='ignore'):
+        w32 = np.ascontiguousarray(w, dtype=np.float32)
+    bad = np.flatnonzero(~(np.isfinite(w32) & (w32 >= 0)))          # (as float32: what the device will hold)
+    if len(bad):
+        raise ValueError('sample_weight must be finite and >= 0: sample_weight[%d] is %r' % (bad[0], w[bad[0]].item()))
+    return w32
+
+
+def _device_weights(w):
+    """(pointer, device_index, owner, stream) of 1-D device weights as contiguous float32 (see _device_rows)."""
+    if type(w).__module__.split(".")[0] == "torch":
+        import torch
+        t = w.detach()
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            t = t.to(torch.float32).contiguous()
+        torch.cuda.current_stream(t.device).synchronize()
+        return t.data_ptr(), t.device.index, t, "done"
+    cai = w.__cuda_array_interface__
+    return int(cai["data"][0]), None, w, cai.get("stream")
+
+
 def _host_rows(x, engine=None):
     """float32 host view of array-like input; device rows are copied back through ``engine()`` (analysis
     calls only; the engine is not created for host input)."""
@@ -284,8 +351,15 @@ class XPySom:
             raise ValueError(msg)
 
     # ------------------------------------------------------------------ training
-    def train(self, data, num_epochs, iter_beg=0, iter_end=None, verbose=False):
+    def train(self, data, num_epochs, iter_beg=0, iter_end=None, verbose=False, *, sample_weight=None):
         """Trains the SOM (batch algorithm); same contract as xpysom.py:458-594.
+
+        ``sample_weight`` (keyword-only; not in the reference) gives the rows unequal importance: one finite value >= 0
+        per row of ``data``; a row of weight w adds w times its features to its BMU's sum and w to its count -- an
+        integer weight m is the row repeated m times, a weight of 0 leaves the row out (its features are not read).  The
+        BMU search does not see the weights.  A host array-like, or next to device rows a device array on the same
+        device.  Under a process group the weights are cut like the rows.  An argument of this call, not state: a later
+        ``train`` without it is unweighted.
 
         ``iter_beg``/``iter_end`` resume the schedule mid-run (decays are pure functions of
         (iteration, num_epochs)).  Under an initialised torch.distributed group the rows are
@@ -295,7 +369,17 @@ class XPySom:
             iter_end = num_epochs
 
         rank, world = _dist.dist_info()
-        if _device_rows(data) is not None:               # rows already in HBM: no host round trip
+        on_device = _device_rows(data) is not None
+        if not on_device:
+            data = np.asarray(data, dtype=np.float32)
+            if data.ndim != 2:
+                raise ValueError('data must be 2-dimensional (n_samples, input_len)')
+        weights = None
+        if sample_weight is not None:                    # refused here, before an engine (or a GPU) is needed
+            weights = _check_sample_weight(sample_weight, _n_rows(data), on_device)
+            if world > 1 and not self._sharded_input:    # cut like the rows: weight i stays with row i
+                weights = _dist.shard_rows(weights, rank, world, getattr(self, '_shard', 'contiguous'))
+        if on_device:                                    # rows already in HBM: no host round trip
             if world > 1 and not self._sharded_input:
                 data = _dist.shard_rows(data, rank, world, getattr(self, '_shard', 'contiguous'))
             ptr, n, d, dev_index, owner, stream = _device_rows(data)
@@ -308,13 +392,20 @@ class XPySom:
                 eng.sync_producer(stream)
             eng.set_data_device(ptr, n, keepalive=owner)
         else:
-            data = np.asarray(data, dtype=np.float32)
-            if data.ndim != 2:
-                raise ValueError('data must be 2-dimensional (n_samples, input_len)')
             if world > 1 and not self._sharded_input:
                 data = _dist.shard_rows(data, rank, world, getattr(self, '_shard', 'contiguous'))
             eng = self._upload_weights()
             eng.set_data(data)
+        # (set_data* has dropped any earlier call's weights: without sample_weight this call is the unweighted one)
+        if weights is not None and _is_device_array(weights):
+            wptr, wdev, wowner, wstream = _device_weights(weights)
+            if wdev is not None and wdev != eng.device:
+                raise ValueError('sample_weight lives on cuda:%d, the engine on cuda:%d' % (wdev, eng.device))
+            if wstream != "done":
+                eng.sync_producer(wstream)
+            eng.set_sample_weights_device(wptr, eng.n_rows, keepalive=wowner)
+        elif weights is not None:
+            eng.set_sample_weights(weights)
 
         try:
             for iteration in range(iter_beg, iter_end):
@@ -350,7 +441,8 @@ class XPySom:
 
         ``chunks`` is a callable returning a fresh iterable of ``(n_i, input_len)`` row blocks for each
         epoch (e.g. slices of a ``numpy.memmap``) -- the role Dask blocks play in the reference
-        (xpysom.py:545-556).  Every block goes host -> HBM, through the BMU kernel and into the same
+        (xpysom.py:545-556).  A block may also be a ``(rows, weights)`` pair with one sample weight per row
+        (``train``'s ``sample_weight``); an epoch's blocks are all of one form or all of the other (``ValueError``).  Every block goes host -> HBM, through the BMU kernel and into the same
         segment sums; the epoch ends with the usual transform, all-reduce and merge.  Under a process
         group each rank streams its own blocks."""
         if iter_end is None:
