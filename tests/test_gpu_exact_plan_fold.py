@@ -10,8 +10,8 @@ full), features 7, 33, 64, 100, 128 (every KS32 with a padded tail), fused and s
 epoch is repeated without a merge: the first planned launch is one the policy times (always the split kernels), the next ones are
 not, and take the fused launch where it is switched on.
 
-No case runs bfloat16 operands: every exact handle's screen and plan run IEEE half, and no switch selects another operand type for
-them -- the plan kernels' Bf16 instances are compiled and never launched; the bfloat16 split (8-bit parts) is checked on the CPU.
+No case runs bfloat16 operands: every exact handle's screen and plan run IEEE half (ExactEl, csrc/bmu_exact.hpp), and the plan
+kernels have no Bf16 instance (tests/test_kernel_instances_cpu.py); the bfloat16 split (8-bit parts) is checked on the CPU.
 
 MEASURED on an MI355X, blocks run by the four launches under B, folded against compared: identical ids in all forty cases; the
 folded plan never ran fewer blocks and in 18 of the 40 cases ran a few more -- per launch 0 to 4 of 600 to 1 200 (0.6 % at most);

@@ -82,6 +82,11 @@
 
 namespace somhip {
 
+// The exact mode's operand type.  The screen, the plan and the refinement pass run IEEE half: the bound above is derived for its
+// 11 significant bits and for operands scaled into [2^13, 2^14).  The ONE place that says so: the host side (exact_host.hpp,
+// exact_top2_host.hpp, the exact operand preparation in somhip.hip) instantiates every kernel it launches with ExactEl.
+using ExactEl = F16;
+
 constexpr int EX_GROUP = 64;          // units per group = one stage of the float32 stage image = one stage of the screen
 constexpr int EX_PAIRS = 64;          // least capacity of a pass in (row, group) pairs per row ON AVERAGE (exact_reserve sizes it)
 constexpr int EX_SCAN_SPLIT = 4;      // waves that share a row's groups in the scan

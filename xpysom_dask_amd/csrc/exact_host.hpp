@@ -119,7 +119,7 @@ int exact_reserve_stride(som_handle* h, long stride) {
     return 0;
 }
 
-template <int KS32, class E>
+template <int KS32>
 int exact_screen(som_handle* h, const __bf16* Xb, long n, unsigned long long* best64, const float* xsq, const float* xerr,
                  const float* xmax2, const ExactBound& eb, const float* seed, const int* glist, const int* gcnt,
                  const ScreenSelect& sel, bool* selected) {
@@ -128,7 +128,7 @@ int exact_screen(som_handle* h, const __bf16* Xb, long n, unsigned long long* be
     const int n_groups = (int)cdiv(h->K, EX_GROUP);
     // one pass on scaled half operands: a stage IS a group
     const bool tl = glist != nullptr;
-    const void* kern = tl ? (const void*)bmu_bf16_k16_kernel<KS32, E, true, true> : (const void*)bmu_bf16_k16_kernel<KS32, E, true, false>;
+    const void* kern = tl ? (const void*)bmu_bf16_k16_kernel<KS32, ExactEl, true, true> : (const void*)bmu_bf16_k16_kernel<KS32, ExactEl, true, false>;
     size_t lds = 2 * (size_t)k16_stage_bytes(KS32);
     int per_cu = 1;
     if (int rc = kernel_per_cu(h, kern, 64 * K16_NW, lds, &per_cu)) return rc;
@@ -153,28 +153,28 @@ int exact_screen(som_handle* h, const __bf16* Xb, long n, unsigned long long* be
         // (sel, where the pass asks for it: the workgroup that ends a tile selects its rows' candidates too -- the select tail of
         //  bmu_bf16_k16.hpp; *selected tells the pass that exact_select_kernel has nothing left to do)
         h->ex.screen_slots = (int)std::min<long>(slots, h->ex.item_slots);
-        bmu_bf16_k16_kernel<KS32, E, true, true><<<dim3((unsigned)h->ex.screen_slots), block, lds, h->stream>>>(
+        bmu_bf16_k16_kernel<KS32, ExactEl, true, true><<<dim3((unsigned)h->ex.screen_slots), block, lds, h->stream>>>(
             Xb, n, h->Wst, h->n_stages, h->K, best64, h->ex.gmin, h->ex.stride, h->ex.gflags, xsq, xerr, xmax2, h->wmax2, h->wmax2 + 1, eb,
             seed, glist, gcnt, h->ex.items + 8, (const int*)h->ex.items.p, (int*)h->ex.items.p + 1, nullptr, 0, sel);
         *selected = sel.plist != nullptr;
     } else if (tl)
-        bmu_bf16_k16_kernel<KS32, E, true, true><<<grid, block, lds, h->stream>>>(
+        bmu_bf16_k16_kernel<KS32, ExactEl, true, true><<<grid, block, lds, h->stream>>>(
             Xb, n, h->Wst, h->n_stages, h->K, best64, h->ex.gmin, h->ex.stride, h->ex.gflags, xsq, xerr, xmax2, h->wmax2, h->wmax2 + 1, eb,
             seed, glist, gcnt);
     else
-        bmu_bf16_k16_kernel<KS32, E, true, false><<<grid, block, lds, h->stream>>>(
+        bmu_bf16_k16_kernel<KS32, ExactEl, true, false><<<grid, block, lds, h->stream>>>(
             Xb, n, h->Wst, h->n_stages, h->K, best64, h->ex.gmin, h->ex.stride, h->ex.gflags, xsq, xerr, xmax2, h->wmax2, h->wmax2 + 1, eb,
             seed, nullptr, nullptr);
     return 0;
 }
 
 // beyond 128 features: the wide kernel's GM instance (groups = pairs of its 32-unit stages)
-template <int KS32, class E>
+template <int KS32>
 int exact_screen_wide(som_handle* h, const __bf16* Ximg, long n, unsigned long long* best64, const float* xsq, const float* xerr,
                       const float* xmax2, const ExactBound& eb, const int* glist = nullptr, const int* gcnt = nullptr) {
     if (glist != nullptr) {
         // under a plan (exact_skip_wide.hpp): every workgroup walks its tile's list of groups; parts where the lists are long
-        auto kern = bmu_bf16_wide_kernel<KS32, E, true, true>;
+        auto kern = bmu_bf16_wide_kernel<KS32, ExactEl, true, true>;
         const size_t lds = (size_t)WD_SLOTS * wd_stage_bytes(KS32);
         int per_cu = 1;
         if (int rc = kernel_per_cu(h, (const void*)kern, 64 * WD_NW, lds, &per_cu)) return rc;
@@ -191,18 +191,18 @@ int exact_screen_wide(som_handle* h, const __bf16* Ximg, long n, unsigned long l
         if (h->ex.item_queue && glist == h->ex.glist) {
             // (the plan's lists as a work queue: a workgroup per slot of the chip -- bmu_bf16_wide.hpp; the next plan cuts for this many)
             h->ex.screen_slots = (int)std::min<long>(slots, h->ex.item_slots);
-            bmu_bf16_wide_kernel<KS32, E, true, true><<<dim3((unsigned)h->ex.screen_slots), dim3(64 * WD_NW), lds, h->stream>>>(
+            bmu_bf16_wide_kernel<KS32, ExactEl, true, true><<<dim3((unsigned)h->ex.screen_slots), dim3(64 * WD_NW), lds, h->stream>>>(
                 (const char*)Ximg, n, h->Wst, h->n_stages, best64, h->ex.gmin, h->ex.stride, (uint32_t*)h->ex.gflags.p, xsq, xerr, xmax2,
                 h->wmax2, h->wmax2 + 1, eb, glist, gcnt, n_groups, nullptr, nullptr, nullptr, 0, h->ex.items + 8, (const int*)h->ex.items.p,
                 (int*)h->ex.items.p + 1);
             return 0;
         }
-        bmu_bf16_wide_kernel<KS32, E, true, true><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
+        bmu_bf16_wide_kernel<KS32, ExactEl, true, true><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
             (const char*)Ximg, n, h->Wst, h->n_stages, best64, h->ex.gmin, h->ex.stride, (uint32_t*)h->ex.gflags.p, xsq, xerr, xmax2,
             h->wmax2, h->wmax2 + 1, eb, glist, gcnt, n_groups);
         return 0;
     }
-    auto kern = bmu_bf16_wide_kernel<KS32, E, true>;
+    auto kern = bmu_bf16_wide_kernel<KS32, ExactEl, true>;
     const size_t lds = (size_t)WD_SLOTS * wd_stage_bytes(KS32);
     int per_cu = 1;
     if (int rc = kernel_per_cu(h, (const void*)kern, 64 * WD_NW, lds, &per_cu)) return rc;
@@ -224,23 +224,21 @@ int exact_screen_wide(som_handle* h, const __bf16* Ximg, long n, unsigned long l
     if (h->debug)
         std::fprintf(stderr, "[somhip] exact screen (wide): blocks=%ld per_cu=%d slots=%ld parts=%d groups=%d\n", blocks, per_cu, slots,
                      parts, n_groups);
-    bmu_bf16_wide_kernel<KS32, E, true><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
+    bmu_bf16_wide_kernel<KS32, ExactEl, true><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
         (const char*)Ximg, n, h->Wst, h->n_stages, best64, h->ex.gmin, h->ex.stride, (uint32_t*)h->ex.gflags.p, xsq, xerr, xmax2,
         h->wmax2, h->wmax2 + 1, eb);
     return 0;
 }
 
-template <class E>
 int exact_screen_ks(som_handle* h, const __bf16* Xb, long n, unsigned long long* best64, const float* xsq, const float* xerr,
                     const float* xmax2, const ExactBound& eb, const float* seed, const int* glist, const int* gcnt,
                     const ScreenSelect& sel, bool* selected) {
     *selected = false;
-    if (h->wide) {
-        SOM_WIDE_DISPATCH(exact_screen_wide, h, Xb, n, best64, xsq, xerr, xmax2, eb, glist, gcnt)
-        return fail(h, "exact: no wide screen instance for this input_len");
-    }
-    SOM_KS32_DISPATCH(exact_screen, h, Xb, n, best64, xsq, xerr, xmax2, eb, seed, glist, gcnt, sel, selected)
-    return fail(h, "exact: the screen kernel supports input_len <= 128");
+    if (h->wide)
+        return for_kchunks(h, "exact: no wide screen instance for this input_len", [&](auto k) {
+            return exact_screen_wide<decltype(k)::value>(h, Xb, n, best64, xsq, xerr, xmax2, eb, glist, gcnt); });
+    return for_ks32(h, "exact: the screen kernel supports input_len <= 128", [&](auto k) {
+        return exact_screen<decltype(k)::value>(h, Xb, n, best64, xsq, xerr, xmax2, eb, seed, glist, gcnt, sel, selected); });
 }
 
 
@@ -349,7 +347,6 @@ int exact_skip_reserve(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
 // and initial accumulators
 // (q_blocks > 0: the launch's prep_wsqh_kernel is still due as well -- best64, n_rows: its merge keys -- and rides along where the
 //  images go out in one grid; *q_done says whether it did)
-template <class E>
 int exact_skip_centroids(som_handle* h, const float* xmax2, unsigned q_blocks, unsigned long long* best64, long n_rows, bool* q_done) {
     auto& ex = h->ex;
     const float* Wsrc = h->ex_patch ? h->Wp : h->W;
@@ -374,7 +371,7 @@ int exact_skip_centroids(som_handle* h, const float* xmax2, unsigned q_blocks, u
         float* cm2 = cm ? (float*)c1.cmax2 : nullptr;
         const unsigned w_blocks = (unsigned)cdiv((long)h->n_stages * K16_T, 4);
         switch (h->ks32) {
-#define SOM_PIMG_CASE(k) case k: exact_prep_images_kernel<k, E><<<dim3(w_blocks + tgrid.x + q_blocks), block, 0, h->stream>>>(w_blocks, tgrid.x, Wex, h->K, h->D, h->Wst, h->n_stages, \
+#define SOM_PIMG_CASE(k) case k: exact_prep_images_kernel<k, ExactEl><<<dim3(w_blocks + tgrid.x + q_blocks), block, 0, h->stream>>>(w_blocks, tgrid.x, Wex, h->K, h->D, h->Wst, h->n_stages, \
             h->wmax2 + 1, h->Wst_lo, cm1, cm2, l1, c0.Cst, c0.n_cstages, l2, c1.Cst, nst2, xmax2, h->wmax2, plain, h->wn, h->stage_units, best64, n_rows); break;
         SOM_PIMG_CASE(1) SOM_PIMG_CASE(2) SOM_PIMG_CASE(3) SOM_PIMG_CASE(4)
 #undef SOM_PIMG_CASE
@@ -385,7 +382,7 @@ int exact_skip_centroids(som_handle* h, const float* xmax2, unsigned q_blocks, u
         return 0;
     }
     switch (h->ks32) {
-#define SOM_CIMG_CASE(k) case k: exact_centroid_image_kernel<k, E><<<tgrid, block, 0, h->stream>>>(l1, c0.Cst, c0.n_cstages, l2, c1.Cst, nst2, h->D, xmax2, h->wmax2, plain); break;
+#define SOM_CIMG_CASE(k) case k: exact_centroid_image_kernel<k, ExactEl><<<tgrid, block, 0, h->stream>>>(l1, c0.Cst, c0.n_cstages, l2, c1.Cst, nst2, h->D, xmax2, h->wmax2, plain); break;
     SOM_CIMG_CASE(1) SOM_CIMG_CASE(2) SOM_CIMG_CASE(3) SOM_CIMG_CASE(4)
 #undef SOM_CIMG_CASE
     default: return fail(h, "exact: block skipping supports input_len <= 128");
@@ -408,11 +405,10 @@ int exact_skip_sortkeys(som_handle* h, som_handle::ExactScratch::SortedRows& sr,
     return radix_sort_rows(h, ex.sk_keys, n, bits, ex.sk_keys2, sr.order + s0, ex.sk_tmp);
 }
 // ... and the operands gathered in that order (`order`: n positions -> rows of the pass) into sr at positions s0 ...
-template <class E>
 int exact_skip_gather(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, const int* order, const float* X, const __bf16* Xb, long n,
                       const float* xsq, const float* xerr, const float* xmax2) {
     const long np = round_up(n, SK_TILE);
-    exact_gather_sorted_kernel<E><<<dim3((unsigned)cdiv(np, 16)), dim3(256), 0, h->stream>>>(
+    exact_gather_sorted_kernel<ExactEl><<<dim3((unsigned)cdiv(np, 16)), dim3(256), 0, h->stream>>>(
         order, n, np, h->dp, h->D, Xb, X, xsq, xerr, xmax2, sr.Xb_s + s0 * h->dp, sr.Xl_s != nullptr ? sr.Xl_s + s0 * h->dp : nullptr, sr.Xf_s + s0 * h->D,
         sr.xsq_s + s0, sr.xerr_s + s0);
     HIPCHK(h, hipGetLastError());
@@ -420,54 +416,52 @@ int exact_skip_gather(som_handle* h, som_handle::ExactScratch::SortedRows& sr, l
 }
 
 // the scout, step 1: every row's nearest group centroid (the plain resident kernel on the plain level-1 centroid image)
-template <int KS32, class E>
+template <int KS32>
 int exact_scout_nearest_ks(som_handle* h, const __bf16* Xb, long n, unsigned long long* best64, int* g_out) {
     auto& ex = h->ex;
     const auto& c0 = ex.cen[0];
-    const void* kern = (const void*)bmu_bf16_k16_kernel<KS32, E, false, false>;
+    const void* kern = (const void*)bmu_bf16_k16_kernel<KS32, ExactEl, false, false>;
     const size_t lds = 2 * (size_t)k16_stage_bytes(KS32);
     int per_cu = 1;
     if (int rc = kernel_per_cu(h, kern, 64 * K16_NW, lds, &per_cu)) return rc;
     const long blocks = cdiv(n, K16_WG_SAMPLES);
     const long slots = resident_slots(h, per_cu);
     const int parts = std::max(1, std::min(choose_parts(h, blocks, slots, c0.n_cstages), c0.n_cstages));
-    bmu_bf16_k16_kernel<KS32, E, false, false><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * K16_NW), lds, h->stream>>>(
+    bmu_bf16_k16_kernel<KS32, ExactEl, false, false><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * K16_NW), lds, h->stream>>>(
         Xb, n, c0.Cst_plain, c0.n_cstages, c0.n_slots, best64);
     bmu_finalize_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(best64, n, c0.n_slots, g_out);
     HIPCHK(h, hipMemsetAsync(best64, 0xFF, (size_t)n * sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipGetLastError());
     return 0;
 }
-template <class E>
 int exact_scout_nearest(som_handle* h, const __bf16* Xb, long n, unsigned long long* best64, int* g_out) {
-    SOM_KS32_DISPATCH(exact_scout_nearest_ks, h, Xb, n, best64, g_out)
-    return fail(h, "exact: the scout supports input_len <= 128");
+    return for_ks32(h, "exact: the scout supports input_len <= 128",
+                    [&](auto k) { return exact_scout_nearest_ks<decltype(k)::value>(h, Xb, n, best64, g_out); });
 }
 
 // the scout, step 3: per tile of the SORTED pass the groups of its rows' keys (`keys`: the pass's sorted keys), the plain
 // kernel over those groups' units with indices kept: the best of them -> lastpos (the pseudo last BMU)
-template <int KS32, class E>
+template <int KS32>
 int exact_scout_pick_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, long n, const int* keys, unsigned long long* best64) {
     auto& ex = h->ex;
     const int n_groups = (int)cdiv(h->K, EX_GROUP);
     const long tiles = round_up(n, SK_TILE) / SK_TILE;
     const size_t lds_l = (size_t)cdiv(n_groups, 64) * sizeof(unsigned long long);
     exact_scout_lists_kernel<<<dim3((unsigned)tiles), dim3(64), lds_l, h->stream>>>(keys, nullptr, n, n_groups, ex.tlist, ex.tcnt);
-    const void* kern = (const void*)bmu_bf16_k16_kernel<KS32, E, false, true>;
+    const void* kern = (const void*)bmu_bf16_k16_kernel<KS32, ExactEl, false, true>;
     const size_t lds = 2 * (size_t)k16_stage_bytes(KS32);
     int per_cu = 1;
     if (int rc = kernel_per_cu(h, kern, 64 * K16_NW, lds, &per_cu)) return rc;
-    bmu_bf16_k16_kernel<KS32, E, false, true><<<dim3((unsigned)tiles, 1), dim3(64 * K16_NW), lds, h->stream>>>(
+    bmu_bf16_k16_kernel<KS32, ExactEl, false, true><<<dim3((unsigned)tiles, 1), dim3(64 * K16_NW), lds, h->stream>>>(
         sr.Xb_s + s0 * h->dp, n, h->Wst, h->n_stages, h->K, best64, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ExactBound(),
         nullptr, ex.tlist, ex.tcnt);
     exact_scout_pos_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(best64, n, h->K, sr.lastpos_s + s0);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
-template <class E>
 int exact_scout_pick(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, long n, const int* keys, unsigned long long* best64) {
-    SOM_KS32_DISPATCH(exact_scout_pick_ks, h, sr, s0, n, keys, best64)
-    return fail(h, "exact: the scout supports input_len <= 128");
+    return for_ks32(h, "exact: the scout supports input_len <= 128",
+                    [&](auto k) { return exact_scout_pick_ks<decltype(k)::value>(h, sr, s0, n, keys, best64); });
 }
 
 // the need bitmaps of a pass's plan -> the tiles' lists, their totals and the screen's work queue (the lists cut into items of
@@ -491,17 +485,12 @@ void exact_plan_lists(som_handle* h, long tiles, int n_cstages, const unsigned l
                                                                   n_items, n_items + 1, ex.item_len_pct);
 }
 
-// (the instances of exact_plan_fused_kernel that keep three workgroups a CU without scratch: <4, Bf16> comparing against P does
-//  not -- 168 VGPRs and 8 bytes of scratch a lane, bf16's conversions in the prologue -- and is not built: see plan_folds)
-template <int KS32, class E> constexpr bool plan_fused_fits() { return true; }
-// SOM_EXACT_PLAN_FOLD=0 (the plan kernels compare against P as before) is built for the F16 instances -- the operands of every
-// exact handle today --; a Bf16 instance always folds.
-template <class E> bool plan_folds(bool asked) { return asked || !std::is_same<E, F16>::value; }
+// (every ExactEl instance of the plan kernels is built both ways -- the threshold folded into the extra MFMA step, ex.plan_fold, and
+//  compared against P, SOM_EXACT_PLAN_FOLD=0 -- and every one of exact_plan_fused_kernel keeps three workgroups a CU without scratch)
 // one pass's plan on the sorted rows sr[s0, s0 + n): level 1 (+ the seeds, from lastpos_s), level 2, the tiles' item lists
 // -- in ONE launch (exact_plan_fused_kernel) where the pass is planned with level 2, from last BMUs alone (no scout), by one
 // workgroup per tile, and the policy does not time level 2 in this launch (time_l2: the split pair keeps cost.ev[3] .. ev[4]
 // around level 2, so that policy::Costs is fed as before); SOM_EXACT_FUSE_PLAN=0 / SOM_EXACT_CHAIN=0: always the split sequence
-template <class E>
 int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, long n, const float* xmax2, const ExactBound& eb,
                     const int* lastpos2, bool time_l2 = false) {
     auto& ex = h->ex;
@@ -526,9 +515,7 @@ int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
     // (the stage slots, the list of kept groups, level 2's and level 1's words, level 2's thresholds of the tile's rows: within the
     //  CU's 160 KB wherever level 2's own list fits -- policy::LaunchFacts::l2_fits_lds leaves 10 KB --, checked all the same)
     const size_t lds = lds2 + (size_t)c0.n_cstages * 8 + (size_t)SK_TILE * 8;   // (8 bytes a row: level 2's threshold as MFMA operands, exact_plan_fused_kernel)
-    const bool fits = h->ks32 != 4 || plan_fused_fits<4, E>();
-    const bool fold = plan_folds<E>(ex.plan_fold);
-    if (ex.fuse_plan && ex.chain && l2 && lastpos2 == nullptr && pgrid.y == 1 && !time_l2 && lds <= 160 * 1024 && fits) {
+    if (ex.fuse_plan && ex.chain && l2 && lastpos2 == nullptr && pgrid.y == 1 && !time_l2 && lds <= 160 * 1024) {
         PlanListsOut lo;
         lo.n_groups = (int)cdiv(h->K, EX_GROUP);
         lo.glist = ex.glist; lo.gcnt = ex.gcnt; lo.tile_counts = ex.tile_counts; lo.tlist = ex.tlist; lo.tcnt = ex.tcnt;
@@ -538,12 +525,10 @@ int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
         lo.items = ex.item_queue ? ex.items + 8 : nullptr;        // (as exact_plan_lists hands them to exact_lists_totals_kernel)
         lo.n_items = (int*)ex.items.p; lo.item_ctr = lo.n_items + 1; lo.len_pct = ex.item_len_pct;
 #define SOM_PLAN_FUSED_RUN(k, F) { \
-        { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_fused_kernel<k, E, F>, 64 * K16_NW, lds, &pc)) return rc; } \
-        exact_plan_fused_kernel<k, E, F><<<dim3((unsigned)tiles), block, lds, h->stream>>>(Xs, n, c0.Cst, c0.n_cstages, c0.cmax2, c1.Cst, c1.n_slots, \
+        { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_fused_kernel<k, ExactEl, F>, 64 * K16_NW, lds, &pc)) return rc; } \
+        exact_plan_fused_kernel<k, ExactEl, F><<<dim3((unsigned)tiles), block, lds, h->stream>>>(Xs, n, c0.Cst, c0.n_cstages, c0.cmax2, c1.Cst, c1.n_slots, \
             c1.cmax2, sr.xsq_s + s0, sr.xerr_s + s0, xmax2, h->wmax2, h->wmax2 + 1, eb, sr.lastpos_s + s0, h->Wst, sr.seed_s + s0, force, lo); }
-#define SOM_PLAN_FUSED_CASE(k) case k: if constexpr (plan_fused_fits<k, E>()) { \
-        if (fold) SOM_PLAN_FUSED_RUN(k, true) else if constexpr (std::is_same<E, F16>::value) SOM_PLAN_FUSED_RUN(k, false) \
-        } break;
+#define SOM_PLAN_FUSED_CASE(k) case k: if (ex.plan_fold) SOM_PLAN_FUSED_RUN(k, true) else SOM_PLAN_FUSED_RUN(k, false) break;
         switch (h->ks32) {
         SOM_PLAN_FUSED_CASE(1) SOM_PLAN_FUSED_CASE(2) SOM_PLAN_FUSED_CASE(3) SOM_PLAN_FUSED_CASE(4)
         default: return fail(h, "exact: block skipping supports input_len <= 128");
@@ -551,30 +536,30 @@ int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
 #undef SOM_PLAN_FUSED_CASE
 #undef SOM_PLAN_FUSED_RUN
         ++ex.plan_fused_launches;
-        ++(fold ? ex.plan_folded : ex.plan_compared);
+        ++(ex.plan_fold ? ex.plan_folded : ex.plan_compared);
         HIPCHK(h, hipGetLastError());
         return 0;
     }
     ++ex.plan_split_launches;
-    ++(fold ? ex.plan_folded : ex.plan_compared);
+    ++(ex.plan_fold ? ex.plan_folded : ex.plan_compared);
     // (level 1 stores every word; level 2 only those of the stages it walks: its words start from zero -- cleared by the level-1
     //  workgroups, each the words of its own stages; SOM_EXACT_CHAIN=0: by a fill)
     unsigned long long* const need2_clear = l2 && ex.chain ? ex.need2.p : nullptr;
     if (l2 && !ex.chain) HIPCHK(h, hipMemsetAsync(ex.need2, 0, (size_t)tiles * c1.n_cstages * sizeof(unsigned long long), h->stream));
 #define SOM_PLAN_RUN(k, F) { \
-        { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_kernel<k, E, false, F>, 64 * K16_NW, lds1, &pc)) return rc; } \
-        exact_plan_kernel<k, E, false, F><<<pgrid, block, lds1, h->stream>>>(Xs, n, c0.Cst, c0.n_cstages, c0.rg, c0.n_slots, \
+        { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_kernel<k, ExactEl, false, F>, 64 * K16_NW, lds1, &pc)) return rc; } \
+        exact_plan_kernel<k, ExactEl, false, F><<<pgrid, block, lds1, h->stream>>>(Xs, n, c0.Cst, c0.n_cstages, c0.rg, c0.n_slots, \
             sr.xsq_s + s0, sr.xerr_s + s0, sr.sU_s + s0, xmax2, c0.cmax2, h->wmax2, h->wmax2 + 1, eb, ex.need, sr.lastpos_s + s0, \
             h->Wst, sr.seed_s + s0, nullptr, 0, force, lastpos2, lastpos2 != nullptr ? &ctr->scout_wins : nullptr, need2_clear); \
         if (l2) { \
             if (time_l2) (void)hipEventRecord(ex.cost.ev[3], h->stream); \
-            { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_kernel<k, E, true, F>, 64 * K16_NW, lds2, &pc)) return rc; } \
-            exact_plan_kernel<k, E, true, F><<<dim3((unsigned)tiles, pgrid.y), block, lds2, h->stream>>>(Xs, n, c1.Cst, c1.n_cstages, c1.rg, c1.n_slots, \
+            { int pc; if (int rc = kernel_per_cu(h, (const void*)exact_plan_kernel<k, ExactEl, true, F>, 64 * K16_NW, lds2, &pc)) return rc; } \
+            exact_plan_kernel<k, ExactEl, true, F><<<dim3((unsigned)tiles, pgrid.y), block, lds2, h->stream>>>(Xs, n, c1.Cst, c1.n_cstages, c1.rg, c1.n_slots, \
                 sr.xsq_s + s0, sr.xerr_s + s0, sr.sU_s + s0, xmax2, c1.cmax2, h->wmax2, h->wmax2 + 1, eb, ex.need2, nullptr, \
                 nullptr, nullptr, ex.need, c0.n_cstages, force); \
             if (time_l2) (void)hipEventRecord(ex.cost.ev[4], h->stream); \
         } }
-#define SOM_PLAN_CASE(k) case k: if (fold) SOM_PLAN_RUN(k, true) else if constexpr (std::is_same<E, F16>::value) SOM_PLAN_RUN(k, false) break;
+#define SOM_PLAN_CASE(k) case k: if (ex.plan_fold) SOM_PLAN_RUN(k, true) else SOM_PLAN_RUN(k, false) break;
     switch (h->ks32) {
     SOM_PLAN_CASE(1) SOM_PLAN_CASE(2) SOM_PLAN_CASE(3) SOM_PLAN_CASE(4)
     default: return fail(h, "exact: block skipping supports input_len <= 128");
@@ -589,7 +574,6 @@ int exact_skip_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
 // ---- block skipping beyond 128 features (exact_skip_wide.hpp) ---------------------------------------------------------------
 // centroids, radii, |c|^2 of the groups under the current codebook; their 32-to-a-stage image with its tails and its measured
 // rounding error
-template <class E>
 int exact_wide_centroids(som_handle* h, const float* xmax2) {
     auto& ex = h->ex;
     auto& c0 = ex.cen[0];
@@ -597,9 +581,9 @@ int exact_wide_centroids(som_handle* h, const float* xmax2) {
     const int n_groups = (int)cdiv(h->K, EX_GROUP);
     wide_centroids_kernel<<<dim3((unsigned)n_groups), dim3(256), 0, h->stream>>>(Wsrc, h->K, h->D, n_groups, c0.Cc, c0.rg, c0.csq, c0.cmax2, h->wmax2);
     const long total = (long)c0.n_img_stages * WD_T * h->n_kchunks * 64;
-    prep_w_bf16_wide_kernel<E><<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(c0.Cc, n_groups, h->D, h->n_kchunks, c0.Cst, c0.n_img_stages,
+    prep_w_bf16_wide_kernel<ExactEl><<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(c0.Cc, n_groups, h->D, h->n_kchunks, c0.Cst, c0.n_img_stages,
                                                                                              nullptr, h->wmax2);
-    exact_werr_kernel<E><<<dim3((unsigned)cdiv(n_groups, 4 * EX_WERR_UNITS)), dim3(256), 0, h->stream>>>(c0.Cc, n_groups, h->D, h->wmax2, c0.cmax2 + 1, nullptr);
+    exact_werr_kernel<ExactEl><<<dim3((unsigned)cdiv(n_groups, 4 * EX_WERR_UNITS)), dim3(256), 0, h->stream>>>(c0.Cc, n_groups, h->D, h->wmax2, c0.cmax2 + 1, nullptr);
     char* plain = ex.lp.scout ? c0.Cst_plain : nullptr;
     if (plain) HIPCHK(h, hipMemcpyAsync(plain, c0.Cst, (size_t)c0.n_img_stages * h->stage_bytes, hipMemcpyDeviceToDevice, h->stream));
     wide_centroid_tail_kernel<<<dim3((unsigned)cdiv((long)c0.n_img_stages * WD_STAGE_UNITS, 256)), dim3(256), 0, h->stream>>>(
@@ -609,7 +593,6 @@ int exact_wide_centroids(som_handle* h, const float* xmax2) {
 }
 
 // the sorted pass: float32 rows, norms, last BMUs gathered in the order, the tile image built from the sorted rows
-template <class E>
 int exact_wide_gather(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, const float* X, long n, const float* xsq, const float* xerr,
                       const int* prev, const float* xmax2) {
     const long np = round_up(n, SK_TILE);
@@ -617,24 +600,24 @@ int exact_wide_gather(som_handle* h, som_handle::ExactScratch::SortedRows& sr, l
                                                                                       sr.Xf_s + s0 * h->D, sr.xsq_s + s0, sr.xerr_s + s0, sr.lastpos_s + s0);
     const long n_blocks = np / h->tl_bm;
     const long total = n_blocks * h->n_kchunks * (h->tl_bm / 16) * TL_KS * 64;
-    prep_tiles_bf16_kernel<E><<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
+    prep_tiles_bf16_kernel<ExactEl><<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
         sr.Xf_s + s0 * h->D, n, h->D, h->n_kchunks, n_blocks, h->tl_bm, h->tl_xtile, 1.0f, nullptr, (char*)(sr.Xb_s + s0 * h->dp), xmax2);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
 
 // the scout beyond 128 features, step 1: every row's nearest group centroid (the plain wide kernel on the plain centroid image)
-template <int KS32, class E>
+template <int KS32>
 int exact_wide_scout_nearest_ks(som_handle* h, const __bf16* Ximg, long n, unsigned long long* best64, int* g_out) {
     auto& ex = h->ex;
     const auto& c0 = ex.cen[0];
     const size_t lds = (size_t)WD_SLOTS * wd_stage_bytes(KS32);
     int per_cu = 1;
-    if (int rc = kernel_per_cu(h, (const void*)bmu_bf16_wide_kernel<KS32, E>, 64 * WD_NW, lds, &per_cu)) return rc;
+    if (int rc = kernel_per_cu(h, (const void*)bmu_bf16_wide_kernel<KS32, ExactEl>, 64 * WD_NW, lds, &per_cu)) return rc;
     const long blocks = cdiv(n, WD_WG_SAMPLES);
     const long slots = resident_slots(h, per_cu);
     const int parts = (int)std::max<long>(1, std::min<long>({cdiv(2 * slots, blocks), 8L, (long)c0.n_img_stages}));
-    bmu_bf16_wide_kernel<KS32, E><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
+    bmu_bf16_wide_kernel<KS32, ExactEl><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
         (const char*)Ximg, n, c0.Cst_plain, c0.n_img_stages, best64);
     bmu_finalize_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(best64, n, c0.n_slots, g_out);
     HIPCHK(h, hipMemsetAsync(best64, 0xFF, (size_t)n * sizeof(unsigned long long), h->stream));
@@ -643,7 +626,7 @@ int exact_wide_scout_nearest_ks(som_handle* h, const __bf16* Ximg, long n, unsig
 }
 // ... step 3: per tile of the sorted pass the groups of its rows' keys, the plain wide kernel over those groups' units with
 // indices kept: the best of them, as a UNIT id, -> lastpos_s (what the wide plan's float32 seed evaluates)
-template <int KS32, class E>
+template <int KS32>
 int exact_wide_scout_pick_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, long n, const int* keys, unsigned long long* best64) {
     auto& ex = h->ex;
     const int n_groups = (int)cdiv(h->K, EX_GROUP);
@@ -652,28 +635,26 @@ int exact_wide_scout_pick_ks(som_handle* h, som_handle::ExactScratch::SortedRows
     exact_scout_lists_kernel<<<dim3((unsigned)tiles), dim3(64), lds_l, h->stream>>>(keys, nullptr, n, n_groups, ex.glist, ex.gcnt, 1);
     const size_t lds = (size_t)WD_SLOTS * wd_stage_bytes(KS32);
     int per_cu = 1;
-    if (int rc = kernel_per_cu(h, (const void*)bmu_bf16_wide_kernel<KS32, E, false, true>, 64 * WD_NW, lds, &per_cu)) return rc;
-    bmu_bf16_wide_kernel<KS32, E, false, true><<<dim3((unsigned)tiles, 1), dim3(64 * WD_NW), lds, h->stream>>>(
+    if (int rc = kernel_per_cu(h, (const void*)bmu_bf16_wide_kernel<KS32, ExactEl, false, true>, 64 * WD_NW, lds, &per_cu)) return rc;
+    bmu_bf16_wide_kernel<KS32, ExactEl, false, true><<<dim3((unsigned)tiles, 1), dim3(64 * WD_NW), lds, h->stream>>>(
         (const char*)(sr.Xb_s + s0 * h->dp), n, h->Wst, h->n_stages, best64, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ExactBound(),
         ex.glist, ex.gcnt, n_groups);
     exact_scout_pos_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(best64, n, h->K, sr.lastpos_s + s0, h->ex_perm);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
-template <class E>
 int exact_wide_scout_nearest(som_handle* h, const __bf16* Ximg, long n, unsigned long long* best64, int* g_out) {
-    SOM_WIDE_DISPATCH(exact_wide_scout_nearest_ks, h, Ximg, n, best64, g_out)
-    return fail(h, "exact: no wide scout instance for this input_len");
+    return for_kchunks(h, "exact: no wide scout instance for this input_len",
+                       [&](auto k) { return exact_wide_scout_nearest_ks<decltype(k)::value>(h, Ximg, n, best64, g_out); });
 }
-template <class E>
 int exact_wide_scout_pick(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, long n, const int* keys, unsigned long long* best64) {
-    SOM_WIDE_DISPATCH(exact_wide_scout_pick_ks, h, sr, s0, n, keys, best64)
-    return fail(h, "exact: no wide scout instance for this input_len");
+    return for_kchunks(h, "exact: no wide scout instance for this input_len",
+                       [&](auto k) { return exact_wide_scout_pick_ks<decltype(k)::value>(h, sr, s0, n, keys, best64); });
 }
 
 // one pass's plan on the sorted rows: the float32 score of every row's last BMU, the rows' thresholds, the wide kernel in its
 // PLAN mode over the centroid image, the tiles' lists
-template <int KS32, class E>
+template <int KS32>
 int exact_wide_plan_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, long n, const float* xmax2, const ExactBound& eb) {
     auto& ex = h->ex;
     const auto& c0 = ex.cen[0];
@@ -685,13 +666,13 @@ int exact_wide_plan_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
     wide_plan_rows_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(n, sr.xsq_s + s0, sr.xerr_s + s0, ex.tq, xmax2, c0.cmax2, h->wmax2,
                                                                                   h->wmax2 + 1, eb, ex.skip_mode == 3 ? 1 : 0, sr.seed_s + s0, sr.sU_s + s0);
     HIPCHK(h, hipMemsetAsync(ex.need, 0, (size_t)tiles * c0.n_cstages * sizeof(unsigned long long), h->stream));
-    auto kern = bmu_bf16_wide_kernel<KS32, E, false, false, true>;
+    auto kern = bmu_bf16_wide_kernel<KS32, ExactEl, false, false, true>;
     const size_t lds = (size_t)WD_SLOTS * wd_stage_bytes(KS32) + (size_t)c0.n_cstages * sizeof(unsigned long long);
     int per_cu = 1;
     if (int rc = kernel_per_cu(h, (const void*)kern, 64 * WD_NW, lds, &per_cu)) return rc;
     const long slots = resident_slots(h, per_cu);
     int parts = (int)std::max<long>(1, std::min<long>({cdiv(2 * slots, tiles), 8L, (long)c0.n_img_stages}));
-    bmu_bf16_wide_kernel<KS32, E, false, false, true><<<dim3((unsigned)tiles, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
+    bmu_bf16_wide_kernel<KS32, ExactEl, false, false, true><<<dim3((unsigned)tiles, (unsigned)parts), dim3(64 * WD_NW), lds, h->stream>>>(
         (const char*)(sr.Xb_s + s0 * h->dp), n, c0.Cst, c0.n_img_stages, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ExactBound(),
         nullptr, nullptr, 0, sr.seed_s + s0, sr.sU_s + s0, ex.need, c0.n_cstages);
     // (the tiles' lists and the listed screen's work queue: the lists -- counted in 16-unit blocks, four to a group -- cut into items)
@@ -699,10 +680,9 @@ int exact_wide_plan_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, 
     HIPCHK(h, hipGetLastError());
     return 0;
 }
-template <class E>
 int exact_wide_plan(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, long n, const float* xmax2, const ExactBound& eb) {
-    SOM_WIDE_DISPATCH(exact_wide_plan_ks, h, sr, s0, n, xmax2, eb)
-    return fail(h, "exact: no wide plan instance for this input_len");
+    return for_kchunks(h, "exact: no wide plan instance for this input_len",
+                       [&](auto k) { return exact_wide_plan_ks<decltype(k)::value>(h, sr, s0, n, xmax2, eb); });
 }
 
 template <int KG>
@@ -724,7 +704,7 @@ int exact_rescore_kg(som_handle* h, const float* X, unsigned long long* best64, 
 inline unsigned exact_tiles_blocks(const som_handle* h) { return h->ex.chain ? 16u : 1u; }
 
 // the refinement pass over a sorted pass's candidate pairs (bmu_exact.hpp): tiles -> refined minima -> lists compacted in place
-template <int KS32, class E>
+template <int KS32>
 int exact_refine_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long r0, long n, const float* xmax2, const ExactBound& eb) {
     auto& ex = h->ex;
     const PassCtr pc = pass_ctr(h);
@@ -738,9 +718,9 @@ int exact_refine_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
     if (!ex.chain) HIPCHK(h, hipMemsetAsync(rowmin2, 0xFF, (size_t)n * sizeof(uint32_t), h->stream));
     const size_t lds = (size_t)k16_stage_bytes(KS32) + (size_t)K16_T * KS32 * 1024;
     int per_cu = 1;
-    if (int rc = kernel_per_cu(h, (const void*)exact_refine_kernel<KS32, E>, 256, lds, &per_cu)) return rc;
+    if (int rc = kernel_per_cu(h, (const void*)exact_refine_kernel<KS32, ExactEl>, 256, lds, &per_cu)) return rc;
     const long grid = std::min<long>(ex.max_tiles, h->ex.grid_mult * resident_slots(h, per_cu));
-    exact_refine_kernel<KS32, E><<<dim3((unsigned)grid), dim3(256), lds, h->stream>>>(
+    exact_refine_kernel<KS32, ExactEl><<<dim3((unsigned)grid), dim3(256), lds, h->stream>>>(
         sr.Xb_s + r0 * h->dp, sr.Xl_s + r0 * h->dp, h->Wst, h->Wst_lo, ex.tile_tab, n_tiles, ex.plist, ex.gmin, rowmin2);
     exact_thr2_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(rowmin2, n, sr.xsq_s + r0, sr.xerr_s + r0, h->wmax2, xmax2,
                                                                                h->wmax2 + 1, eb);
@@ -748,10 +728,9 @@ int exact_refine_ks(som_handle* h, som_handle::ExactScratch::SortedRows& sr, lon
     HIPCHK(h, hipGetLastError());
     return 0;
 }
-template <class E>
 int exact_refine(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long r0, long n, const float* xmax2, const ExactBound& eb) {
-    SOM_KS32_DISPATCH(exact_refine_ks, h, sr, r0, n, xmax2, eb)
-    return fail(h, "exact: the refinement pass supports input_len <= 128");
+    return for_ks32(h, "exact: the refinement pass supports input_len <= 128",
+                    [&](auto k) { return exact_refine_ks<decltype(k)::value>(h, sr, r0, n, xmax2, eb); });
 }
 
 // the lists' entries from gstart on -> tiles -> float32 scores merged into best64 (the pass's slice of the merge keys)
@@ -841,14 +820,14 @@ int exact_sample_tiles(som_handle* h, const ExactLaunch& L, som_handle::ExactScr
     int* s_order = ex.sk_keys;                    // (the sort's input keys and row ids: free since the sort)
     int* s_keys = ex.sk_vals;
     exact_sample_tiles_kernel<<<dim3((unsigned)n_st), dim3(SK_TILE), 0, h->stream>>>(sr.order + s0, ex.sk_keys2, st, s_order, s_keys);
-    if (int rc = SOM_HALF(h, exact_skip_gather, h, ss, 0L, s_order, L.X + r0 * h->D, L.Xb + r0 * h->dp, ns, L.xsq + r0, L.xerr + r0, L.xmax2)) return rc;
-    if (int rc = SOM_HALF(h, exact_scout_pick, h, ss, 0L, ns, s_keys, best)) return rc;
+    if (int rc = exact_skip_gather(h, ss, 0L, s_order, L.X + r0 * h->D, L.Xb + r0 * h->dp, ns, L.xsq + r0, L.xerr + r0, L.xmax2)) return rc;
+    if (int rc = exact_scout_pick(h, ss, 0L, ns, s_keys, best)) return rc;
     const int* lp2 = nullptr;
     if (L.f.have_last) {
         exact_lastpos_kernel<<<dim3((unsigned)cdiv(ns, 256)), dim3(256), 0, h->stream>>>(L.out + r0, s_order, h->ex_inv, ns, h->K, ex.scout_g);
         lp2 = ex.scout_g;                         // (the nearest groups have gone into the sort keys: free)
     }
-    if (int rc = SOM_HALF(h, exact_skip_plan, h, ss, 0L, ns, L.xmax2, L.eb, lp2)) return rc;
+    if (int rc = exact_skip_plan(h, ss, 0L, ns, L.xmax2, L.eb, lp2)) return rc;
     HIPCHK(h, hipMemcpyAsync(ex.pass_host, pc.tail(), sizeof(PassCounters), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     // (the sample's count of the scout's wins is not the pass's: cleared again)
@@ -914,9 +893,9 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
     const int* p_order = nullptr;
     if (lp.skip) {
         unsigned long long* best = h->best64 + r0;
-        if (lp.scout && h->wide) { if (int rc = SOM_HALF(h, exact_wide_scout_nearest, h, Xb + r0 * h->dp, n, best, ex.scout_g)) return rc; }
+        if (lp.scout && h->wide) { if (int rc = exact_wide_scout_nearest(h, Xb + r0 * h->dp, n, best, ex.scout_g)) return rc; }
         else if (lp.scout)
-            if (int rc = SOM_HALF(h, exact_scout_nearest, h, Xb + r0 * h->dp, n, best, ex.scout_g)) return rc;
+            if (int rc = exact_scout_nearest(h, Xb + r0 * h->dp, n, best, ex.scout_g)) return rc;
         if (lp.resort) {
             if (lp.time_phases) { HIPCHK(h, hipEventRecord(cost.ev[5], h->stream)); }
             if (int rc = exact_skip_sortkeys(h, sr, s0, n, out + r0, lp.scout ? ex.scout_g : nullptr)) return rc;
@@ -937,26 +916,26 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
         // beyond 128 features: the sorted float32 rows + the tile image built from them, the plan as a mode of the wide kernel
         if (lp.resort) {
             // (no last BMUs: `out` holds nothing yet -- the gather's copy of it is overwritten by the scout's picks below)
-            if (int rc = SOM_HALF(h, exact_wide_gather, h, sr, s0, X + r0 * h->D, n, xsq + r0, xerr + r0, have_last ? out + r0 : ex.scout_g, xmax2)) return rc;
+            if (int rc = exact_wide_gather(h, sr, s0, X + r0 * h->D, n, xsq + r0, xerr + r0, have_last ? out + r0 : ex.scout_g, xmax2)) return rc;
             if (lp.time_phases) { HIPCHK(h, hipEventRecord(cost.ev[6], h->stream)); L.o.sort_timed = true; }
             if (lp.scout)
-                if (int rc = SOM_HALF(h, exact_wide_scout_pick, h, sr, s0, n, ex.sk_keys2, h->best64 + r0)) return rc;
+                if (int rc = exact_wide_scout_pick(h, sr, s0, n, ex.sk_keys2, h->best64 + r0)) return rc;
         } else {
             wide_prev_sorted_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(sr.order + s0, n, out + r0, sr.lastpos_s + s0);
         }
-        if (int rc = SOM_HALF(h, exact_wide_plan, h, sr, s0, n, xmax2, eb)) return rc;
+        if (int rc = exact_wide_plan(h, sr, s0, n, xmax2, eb)) return rc;
         p_xsq = sr.xsq_s + s0; p_xerr = sr.xerr_s + s0; p_seed = nullptr; p_Xb = sr.Xb_s + s0 * h->dp; p_order = sr.order + s0;
         p_X = sr.Xf_s + s0 * h->D;
     } else if (lp.skip) {
         unsigned long long* best = h->best64 + r0;
         if (lp.resort) {
-            if (int rc = SOM_HALF(h, exact_skip_gather, h, sr, s0, sr.order + s0, X + r0 * h->D, Xb + r0 * h->dp, n, xsq + r0, xerr + r0, xmax2)) return rc;
+            if (int rc = exact_skip_gather(h, sr, s0, sr.order + s0, X + r0 * h->D, Xb + r0 * h->dp, n, xsq + r0, xerr + r0, xmax2)) return rc;
             if (lp.time_phases) { HIPCHK(h, hipEventRecord(cost.ev[6], h->stream)); L.o.sort_timed = true; }
             if (sr.Xl_s != nullptr && r0 + n >= N) sr.xl_filled = true;
         }
         const int* lastpos2 = nullptr;
         if (lp.scout) {
-            if (int rc = SOM_HALF(h, exact_scout_pick, h, sr, s0, n, ex.sk_keys2, best)) return rc;
+            if (int rc = exact_scout_pick(h, sr, s0, n, ex.sk_keys2, best)) return rc;
             if (have_last) {
                 // (the rows' real last BMUs beside the scout's picks: the plan's prologue keeps the better unit; sk_vals: free since the sort)
                 exact_lastpos_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(out + r0, sr.order + s0, h->ex_inv, n, h->K, ex.sk_vals);
@@ -966,7 +945,7 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
             // (carried: the last epoch's finalize has left exactly these positions in lastpos_s -- launch_bmu_exact)
             exact_lastpos_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(out + r0, sr.order + s0, h->ex_inv, n, h->K, sr.lastpos_s + s0);
         }
-        if (int rc = SOM_HALF(h, exact_skip_plan, h, sr, s0, n, xmax2, eb, lastpos2, lp.time_phases && lp.level2)) return rc;
+        if (int rc = exact_skip_plan(h, sr, s0, n, xmax2, eb, lastpos2, lp.time_phases && lp.level2)) return rc;
         if (lp.time_phases && lp.level2) L.o.l2_timed = true;
         p_xsq = sr.xsq_s + s0; p_xerr = sr.xerr_s + s0; p_seed = sr.seed_s + s0; p_Xb = sr.Xb_s + s0 * h->dp; p_order = sr.order + s0;
         p_X = sr.Xf_s + s0 * h->D;
@@ -983,7 +962,7 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
         Timed ts(h, SOM_K_SCREEN);
         if (lp.time_phases) { HIPCHK(h, hipEventRecord(cost.ev[1], h->stream)); }
         // (the lists the screen walks: dense 16-unit tiles up to 128 features, whole groups beyond)
-        if (int rc = SOM_HALF(h, exact_screen_ks, h, p_Xb, n, h->best64 + r0, p_xsq, p_xerr, xmax2, eb, p_seed,
+        if (int rc = exact_screen_ks(h, p_Xb, n, h->best64 + r0, p_xsq, p_xerr, xmax2, eb, p_seed,
                               lp.skip ? (h->wide ? ex.glist : ex.tlist) : nullptr,
                               lp.skip ? (h->wide ? ex.gcnt : ex.tcnt) : nullptr, screen_sel, &sel_fused)) return rc;
         if (lp.time_phases) { HIPCHK(h, hipEventRecord(cost.ev[2], h->stream)); L.o.screen_timed = true; }
@@ -1013,7 +992,7 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
                 pc.gcount(), ex.rowcnt, nullptr, p_seed, lp.skip ? ex.glist : nullptr, lp.skip ? ex.gcnt : nullptr, SK_TILE,
                 nullptr, 0, 0, lp.refine && ex.chain ? (uint32_t*)ex.rowarg.p : nullptr);
         if (lp.refine)
-            if (int rc = SOM_HALF(h, exact_refine, h, sr, s0, n, xmax2, eb)) return rc;
+            if (int rc = exact_refine(h, sr, s0, n, xmax2, eb)) return rc;
         if (int rc = exact_rescore_round(h, p_X, xsq + r0, best, nullptr, nullptr, lp.skip, !lp.refine)) return rc;
     }
     // (a sorted resident pass up to 128 features: the ids' positions in patch order stay behind for the next epoch's plan)
@@ -1130,8 +1109,8 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
         lp.cancel(); ex.skip_mode = 0;
     }
     if (lp.skip) {
-        if (h->wide) { if (int rc = SOM_HALF(h, exact_wide_centroids, h, xmax2)) return rc; }
-        else if (int rc = SOM_HALF(h, exact_skip_centroids, h, xmax2, wsqh_done ? 0u : wsqh_blocks, h->best64.p, N, &wsqh_done)) return rc;
+        if (h->wide) { if (int rc = exact_wide_centroids(h, xmax2)) return rc; }
+        else if (int rc = exact_skip_centroids(h, xmax2, wsqh_done ? 0u : wsqh_blocks, h->best64.p, N, &wsqh_done)) return rc;
     }
     if (int rc = flush_prep_w(h)) return rc;                 // (no plan, or the wide plan: the codebook's 16-bit image on its own)
     if (!wsqh_done) launch_wsqh();

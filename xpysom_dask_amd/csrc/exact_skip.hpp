@@ -332,6 +332,7 @@ template <> struct PlanPartFmt<F16> {                       // IEEE half: 11 sig
     static constexpr int M = 10, CMIN = -14, CMAX = 15;
     static constexpr float MINN = 0x1p-14f, MAXV = 65504.0f;
 };
+// (no kernel behind this one: the plan kernels are built for ExactEl = F16 alone; som_debug_plan_split runs the split on the host)
 template <> struct PlanPartFmt<Bf16> {                      // bfloat16: 8 significant bits, float32's exponents
     static constexpr int M = 7, CMIN = -100, CMAX = 100;
     static constexpr float MINN = 0x1p-126f, MAXV = 0x1.FEp127f;

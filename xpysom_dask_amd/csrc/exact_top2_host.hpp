@@ -13,10 +13,10 @@ bool exact_top2_fast(const som_handle* h) {
     return h->exact && !h->wide && !h->tiled && h->cfg.distance == SOM_DIST_EUCLIDEAN && h->D <= 128 && h->K >= 2 && h->t2.on;
 }
 
-template <int KS32, class E>
+template <int KS32>
 int exact_top2_screen(som_handle* h, const __bf16* Xb, long n, unsigned long long* best64, const float* xsq, const float* xerr,
                       const float* xmax2, const ExactBound& eb, int* parts_out, long* pitch_out) {
-    const void* kern = (const void*)bmu_bf16_k16_kernel<KS32, E, true, false, true>;
+    const void* kern = (const void*)bmu_bf16_k16_kernel<KS32, ExactEl, true, false, true>;
     const size_t lds = 2 * (size_t)k16_stage_bytes(KS32);
     int per_cu = 1;
     if (int rc = kernel_per_cu(h, kern, 64 * K16_NW, lds, &per_cu)) return rc;
@@ -29,17 +29,16 @@ int exact_top2_screen(som_handle* h, const __bf16* Xb, long n, unsigned long lon
     if (h->debug)
         std::fprintf(stderr, "[somhip] exact top-2 screen: blocks=%ld per_cu=%d slots=%ld parts=%d groups=%d\n", blocks, per_cu, slots,
                      parts, (int)cdiv(h->K, EX_GROUP));
-    bmu_bf16_k16_kernel<KS32, E, true, false, true><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * K16_NW), lds, h->stream>>>(
+    bmu_bf16_k16_kernel<KS32, ExactEl, true, false, true><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * K16_NW), lds, h->stream>>>(
         Xb, n, h->Wst, h->n_stages, h->K, best64, h->ex.gmin, h->ex.stride, h->ex.gflags, xsq, xerr, xmax2, h->wmax2, h->wmax2 + 1, eb,
         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->t2.m, pitch);
     *parts_out = parts; *pitch_out = pitch;
     return 0;
 }
-template <class E>
 int exact_top2_screen_ks(som_handle* h, const __bf16* Xb, long n, unsigned long long* best64, const float* xsq, const float* xerr,
                          const float* xmax2, const ExactBound& eb, int* parts_out, long* pitch_out) {
-    SOM_KS32_DISPATCH(exact_top2_screen, h, Xb, n, best64, xsq, xerr, xmax2, eb, parts_out, pitch_out)
-    return fail(h, "exact top-2: the screen kernel supports input_len <= 128");
+    return for_ks32(h, "exact top-2: the screen kernel supports input_len <= 128", [&](auto k) {
+        return exact_top2_screen<decltype(k)::value>(h, Xb, n, best64, xsq, xerr, xmax2, eb, parts_out, pitch_out); });
 }
 
 // round 2: the tiles of round 1 once more, every row's argmin without the unit at excl[row]
@@ -98,7 +97,7 @@ int exact_top2_pass(som_handle* h, const float* X, const float* xsq, const float
     long pitch = 0;
     {
         Timed ts(h, SOM_K_SCREEN);
-        if (int rc = SOM_HALF(h, exact_top2_screen_ks, h, Xb + r0 * h->dp, n, best1, xsq + r0, xerr + r0, xmax2, eb, &parts, &pitch)) return rc;
+        if (int rc = exact_top2_screen_ks(h, Xb + r0 * h->dp, n, best1, xsq + r0, xerr + r0, xmax2, eb, &parts, &pitch)) return rc;
     }
     exact_select_kernel<false, true><<<dim3((unsigned)cdiv(n, 64)), dim3(64 * EX_SCAN_SPLIT), 0, h->stream>>>(
         ex.gmin, ex.gflags, ex.stride, n_groups, n, best1, xsq + r0, h->wmax2, xmax2, eb, xerr + r0, h->wmax2 + 1, ex.plist, pc.gcount(),

@@ -471,35 +471,45 @@ int resolve_profile(som_handle* h) {
 }
 
 // ---- codebook-derived operands (w_sq cache, xpysom.py:529-537; bf16 / f16 stage image) -----
-// The half-precision paths are templates on the operand type's tag E (Bf16 or F16, som_common.hpp); SOM_HALF picks
-// the instance from the handle.
+// The 'bf16' and 'f16' paths are templates on the operand type's tag E (Bf16 or F16, som_common.hpp); SOM_HALF picks
+// the instance from the handle.  (The exact mode has one operand type, ExactEl -- bmu_exact.hpp -- and no such template.)
 #define SOM_HALF(h, fn, ...) ((h)->f16 ? fn<F16>(__VA_ARGS__) : fn<Bf16>(__VA_ARGS__))
-// ... and these the instance fn<KS32, E> for the handle's feature count: ks32 32-feature steps up to 128 features, n_kchunks
-// 64-feature chunks beyond (the wide kernel).  They return from the calling function; a count without an instance falls through.
-#define SOM_KS32_DISPATCH(fn, ...) \
-    switch (h->ks32) { \
-    case 1: return fn<1, E>(__VA_ARGS__); case 2: return fn<2, E>(__VA_ARGS__); case 3: return fn<3, E>(__VA_ARGS__); case 4: return fn<4, E>(__VA_ARGS__); }
-#define SOM_WIDE_DISPATCH(fn, ...) \
-    switch (h->n_kchunks) { \
-    case 5: return fn<5, E>(__VA_ARGS__); case 6: return fn<6, E>(__VA_ARGS__); case 7: return fn<7, E>(__VA_ARGS__); case 8: return fn<8, E>(__VA_ARGS__); \
-    case 9: return fn<9, E>(__VA_ARGS__); case 10: return fn<10, E>(__VA_ARGS__); case 11: return fn<11, E>(__VA_ARGS__); case 12: return fn<12, E>(__VA_ARGS__); \
-    case 13: return fn<13, E>(__VA_ARGS__); case 14: return fn<14, E>(__VA_ARGS__); case 15: return fn<15, E>(__VA_ARGS__); case 16: return fn<16, E>(__VA_ARGS__); \
-    case 17: return fn<17, E>(__VA_ARGS__); case 18: return fn<18, E>(__VA_ARGS__); case 19: return fn<19, E>(__VA_ARGS__); case 20: return fn<20, E>(__VA_ARGS__); \
-    case 21: return fn<21, E>(__VA_ARGS__); case 22: return fn<22, E>(__VA_ARGS__); case 23: return fn<23, E>(__VA_ARGS__); case 24: return fn<24, E>(__VA_ARGS__); \
-    case 25: return fn<25, E>(__VA_ARGS__); }
+// ... and these call f with the handle's feature count as a std::integral_constant, so that f names the instance it wants:
+// ks32 32-feature steps up to 128 features, n_kchunks 64-feature chunks beyond (the wide kernel).  A count without an
+// instance fails with `none`.
+template <class F>
+int for_ks32(som_handle* h, const char* none, F&& f) {
+    switch (h->ks32) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    }
+    return fail(h, none);
+}
+template <class F>
+int for_kchunks(som_handle* h, const char* none, F&& f) {
+    switch (h->n_kchunks) {
+#define SOM_KCHUNKS_CASE(k) case k: return f(std::integral_constant<int, k>{});
+    SOM_KCHUNKS_CASE(5) SOM_KCHUNKS_CASE(6) SOM_KCHUNKS_CASE(7) SOM_KCHUNKS_CASE(8) SOM_KCHUNKS_CASE(9) SOM_KCHUNKS_CASE(10) SOM_KCHUNKS_CASE(11)
+    SOM_KCHUNKS_CASE(12) SOM_KCHUNKS_CASE(13) SOM_KCHUNKS_CASE(14) SOM_KCHUNKS_CASE(15) SOM_KCHUNKS_CASE(16) SOM_KCHUNKS_CASE(17) SOM_KCHUNKS_CASE(18)
+    SOM_KCHUNKS_CASE(19) SOM_KCHUNKS_CASE(20) SOM_KCHUNKS_CASE(21) SOM_KCHUNKS_CASE(22) SOM_KCHUNKS_CASE(23) SOM_KCHUNKS_CASE(24) SOM_KCHUNKS_CASE(25)
+#undef SOM_KCHUNKS_CASE
+    }
+    return fail(h, none);
+}
 
 // the exact mode's 16-bit stage image up to 128 features (cm: with the centroid levels' maxima -- the fused merge wrote the
 // centroids).  It is due whenever the codebook has changed; a planned launch writes it in one grid with its centroid images
 // (exact_prep_images_kernel), which only launch_bmu_exact can know: its caller lets the refresh leave this one kernel pending
 // (operands::State), and the launch -- or, should it not get there, the next refresh -- pays it
-template <class E>
 int launch_prep_w_exact(som_handle* h, bool cm) {
     const float* Wex = h->ex_patch ? h->Wp : h->W;
     float* cm1 = cm ? (float*)h->ex.cen[0].cmax2 : nullptr;
     float* cm2 = cm ? (float*)h->ex.cen[1].cmax2 : nullptr;
     const dim3 tgrid((unsigned)cdiv((long)h->n_stages * K16_T, 4)), block(256);
     switch (h->ks32) {
-#define SOM_PREPX_CASE(k) case k: prep_w_exact_k16_kernel<k, E><<<tgrid, block, 0, h->stream>>>(Wex, h->K, h->D, h->Wst, h->n_stages, h->wmax2, h->wmax2 + 1, h->Wst_lo, cm1, cm2); break;
+#define SOM_PREPX_CASE(k) case k: prep_w_exact_k16_kernel<k, ExactEl><<<tgrid, block, 0, h->stream>>>(Wex, h->K, h->D, h->Wst, h->n_stages, h->wmax2, h->wmax2 + 1, h->Wst_lo, cm1, cm2); break;
     SOM_PREPX_CASE(1) SOM_PREPX_CASE(2) SOM_PREPX_CASE(3) SOM_PREPX_CASE(4)
 #undef SOM_PREPX_CASE
     default: return fail(h, "the resident half-precision kernel supports input_len <= 128");
@@ -509,39 +519,55 @@ int launch_prep_w_exact(som_handle* h, bool cm) {
 int flush_prep_w(som_handle* h) {
     bool cm = false;
     if (!h->ops.take_pending_image(&cm)) return 0;
-    if (int rc = SOM_HALF(h, launch_prep_w_exact, h, cm)) return rc;
+    if (int rc = launch_prep_w_exact(h, cm)) return rc;
     HIPCHK(h, hipGetLastError());
     return 0;
 }
 
-// the 16-bit operand images of the codebook: stage / tile image, |w~|^2 per unit and its maximum
-// (r: the refresh's decision -- exact mode up to 128 features skips the norms step behind a fused merge and may leave the image kernel pending)
-template <class E>
-int prep_codebook_half(som_handle* h, const operands::Rebuilds& r) {
-    const float* unit = h->cfg.distance == SOM_DIST_COSINE ? h->wsq : nullptr;
-    // exact mode in patch order: the screen's image from the permuted codebook (refresh_codebook_operands wrote it)
+// the exact mode's 16-bit operand images of the codebook, in patch order where the handle has one (the screen's image from the
+// permuted codebook: refresh_codebook_operands wrote it)
+// (r: the refresh's decision -- up to 128 features it skips the norms step behind a fused merge and may leave the image kernel pending)
+int prep_codebook_exact(som_handle* h, const operands::Rebuilds& r) {
     const float* Wex = h->ex_patch ? h->Wp : h->W;
     const float* qex = h->ex_patch ? h->wsq_p : h->wsq;
     const dim3 block(256);
-    if (h->tiled) {
-        if (h->wide && h->exact) {
-            if (unit) unit = qex;
-            // exact mode beyond 128 features: the float32 kernel's own |w|^2 as the norm term (euclidean) or none (cosine:
-            // unit-length units, max |w| = 1), the units scaled by a power of two, their rounding errors measured
-            if (unit) {
-                HIPCHK(h, hipMemsetAsync(h->wn, 0, (size_t)h->K * sizeof(float), h->stream));
-                HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->wmax2, 0x3F800000, 1, h->stream));
-            } else {
-                HIPCHK(h, hipMemsetAsync(h->wmax2, 0, sizeof(float), h->stream));
-                exact_copy_wsq_kernel<<<dim3((unsigned)cdiv(h->K, 1024)), dim3(1024), 0, h->stream>>>(qex, h->K, h->wn, h->wmax2);
-            }
-            long total = (long)h->n_stages * WD_T * h->n_kchunks * 64;
-            prep_w_bf16_wide_kernel<E><<<dim3((unsigned)cdiv(total, 256)), block, 0, h->stream>>>(
-                Wex, h->K, h->D, h->n_kchunks, h->Wst, h->n_stages, unit, h->wmax2);
-            HIPCHK(h, hipMemsetAsync(h->wmax2 + 1, 0, sizeof(float), h->stream));
-            exact_werr_kernel<E><<<dim3((unsigned)cdiv(h->K, 4 * EX_WERR_UNITS)), block, 0, h->stream>>>(Wex, h->K, h->D, h->wmax2, h->wmax2 + 1, unit);
-            return 0;
+    if (h->wide) {
+        // beyond 128 features: the float32 kernel's own |w|^2 as the norm term (euclidean) or none (cosine:
+        // unit-length units, max |w| = 1), the units scaled by a power of two, their rounding errors measured
+        const float* unit = h->cfg.distance == SOM_DIST_COSINE ? qex : nullptr;
+        if (unit) {
+            HIPCHK(h, hipMemsetAsync(h->wn, 0, (size_t)h->K * sizeof(float), h->stream));
+            HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->wmax2, 0x3F800000, 1, h->stream));
+        } else {
+            HIPCHK(h, hipMemsetAsync(h->wmax2, 0, sizeof(float), h->stream));
+            exact_copy_wsq_kernel<<<dim3((unsigned)cdiv(h->K, 1024)), dim3(1024), 0, h->stream>>>(qex, h->K, h->wn, h->wmax2);
         }
+        long total = (long)h->n_stages * WD_T * h->n_kchunks * 64;
+        prep_w_bf16_wide_kernel<ExactEl><<<dim3((unsigned)cdiv(total, 256)), block, 0, h->stream>>>(
+            Wex, h->K, h->D, h->n_kchunks, h->Wst, h->n_stages, unit, h->wmax2);
+        HIPCHK(h, hipMemsetAsync(h->wmax2 + 1, 0, sizeof(float), h->stream));
+        exact_werr_kernel<ExactEl><<<dim3((unsigned)cdiv(h->K, 4 * EX_WERR_UNITS)), block, 0, h->stream>>>(Wex, h->K, h->D, h->wmax2, h->wmax2 + 1, unit);
+        return 0;
+    }
+    // up to 128 features: the float32 kernel's own |w|^2 (refreshed just before) and its maximum first: the units go in scaled by
+    // ex_scale(max |w|^2); then the scaled stage image and the units' rounding errors in one pass
+    // (after a fused merge both are there already, and the pair was zeroed in front of it: exact_merge_prep_kernel)
+    if (!r.skip_norms) {
+        HIPCHK(h, hipMemsetAsync(h->wmax2, 0, 2 * sizeof(float), h->stream));     // [0]: max |w|^2, [1]: max_k |w^_k - w~_k|^2
+        exact_copy_wsq_kernel<<<dim3((unsigned)cdiv(h->K, 1024)), dim3(1024), 0, h->stream>>>(qex, h->K, h->wn, h->wmax2);
+    }
+    // (r.cm: centroids the fused merge wrote: their levels' maxima are due now that max |w|^2 is final)
+    if (h->ks32 < 1 || h->ks32 > 4) return fail(h, "the resident half-precision kernel supports input_len <= 128");
+    if (r.deferred) return 0;
+    return launch_prep_w_exact(h, r.cm);
+}
+
+// precisions 'bf16' and 'f16': the 16-bit operand images of the codebook -- stage / tile image, |w~|^2 per unit and its maximum
+template <class E>
+int prep_codebook_half(som_handle* h) {
+    const float* unit = h->cfg.distance == SOM_DIST_COSINE ? h->wsq : nullptr;
+    const dim3 block(256);
+    if (h->tiled) {
         if (h->wide) {
             long total = (long)h->n_stages * WD_T * h->n_kchunks * 64;
             prep_w_bf16_wide_kernel<E><<<dim3((unsigned)cdiv(total, 256)), block, 0, h->stream>>>(
@@ -558,19 +584,6 @@ int prep_codebook_half(som_handle* h, const operands::Rebuilds& r) {
     }
     const long total = (long)h->n_stages * K16_T * h->ks32 * 64;
     const dim3 grid((unsigned)cdiv(total, 256));
-    if (h->exact) {
-        // the float32 kernel's own |w|^2 (refreshed just before) and its maximum first: the units go in scaled by
-        // ex_scale(max |w|^2); then the scaled stage image and the units' rounding errors in one pass
-        // (after a fused merge both are there already, and the pair was zeroed in front of it: exact_merge_prep_kernel)
-        if (!r.skip_norms) {
-            HIPCHK(h, hipMemsetAsync(h->wmax2, 0, 2 * sizeof(float), h->stream));     // [0]: max |w|^2, [1]: max_k |w^_k - w~_k|^2
-            exact_copy_wsq_kernel<<<dim3((unsigned)cdiv(h->K, 1024)), dim3(1024), 0, h->stream>>>(qex, h->K, h->wn, h->wmax2);
-        }
-        // (r.cm: centroids the fused merge wrote: their levels' maxima are due now that max |w|^2 is final)
-        if (h->ks32 < 1 || h->ks32 > 4) return fail(h, "the resident half-precision kernel supports input_len <= 128");
-        if (r.deferred) return 0;
-        return launch_prep_w_exact<E>(h, r.cm);
-    }
     const float* sc = nullptr;
     switch (h->ks32) {
     case 1: prep_w_bf16_k16_kernel<1, E><<<grid, block, 0, h->stream>>>(h->W, h->K, h->D, h->Wst, h->n_stages, unit, sc); break;
@@ -595,7 +608,7 @@ int refresh_codebook_operands(som_handle* h, operands::Request rq, bool may_defe
     const operands::Rebuilds r = h->ops.decide(rq, may_defer);
     // (an image a BMU launch left pending and did not get to: whoever reads the operands next pays it)
     if (r.flush) {
-        if (int rc = SOM_HALF(h, launch_prep_w_exact, h, r.flush_cm)) return rc;
+        if (int rc = launch_prep_w_exact(h, r.flush_cm)) return rc;
         HIPCHK(h, hipGetLastError());
     }
     if (r.any()) {
@@ -620,7 +633,7 @@ int refresh_codebook_operands(som_handle* h, operands::Request rq, bool may_defe
                     Wsrc, qsrc, h->K, h->D, h->fr_kg, h->Wfst, h->fr_stages);
             }
         }
-        if (r.half) if (int rc = SOM_HALF(h, prep_codebook_half, h, r)) return rc;
+        if (r.half) if (int rc = h->exact ? prep_codebook_exact(h, r) : SOM_HALF(h, prep_codebook_half, h)) return rc;
         HIPCHK(h, hipGetLastError());
     }
     h->ops.commit(r);
@@ -819,10 +832,9 @@ int launch_bmu_bf16_wide(som_handle* h, const __bf16* Ximg, const float* xmax2, 
 
 template <class E>
 int launch_bmu_bf16_tiled(som_handle* h, const __bf16* Ximg, const float* xmax2, long N, int* out) {
-    if (h->wide) {
-        SOM_WIDE_DISPATCH(launch_bmu_bf16_wide, h, Ximg, xmax2, N, out)
-        return fail(h, "bmu_bf16_wide: no instance for this input_len");
-    }
+    if (h->wide)
+        return for_kchunks(h, "bmu_bf16_wide: no instance for this input_len",
+                           [&](auto k) { return launch_bmu_bf16_wide<decltype(k)::value, E>(h, Ximg, xmax2, N, out); });
     long cin = (long)h->n_ublocks * h->n_kchunks * h->tl_bn;
     prep_tiles_cin_kernel<<<dim3((unsigned)cdiv(cin, 256)), dim3(256), 0, h->stream>>>(
         h->wn, h->K, h->wmax2, xmax2, h->n_kchunks, h->n_ublocks, h->tl_bn, h->tl_wfrag, h->tl_wtile, h->Wst);
@@ -839,8 +851,8 @@ int launch_bmu_half(som_handle* h, const __bf16* Xb, const float* xmax2, long N,
     if (int rc = h->best64.reserve(h, (size_t)N, 1024)) return rc;
     prep_wsqh_kernel<<<dim3((unsigned)cdiv(std::max(units, N), 256)), dim3(256), 0, h->stream>>>(
         h->wn, h->K, h->wmax2, xmax2, h->Wst, h->n_stages, h->stage_bytes, h->stage_units, h->best64, N);
-    SOM_KS32_DISPATCH(launch_bmu_bf16_k16, h, Xb, N, out)
-    return fail(h, "bf16 precision supports input_len <= 128");
+    return for_ks32(h, "bf16 precision supports input_len <= 128",
+                    [&](auto k) { return launch_bmu_bf16_k16<decltype(k)::value, E>(h, Xb, N, out); });
 }
 
 int launch_bmu_bf16(som_handle* h, const __bf16* Xb, const float* xmax2, long N, int* out) {
@@ -857,29 +869,44 @@ float* exact_err_of(som_handle* h, const float* xsq) {
     return nullptr;
 }
 
-// rows -> bf16 operand image (+ max |x~|^2 for the offset B).  Cosine: the rows go in at unit length -- the
-// argmin does not depend on |x|, and B = max|x~| max|w~| then resolves every row alike (a short row next to
+// the exact mode's rows -> half operand image, max |x|^2 and the rows' measured rounding errors.  xsq_scratch: the rows' |x|^2 in
+// NumPy's order (the caller's row_sq); its second half takes the errors (exact_err_of)
+int prep_rows_exact(som_handle* h, const float* X, long N, long Np, __bf16* Xb, float* xmax2, float* xsq_scratch) {
+    HIPCHK(h, hipMemsetAsync(xmax2, 0, sizeof(float), h->stream));
+    if (h->tiled) {
+        // beyond 128 features: the tile image; cosine: the rows go in at unit length
+        float* xerr = exact_err_of(h, xsq_scratch);
+        if ((!xsq_scratch || !xerr) && N > 0) return fail(h, "exact: no row-norm buffer");
+        const bool unit = h->cfg.distance == SOM_DIST_COSINE;
+        const float* usq = unit ? xsq_scratch : nullptr;
+        if (unit) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)xmax2, 0x3F800000, 1, h->stream));   // unit-length rows: max |x| = 1
+        else if (N > 0) exact_max_kernel<<<dim3((unsigned)std::min<long>(cdiv(N, 256), 512)), dim3(256), 0, h->stream>>>(xsq_scratch, N, xmax2);
+        const long n_blocks = Np / h->tl_bm;
+        const long total = n_blocks * h->n_kchunks * (h->tl_bm / 16) * TL_KS * 64;
+        prep_tiles_bf16_kernel<ExactEl><<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
+            X, N, h->D, h->n_kchunks, n_blocks, h->tl_bm, h->tl_xtile, 1.0f, usq, (char*)Xb, xmax2);
+        if (N > 0) exact_rowerr_kernel<ExactEl><<<dim3((unsigned)cdiv(N, 4)), dim3(256), 0, h->stream>>>(X, N, h->D, usq, xmax2, xerr);
+        HIPCHK(h, hipGetLastError());
+        return 0;
+    }
+    // up to 128 features: max |x|^2 from the rows' float32 norms, then the rows scaled by ex_scale of it
+    if (!xsq_scratch && N > 0) return fail(h, "exact: no row norms");
+    float* xerr = exact_err_of(h, xsq_scratch);
+    if (!xerr && N > 0) return fail(h, "exact: unknown row-norm buffer");
+    if (N > 0) exact_max_kernel<<<dim3((unsigned)std::min<long>(cdiv(N, 256), 512)), dim3(256), 0, h->stream>>>(xsq_scratch, N, xmax2);
+    prep_x_bf16_kernel<ExactEl><<<dim3((unsigned)cdiv(Np, 4)), dim3(256), 0, h->stream>>>(X, N, h->D, h->dp, Np, Xb, nullptr, 0, xmax2, xerr);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// precisions 'bf16' and 'f16': rows -> 16-bit operand image (+ max |x~|^2 for the offset B).  Cosine: the rows go in at unit
+// length -- the argmin does not depend on |x|, and B = max|x~| max|w~| then resolves every row alike (a short row next to
 // long ones would otherwise be compared at B's absolute precision).  xsq_scratch: N floats, cosine + tiled only.
 template <class E>
 int prep_rows_half(som_handle* h, const float* X, long N, long Np, __bf16* Xb, float* xmax2, float* xsq_scratch) {
     const int Dp = h->dp;
     const bool unit = h->cfg.distance == SOM_DIST_COSINE;
     HIPCHK(h, hipMemsetAsync(xmax2, 0, sizeof(float), h->stream));
-    if (h->tiled && h->exact) {
-        // |x|^2 in NumPy's order is in xsq_scratch (the caller's row_sq); its second half takes the rounding errors
-        float* xerr = exact_err_of(h, xsq_scratch);
-        if ((!xsq_scratch || !xerr) && N > 0) return fail(h, "exact: no row-norm buffer");
-        const float* usq = unit ? xsq_scratch : nullptr;
-        if (unit) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)xmax2, 0x3F800000, 1, h->stream));   // unit-length rows: max |x| = 1
-        else if (N > 0) exact_max_kernel<<<dim3((unsigned)std::min<long>(cdiv(N, 256), 512)), dim3(256), 0, h->stream>>>(xsq_scratch, N, xmax2);
-        const long n_blocks = Np / h->tl_bm;
-        const long total = n_blocks * h->n_kchunks * (h->tl_bm / 16) * TL_KS * 64;
-        prep_tiles_bf16_kernel<E><<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(
-            X, N, h->D, h->n_kchunks, n_blocks, h->tl_bm, h->tl_xtile, 1.0f, usq, (char*)Xb, xmax2);
-        if (N > 0) exact_rowerr_kernel<E><<<dim3((unsigned)cdiv(N, 4)), dim3(256), 0, h->stream>>>(X, N, h->D, usq, xmax2, xerr);
-        HIPCHK(h, hipGetLastError());
-        return 0;
-    }
     if (h->tiled) {
         const float* usq = nullptr;
         if (unit && N > 0) {
@@ -896,20 +923,13 @@ int prep_rows_half(som_handle* h, const float* X, long N, long Np, __bf16* Xb, f
         HIPCHK(h, hipGetLastError());
         return 0;
     }
-    if (h->exact) {
-        // max |x|^2 from the rows' float32 norms (xsq_scratch: computed by the caller), then the rows scaled by ex_scale of it
-        if (!xsq_scratch && N > 0) return fail(h, "exact: no row norms");
-        float* xerr = exact_err_of(h, xsq_scratch);
-        if (!xerr && N > 0) return fail(h, "exact: unknown row-norm buffer");
-        if (N > 0) exact_max_kernel<<<dim3((unsigned)std::min<long>(cdiv(N, 256), 512)), dim3(256), 0, h->stream>>>(xsq_scratch, N, xmax2);
-        prep_x_bf16_kernel<E><<<dim3((unsigned)cdiv(Np, 4)), dim3(256), 0, h->stream>>>(X, N, h->D, Dp, Np, Xb, nullptr, 0, xmax2, xerr);
-    } else
-        prep_x_bf16_kernel<E><<<dim3((unsigned)cdiv(Np, 4)), dim3(256), 0, h->stream>>>(X, N, h->D, Dp, Np, Xb, xmax2, unit ? 1 : 0);
+    prep_x_bf16_kernel<E><<<dim3((unsigned)cdiv(Np, 4)), dim3(256), 0, h->stream>>>(X, N, h->D, Dp, Np, Xb, xmax2, unit ? 1 : 0);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
 
 int prep_rows_bf16(som_handle* h, const float* X, long N, long Np, __bf16* Xb, float* xmax2, float* xsq_scratch) {
+    if (h->exact) return prep_rows_exact(h, X, N, Np, Xb, xmax2, xsq_scratch);
     return SOM_HALF(h, prep_rows_half, h, X, N, Np, Xb, xmax2, xsq_scratch);
 }
 
