@@ -156,6 +156,15 @@ int som_policy_replay(int32_t n_launches, const double* script, double* out);
 #define SOM_OPERANDS_REPLAY_OUT 14
 int som_operands_replay(const int32_t* config, int32_t n_events, const int32_t* script, int32_t* out);
 
+/* The ROW SETS' size rule (csrc/row_set.hpp, rowset::sizes: what the resident rows, the query scratch and a pinned-chunk slot
+ * allocate for n rows) on caller-supplied numbers -- pure host arithmetic, NO device needed (tests/test_row_sets_cpu.py).
+ *   kind: 0 resident  1 query scratch  2 pinned-chunk slot;  dp: the feature stride of the 16-bit row image
+ *   flags: bit 0 precision is f32 (no 16-bit image)  bit 1 exact (|x|^2 holds the rows' errors in a second half)
+ *          bit 2 the configured search reads |x|^2  bit 3 cosine on the tiled 16-bit path (|x|^2 as scratch)
+ *   out5 = {cap, X, xsq, Xb, ids}: the rows the derived buffers hold, then elements per buffer (0: the set holds no such buffer;
+ *          a buffer that exists holds at least one element).  Returns non-zero for a NULL or out-of-range argument. */
+int som_debug_row_set_sizes(int32_t kind, int64_t n, int32_t input_len, int32_t dp, int32_t flags, int64_t* out5);
+
 #ifdef __cplusplus
 }
 #endif

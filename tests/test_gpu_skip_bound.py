@@ -7,7 +7,7 @@ radius that forgot a unit, centroids of the codebook before set_weights, a seed 
 under the wrong slot or the ignored tail of a partial group into a dropped BMU block -- a wrong id here.
 
 Every exact engine is paired with a precision='f32' engine.  Teacher-forced resident epoch: set_weights(A), set_data,
-epoch_accumulate (the last BMUs are the sheet units), set_weights(B) (bmu_valid survives it), epoch_accumulate -- ids equal
+epoch_accumulate (the last BMUs are the sheet units), set_weights(B) (ids_valid survives it), epoch_accumulate -- ids equal
 the float32 engine's on every row and the float64 BMU on every adversarial row, the launch ran under a plan and skipped
 (blocks_run < blocks_total); then a real merge (sigma 0.05: most units are reached by no row, den == 0) and a second epoch
 on the fused merge's centroids.  After both epochs the device's centroids, radii and |c|^2 are read back

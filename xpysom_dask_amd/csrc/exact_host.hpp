@@ -786,10 +786,10 @@ bool exact_skip_wanted(const som_handle* h) {
     return ex.skip_mode > 0 && ex.seed_on && (ex.skip_mode > 1 ? cdiv(h->K, EX_GROUP) >= 2 : h->K >= 4096);
 }
 
-// a launch: the row set (float32 rows, |x|^2 and measured operand errors, hi / lo operand image, the ids to write), the facts the
+// a launch: the row set (float32 rows, |x|^2 and measured operand errors, operand image, the ids to write), the facts the
 // policy decided on, and what the passes have measured and counted so far
 struct ExactLaunch {
-    const float* X; long N; const float* xsq; const float* xerr; const __bf16* Xb; const float* xmax2; int* out;
+    const Rows rows;
     ExactBound eb;
     int n_groups;
     bool two_round;
@@ -820,14 +820,15 @@ int exact_sample_tiles(som_handle* h, const ExactLaunch& L, som_handle::ExactScr
     int* s_order = ex.sk_keys;                    // (the sort's input keys and row ids: free since the sort)
     int* s_keys = ex.sk_vals;
     exact_sample_tiles_kernel<<<dim3((unsigned)n_st), dim3(SK_TILE), 0, h->stream>>>(sr.order + s0, ex.sk_keys2, st, s_order, s_keys);
-    if (int rc = exact_skip_gather(h, ss, 0L, s_order, L.X + r0 * h->D, L.Xb + r0 * h->dp, ns, L.xsq + r0, L.xerr + r0, L.xmax2)) return rc;
+    const Rows& R = L.rows;
+    if (int rc = exact_skip_gather(h, ss, 0L, s_order, R.X + r0 * h->D, R.Xb + r0 * h->dp, ns, R.xsq + r0, R.xerr + r0, R.xmax2)) return rc;
     if (int rc = exact_scout_pick(h, ss, 0L, ns, s_keys, best)) return rc;
     const int* lp2 = nullptr;
     if (L.f.have_last) {
-        exact_lastpos_kernel<<<dim3((unsigned)cdiv(ns, 256)), dim3(256), 0, h->stream>>>(L.out + r0, s_order, h->ex_inv, ns, h->K, ex.scout_g);
+        exact_lastpos_kernel<<<dim3((unsigned)cdiv(ns, 256)), dim3(256), 0, h->stream>>>(R.out + r0, s_order, h->ex_inv, ns, h->K, ex.scout_g);
         lp2 = ex.scout_g;                         // (the nearest groups have gone into the sort keys: free)
     }
-    if (int rc = exact_skip_plan(h, ss, 0L, ns, L.xmax2, L.eb, lp2)) return rc;
+    if (int rc = exact_skip_plan(h, ss, 0L, ns, R.xmax2, L.eb, lp2)) return rc;
     HIPCHK(h, hipMemcpyAsync(ex.pass_host, pc.tail(), sizeof(PassCounters), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     // (the sample's count of the scout's wins is not the pass's: cleared again)
@@ -848,13 +849,13 @@ int exact_sample_tiles(som_handle* h, const ExactLaunch& L, som_handle::ExactScr
 // rows the scheme could not settle (normally none): the float32 kernel itself
 int exact_fallback_rows(som_handle* h, const ExactLaunch& L, long r0, int n_fb) {
     auto& ex = h->ex;
-    int* out = L.out;
+    int* out = L.rows.out;
     if (int rc = ex.fbX.reserve(h, (size_t)n_fb * h->D, (size_t)1024 * h->D)) return rc;
     if (int rc = ex.fb_ids.reserve(h, (size_t)n_fb, 1024)) return rc;
     // the float32 kernel names units by their place in its image: the units' own order for it
     if (h->ops.f32_in_patch_order()) if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
     exact_gather_rows_kernel<<<dim3((unsigned)cdiv((long)n_fb * h->D, 256)), dim3(256), 0, h->stream>>>(
-        L.X + r0 * h->D, ex.fb_list, n_fb, h->D, ex.fbX);
+        L.rows.X + r0 * h->D, ex.fb_list, n_fb, h->D, ex.fbX);
     // (its part merge may reuse best64[0 .. n_fb): rows this pass has already settled)
     if (h->cfg.distance == SOM_DIST_COSINE) {
         // (|x|^2 of the gathered rows in NumPy's order, into the head of the pass's spent minima)
@@ -876,9 +877,9 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
     auto& lp = ex.lp;
     const PassCtr pc = pass_ctr(h);
     const int n_groups = L.n_groups;
-    const float* X = L.X; const float* xsq = L.xsq; const float* xerr = L.xerr; const __bf16* Xb = L.Xb; const float* xmax2 = L.xmax2;
-    int* out = L.out;
-    const long N = L.N;
+    const Rows& R = L.rows;
+    const float* X = R.X; const float* xsq = R.xsq; const float* xerr = R.xerr; const __bf16* Xb = R.Xb; const float* xmax2 = R.xmax2;
+    int* out = R.out; const long N = R.N;
     const ExactBound& eb = L.eb;
     const bool have_last = L.f.have_last;
     const long s0 = L.f.resident ? r0 : 0;               // where the pass sits in the sorted copies
@@ -1004,7 +1005,7 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(ex.pass_host, pc.tail(), sizeof(PassCounters), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipEventRecord(cost.ev[7], h->stream));
-    if (h->early.armed && !h->early.done && out == h->bmu && r0 + n >= N) {
+    if (h->early.armed && !h->early.done && R.resident && r0 + n >= N) {
         // the last pass of a resident epoch: the host waits for the counter only (an event behind the copy); what the
         // update needs besides the BMUs is queued behind it and runs while the host wakes up
         if (!ex.fb_ready) HIPCHK(h, hipEventCreateWithFlags(&ex.fb_ready, hipEventDisableTiming));
@@ -1041,12 +1042,11 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
     return 0;
 }
 
-// X, xsq, Xb, out: the row set's float32 rows, their |x|^2, their hi / lo operand image, the ids to write.
-int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, const __bf16* Xb, const float* xmax2, int* out) {
+// R: the row set's float32 rows, their |x|^2 and measured errors, their operand image, the ids to write.
+int launch_bmu_exact(som_handle* h, const Rows& R) {
     if (h->capturing) return fail(h, "precision 'exact' reads a counter back per pass: not capturable");
-    if (!xsq) return fail(h, "exact: no row norms");
-    const float* xerr = exact_err_of(h, xsq);
-    if (!xerr) return fail(h, "exact: unknown row-norm buffer");
+    if (!R.xsq || !R.xerr) return fail(h, "exact: no row norms");
+    const float* X = R.X; const long N = R.N; const float* xmax2 = R.xmax2;
     auto& ex = h->ex;
     auto& cost = ex.cost;
     auto& lp = ex.lp;
@@ -1069,7 +1069,7 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
     if (wsqh_done) launch_wsqh();
     const int n_groups = (int)cdiv(h->K, EX_GROUP);
     const long chunk = std::min(exact_chunk_rows(h), ex.stride);
-    ExactLaunch L{X, N, xsq, xerr, Xb, xmax2, out, exact_bound(h), n_groups, ex.two_round >= 0 ? ex.two_round != 0 : h->wide, {}, {}};
+    ExactLaunch L{R, exact_bound(h), n_groups, ex.two_round >= 0 ? ex.two_round != 0 : h->wide, {}, {}};
     // THE FACTS.  Block skipping (exact_skip.hpp), one round, <= 128 features, maps of >= 4096 units: a plan needs, per row, SOME
     // unit whose distance bounds the distance to the BMU.  RESIDENT rows from their second epoch on have last epoch's BMU; every
     // other row set (query rows, streamed chunks, a row set's first epoch) -- and resident rows while last epoch's BMUs say
@@ -1077,8 +1077,8 @@ int launch_bmu_exact(som_handle* h, const float* X, long N, const float* xsq, co
     // than its own fixed part (some thirty small launches) several times over: 2 N K D flop at the screen's rate against a
     // quarter of a millisecond, i.e. from some 40 000 rows of a 256 x 256 x 128 map on.
     policy::LaunchFacts& f = L.f;
-    f.resident = out == h->bmu;
-    f.have_last = f.resident && h->bmu_valid;
+    f.resident = R.resident;
+    f.have_last = R.ids_valid;
     f.rows = (const void*)X; f.n_rows = N;
     const bool scout_size_ok = ex.scout_on && n_groups <= 262144 &&
                                (ex.skip_mode > 1 || policy::rows_worth_a_scout((double)N, (double)h->K, (double)h->D));

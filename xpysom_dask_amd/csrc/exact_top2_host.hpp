@@ -84,9 +84,10 @@ int exact_top2_list_rows(som_handle* h, const float* X, const int* list, int n_l
 
 // ONE PASS over the rows [r0, r0 + n): best1 / best2 are the pass's slices of the two rounds' merge keys.  *bad_w: the codebook
 // holds a unit the scheme does not cover (the caller hands every row to the float32 kernel).
-int exact_top2_pass(som_handle* h, const float* X, const float* xsq, const float* xerr, const __bf16* Xb, const float* xmax2,
-                    const ExactBound& eb, long r0, long n, unsigned long long* best1, unsigned long long* best2, int* out1, int* out2,
+int exact_top2_pass(som_handle* h, const Rows& R, const ExactBound& eb, long r0, long n, unsigned long long* best1, unsigned long long* best2,
                     bool* bad_w) {
+    const float* X = R.X; const float* xsq = R.xsq; const float* xerr = R.xerr; const __bf16* Xb = R.Xb; const float* xmax2 = R.xmax2;
+    int* out1 = R.out; int* out2 = R.out2;
     auto& ex = h->ex;
     const PassCtr pc = pass_ctr(h);
     const int n_groups = pc.n_groups;
@@ -125,11 +126,11 @@ int exact_top2_pass(som_handle* h, const float* X, const float* xsq, const float
     return 0;
 }
 
-// X, xsq, Xb: the query rows, their |x|^2 (+ measured operand errors behind them), their half image; out1 / out2: the ids
-int launch_top2_exact(som_handle* h, const float* X, long N, const float* xsq, const __bf16* Xb, const float* xmax2, int* out1, int* out2) {
+// R: the query rows, their |x|^2 and measured operand errors, their half image; out / out2: the ids
+int launch_top2_exact(som_handle* h, const Rows& R) {
     if (h->capturing) return fail(h, "precision 'exact' reads a counter back per pass: not capturable");
-    const float* xerr = exact_err_of(h, xsq);
-    if (!xerr) return fail(h, "exact top-2: unknown row-norm buffer");
+    if (!R.xsq || !R.xerr) return fail(h, "exact top-2: no row norms");
+    const long N = R.N;
     auto& ex = h->ex;
     // the pass scratch: what there is, unless there is none -- or too little and no resident order that growing it would forget
     if (ex.stride == 0 || (ex.stride < round_up(std::min(N, exact_chunk_rows(h)), 256) && !ex.plan.order_valid()))
@@ -140,20 +141,19 @@ int launch_top2_exact(som_handle* h, const float* X, long N, const float* xsq, c
     if (int rc = h->t2.excl.reserve(h, (size_t)std::min(N, chunk), 1024)) return rc;
     const long units = (long)h->n_stages * h->stage_units;
     prep_wsqh_kernel<<<dim3((unsigned)cdiv(std::max(units, N), 256)), dim3(256), 0, h->stream>>>(
-        h->wn, h->K, h->wmax2, xmax2, h->Wst, h->n_stages, h->stage_bytes, h->stage_units, h->best64, N, 1);
+        h->wn, h->K, h->wmax2, R.xmax2, h->Wst, h->n_stages, h->stage_bytes, h->stage_units, h->best64, N, 1);
     HIPCHK(h, hipMemsetAsync(h->best64 + off2, 0xFF, (size_t)N * sizeof(unsigned long long), h->stream));
     const ExactBound eb = exact_bound(h);
     h->t2.rows += N;
     const int64_t f32_before = h->t2.rows_f32;
     for (long r0 = 0; r0 < N; r0 += chunk) {
         bool bad_w = false;
-        if (int rc = exact_top2_pass(h, X, xsq, xerr, Xb, xmax2, eb, r0, std::min(chunk, N - r0), h->best64 + r0, h->best64 + off2 + r0, out1,
-                                     out2, &bad_w)) return rc;
+        if (int rc = exact_top2_pass(h, R, eb, r0, std::min(chunk, N - r0), h->best64 + r0, h->best64 + off2 + r0, &bad_w)) return rc;
         if (bad_w) {
             // a unit with a NaN or infinite norm: the float32 kernel for every row of the call
             h->t2.rows_f32 = f32_before + N;
             if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
-            return launch_bmu_top2(h, X, N, xsq, out1, out2);
+            return launch_bmu_top2(h, R.X, N, R.xsq, R.out, R.out2);
         }
     }
     return 0;

@@ -27,6 +27,7 @@
 #include "exact_skip.hpp"
 #include "exact_policy.hpp"
 #include "codebook_operands.hpp"
+#include "row_set.hpp"
 #include "exact_skip_wide.hpp"
 #include "bmu_f32.hpp"
 #include "bmu_f32_res.hpp"
@@ -90,6 +91,34 @@ struct DevBuf {
     int alloc(som_handle* h, size_t n);   // (defined with the handle: capture refusal, graph staleness, error message)
     int reserve(som_handle* h, size_t n, size_t round = 1) { return n <= cap ? 0 : alloc(h, (n + round - 1) / round * round); }
     operator T*() const { return p; }
+};
+
+// what a search, a segment sum or the canary reads of a row set, by value: nobody downstream asks the handle which set it was
+struct Rows {
+    const float* X; long N; const float* xsq; const float* xerr; const __bf16* Xb; const float* xmax2; int* out; int* out2;
+    const float* wgt; bool resident; bool ids_valid;
+};
+
+// One row set (row_set.hpp) and everything derived from its rows: the one owner of these buffers.  The handle holds three --
+// `res` the resident training rows, `q` the query scratch (also the pageable streamed chunks), Slot::rows the pinned chunks.
+struct RowSet {
+    rowset::Kind kind = rowset::Kind::Query;
+    const float* X = nullptr;    // the float32 rows: X_owned, or the caller's device rows (som_set_data_device, the *_device queries)
+    DevBuf<float> X_owned;
+    long N = 0, cap = 0;         // rows in it now; rows its derived buffers hold
+    DevBuf<float> xsq;           // |x|^2 in NumPy's order; exact mode: twice cap, see xerr()
+    DevBuf<__bf16> Xb;           // the 16-bit operand image
+    DevBuf<int> bmu, bmu2;       // the ids a search writes (bmu2: the query set's second-best units)
+    // per-row sample weights: float32, finite, >= 0; nullptr = every row counts 1 (update.hpp, runsum_kernel<.., WEIGHTED>: level 0 only)
+    const float* wgt = nullptr;  // wgt_owned, or the caller's device array (som_set_sample_weights_device)
+    DevBuf<float> wgt_owned;
+    float* xmax2 = nullptr;      // max_n |x~_n|^2: this set's float of som_handle::xmax2 ([0] resident, [1] every transient set)
+    bool err_half = false;       // precision 'exact'
+    bool ids_valid = false;      // bmu holds the ids of a completed BMU pass over THESE rows (resident set only: a transient set's never outlive the call)
+    bool resident() const { return kind == rowset::Kind::Resident; }
+    // precision 'exact': the rows' measured operand rounding errors (bmu_exact.hpp) live in the second half of xsq.  The only place that knows.
+    float* xerr() const { return err_half && xsq.p != nullptr ? xsq.p + cap : nullptr; }
+    Rows view() const { return Rows{X, N, xsq, xerr(), Xb, xmax2, bmu, bmu2, wgt, resident(), ids_valid}; }
 };
 
 struct som_handle {
@@ -235,16 +264,7 @@ struct som_handle {
     // which of the operands derived from W are current (rebuilt lazily: refresh_codebook_operands): codebook_operands.hpp
     operands::State ops;
 
-    // resident training rows
-    const float* Xd = nullptr;   // X_owned, or the caller's device rows (som_set_data_device)
-    DevBuf<float> X_owned;
-    long N = 0, Np = 0;
-    // per-row sample weights of the resident rows (som_set_sample_weights*): float32 [N], finite, >= 0; nullptr = every row counts 1.
-    // They enter at level 0 of the run sum and nowhere else (update.hpp, runsum_kernel<.., WEIGHTED>)
-    const float* wgt = nullptr;  // wgt_owned, or the caller's device array (som_set_sample_weights_device)
-    DevBuf<float> wgt_owned;
-    DevBuf<int> bmu;
-    bool bmu_valid = false;  // bmu holds the ids of a completed BMU pass over the resident rows
+    RowSet res{rowset::Kind::Resident};   // the resident training rows (som_set_data*), their sample weights (som_set_sample_weights*)
     // precision 'exact': the update-side work that does not depend on the BMUs (the zeroed segment sums, the neighbourhood
     // tables) is queued BEFORE the pass's counter read-back, so the GPU has it to do while the host wakes up
     struct EarlyUpdate { bool armed = false, done = false; double sigma = 0, eta = 0; int neigh_f64 = 0; } early;
@@ -261,17 +281,12 @@ struct som_handle {
         long cs_blocks = 0;
     };
     SegScratch seg;                              // resident rows
-    DevBuf<float> xsq;
-    DevBuf<__bf16> Xb;
-    DevBuf<float> xmax2;     // [0] resident rows, [1] query scratch: max_n |x~_n|^2
+    DevBuf<float> xmax2;     // [0] resident rows, [1] every transient row set: max_n |x~_n|^2 (RowSet::xmax2)
     DevBuf<float> wn;        // |w~_k|^2 per unit
     DevBuf<float> wmax2;
 
-    // scratch for som_bmu / som_quantization_error
-    DevBuf<float> qX; DevBuf<int> qbmu, qbmu2; DevBuf<float> qxsq; DevBuf<__bf16> qXb;
-    DevBuf<float> qw;        // som_stream_rows_weighted, pageable chunk: its weights
+    RowSet q;                // the rows of a query (som_bmu*, som_quantization_error*, ...) or of a pageable streamed chunk
     DevBuf<double> qX64;     // som_bmu_f64: float64 query rows
-    long qcap = 0;
     DevBuf<double> dsum;
     // precision 'exact', value-only quantization BMUs (run_quantization_bmu): the rows whose screen pick a tie of the sqrt'd
     // distance could overturn, gathered for the float32 SQRT kernel, and how many rows went each way (som_debug_qe_stats)
@@ -292,9 +307,7 @@ struct som_handle {
     bool streaming = false;
     // double-buffered device staging for chunks that arrive in pinned host memory
     struct Slot {
-        DevBuf<float> dX; DevBuf<__bf16> dXb; DevBuf<float> dxsq; DevBuf<int> dbmu;
-        DevBuf<float> dw;                        // the chunk's sample weights (som_stream_rows_weighted), allocated on first use
-        long cap = 0;
+        RowSet rows{rowset::Kind::Slot};         // (its sample weights, som_stream_rows_weighted: allocated on first use)
         hipEvent_t copied = nullptr, consumed = nullptr;
         bool used = false;
     } slot[2];
@@ -437,7 +450,7 @@ inline long resident_slots(const som_handle* h, int per_cu) { return (long)per_c
 inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 inline long round_up(long a, long b) { return cdiv(a, b) * b; }
 constexpr float HALF_MAX = 65504.0f;   // largest finite _Float16
-constexpr long ROW_PAD = 3072;   // bf16 row images are padded to a multiple of every kernel's workgroup tile
+using rowset::ROW_PAD;
 
 // ---- profiling: event pairs recorded around kernel families, resolved lazily ---------------
 struct Timed {
@@ -855,28 +868,19 @@ int launch_bmu_half(som_handle* h, const __bf16* Xb, const float* xmax2, long N,
                     [&](auto k) { return launch_bmu_bf16_k16<decltype(k)::value, E>(h, Xb, N, out); });
 }
 
-int launch_bmu_bf16(som_handle* h, const __bf16* Xb, const float* xmax2, long N, int* out) {
-    return SOM_HALF(h, launch_bmu_half, h, Xb, xmax2, N, out);
+int launch_bmu_bf16(som_handle* h, const Rows& r) {
+    return SOM_HALF(h, launch_bmu_half, h, r.Xb, r.xmax2, r.N, r.out);
 }
 
-// precision 'exact': every |x|^2 buffer is allocated with twice its row capacity; the second half holds the rows'
-// measured operand rounding errors (bmu_exact.hpp).  Which half-way point belongs to this buffer:
-float* exact_err_of(som_handle* h, const float* xsq) {
-    if (!xsq) return nullptr;
-    if (xsq == h->xsq) return h->xsq + h->N;
-    if (xsq == h->qxsq) return h->qxsq + h->qcap;
-    for (auto& sl : h->slot) if (xsq == sl.dxsq) return sl.dxsq + sl.cap;
-    return nullptr;
-}
-
-// the exact mode's rows -> half operand image, max |x|^2 and the rows' measured rounding errors.  xsq_scratch: the rows' |x|^2 in
-// NumPy's order (the caller's row_sq); its second half takes the errors (exact_err_of)
-int prep_rows_exact(som_handle* h, const float* X, long N, long Np, __bf16* Xb, float* xmax2, float* xsq_scratch) {
+// the exact mode's rows -> half operand image, max |x|^2 and the rows' measured rounding errors.  The set's xsq holds the rows'
+// |x|^2 in NumPy's order (the caller's row_sq); its second half takes the errors (RowSet::xerr)
+int prep_rows_exact(som_handle* h, RowSet& s) {
+    const float* X = s.X; const long N = s.N, Np = round_up(N, ROW_PAD);
+    __bf16* Xb = s.Xb; float* xmax2 = s.xmax2; float* xsq_scratch = s.xsq; float* xerr = s.xerr();
     HIPCHK(h, hipMemsetAsync(xmax2, 0, sizeof(float), h->stream));
+    if (!xerr && N > 0) return fail(h, "exact: no row norms");
     if (h->tiled) {
         // beyond 128 features: the tile image; cosine: the rows go in at unit length
-        float* xerr = exact_err_of(h, xsq_scratch);
-        if ((!xsq_scratch || !xerr) && N > 0) return fail(h, "exact: no row-norm buffer");
         const bool unit = h->cfg.distance == SOM_DIST_COSINE;
         const float* usq = unit ? xsq_scratch : nullptr;
         if (unit) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)xmax2, 0x3F800000, 1, h->stream));   // unit-length rows: max |x| = 1
@@ -890,9 +894,6 @@ int prep_rows_exact(som_handle* h, const float* X, long N, long Np, __bf16* Xb, 
         return 0;
     }
     // up to 128 features: max |x|^2 from the rows' float32 norms, then the rows scaled by ex_scale of it
-    if (!xsq_scratch && N > 0) return fail(h, "exact: no row norms");
-    float* xerr = exact_err_of(h, xsq_scratch);
-    if (!xerr && N > 0) return fail(h, "exact: unknown row-norm buffer");
     if (N > 0) exact_max_kernel<<<dim3((unsigned)std::min<long>(cdiv(N, 256), 512)), dim3(256), 0, h->stream>>>(xsq_scratch, N, xmax2);
     prep_x_bf16_kernel<ExactEl><<<dim3((unsigned)cdiv(Np, 4)), dim3(256), 0, h->stream>>>(X, N, h->D, h->dp, Np, Xb, nullptr, 0, xmax2, xerr);
     HIPCHK(h, hipGetLastError());
@@ -901,16 +902,17 @@ int prep_rows_exact(som_handle* h, const float* X, long N, long Np, __bf16* Xb, 
 
 // precisions 'bf16' and 'f16': rows -> 16-bit operand image (+ max |x~|^2 for the offset B).  Cosine: the rows go in at unit
 // length -- the argmin does not depend on |x|, and B = max|x~| max|w~| then resolves every row alike (a short row next to
-// long ones would otherwise be compared at B's absolute precision).  xsq_scratch: N floats, cosine + tiled only.
+// long ones would otherwise be compared at B's absolute precision).  The set's xsq is scratch here: N floats, cosine + tiled only.
 template <class E>
-int prep_rows_half(som_handle* h, const float* X, long N, long Np, __bf16* Xb, float* xmax2, float* xsq_scratch) {
-    const int Dp = h->dp;
+int prep_rows_half(som_handle* h, RowSet& s) {
+    const float* X = s.X; const long N = s.N, Np = round_up(N, ROW_PAD);
+    __bf16* Xb = s.Xb; float* xmax2 = s.xmax2; float* xsq_scratch = s.xsq;
     const bool unit = h->cfg.distance == SOM_DIST_COSINE;
     HIPCHK(h, hipMemsetAsync(xmax2, 0, sizeof(float), h->stream));
     if (h->tiled) {
         const float* usq = nullptr;
         if (unit && N > 0) {
-            if (!xsq_scratch) return fail(h, "prep_rows_bf16: no row-norm scratch");
+            if (!xsq_scratch) return fail(h, "prep_rows_half: no row-norm scratch");
             row_sq_f32_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(X, N, h->D, xsq_scratch);
             usq = xsq_scratch;
         }
@@ -923,17 +925,34 @@ int prep_rows_half(som_handle* h, const float* X, long N, long Np, __bf16* Xb, f
         HIPCHK(h, hipGetLastError());
         return 0;
     }
-    prep_x_bf16_kernel<E><<<dim3((unsigned)cdiv(Np, 4)), dim3(256), 0, h->stream>>>(X, N, h->D, Dp, Np, Xb, xmax2, unit ? 1 : 0);
+    prep_x_bf16_kernel<E><<<dim3((unsigned)cdiv(Np, 4)), dim3(256), 0, h->stream>>>(X, N, h->D, h->dp, Np, Xb, xmax2, unit ? 1 : 0);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
 
-int prep_rows_bf16(som_handle* h, const float* X, long N, long Np, __bf16* Xb, float* xmax2, float* xsq_scratch) {
-    if (h->exact) return prep_rows_exact(h, X, N, Np, Xb, xmax2, xsq_scratch);
-    return SOM_HALF(h, prep_rows_half, h, X, N, Np, Xb, xmax2, xsq_scratch);
+bool needs_xsq(const som_handle* h) {
+    if (h->exact) return true;                          // |x_n| scales the row's error bound (bmu_exact.hpp)
+    return h->cfg.precision == SOM_PREC_F32 &&
+           (h->cfg.distance == SOM_DIST_EUCLIDEAN_NO_OPT || h->cfg.distance == SOM_DIST_COSINE);
 }
 
-// single-pass half precision ('bf16' or 'f16'), as opposed to the hi/lo split modes
+int row_sq(som_handle* h, const float* X, long N, float* out) {
+    if (N == 0) return 0;
+    row_sq_f32_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(X, N, h->D, out);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// what a search reads besides the set's float32 rows: |x|^2 where the caller wants it, the 16-bit operand image (with max |x~|^2
+// and, exact mode, the rows' measured errors) unless the precision is f32.  The one place that prepares a row set.
+int prepare(som_handle* h, RowSet& s, bool want_xsq) {
+    if (s.N == 0) return 0;
+    if (want_xsq) if (int rc = row_sq(h, s.X, s.N, s.xsq)) return rc;
+    if (h->cfg.precision == SOM_PREC_F32) return 0;
+    return h->exact ? prep_rows_exact(h, s) : SOM_HALF(h, prep_rows_half, h, s);
+}
+
+// precision 'bf16' or 'f16': 16-bit operands and no float32 re-score (as opposed to 'exact', whose screen reads them too)
 inline bool is_half1(const som_handle* h) { return h->cfg.precision == SOM_PREC_BF16 || h->cfg.precision == SOM_PREC_F16; }
 
 template <class E>
@@ -980,8 +999,8 @@ int launch_bmu_pairwise(som_handle* h, const float* X, long N, int p, bool even,
 #include "exact_host.hpp"   // launch_bmu_exact and everything it drives (precision 'exact'): same translation unit
 
 // ---- canary: re-score a strided sample of a BMU launch's rows with the float32 kernel (bmu_exact.hpp) -------------
-int verify_bmu_launch(som_handle* h, const float* X, long N, const int* ids) {
-    const int n = (int)std::min<long>(h->verify_rows, N);
+int verify_bmu_launch(som_handle* h, const Rows& r) {
+    const int n = (int)std::min<long>(h->verify_rows, r.N);
     if (n <= 0 || h->cfg.distance > SOM_DIST_COSINE) return 0;     // (the VALU distances have one precision: nothing to cross-check)
     if (h->capturing) return fail(h, "SOM_VERIFY reads a flag back per launch: not capturable");
     if (n > h->vf_cap) {
@@ -993,12 +1012,12 @@ int verify_bmu_launch(som_handle* h, const float* X, long N, const int* ids) {
         if (!h->vf_bad) if (int rc = h->vf_bad.alloc(h, 4)) return rc;
         h->vf_cap = n;
     }
-    verify_pick_rows_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(N, n, ids, h->vf_rows, h->vf_picks);
-    exact_gather_rows_kernel<<<dim3((unsigned)cdiv((long)n * h->D, 256)), dim3(256), 0, h->stream>>>(X, h->vf_rows, n, h->D, h->vf_X);
+    verify_pick_rows_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(r.N, n, r.out, h->vf_rows, h->vf_picks);
+    exact_gather_rows_kernel<<<dim3((unsigned)cdiv((long)n * h->D, 256)), dim3(256), 0, h->stream>>>(r.X, h->vf_rows, n, h->D, h->vf_X);
     HIPCHK(h, hipMemsetAsync(h->vf_bad, 0, 4 * sizeof(int), h->stream));
-    if (const operands::Rebuilds r = h->ops.decide_wsq(); r.wsq) {
+    if (const operands::Rebuilds rb = h->ops.decide_wsq(); rb.wsq) {
         launch_codebook_wsq(h);
-        h->ops.commit(r);
+        h->ops.commit(rb);
     }
     const dim3 grid((unsigned)n), block(256);
     const size_t lds = (size_t)h->D * sizeof(float);
@@ -1031,44 +1050,46 @@ int verify_bmu_launch(som_handle* h, const float* X, long N, const int* ids) {
     return 0;
 }
 
-// BMU of `N` device rows with the configured activation distance (xpysom.py:410-417)
-int run_activation_bmu_launch(som_handle* h, const float* X, long N, const float* xsq, const __bf16* Xb, const float* xmax2,
-                              int* out) {
+// BMU of a row set's device rows with the configured activation distance (xpysom.py:410-417)
+int run_activation_bmu_launch(som_handle* h, const Rows& r) {
     // (exact mode up to 128 features: the launch writes the codebook's 16-bit image itself, in one grid with its plan's centroid images)
     if (int rc = refresh_codebook_operands(h, operands::Request::Search, h->exact && h->ex.chain)) return rc;
     Timed t(h, SOM_K_BMU);
-    if (h->exact) return launch_bmu_exact(h, X, N, xsq, Xb, xmax2, out);
-    if (h->cfg.precision != SOM_PREC_F32) return launch_bmu_bf16(h, Xb, xmax2, N, out);
+    if (h->exact) return launch_bmu_exact(h, r);
+    if (h->cfg.precision != SOM_PREC_F32) return launch_bmu_bf16(h, r);
     switch (h->cfg.distance) {
-    case SOM_DIST_EUCLIDEAN: return launch_bmu_f32_any<SCORE_EUCLID_PART>(h, X, N, xsq, out);
-    case SOM_DIST_EUCLIDEAN_NO_OPT: return launch_bmu_f32_any<SCORE_EUCLID_SQ>(h, X, N, xsq, out);
-    case SOM_DIST_COSINE: return launch_bmu_f32_any<SCORE_COSINE>(h, X, N, xsq, out);
-    case SOM_DIST_MANHATTAN: return launch_bmu_pairwise(h, X, N, 1, false, out);
-    case SOM_DIST_NORM_P_NO_OPT: return launch_bmu_pairwise(h, X, N, h->norm_p, false, out);
-    case SOM_DIST_NORM_P: return launch_bmu_pairwise(h, X, N, h->norm_p, h->norm_p % 2 == 0, out);
+    case SOM_DIST_EUCLIDEAN: return launch_bmu_f32_any<SCORE_EUCLID_PART>(h, r.X, r.N, r.xsq, r.out);
+    case SOM_DIST_EUCLIDEAN_NO_OPT: return launch_bmu_f32_any<SCORE_EUCLID_SQ>(h, r.X, r.N, r.xsq, r.out);
+    case SOM_DIST_COSINE: return launch_bmu_f32_any<SCORE_COSINE>(h, r.X, r.N, r.xsq, r.out);
+    case SOM_DIST_MANHATTAN: return launch_bmu_pairwise(h, r.X, r.N, 1, false, r.out);
+    case SOM_DIST_NORM_P_NO_OPT: return launch_bmu_pairwise(h, r.X, r.N, h->norm_p, false, r.out);
+    case SOM_DIST_NORM_P: return launch_bmu_pairwise(h, r.X, r.N, h->norm_p, h->norm_p % 2 == 0, r.out);
     }
     return fail(h, "unknown distance id");
 }
 
-int run_activation_bmu(som_handle* h, const float* X, long N, const float* xsq, const __bf16* Xb, const float* xmax2,
-                       int* out) {
-    if (N == 0) return 0;
-    if (int rc = run_activation_bmu_launch(h, X, N, xsq, Xb, xmax2, out)) return rc;
-    if (out == h->bmu) h->bmu_valid = true;               // (the next epoch's exact screen seeds its thresholds from these ids)
-    if (h->verify_rows > 0 && !h->verifying) return verify_bmu_launch(h, X, N, out);
+int run_activation_bmu(som_handle* h, const Rows& r) {
+    if (r.N == 0) return 0;
+    if (int rc = run_activation_bmu_launch(h, r)) return rc;
+    if (r.resident) h->res.ids_valid = true;              // (the next epoch's exact screen seeds its thresholds from these ids)
+    if (h->verify_rows > 0 && !h->verifying) return verify_bmu_launch(h, r);
     return 0;
 }
 
-bool needs_xsq(const som_handle* h) {
-    if (h->exact) return true;                          // |x_n| scales the row's error bound (bmu_exact.hpp)
-    return h->cfg.precision == SOM_PREC_F32 &&
-           (h->cfg.distance == SOM_DIST_EUCLIDEAN_NO_OPT || h->cfg.distance == SOM_DIST_COSINE);
-}
-
-int row_sq(som_handle* h, const float* X, long N, float* out) {
-    if (N == 0) return 0;
-    row_sq_f32_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(X, N, h->D, out);
-    HIPCHK(h, hipGetLastError());
+// `s`'s buffers for n rows, by the size rule of row_set.hpp: a transient set only grows (free first, then allocate), the resident set is
+// rebuilt, cap == N, for every row set the handle adopts.  with_rows: host rows will be staged through the set's own float32 buffer
+int reserve(som_handle* h, RowSet& s, long n, bool with_rows) {
+    const rowset::Sizes z = rowset::sizes(s.kind, n, h->D, h->dp, rowset::Flags{h->cfg.precision == SOM_PREC_F32, h->exact, needs_xsq(h),
+                                                                                h->cfg.distance == SOM_DIST_COSINE && h->tiled});
+    if (with_rows) if (int rc = s.resident() ? s.X_owned.alloc(h, z.X) : s.X_owned.reserve(h, z.X)) return rc;
+    if (!s.resident() && n <= s.cap) return 0;
+    s.bmu.reset(); s.bmu2.reset(); s.xsq.reset(); s.Xb.reset(); s.cap = 0;
+    if (s.kind == rowset::Kind::Slot) s.wgt_owned.reset();
+    if (int rc = s.bmu.alloc(h, z.ids)) return rc;
+    if (s.kind == rowset::Kind::Query) if (int rc = s.bmu2.alloc(h, z.ids)) return rc;
+    if (z.xsq) if (int rc = s.xsq.alloc(h, z.xsq)) return rc;
+    if (z.Xb) if (int rc = s.Xb.alloc(h, z.Xb)) return rc;
+    s.cap = z.cap;
     return 0;
 }
 
@@ -1127,11 +1148,11 @@ long launch_runsum(som_handle* h, const float* X, const int* keys, const int* sr
 // SC[b] += sum of the rows whose BMU is b (and their count): sort by BMU, then the levels of update.hpp's
 // run sum (rows -> partial lists) until one workgroup holds the whole list.  zero_first: SC starts from zero and
 // every unit is written once (plain stores); otherwise the chunk's sums are added to what SC holds.
-// wgt != nullptr: the sample weights of these N rows (device, indexed like X's rows): SC[b] = sum of w_n x_n, count = sum of w_n.
-int segsum_rows(som_handle* h, const float* X, const int* bmu, long N, som_handle::SegScratch& sg, bool zero_first,
-                const float* wgt = nullptr) {
+// r.wgt != nullptr: the sample weights of these N rows (device, indexed like X's rows): SC[b] = sum of w_n x_n, count = sum of w_n.
+int segsum_rows(som_handle* h, const Rows& r, som_handle::SegScratch& sg, bool zero_first) {
+    const float* X = r.X; const int* bmu = r.out; const long N = r.N;
     Timed t(h, SOM_K_SEGSUM);
-    if (zero_first && !(h->early.done && X == h->Xd))   // (exact mode: already zeroed before the pass's read-back)
+    if (zero_first && !(h->early.done && r.resident))   // (exact mode: already zeroed before the pass's read-back)
         HIPCHK(h, hipMemsetAsync(h->SC, 0, (size_t)h->K * (h->D1p + 1) * sizeof(float), h->stream));
     if (N > 0) {
         if (N > sg.cap) return fail(h, "segment sum: scratch smaller than the row set");
@@ -1151,7 +1172,7 @@ int segsum_rows(som_handle* h, const float* X, const int* bmu, long N, som_handl
             if (int rc = radix_sort_rows(h, bmu, N, bits, sg.skey, sg.srow, sg.tmp)) return rc;
         }
         const int acc = zero_first ? 0 : 1;
-        long blocks = launch_runsum<true>(h, X, sg.skey, sg.srow, nullptr, N, acc, sg.kA, sg.vA, wgt);
+        long blocks = launch_runsum<true>(h, X, sg.skey, sg.srow, nullptr, N, acc, sg.kA, sg.vA, r.wgt);
         int *kin = sg.kA, *kout = sg.kB;
         float *vin = sg.vA, *vout = sg.vB;
         while (blocks > 1) {                             // 2 * blocks entries are waiting in (kin, vin)
@@ -1182,7 +1203,7 @@ NeighParams make_neigh_params(const som_handle* h, double sigma, double eta, int
 }
 
 int run_update(som_handle* h, double sigma, double eta, int neigh_f64) {
-    if (int rc = segsum_rows(h, h->Xd, h->bmu, h->N, h->seg, true, h->wgt)) return rc;
+    if (int rc = segsum_rows(h, h->res.view(), h->seg, true)) return rc;
     return run_transform(h, sigma, eta, neigh_f64);
 }
 
@@ -1314,21 +1335,16 @@ int run_transform(som_handle* h, double sigma, double eta, int neigh_f64) {
     return run_transform_stage2(h, 0, (int)cdiv(h->X, LM_BM));
 }
 
-// with_rows: the caller stages host rows through qX (device rows of the caller's are read where they are)
-int ensure_query_scratch(som_handle* h, long n, bool with_rows = true) {
-    if (with_rows) if (int rc = h->qX.reserve(h, (size_t)n * h->D, (size_t)1024 * h->D)) return rc;
-    if (n <= h->qcap) return 0;
-    long cap = round_up(n, 1024);
-    h->qbmu.reset(); h->qbmu2.reset(); h->qxsq.reset(); h->qXb.reset(); h->qcap = 0;
-    if (int rc = h->qbmu.alloc(h, (size_t)cap)) return rc;
-    if (int rc = h->qbmu2.alloc(h, (size_t)cap)) return rc;
-    if (int rc = h->qxsq.alloc(h, (size_t)cap * (h->exact ? 2 : 1))) return rc;
-    if (h->cfg.precision != SOM_PREC_F32) {
-        long capp = round_up(cap, ROW_PAD);
-        if (int rc = h->qXb.alloc(h, (size_t)capp * h->dp)) return rc;
-    }
-    h->qcap = cap;
+// `s` takes the n rows at x, without weights: host rows staged through its own buffer, or the caller's device rows read where they are
+int take_rows(som_handle* h, RowSet& s, const void* x, long n, bool host) {
+    s.X = nullptr; s.N = 0; s.wgt = nullptr;
+    if (int rc = reserve(h, s, n, host)) return rc;
+    if (host && n > 0) if (int rc = h2d_blocking(h, s.X_owned, x, (size_t)n * h->D * sizeof(float))) return rc;
+    s.X = host ? (const float*)s.X_owned : (const float*)x; s.N = n;
     return 0;
+}
+int query_rows(som_handle* h, const float* x_host, const void* x_dev, long n) {
+    return take_rows(h, h->q, x_host ? (const void*)x_host : x_dev, n, x_host != nullptr);
 }
 
 #include "exact_top2_host.hpp"   // launch_top2_exact (precision 'exact', top-2): same translation unit
@@ -1338,7 +1354,7 @@ int launch_dist_matrix(som_handle* h, long N, float* out) {
     const int Dp = (int)round_up(h->D, F32_KC);
     size_t lds = (size_t)(F32_UB * (F32_KC + 1) + F32_UB + F32_SB * (F32_KC + 1)) * sizeof(float);
     dim3 grid((unsigned)cdiv(N, F32_SB), (unsigned)cdiv(h->K, F32_UB));
-    dist_matrix_f32_kernel<MODE><<<grid, dim3(256), lds, h->stream>>>(h->qX, N, h->D, Dp, h->W, h->wsq, h->K, h->qxsq, out);
+    dist_matrix_f32_kernel<MODE><<<grid, dim3(256), lds, h->stream>>>(h->q.X, N, h->D, Dp, h->W, h->wsq, h->K, h->q.xsq, out);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -1459,6 +1475,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         h->exact = false; h->f16 = false; h->tiled = false;
         h->cfg.precision = SOM_PREC_F32;
     }
+    for (RowSet* s : {&h->res, &h->q, &h->slot[0].rows, &h->slot[1].rows}) s->err_half = h->exact;
     h->ex_patch = h->exact && h->K >= 2 * EX_GROUP;      // (a map of one group has nothing to order)
     if (const char* e = dev_env("SOM_EXACT_PATCH")) if (std::atoi(e) == 0) h->ex_patch = false;   // A/B: groups = strips of a map row
     h->ops = operands::State(operands::Config{h->cfg.precision != SOM_PREC_F32, h->exact, h->ex_patch, h->cfg.distance == SOM_DIST_COSINE,
@@ -1583,6 +1600,8 @@ int som_create(const som_config* cfg, som_handle** out) {
             if (hipMemsetAsync(h->Wst_lo, 0, bytes, h->stream) != hipSuccess) return bail(fail(h, "hipMemsetAsync failed"));
         }
         if ((rc = h->xmax2.alloc(h, 2))) return bail(rc);
+        h->res.xmax2 = h->xmax2;                         // (the one place that binds a row set to its float)
+        h->q.xmax2 = h->slot[0].rows.xmax2 = h->slot[1].rows.xmax2 = h->xmax2 + 1;
         if ((rc = h->wn.alloc(h, (size_t)h->K))) return bail(rc);
         if ((rc = h->wmax2.alloc(h, 2))) return bail(rc);
         if (hipMemsetAsync(h->Wst, 0, bytes, h->stream) != hipSuccess) return bail(fail(h, "hipMemsetAsync failed"));
@@ -1644,39 +1663,33 @@ namespace { void drop_graph(som_handle* h); }
 // no sample weights from here on; a captured epoch graph has the weighted or the unweighted instance of the segment sum baked in,
 // so it goes, and its warm-up epoch runs again
 static void clear_sample_weights(som_handle* h) {
-    if (h->wgt == nullptr) return;
-    h->wgt = nullptr;
-    h->wgt_owned.reset();
+    if (h->res.wgt == nullptr) return;
+    h->res.wgt = nullptr;
+    h->res.wgt_owned.reset();
     drop_graph(h);
     h->graph_warm = 0;
 }
 
-static int adopt_rows(som_handle* h, int64_t n_rows) {
+// the resident set takes n_rows rows at x: host rows through its own buffer, or the caller's device rows where they are
+static int adopt_rows(som_handle* h, const std::string& who, const void* x, int64_t n_rows, bool host) {
+    DeviceGuard dev_guard(h);
+    if (!h || n_rows < 0 || (!x && n_rows > 0)) return fail(h, who + ": bad argument");
+    RowSet& s = h->res;
     clear_sample_weights(h);                             // (weights belong to the rows they were set for)
-    h->bmu.reset(); h->xsq.reset(); h->Xb.reset();
-    h->bmu_valid = false;
+    if (!host) s.X_owned.reset();
+    s.ids_valid = false;
     h->ex.plan.order_lost();                             // (the resident sorted pass belongs to the rows it was sorted from)
     h->ex.srt[0].lastpos_valid = false;
     h->seg = som_handle::SegScratch{};
-    h->N = n_rows;
-    h->Np = round_up(n_rows, ROW_PAD);
     if (n_rows > 0x7fffffffL) return fail(h, "som_set_data: more than 2^31-1 rows per GPU");
-    if (int rc = h->bmu.alloc(h, (size_t)n_rows)) return rc;
+    if (int rc = take_rows(h, s, x, n_rows, host)) return rc;
     if (n_rows > 0)
         if (int rc = seg_reserve(h, h->seg, n_rows)) return rc;
-    const bool bf_cos_tiled = h->cfg.precision != SOM_PREC_F32 && h->cfg.distance == SOM_DIST_COSINE && h->tiled;
-    if (needs_xsq(h) || bf_cos_tiled) {
-        if (int rc = h->xsq.alloc(h, (size_t)n_rows * (h->exact ? 2 : 1))) return rc;
-        if (needs_xsq(h)) if (int rc = row_sq(h, h->Xd, n_rows, h->xsq)) return rc;
-    }
-    if (h->cfg.precision != SOM_PREC_F32 && n_rows > 0) {
-        if (int rc = h->Xb.alloc(h, (size_t)h->Np * h->dp)) return rc;
-        if (int rc = prep_rows_bf16(h, h->Xd, n_rows, h->Np, h->Xb, h->xmax2, h->xsq)) return rc;
-    }
+    if (int rc = prepare(h, s, needs_xsq(h))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->f16 && !h->exact && n_rows > 0) {             // IEEE half tops out at 65504: refuse rows that do not fit
         float m2 = 0.0f;
-        if (int rc = d2h_blocking(h, &m2, h->xmax2, sizeof(float))) return rc;
+        if (int rc = d2h_blocking(h, &m2, s.xmax2, sizeof(float))) return rc;
         if (!(m2 <= HALF_MAX * HALF_MAX))
             return fail(h, "som_set_data: precision 'f16' needs rows of norm <= 65504 (float16 range): scale the data, or use 'bf16' / 'f32'");
     }
@@ -1692,24 +1705,8 @@ static int adopt_rows(som_handle* h, int64_t n_rows) {
     return 0;
 }
 
-int som_set_data(som_handle* h, const float* x_host, int64_t n_rows) {
-    DeviceGuard dev_guard(h);
-    if (!h || n_rows < 0 || (!x_host && n_rows > 0)) return fail(h, "som_set_data: bad argument");
-    h->Xd = nullptr;
-    if (int rc = h->X_owned.alloc(h, (size_t)n_rows * h->D)) return rc;
-    if (n_rows > 0)
-        if (int rc = h2d_blocking(h, h->X_owned, x_host, (size_t)n_rows * h->D * sizeof(float))) return rc;
-    h->Xd = h->X_owned;
-    return adopt_rows(h, n_rows);
-}
-
-int som_set_data_device(som_handle* h, const void* x_dev, int64_t n_rows) {
-    DeviceGuard dev_guard(h);
-    if (!h || n_rows < 0 || (!x_dev && n_rows > 0)) return fail(h, "som_set_data_device: bad argument");
-    h->X_owned.reset();
-    h->Xd = (const float*)x_dev;
-    return adopt_rows(h, n_rows);
-}
+int som_set_data(som_handle* h, const float* x_host, int64_t n_rows) { return adopt_rows(h, "som_set_data", x_host, n_rows, true); }
+int som_set_data_device(som_handle* h, const void* x_dev, int64_t n_rows) { return adopt_rows(h, "som_set_data_device", x_dev, n_rows, false); }
 
 // Order the engine behind whoever produced device rows handed to som_set_data_device: a
 // __cuda_array_interface__ `stream` value (1 = legacy default stream, 2 = per-thread default stream, else a
@@ -1735,9 +1732,9 @@ namespace {
 
 int epoch_accumulate_eager(som_handle* h, double sigma, double eta, int neigh_f64) {
     h->early = som_handle::EarlyUpdate();
-    h->early.armed = h->exact && !h->capturing && h->N > 0;
+    h->early.armed = h->exact && !h->capturing && h->res.N > 0;
     h->early.sigma = sigma; h->early.eta = eta; h->early.neigh_f64 = neigh_f64;
-    int rc = run_activation_bmu(h, h->Xd, h->N, h->xsq, h->Xb, h->xmax2, h->bmu);
+    int rc = run_activation_bmu(h, h->res.view());
     if (rc == 0) rc = run_update(h, sigma, eta, neigh_f64);
     h->early = som_handle::EarlyUpdate();
     return rc;
@@ -1778,8 +1775,8 @@ int capture_epoch_graph(som_handle* h) {
         return 0;
     }
     h->gexec_gen = h->alloc_gen;
-    h->gexec_rows = h->Xd;
-    h->gexec_n = h->N;
+    h->gexec_rows = h->res.X;
+    h->gexec_n = h->res.N;
     return 0;
 }
 
@@ -1788,16 +1785,17 @@ int capture_epoch_graph(som_handle* h) {
 int som_epoch_accumulate(som_handle* h, double sigma, double eta, int neigh_f64) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
-    if (!h->Xd && h->N > 0) return fail(h, "som_epoch_accumulate: no resident data (call som_set_data)");
+    const RowSet& res = h->res;
+    if (!res.X && res.N > 0) return fail(h, "som_epoch_accumulate: no resident data (call som_set_data)");
     // launch-bound maps (many short kernels per epoch) replay a captured graph; profiling needs the
     // per-kernel events of the eager path
-    if (h->use_graph && !h->prof && h->N > 0 && !h->exact) {
-        const bool same = h->gexec && h->gexec_gen == h->alloc_gen && h->gexec_rows == h->Xd && h->gexec_n == h->N;
+    if (h->use_graph && !h->prof && res.N > 0 && !h->exact) {
+        const bool same = h->gexec && h->gexec_gen == h->alloc_gen && h->gexec_rows == res.X && h->gexec_n == res.N;
         if (!same) {
-            if (h->graph_warm == 0 || h->gexec_rows != h->Xd || h->gexec_n != h->N) {
+            if (h->graph_warm == 0 || h->gexec_rows != res.X || h->gexec_n != res.N) {
                 // first epoch over these rows runs eagerly: it sizes every scratch buffer
                 drop_graph(h);
-                h->gexec_rows = h->Xd; h->gexec_n = h->N; h->graph_warm = 1;
+                h->gexec_rows = res.X; h->gexec_n = res.N; h->graph_warm = 1;
                 return epoch_accumulate_eager(h, sigma, eta, neigh_f64);
             }
             if (int rc = capture_epoch_graph(h)) return rc;
@@ -1819,17 +1817,18 @@ int som_epoch_accumulate(som_handle* h, double sigma, double eta, int neigh_f64)
 int som_epoch_accumulate_faithful(som_handle* h, double sigma, double eta, int neigh_f64) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
-    if (!h->Xd && h->N > 0) return fail(h, "som_epoch_accumulate_faithful: no resident data (call som_set_data)");
+    const Rows r = h->res.view();
+    if (!r.X && r.N > 0) return fail(h, "som_epoch_accumulate_faithful: no resident data (call som_set_data)");
     if (h->swapped) return fail(h, "som_epoch_accumulate_faithful: mexican_hat with compact_support on the rectangular "
                                    "topology is not a sum of row factor x column factor terms");
-    if (h->wgt) return fail(h, "som_epoch_accumulate_faithful: sample weights are set; the faithful form is the cross-check of the "
+    if (r.wgt) return fail(h, "som_epoch_accumulate_faithful: sample weights are set; the faithful form is the cross-check of the "
                                "unweighted update (clear them with som_set_sample_weights(h, NULL, 0))");
-    if (int rc = run_activation_bmu(h, h->Xd, h->N, h->xsq, h->Xb, h->xmax2, h->bmu)) return rc;
+    if (int rc = run_activation_bmu(h, r)) return rc;
     Timed t(h, SOM_K_KRON);
     if (int rc = build_tables(h, sigma, eta, neigh_f64, h->stream)) return rc;
     HIPCHK(h, hipMemsetAsync(h->ACC, 0, (size_t)h->K * h->D1p * sizeof(float), h->stream));
     const dim3 grid((unsigned)cdiv(h->D, LM_BN), (unsigned)cdiv(h->K, LM_BM));
-    faithful_update_f32_kernel<<<grid, dim3(256), 0, h->stream>>>(h->Xd, h->bmu, h->N, h->D, h->D1p, h->X, h->Y, h->nt, h->P1,
+    faithful_update_f32_kernel<<<grid, dim3(256), 0, h->stream>>>(r.X, r.out, r.N, h->D, h->D1p, h->X, h->Y, h->nt, h->P1,
                                                               h->P2, h->ACC);
     HIPCHK(h, hipGetLastError());
     return 0;
@@ -1837,12 +1836,12 @@ int som_epoch_accumulate_faithful(som_handle* h, double sigma, double eta, int n
 
 int som_epoch_accumulate_forced(som_handle* h, const int32_t* bmu_host, double sigma, double eta, int neigh_f64) {
     DeviceGuard dev_guard(h);
-    if (!h || (!bmu_host && h->N > 0)) return fail(h, "som_epoch_accumulate_forced: bad argument");
-    for (long i = 0; i < h->N; ++i)
+    if (!h || (!bmu_host && h->res.N > 0)) return fail(h, "som_epoch_accumulate_forced: bad argument");
+    for (long i = 0; i < h->res.N; ++i)
         if (bmu_host[i] < 0 || bmu_host[i] >= h->K) return fail(h, "som_epoch_accumulate_forced: id out of range");
     h->ex.srt[0].lastpos_valid = false;                  // (ids from outside: the sorted rows' carried positions are not theirs)
-    if (h->N > 0)
-        if (int rc = h2d_blocking(h, h->bmu, bmu_host, (size_t)h->N * sizeof(int))) return rc;
+    if (h->res.N > 0)
+        if (int rc = h2d_blocking(h, h->res.bmu, bmu_host, (size_t)h->res.N * sizeof(int))) return rc;
     return run_update(h, sigma, eta, neigh_f64);
 }
 
@@ -1863,13 +1862,13 @@ int som_set_sample_weights(som_handle* h, const float* w_host, int64_t n_rows) {
     DeviceGuard dev_guard(h);
     if (!h || n_rows < 0) return fail(h, "som_set_sample_weights: bad argument");
     if (!w_host || n_rows == 0) { clear_sample_weights(h); return 0; }
-    if (n_rows != h->N) return fail(h, "som_set_sample_weights: one weight per resident row (set the rows first: som_set_data)");
+    if (n_rows != h->res.N) return fail(h, "som_set_sample_weights: one weight per resident row (set the rows first: som_set_data)");
     if (const int64_t bad = first_bad_weight(w_host, n_rows); bad >= 0) return fail_bad_weight(h, "som_set_sample_weights", w_host, bad);
     clear_sample_weights(h);
-    if (int rc = h->wgt_owned.alloc(h, (size_t)n_rows)) return rc;
-    if (int rc = h2d_blocking(h, h->wgt_owned, w_host, (size_t)n_rows * sizeof(float))) return rc;
+    if (int rc = h->res.wgt_owned.alloc(h, (size_t)n_rows)) return rc;
+    if (int rc = h2d_blocking(h, h->res.wgt_owned, w_host, (size_t)n_rows * sizeof(float))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->wgt = h->wgt_owned;
+    h->res.wgt = h->res.wgt_owned;
     drop_graph(h);
     h->graph_warm = 0;
     return 0;
@@ -1879,9 +1878,9 @@ int som_set_sample_weights_device(som_handle* h, const void* w_dev, int64_t n_ro
     DeviceGuard dev_guard(h);
     if (!h || n_rows < 0) return fail(h, "som_set_sample_weights_device: bad argument");
     if (!w_dev || n_rows == 0) { clear_sample_weights(h); return 0; }
-    if (n_rows != h->N) return fail(h, "som_set_sample_weights_device: one weight per resident row (set the rows first: som_set_data)");
+    if (n_rows != h->res.N) return fail(h, "som_set_sample_weights_device: one weight per resident row (set the rows first: som_set_data)");
     clear_sample_weights(h);
-    h->wgt = (const float*)w_dev;
+    h->res.wgt = (const float*)w_dev;
     drop_graph(h);
     h->graph_warm = 0;
     return 0;
@@ -1897,24 +1896,6 @@ int som_stream_begin(som_handle* h) {
     return 0;
 }
 
-static int ensure_slot(som_handle* h, som_handle::Slot& sl, long n) {
-    if (!sl.copied) {
-        HIPCHK(h, hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&sl.consumed, hipEventDisableTiming));
-    }
-    if (n <= sl.cap) return 0;
-    if (sl.used) HIPCHK(h, hipEventSynchronize(sl.consumed));
-    sl.dX.reset(); sl.dXb.reset(); sl.dxsq.reset(); sl.dbmu.reset(); sl.dw.reset(); sl.cap = 0;
-    long cap = round_up(n, ROW_PAD);
-    if (int rc = sl.dX.alloc(h, (size_t)cap * h->D)) return rc;
-    if (int rc = sl.dbmu.alloc(h, (size_t)cap)) return rc;
-    if (int rc = sl.dxsq.alloc(h, (size_t)cap * (h->exact ? 2 : 1))) return rc;
-    if (h->cfg.precision != SOM_PREC_F32)
-        if (int rc = sl.dXb.alloc(h, (size_t)cap * h->dp)) return rc;
-    sl.cap = cap;
-    return 0;
-}
-
 static bool is_pinned_host(const void* p) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -1927,12 +1908,13 @@ static int stream_rows(som_handle* h, const float* x_host, const float* w_host, 
     if (n_rows == 0) return 0;
     if (n_rows > 0x7fffffffL) return fail(h, "som_stream_rows: more than 2^31-1 rows in one chunk");
     const bool pinned = is_pinned_host(x_host);
-    if (!pinned) if (int rc = ensure_query_scratch(h, n_rows)) return rc;
     if (n_rows > h->st_seg.cap) {
         HIPCHK(h, hipStreamSynchronize(h->stream));       // earlier chunks' kernels still read the old scratch
         if (int rc = seg_reserve(h, h->st_seg, round_up(n_rows, 1024))) return rc;
     }
-    const size_t bytes = (size_t)n_rows * h->D * sizeof(float);
+    // how the bytes arrive: a slot's on the copy stream, the search behind an event; pageable ones staged by the runtime, synchronous
+    som_handle::Slot* const sl = pinned ? &h->slot[h->slot_idx] : nullptr;
+    RowSet& s = pinned ? sl->rows : h->q;
     if (pinned) {
         // Pinned chunk: copy on a second stream into one of two device slots, so the transfer of
         // chunk i+1 runs under the kernels of chunk i.  The caller may reuse the buffer of call i
@@ -1940,38 +1922,38 @@ static int stream_rows(som_handle* h, const float* x_host, const float* w_host, 
         if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
         som_handle::Slot& prev = h->slot[h->slot_idx ^ 1];
         if (prev.used) HIPCHK(h, hipEventSynchronize(prev.copied));
-        som_handle::Slot& sl = h->slot[h->slot_idx];
         h->slot_idx ^= 1;
-        if (int rc = ensure_slot(h, sl, n_rows)) return rc;
-        if (sl.used) HIPCHK(h, hipEventSynchronize(sl.consumed));     // the kernels that read this slot are done
-        if (w_host) {                                    // the weights travel with the rows, on the copy stream, into the slot
-            if (int rc = sl.dw.reserve(h, (size_t)sl.cap)) return rc;
-            HIPCHK(h, hipMemcpyAsync(sl.dw, w_host, (size_t)n_rows * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
+        if (!sl->copied) {
+            HIPCHK(h, hipEventCreateWithFlags(&sl->copied, hipEventDisableTiming));
+            HIPCHK(h, hipEventCreateWithFlags(&sl->consumed, hipEventDisableTiming));
         }
-        HIPCHK(h, hipMemcpyAsync(sl.dX, x_host, bytes, hipMemcpyHostToDevice, h->copy_stream));
-        HIPCHK(h, hipEventRecord(sl.copied, h->copy_stream));
-        HIPCHK(h, hipStreamWaitEvent(h->stream, sl.copied, 0));
-        if (needs_xsq(h)) if (int rc = row_sq(h, sl.dX, n_rows, sl.dxsq)) return rc;
-        if (h->cfg.precision != SOM_PREC_F32)
-            if (int rc = prep_rows_bf16(h, sl.dX, n_rows, round_up(n_rows, ROW_PAD), sl.dXb, h->xmax2 + 1, sl.dxsq)) return rc;
-        if (int rc = run_activation_bmu(h, sl.dX, n_rows, sl.dxsq, sl.dXb, h->xmax2 + 1, sl.dbmu)) return rc;
-        if (int rc = segsum_rows(h, sl.dX, sl.dbmu, n_rows, h->st_seg, false, w_host ? (const float*)sl.dw : nullptr)) return rc;
-        HIPCHK(h, hipEventRecord(sl.consumed, h->stream));
-        sl.used = true;
-        return 0;
+        if (sl->used) HIPCHK(h, hipEventSynchronize(sl->consumed));   // the kernels that read this slot are done: it may grow, and be written
+        if (int rc = reserve(h, s, n_rows, true)) return rc;
+        if (w_host) {                                    // the weights travel with the rows, on the copy stream, into the slot
+            if (int rc = s.wgt_owned.reserve(h, (size_t)s.cap)) return rc;
+            HIPCHK(h, hipMemcpyAsync(s.wgt_owned, w_host, (size_t)n_rows * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
+        }
+        HIPCHK(h, hipMemcpyAsync(s.X_owned, x_host, (size_t)n_rows * h->D * sizeof(float), hipMemcpyHostToDevice, h->copy_stream));
+        HIPCHK(h, hipEventRecord(sl->copied, h->copy_stream));
+        HIPCHK(h, hipStreamWaitEvent(h->stream, sl->copied, 0));
+        s.X = s.X_owned; s.N = n_rows;
+    } else {
+        if (int rc = take_rows(h, s, x_host, n_rows, true)) return rc;
+        if (w_host) {                                    // (the stream is drained: nothing reads the old weights)
+            if (int rc = s.wgt_owned.reserve(h, (size_t)n_rows, 1024)) return rc;
+            if (int rc = h2d_blocking(h, s.wgt_owned, w_host, (size_t)n_rows * sizeof(float))) return rc;
+        }
     }
-    // pageable chunk: staged by the runtime, synchronous; the caller's buffer is free on return
-    if (int rc = h2d_blocking(h, h->qX, x_host, bytes)) return rc;
-    if (w_host) {                                        // (the stream is drained: nothing reads the old qw)
-        if (int rc = h->qw.reserve(h, (size_t)n_rows, 1024)) return rc;
-        if (int rc = h2d_blocking(h, h->qw, w_host, (size_t)n_rows * sizeof(float))) return rc;
-    }
-    if (needs_xsq(h)) if (int rc = row_sq(h, h->qX, n_rows, h->qxsq)) return rc;
-    if (h->cfg.precision != SOM_PREC_F32)
-        if (int rc = prep_rows_bf16(h, h->qX, n_rows, round_up(n_rows, ROW_PAD), h->qXb, h->xmax2 + 1, h->qxsq)) return rc;
-    if (int rc = run_activation_bmu(h, h->qX, n_rows, h->qxsq, h->qXb, h->xmax2 + 1, h->qbmu)) return rc;
-    if (int rc = segsum_rows(h, h->qX, h->qbmu, n_rows, h->st_seg, false, w_host ? (const float*)h->qw : nullptr)) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    s.wgt = w_host ? (const float*)s.wgt_owned : nullptr;
+    // the one tail: prepare, search, segment sum
+    if (int rc = prepare(h, s, needs_xsq(h))) return rc;
+    const Rows r = s.view();
+    if (int rc = run_activation_bmu(h, r)) return rc;
+    if (int rc = segsum_rows(h, r, h->st_seg, false)) return rc;
+    // a slot is free again behind this event; a pageable chunk's buffer -- the caller's and ours -- on return
+    if (!pinned) { HIPCHK(h, hipStreamSynchronize(h->stream)); return 0; }
+    HIPCHK(h, hipEventRecord(sl->consumed, h->stream));
+    sl->used = true;
     return 0;
 }
 
@@ -2179,9 +2161,10 @@ int som_epoch(som_handle* h, double sigma, double eta, int neigh_f64) {
 int som_epoch_accumulate_begin(som_handle* h, double sigma, double eta, int neigh_f64) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
-    if (!h->Xd && h->N > 0) return fail(h, "som_epoch_accumulate_begin: no resident data (call som_set_data)");
-    if (int rc = run_activation_bmu(h, h->Xd, h->N, h->xsq, h->Xb, h->xmax2, h->bmu)) return rc;
-    if (int rc = segsum_rows(h, h->Xd, h->bmu, h->N, h->seg, true, h->wgt)) return rc;
+    const Rows r = h->res.view();
+    if (!r.X && r.N > 0) return fail(h, "som_epoch_accumulate_begin: no resident data (call som_set_data)");
+    if (int rc = run_activation_bmu(h, r)) return rc;
+    if (int rc = segsum_rows(h, r, h->seg, true)) return rc;
     Timed t(h, SOM_K_KRON);
     if (int rc = run_transform_stage1(h, sigma, eta, neigh_f64)) return rc;
     h->staged_blocks_done = 0;
@@ -2236,7 +2219,7 @@ int som_epoch_fetch(som_handle* h, float* num, float* den, int32_t* bmu) {
             if (den) den[k] = acc[k * h->D1p + h->D];
         }
     }
-    if (bmu && h->N > 0) HIPCHK(h, hipMemcpy(bmu, h->bmu, (size_t)h->N * sizeof(int), hipMemcpyDeviceToHost));
+    if (bmu && h->res.N > 0) HIPCHK(h, hipMemcpy(bmu, h->res.bmu, (size_t)h->res.N * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2250,18 +2233,18 @@ namespace {
 // sqrt'd distance: where |x|^2 is large against the distances (un-centred data) the radicand rounds, or clamps to 0, so that
 // units at different distances tie under the sqrt and the lowest id wins.  exact_qe_window_kernel keeps the rows whose pick
 // no such tie can overturn; the others go through the float32 SQRT kernel, so the ids are float32's bit for bit.
-int run_quantization_bmu(som_handle* h, const float* X, long n_rows, bool value_only = false) {
+int run_quantization_bmu(som_handle* h, bool value_only = false) {
+    RowSet& q = h->q; const float* X = q.X; const long n_rows = q.N;
     if (h->cfg.precision != SOM_PREC_F32 && h->cfg.distance == SOM_DIST_EUCLIDEAN && (!h->exact || value_only)) {
-        if (h->exact) if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
-        if (int rc = prep_rows_bf16(h, X, n_rows, round_up(n_rows, ROW_PAD), h->qXb, h->xmax2 + 1, h->qxsq)) return rc;
-        if (int rc = run_activation_bmu(h, X, n_rows, h->qxsq, h->qXb, h->xmax2 + 1, h->qbmu)) return rc;
+        if (int rc = prepare(h, q, h->exact)) return rc;
+        if (int rc = run_activation_bmu(h, q.view())) return rc;
         if (!h->exact) return 0;
         if (int rc = h->qe_list.reserve(h, (size_t)n_rows, 1024)) return rc;
         if (int rc = h->qe_cnt.reserve(h, 1, 1)) return rc;
         if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;       // (|w|^2; the float32 image in the units' order)
         HIPCHK(h, hipMemsetAsync(h->qe_cnt, 0, sizeof(int), h->stream));
         exact_qe_window_kernel<<<dim3((unsigned)cdiv(n_rows, 256)), dim3(256), 0, h->stream>>>(
-            X, n_rows, h->D, h->W, h->wsq, h->qxsq, h->qbmu, h->qe_list, h->qe_cnt);
+            X, n_rows, h->D, h->W, h->wsq, q.xsq, q.bmu, h->qe_list, h->qe_cnt);
         HIPCHK(h, hipGetLastError());
         int n_sq = 0;
         if (int rc = d2h_blocking(h, &n_sq, h->qe_cnt, sizeof(int))) return rc;
@@ -2277,55 +2260,68 @@ int run_quantization_bmu(som_handle* h, const float* X, long n_rows, bool value_
             Timed t(h, SOM_K_BMU);
             if (int rc = launch_bmu_f32_any<SCORE_EUCLID_SQRT>(h, h->qe_X, n_sq, h->qe_xsq, h->qe_ids)) return rc;
         }
-        exact_scatter_ids_kernel<<<dim3((unsigned)cdiv(n_sq, 256)), dim3(256), 0, h->stream>>>(h->qe_ids, h->qe_list, n_sq, h->qbmu);
+        exact_scatter_ids_kernel<<<dim3((unsigned)cdiv(n_sq, 256)), dim3(256), 0, h->stream>>>(h->qe_ids, h->qe_list, n_sq, q.bmu);
         HIPCHK(h, hipGetLastError());
         return 0;
     }
     if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
-    if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
+    if (int rc = row_sq(h, X, n_rows, q.xsq)) return rc;
     Timed t(h, SOM_K_BMU);
-    return launch_bmu_f32_any<SCORE_EUCLID_SQRT>(h, X, n_rows, h->qxsq, h->qbmu);
+    return launch_bmu_f32_any<SCORE_EUCLID_SQRT>(h, X, n_rows, q.xsq, q.bmu);
 }
 
-// BMUs (activation or quantization rule) of n device rows into qbmu
-int run_query_bmu(som_handle* h, const float* X, long n_rows, int mode) {
-    if (mode == SOM_BMU_QUANTIZATION) return run_quantization_bmu(h, X, n_rows);
-    if (needs_xsq(h)) if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
-    if (h->cfg.precision != SOM_PREC_F32)
-        if (int rc = prep_rows_bf16(h, X, n_rows, round_up(n_rows, ROW_PAD), h->qXb, h->xmax2 + 1, h->qxsq)) return rc;
-    return run_activation_bmu(h, X, n_rows, h->qxsq, h->qXb, h->xmax2 + 1, h->qbmu);
-}
-
-// best and second-best unit of n device rows under the sqrt'd Euclidean distance into qbmu / qbmu2: the exact mode's screen
+// best and second-best unit of the query set's rows under the sqrt'd Euclidean distance into its bmu / bmu2: the exact mode's screen
 // + two re-score rounds where they serve (exact_top2_fast), else -- and for every row they cannot settle -- the float32 kernel
-int run_top2(som_handle* h, const float* X, long n_rows) {
+int run_top2(som_handle* h) {
+    RowSet& q = h->q;
     if (exact_top2_fast(h)) {
-        if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
-        if (int rc = prep_rows_bf16(h, X, n_rows, round_up(n_rows, ROW_PAD), h->qXb, h->xmax2 + 1, h->qxsq)) return rc;
+        if (int rc = prepare(h, q, true)) return rc;
         if (int rc = refresh_codebook_operands(h, operands::Request::ExactScreen)) return rc;
         Timed t(h, SOM_K_BMU);
-        return launch_top2_exact(h, X, n_rows, h->qxsq, h->qXb, h->xmax2 + 1, h->qbmu, h->qbmu2);
+        return launch_top2_exact(h, q.view());
     }
     if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
-    if (int rc = row_sq(h, X, n_rows, h->qxsq)) return rc;
-    h->t2.rows += n_rows; h->t2.rows_f32 += n_rows;
+    if (int rc = row_sq(h, q.X, q.N, q.xsq)) return rc;
+    h->t2.rows += q.N; h->t2.rows_f32 += q.N;
     Timed t(h, SOM_K_BMU);
-    return launch_bmu_top2(h, X, n_rows, h->qxsq, h->qbmu, h->qbmu2);
-}
-// ... and the pair to the host (one unit: it is named twice -- include/somhip.h)
-int fetch_top2(som_handle* h, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out) {
-    if (int rc = d2h_blocking(h, ids1_out, h->qbmu, (size_t)n_rows * sizeof(int))) return rc;
-    if (h->K == 1) {
-        std::memcpy(ids2_out, ids1_out, (size_t)n_rows * sizeof(int));
-        return 0;
-    }
-    return d2h_blocking(h, ids2_out, h->qbmu2, (size_t)n_rows * sizeof(int));
+    return launch_bmu_top2(h, q.X, q.N, q.xsq, q.bmu, q.bmu2);
 }
 
-int run_quantization_error(som_handle* h, const float* X, long n_rows, double* qe_out) {
-    if (int rc = run_quantization_bmu(h, X, n_rows, true)) return rc;
+// ---- the queries: the host and the device entry point of a pair (x_host or x_dev is NULL; `who` names it in the messages) share
+// their argument checks and everything after "the rows are on the device" (query_rows) ----
+int query_bmu(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, int32_t mode, int32_t* ids_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || n_rows < 0 || (n_rows > 0 && ((!x_host && !x_dev) || !ids_out))) return fail(h, who + ": bad argument");
+    if (mode != SOM_BMU_ACTIVATION && mode != SOM_BMU_QUANTIZATION) return fail(h, who + ": unknown mode");
+    if (n_rows == 0) return 0;
+    if (x_dev && n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
+    if (mode == SOM_BMU_ACTIVATION) if (int rc = prepare(h, h->q, needs_xsq(h))) return rc;
+    if (int rc = mode == SOM_BMU_QUANTIZATION ? run_quantization_bmu(h) : run_activation_bmu(h, h->q.view())) return rc;
+    return d2h_blocking(h, ids_out, h->q.bmu, (size_t)n_rows * sizeof(int));
+}
+// ... the pair to the host (one unit: it is named twice -- include/somhip.h)
+int query_top2(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || n_rows < 0 || (n_rows > 0 && ((!x_host && !x_dev) || !ids1_out || !ids2_out))) return fail(h, who + ": bad argument");
+    if (n_rows == 0) return 0;
+    if (x_dev && n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
+    if (int rc = run_top2(h)) return rc;
+    const size_t bytes = (size_t)n_rows * sizeof(int);
+    if (int rc = d2h_blocking(h, ids1_out, h->q.bmu, bytes)) return rc;
+    if (h->K == 1) { std::memcpy(ids2_out, ids1_out, bytes); return 0; }
+    return d2h_blocking(h, ids2_out, h->q.bmu2, bytes);
+}
+int query_quantization_error(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, double* qe_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || !qe_out || n_rows < 0 || (n_rows > 0 && !x_host && !x_dev)) return fail(h, who + ": bad argument");
+    if (n_rows == 0) { *qe_out = NAN; return 0; }     // numpy: mean of an empty array
+    if (x_dev && n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
+    if (int rc = run_quantization_bmu(h, true)) return rc;
     HIPCHK(h, hipMemsetAsync(h->dsum, 0, sizeof(double), h->stream));
-    qe_kernel<<<dim3((unsigned)std::min<long>(cdiv(n_rows, 4), 4096)), dim3(256), 0, h->stream>>>(X, h->qbmu, h->W, n_rows, h->D, h->dsum);
+    qe_kernel<<<dim3((unsigned)std::min<long>(cdiv(n_rows, 4), 4096)), dim3(256), 0, h->stream>>>(h->q.X, h->q.bmu, h->W, n_rows, h->D, h->dsum);
     HIPCHK(h, hipGetLastError());
     double s = 0.0;
     if (int rc = d2h_blocking(h, &s, h->dsum, sizeof(double))) return rc;
@@ -2334,36 +2330,12 @@ int run_quantization_error(som_handle* h, const float* X, long n_rows, double* q
 }
 }  // namespace
 
-int som_bmu(som_handle* h, const float* x_host, int64_t n_rows, int32_t mode, int32_t* ids_out) {
-    DeviceGuard dev_guard(h);
-    if (!h || n_rows < 0 || (n_rows > 0 && (!x_host || !ids_out))) return fail(h, "som_bmu: bad argument");
-    if (mode != SOM_BMU_ACTIVATION && mode != SOM_BMU_QUANTIZATION) return fail(h, "som_bmu: unknown mode");
-    if (n_rows == 0) return 0;
-    if (int rc = ensure_query_scratch(h, n_rows)) return rc;
-    if (int rc = h2d_blocking(h, h->qX, x_host, (size_t)n_rows * h->D * sizeof(float))) return rc;
-    if (int rc = run_query_bmu(h, h->qX, n_rows, mode)) return rc;
-    return d2h_blocking(h, ids_out, h->qbmu, (size_t)n_rows * sizeof(int));
-}
-
-int som_bmu_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t mode, int32_t* ids_out) {
-    DeviceGuard dev_guard(h);
-    if (!h || n_rows < 0 || (n_rows > 0 && (!x_dev || !ids_out))) return fail(h, "som_bmu_device: bad argument");
-    if (mode != SOM_BMU_ACTIVATION && mode != SOM_BMU_QUANTIZATION) return fail(h, "som_bmu_device: unknown mode");
-    if (n_rows == 0) return 0;
-    if (n_rows > 0x7fffffffL) return fail(h, "som_bmu_device: more than 2^31-1 rows in one call");
-    if (int rc = ensure_query_scratch(h, n_rows, false)) return rc;
-    if (int rc = run_query_bmu(h, (const float*)x_dev, n_rows, mode)) return rc;
-    return d2h_blocking(h, ids_out, h->qbmu, (size_t)n_rows * sizeof(int));
-}
-
-int som_quantization_error_device(som_handle* h, const void* x_dev, int64_t n_rows, double* qe_out) {
-    DeviceGuard dev_guard(h);
-    if (!h || !qe_out || n_rows < 0 || (n_rows > 0 && !x_dev)) return fail(h, "som_quantization_error_device: bad argument");
-    if (n_rows == 0) { *qe_out = NAN; return 0; }
-    if (n_rows > 0x7fffffffL) return fail(h, "som_quantization_error_device: more than 2^31-1 rows in one call");
-    if (int rc = ensure_query_scratch(h, n_rows, false)) return rc;
-    return run_quantization_error(h, (const float*)x_dev, n_rows, qe_out);
-}
+int som_bmu(som_handle* h, const float* x_host, int64_t n_rows, int32_t mode, int32_t* ids_out) { return query_bmu(h, "som_bmu", x_host, nullptr, n_rows, mode, ids_out); }
+int som_bmu_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t mode, int32_t* ids_out) { return query_bmu(h, "som_bmu_device", nullptr, x_dev, n_rows, mode, ids_out); }
+int som_bmu_top2(som_handle* h, const float* x_host, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out) { return query_top2(h, "som_bmu_top2", x_host, nullptr, n_rows, ids1_out, ids2_out); }
+int som_bmu_top2_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out) { return query_top2(h, "som_bmu_top2_device", nullptr, x_dev, n_rows, ids1_out, ids2_out); }
+int som_quantization_error(som_handle* h, const float* x_host, int64_t n_rows, double* qe_out) { return query_quantization_error(h, "som_quantization_error", x_host, nullptr, n_rows, qe_out); }
+int som_quantization_error_device(som_handle* h, const void* x_dev, int64_t n_rows, double* qe_out) { return query_quantization_error(h, "som_quantization_error_device", nullptr, x_dev, n_rows, qe_out); }
 
 int som_bmu_f64(som_handle* h, const double* x_host, int64_t n_rows, int32_t* ids_out) {
     DeviceGuard dev_guard(h);
@@ -2372,37 +2344,17 @@ int som_bmu_f64(som_handle* h, const double* x_host, int64_t n_rows, int32_t* id
     if (n_rows == 0) return 0;
     const size_t w_bytes = (size_t)PW_UNITS * h->D * sizeof(float);
     if (w_bytes > 150 * 1024) return fail(h, "som_bmu_f64: input_len too large for the LDS unit tile");
-    if (int rc = ensure_query_scratch(h, n_rows)) return rc;
+    if (int rc = reserve(h, h->q, n_rows, true)) return rc;
     if (int rc = h->qX64.reserve(h, (size_t)n_rows * h->D, (size_t)1024 * h->D)) return rc;
     if (int rc = h2d_blocking(h, h->qX64, x_host, (size_t)n_rows * h->D * sizeof(double))) return rc;
     if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;       // |w|^2 in NumPy's float32 order
     {
         Timed t(h, SOM_K_BMU);
         bmu_f64_kernel<<<dim3((unsigned)cdiv(n_rows, PW_SAMPLES)), dim3(PW_SAMPLES), w_bytes, h->stream>>>(
-            h->qX64, n_rows, h->D, h->W, h->wsq, h->K, h->qbmu);
+            h->qX64, n_rows, h->D, h->W, h->wsq, h->K, h->q.bmu);
         HIPCHK(h, hipGetLastError());
     }
-    return d2h_blocking(h, ids_out, h->qbmu, (size_t)n_rows * sizeof(int));
-}
-
-int som_bmu_top2(som_handle* h, const float* x_host, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out) {
-    DeviceGuard dev_guard(h);
-    if (!h || n_rows < 0 || (n_rows > 0 && (!x_host || !ids1_out || !ids2_out))) return fail(h, "som_bmu_top2: bad argument");
-    if (n_rows == 0) return 0;
-    if (int rc = ensure_query_scratch(h, n_rows)) return rc;
-    if (int rc = h2d_blocking(h, h->qX, x_host, (size_t)n_rows * h->D * sizeof(float))) return rc;
-    if (int rc = run_top2(h, h->qX, n_rows)) return rc;
-    return fetch_top2(h, n_rows, ids1_out, ids2_out);
-}
-
-int som_bmu_top2_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out) {
-    DeviceGuard dev_guard(h);
-    if (!h || n_rows < 0 || (n_rows > 0 && (!x_dev || !ids1_out || !ids2_out))) return fail(h, "som_bmu_top2_device: bad argument");
-    if (n_rows == 0) return 0;
-    if (n_rows > 0x7fffffffL) return fail(h, "som_bmu_top2_device: more than 2^31-1 rows in one call");
-    if (int rc = ensure_query_scratch(h, n_rows, false)) return rc;
-    if (int rc = run_top2(h, (const float*)x_dev, n_rows)) return rc;
-    return fetch_top2(h, n_rows, ids1_out, ids2_out);
+    return d2h_blocking(h, ids_out, h->q.bmu, (size_t)n_rows * sizeof(int));
 }
 
 int som_distance_matrix(som_handle* h, const float* x_host, int64_t n_rows, int32_t mode, float* dist_out) {
@@ -2413,10 +2365,9 @@ int som_distance_matrix(som_handle* h, const float* x_host, int64_t n_rows, int3
         return fail(h, "som_distance_matrix: only the GEMM-form distances (euclidean, euclidean_no_opt, cosine)");
     if (n_rows == 0) return 0;
     if ((double)n_rows * h->K > 2.0e9) return fail(h, "som_distance_matrix: n_rows * K too large (analysis call, chunk it)");
-    if (int rc = ensure_query_scratch(h, n_rows)) return rc;
-    if (int rc = h2d_blocking(h, h->qX, x_host, (size_t)n_rows * h->D * sizeof(float))) return rc;
+    if (int rc = query_rows(h, x_host, nullptr, n_rows)) return rc;
     if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
-    if (int rc = row_sq(h, h->qX, n_rows, h->qxsq)) return rc;
+    if (int rc = row_sq(h, h->q.X, n_rows, h->q.xsq)) return rc;
     DevBuf<float> dm;
     if (int rc = dm.alloc(h, (size_t)n_rows * h->K)) return rc;
     int rc = 0;
@@ -2426,15 +2377,6 @@ int som_distance_matrix(som_handle* h, const float* x_host, int64_t n_rows, int3
     else rc = launch_dist_matrix<SCORE_COSINE>(h, n_rows, dm);
     if (rc) return rc;
     return d2h_blocking(h, dist_out, dm, (size_t)n_rows * h->K * sizeof(float));
-}
-
-int som_quantization_error(som_handle* h, const float* x_host, int64_t n_rows, double* qe_out) {
-    DeviceGuard dev_guard(h);
-    if (!h || !qe_out || n_rows < 0 || (n_rows > 0 && !x_host)) return fail(h, "som_quantization_error: bad argument");
-    if (n_rows == 0) { *qe_out = NAN; return 0; }     // numpy: mean of an empty array
-    if (int rc = ensure_query_scratch(h, n_rows)) return rc;
-    if (int rc = h2d_blocking(h, h->qX, x_host, (size_t)n_rows * h->D * sizeof(float))) return rc;
-    return run_quantization_error(h, h->qX, n_rows, qe_out);
 }
 
 int som_set_verify(som_handle* h, int32_t n_rows) {
@@ -2619,6 +2561,14 @@ int som_operands_replay(const int32_t* config, int32_t n_events, const int32_t* 
         o[8] = r.flush; o[9] = r.flush_cm;
         o[10] = st.f32_in_patch_order(); o[11] = st.image_pending(); o[12] = st.centroids_fresh(); o[13] = st.patch_copy_in_step();
     }
+    return 0;
+}
+
+// TEST HOOK (no device needed): the row sets' size rule (csrc/row_set.hpp) on caller-supplied numbers.  Layout: include/somhip_test.h.
+int som_debug_row_set_sizes(int32_t kind, int64_t n, int32_t input_len, int32_t dp, int32_t flags, int64_t* out5) {
+    if (kind < 0 || kind > 2 || n < 0 || input_len < 1 || dp < 0 || !out5) return 1;
+    const rowset::Sizes z = rowset::sizes((rowset::Kind)kind, (long)n, input_len, dp, {(flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, (flags & 8) != 0});
+    out5[0] = z.cap; out5[1] = (int64_t)z.X; out5[2] = (int64_t)z.xsq; out5[3] = (int64_t)z.Xb; out5[4] = (int64_t)z.ids;
     return 0;
 }
 
