@@ -42,8 +42,12 @@ enum { SOM_DIST_EUCLIDEAN = 0,        /* 'euclidean'  -> euclidean_squared_dista
 enum { SOM_NEIGH_GAUSSIAN = 0, SOM_NEIGH_MEXICAN_HAT = 1, SOM_NEIGH_BUBBLE = 2, SOM_NEIGH_TRIANGLE = 3 };
 
 /* map topology: xpysom.py:196-206.  HEXAGONAL selects the *_generic neighbourhoods
- * (neighborhoods.py:35-55, :76-97) on the shifted-row coordinates; bubble ignores the shift. */
-enum { SOM_TOPO_RECTANGULAR = 0, SOM_TOPO_HEXAGONAL = 1 };
+ * (neighborhoods.py:35-55, :76-97) on the shifted-row coordinates; bubble ignores the shift.
+ * TOROIDAL (not in the reference) is the rectangular grid with periodic boundaries on both axes: every neighbourhood
+ * sees the offset to the NEAREST image of the BMU, d - L round(d / L) per axis (one image, never a sum), and the
+ * support mask (bubble, compact_support) is -sigma < offset < sigma.  All four neighbourhoods; mexican_hat with
+ * compact_support is refused. */
+enum { SOM_TOPO_RECTANGULAR = 0, SOM_TOPO_HEXAGONAL = 1, SOM_TOPO_TOROIDAL = 2 };
 
 /* arithmetic of the distance GEMM (the -2 x.w^T term, distances.py:22):
  *   F32  : v_mfma_f32_32x32x2_f32, exact float32 fma chain -- the parity mode

@@ -90,6 +90,21 @@ int som_debug_band_walk(const float* H, int32_t rows, int32_t nseg, int32_t segw
  * the entries with the tables' own nonzeros. */
 int som_debug_band_tables(som_handle* h, int32_t* info4, int32_t* entries_out, float* P1_out, float* P2_out);
 
+/* The same arithmetic for a TOROIDAL table, whose segments are cut at band_wrap_mid(segw) into a low piece [0, mid) and a high
+ * piece [mid, segw) with a range each (csrc/update.hpp) -- NO device needed (tests/test_torus_bands_cpu.py).  Arguments as above;
+ *   tiles_out [ceil(rows / 32)][nseg][2 pieces][2] = {tlo, thi} in segment coordinates per piece, low first;
+ *   wg_out [ceil(rows / wg_rows)][2 pieces][3] = {lo, hi, chunks}: the workgroup stages [lo, lo + 32 chunks) of the low piece of
+ *     every segment, then of the high piece, each piece's columns from its hi on as zeros (the low lo is a multiple of 32, the
+ *     high lo of 8 and never below the cut). */
+int som_debug_band_walk_wrap(const float* H, int32_t rows, int32_t nseg, int32_t segw, int32_t wg_rows, int32_t* tiles_out,
+                             int32_t* wg_out);
+
+/* som_debug_band_tables for a TOROIDAL handle (which that call refuses, as this one refuses the others): info4 as there, with
+ * range entries counted per piece; entries_out [entries][2] with entry 2 e + piece where a rectangular handle has entry e -- the
+ * same {segw - first nonzero column, last nonzero column + 1} pair in segment coordinates, over the nonzeros of the piece alone
+ * (low: columns below band_wrap_mid(side) = ((side / 2 + 4) / 8) * 8; high: the rest).  tests/test_gpu_torus.py. */
+int som_debug_band_tables_wrap(som_handle* h, int32_t* info4, int32_t* entries_out, float* P1_out, float* P2_out);
+
 /* precision EXACT: the plan of the last BMU launch as it ran (policy::LaunchPlan, csrc/exact_policy.hpp):
  *   out8 = [0] skip  [1] resort  [2] scout  [3] level 2  [4] estimate  [5] sample_tiles  [6] refine  [7] time_phases */
 int som_debug_exact_last_plan(som_handle* h, int32_t* out8);

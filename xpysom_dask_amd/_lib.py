@@ -11,7 +11,7 @@ SOM_DIST = {"euclidean": 0, "euclidean_no_opt": 1, "cosine": 2, "manhattan": 3, 
             "norm_p": 4, "norm_p_no_opt": 5}
 SOM_NEIGH = {"gaussian": 0, "mexican_hat": 1, "bubble": 2, "triangle": 3}
 SOM_PREC = {"f32": 0, "bf16": 1, "f16": 3, "exact": 5}      # (ids 2 and 4: the retired split-operand modes)
-SOM_TOPO = {"rectangular": 0, "hexagonal": 1}
+SOM_TOPO = {"rectangular": 0, "hexagonal": 1, "toroidal": 2}
 SOM_BMU_ACTIVATION, SOM_BMU_QUANTIZATION = 0, 1
 SOM_KERNELS = {"bmu": 0, "segsum": 1, "kron": 2, "merge": 3, "prep": 4, "screen": 5}
 
@@ -89,6 +89,8 @@ SIGNATURES = {
     "som_debug_plan_split": (C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "som_debug_band_tables": (C.c_int, [_H, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "som_debug_band_walk": (C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, _I]),
+    "som_debug_band_tables_wrap": (C.c_int, [_H, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "som_debug_band_walk_wrap": (C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, _I]),
     "som_debug_exact_last_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
     "som_policy_eval": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "som_policy_replay": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -246,6 +246,7 @@ struct som_handle {
     int stage_units = 0;     // units per stage
     int nt = 1;              // neighbourhood terms
     bool swapped = false;    // mexican_hat + compact_support, rectangular: row stage, mask, column stage (update.hpp)
+    bool torus = false;      // toroidal topology: wrapped offsets in the tables, two band ranges per tile and segment (update.hpp)
     int norm_p = 2;          // exponent of the norm_p distances
     double norm_pr = 0.0;    // ... when it is not an integer (0: norm_p)
     hipStream_t stream = nullptr;
@@ -1199,6 +1200,7 @@ NeighParams make_neigh_params(const som_handle* h, double sigma, double eta, int
     p.ncls = !p.hex ? 1 : h->cfg.compact_support ? 4 : 3;
     p.base_nt = h->nt / p.ncls;
     p.swapped = h->swapped ? 1 : 0;
+    p.torus = h->torus ? 1 : 0;
     return p;
 }
 
@@ -1226,15 +1228,19 @@ int build_tables(som_handle* h, double sigma, double eta, int neigh_f64, hipStre
 BandRanges band_ranges_from(const som_handle* h, long first) {
     BandRanges br{};
     if (!h->use_bands || h->swapped) return br;
-    br.base = (const int2*)h->bands + first;
+    const int pieces = h->torus ? 2 : 1;                 // toroidal: an entry per piece of a segment (update.hpp, band_wrap_mid)
+    br.base = (const int2*)h->bands + first * pieces;
     br.p_dev = h->capturing ? (const NeighParams*)h->np_dev : nullptr;
-    br.stride = band_entries(h->X, h->Y, h->nt);
+    br.stride = band_entries(h->X, h->Y, h->nt) * pieces;
     br.sel = h->band_sel;
     return br;
 }
 
 // OUT = H * M over C columns (rows of M / OUT ld floats apart): 128-wide MFMA tiles, and a VALU kernel for a last
 // tile of <= LM_NARROW columns.  row_blocks: the 128-row blocks of H.
+// A toroidal handle's ranges come in pairs (update.hpp, band_wrap_mid): its MFMA tiles go to leftmul_wrap_f32_kernel, and
+// its narrow last tile walks everything (the VALU kernel knows one range per tile; skipped columns add exact zeros, so
+// the result is the same, and no map of the flagship kind -- input_len a multiple of 128 -- has a narrow tile).
 void launch_leftmul(som_handle* h, const float* H, int Ro, int Ri, const float* M, long mstride, float* OUT, long ostride,
                     long C, long ld, int row_blocks, int batch, const BandRanges& ranges, int nseg, int segw, long ldo = 0) {
     if (ldo == 0) ldo = ld;                              // rows of OUT as far apart as rows of M unless told otherwise
@@ -1243,8 +1249,9 @@ void launch_leftmul(som_handle* h, const float* H, int Ro, int Ri, const float* 
     if (rem > 0 && rem <= LM_NARROW) {
         --wide;
         const dim3 g(1, (unsigned)row_blocks, (unsigned)batch), b(256);
-        if (rem <= 4) leftmul_narrow_f32_kernel<2><<<g, b, 0, h->stream>>>(H, Ro, Ri, M, mstride, OUT, ostride, C, ld, ldo, C - rem, ranges, nseg, segw);
-        else leftmul_narrow_f32_kernel<4><<<g, b, 0, h->stream>>>(H, Ro, Ri, M, mstride, OUT, ostride, C, ld, ldo, C - rem, ranges, nseg, segw);
+        const BandRanges nr = h->torus ? BandRanges{} : ranges;
+        if (rem <= 4) leftmul_narrow_f32_kernel<2><<<g, b, 0, h->stream>>>(H, Ro, Ri, M, mstride, OUT, ostride, C, ld, ldo, C - rem, nr, nseg, segw);
+        else leftmul_narrow_f32_kernel<4><<<g, b, 0, h->stream>>>(H, Ro, Ri, M, mstride, OUT, ostride, C, ld, ldo, C - rem, nr, nseg, segw);
     }
     if (wide <= 0) return;
     // 64-row tiles where 128-row ones would be half empty (64 x 64 x 32: transform 34.6 -> 26.6 us), and wherever the
@@ -1252,7 +1259,14 @@ void launch_leftmul(som_handle* h, const float* H, int Ro, int Ri, const float* 
     // barriers shrink with the band as the MFMAs do (256 x 256 x 128, sigma 1.2: 21 us a launch against 25; on dense
     // tables the two were measured neutral at that shape, 49 us both).  Without ranges: the 128-row tile as before.
     const bool rows64 = h->lm_rows == 64 || (h->lm_rows == 0 && (Ro <= 64 || ranges.base != nullptr));
-    if (rows64)
+    if (h->torus && ranges.base != nullptr) {
+        if (rows64)
+            leftmul_wrap_f32_kernel<64><<<dim3((unsigned)wide, (unsigned)cdiv(Ro, 64), (unsigned)batch), dim3(256), 0, h->stream>>>(
+                H, Ro, Ri, M, mstride, OUT, ostride, C, ld, ldo, ranges, nseg, segw);
+        else
+            leftmul_wrap_f32_kernel<128><<<dim3((unsigned)wide, (unsigned)row_blocks, (unsigned)batch), dim3(256), 0, h->stream>>>(
+                H, Ro, Ri, M, mstride, OUT, ostride, C, ld, ldo, ranges, nseg, segw);
+    } else if (rows64)
         leftmul_f32_kernel<64><<<dim3((unsigned)wide, (unsigned)cdiv(Ro, 64), (unsigned)batch), dim3(256), 0, h->stream>>>(
             H, Ro, Ri, M, mstride, OUT, ostride, C, ld, ldo, ranges, nseg, segw);
     else
@@ -1418,8 +1432,11 @@ int som_create(const som_config* cfg, som_handle** out) {
         cfg->x != cfg->y)
         return fail(nullptr, "som_create: mexican_hat with compact_support needs a square map on the rectangular topology "
                              "(the reference's second mask on px does not broadcast otherwise, neighborhoods.py:70)");
-    if (cfg->topology != SOM_TOPO_RECTANGULAR && cfg->topology != SOM_TOPO_HEXAGONAL)
+    if (cfg->topology != SOM_TOPO_RECTANGULAR && cfg->topology != SOM_TOPO_HEXAGONAL && cfg->topology != SOM_TOPO_TOROIDAL)
         return fail(nullptr, "som_create: unknown topology id");
+    if (cfg->topology == SOM_TOPO_TOROIDAL && cfg->neighborhood == SOM_NEIGH_MEXICAN_HAT && cfg->compact_support)
+        return fail(nullptr, "som_create: mexican_hat with compact_support is not defined on the toroidal topology (the "
+                             "rectangular form reproduces the reference's double mask; the torus has no reference)");
     if (cfg->topology == SOM_TOPO_HEXAGONAL && cfg->neighborhood == SOM_NEIGH_TRIANGLE)
         return fail(nullptr, "som_create: the hexagonal topology has no triangle neighbourhood (xpysom.py:271-279)");
     if (cfg->precision < SOM_PREC_F32 || cfg->precision > SOM_PREC_EXACT)
@@ -1485,6 +1502,7 @@ int som_create(const som_config* cfg, som_handle** out) {
     h->stage_units = h->wide ? WD_STAGE_UNITS : K16_STAGE_UNITS;
     h->nt = cfg->neighborhood == SOM_NEIGH_MEXICAN_HAT ? (cfg->compact_support ? 4 : 2) : 1;
     h->swapped = cfg->neighborhood == SOM_NEIGH_MEXICAN_HAT && cfg->compact_support && cfg->topology == SOM_TOPO_RECTANGULAR;
+    h->torus = cfg->topology == SOM_TOPO_TOROIDAL;
     // hexagonal: one copy of the terms per parity class of (unit row, BMU row) -- three classes by the x offset
     // difference (0, +0.5, -0.5); four with compact_support, whose mask compares ABSOLUTE x coordinates (update.hpp)
     if (cfg->topology == SOM_TOPO_HEXAGONAL && cfg->neighborhood != SOM_NEIGH_BUBBLE) h->nt *= cfg->compact_support ? 4 : 3;
@@ -1568,7 +1586,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         h->use_bands = h->X > LM_TILE || h->Y > LM_TILE;
         if (const char* e = dev_env("SOM_NO_BANDS")) h->use_bands = std::atoi(e) == 0;
         if (const char* e = dev_env("SOM_LM_ROWS")) h->lm_rows = std::atoi(e) == 64 ? 64 : std::atoi(e) == 128 ? 128 : 0;
-        const size_t nb = (size_t)2 * band_entries(h->X, h->Y, h->nt);   // two buffers, both empty
+        const size_t nb = (size_t)2 * band_entries(h->X, h->Y, h->nt) * (h->torus ? 2 : 1);   // two buffers, both empty (toroidal: an entry per piece)
         if ((rc = h->bands.alloc(h, nb))) return bail(rc);
         if (hipMemsetAsync(h->bands, 0, nb * sizeof(int2), h->stream) != hipSuccess) return bail(fail(h, "hipMemsetAsync failed"));
     }
@@ -2633,6 +2651,7 @@ int som_debug_plan_split(int32_t bf16, int64_t n, const float* P, const float* s
 int som_debug_band_tables(som_handle* h, int32_t* info4, int32_t* entries_out, float* P1_out, float* P2_out) {
     DeviceGuard dev_guard(h);
     if (!h || !info4) return fail(h, "som_debug_band_tables: NULL argument");
+    if (h->torus) return fail(h, "som_debug_band_tables: a toroidal handle keeps two ranges per tile and segment (som_debug_band_tables_wrap)");
     const long nb = band_entries(h->X, h->Y, h->nt);
     info4[0] = h->use_bands && !h->swapped; info4[1] = h->nt; info4[2] = (int32_t)nb; info4[3] = h->band_sel;
     if (entries_out)
@@ -2666,6 +2685,49 @@ int som_debug_band_walk(const float* H, int32_t rows, int32_t nseg, int32_t segw
         band_union(e.data() + (size_t)w * per_wg * nseg, std::min(per_wg, band_tiles(rows - w * wg_rows)), nseg, segw, LM_BK, lo, hi);
         wg_out[3 * w] = lo; wg_out[3 * w + 1] = hi; wg_out[3 * w + 2] = (hi - lo + LM_BK - 1) / LM_BK;
     }
+    return 0;
+}
+
+int som_debug_band_tables_wrap(som_handle* h, int32_t* info4, int32_t* entries_out, float* P1_out, float* P2_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || !info4) return fail(h, "som_debug_band_tables_wrap: NULL argument");
+    if (!h->torus) return fail(h, "som_debug_band_tables_wrap: not a toroidal handle (som_debug_band_tables)");
+    const long nb = 2 * band_entries(h->X, h->Y, h->nt);
+    info4[0] = h->use_bands; info4[1] = h->nt; info4[2] = (int32_t)nb; info4[3] = h->band_sel;
+    if (entries_out)
+        if (int rc = d2h_blocking(h, entries_out, (const int2*)h->bands + (long)h->band_sel * nb, (size_t)nb * sizeof(int2))) return rc;
+    if (P1_out)
+        if (int rc = d2h_blocking(h, P1_out, h->P1, (size_t)h->nt * h->Y * h->Y * sizeof(float))) return rc;
+    if (P2_out)
+        if (int rc = d2h_blocking(h, P2_out, h->P2, (size_t)h->X * h->nt * h->X * sizeof(float))) return rc;
+    return 0;
+}
+
+int som_debug_band_walk_wrap(const float* H, int32_t rows, int32_t nseg, int32_t segw, int32_t wg_rows, int32_t* tiles_out,
+                             int32_t* wg_out) {
+    if (!H || !tiles_out || !wg_out || rows <= 0 || nseg <= 0 || segw <= 0 || (wg_rows != 64 && wg_rows != 128)) return 1;
+    const int nt = band_tiles(rows), per_wg = wg_rows / LM_TILE;
+    std::vector<int2> e((size_t)nt * nseg * 2, make_int2(0, 0));
+    for (int i = 0; i < rows; ++i)
+        for (int sg = 0; sg < nseg; ++sg)
+            for (int k = 0; k < segw; ++k)
+                if (H[((size_t)i * nseg + sg) * segw + k] != 0.0f) {
+                    int2& v = e[((size_t)(i / LM_TILE) * nseg + sg) * 2 + band_wrap_piece(k, segw)];
+                    v = band_entry_with(v, k, segw);
+                }
+    for (size_t i = 0; i < e.size(); ++i) {
+        int lo, hi;
+        band_tile_range(e[i], segw, lo, hi);
+        tiles_out[2 * i] = lo; tiles_out[2 * i + 1] = hi;
+    }
+    for (int w = 0; w * wg_rows < rows; ++w)
+        for (int piece = 0; piece < 2; ++piece) {
+            int lo, hi;
+            band_union(e.data() + (size_t)w * per_wg * nseg * 2 + piece, std::min(per_wg, band_tiles(rows - w * wg_rows)), nseg, segw,
+                       piece ? LM_KG : LM_BK, lo, hi, 2);          // (as leftmul_f32_body rounds the two lower ends)
+            int32_t* o = wg_out + (2 * w + piece) * 3;
+            o[0] = lo; o[1] = hi; o[2] = (hi - lo + LM_BK - 1) / LM_BK;
+        }
     return 0;
 }
 

@@ -435,6 +435,7 @@ struct NeighParams {
     int hex, base_nt, ncls; // hexagonal topology: nt = ncls * base_nt, one copy of the terms per parity class
     int swapped;            // mexican_hat + compact_support on the rectangular topology: row stage first (see below)
     int rsel;               // which of the two band-range buffers this build of the tables fills (BandRanges, below)
+    int torus;              // toroidal topology: the rectangular grid, periodic on both axes (neigh_offset)
 };
 
 __device__ __forceinline__ double neigh_exp(double delta2, const NeighParams& p) {
@@ -450,17 +451,32 @@ __device__ __forceinline__ double neigh_exp(double delta2, const NeighParams& p)
 __device__ __forceinline__ double neigh_box(double n, double c, const NeighParams& p) {
     return (n > c - p.sigma && n < c + p.sigma) ? 1.0 : 0.0;
 }
+// the offset of unit coordinate n from BMU coordinate c along axis `which` (0 = x, side X; 1 = y, side Y).  Toroidal: the
+// NEAREST image, dl - L round(dl / L), |offset| <= L / 2 -- one image, never a sum over images; at the tie |offset| = L / 2
+// (even L) the sign is rint's, and every neighbourhood is even in the offset.
+__device__ __forceinline__ double neigh_offset(int which, double n, double c, const NeighParams& p) {
+    double dl = n - c;
+    if (p.torus) { const double L = (double)(which == 0 ? p.X : p.Y); dl -= L * rint(dl / L); }
+    return dl;
+}
+// the support mask of the unit at offset dl = neigh_offset(..., n, c): the reference's compare on the coordinates (above), or
+// on the torus, which has no reference, the open interval on the wrapped offset itself
+__device__ __forceinline__ double neigh_mask(double n, double c, double dl, const NeighParams& p) {
+    if (p.torus) return (dl > -p.sigma && dl < p.sigma) ? 1.0 : 0.0;
+    return neigh_box(n, c, p);
+}
 __device__ __forceinline__ double neigh_round(double v, const NeighParams& p) { return p.wide ? v : (double)(float)v; }
 
 // value of factor `which` (0 = row factor Px, 1 = column factor Py) of base term t for unit coordinate n and
-// BMU coordinate c (absolute: on the hexagonal topology the x coordinates carry their rows' half-unit offsets)
+// BMU coordinate c (absolute: on the hexagonal topology the x coordinates carry their rows' half-unit offsets; on the
+// toroidal one the offset n - c is wrapped to its nearest image first, and everything below sees only that)
 __device__ double neigh_factor(int which, int t, double n, double c, const NeighParams& p) {
-    const double dl = n - c;
+    const double dl = neigh_offset(which, n, c, p);
     const double d2 = dl * dl;
     switch (p.kind) {
     case 0: {   // gaussian
         double e = neigh_exp(d2, p);
-        if (p.compact) e *= neigh_box(n, c, p);
+        if (p.compact) e *= neigh_mask(n, c, dl, p);
         return e;
     }
     case 1: {   // mexican hat: (ex(1-2px/d)) * ey  -  ex * ((2py/d) ey)
@@ -480,7 +496,7 @@ __device__ double neigh_factor(int which, int t, double n, double c, const Neigh
         // times the h they sum to -- and leave its float32 rounding behind.
         // Rectangular: M = m1(i; ci) m2(i; cj) -- the second mask compares the ROW index with the BMU's COLUMN --:
         // the same four terms with my = m2, which is applied between the row stage and the column stage (`swapped`,
-        // mask_rows_kernel: terms 0 and 1 times m2, term 3 times 1 - m2).
+        // mask_rows_kernel: terms 0 and 1 times m2, term 3 times 1 - m2).  (Toroidal: refused by som_create.)
         const double m = neigh_box(n, c, p);
         if (which == 0) {
             if (t == 0) return neigh_round(m * e * (1.0 - q), p);
@@ -493,11 +509,11 @@ __device__ double neigh_factor(int which, int t, double n, double c, const Neigh
         return (t == 3 && p.hex ? 1.0 - m : 1.0) * neigh_round(e - qe, p);
     }
     case 2:     // bubble
-        return neigh_box(n, c, p);
+        return neigh_mask(n, c, dl, p);
     default: {  // triangle
         double v = p.sigma - fabs(dl);
         if (v < 0.0) v = 0.0;
-        if (p.compact) v *= neigh_box(n, c, p);
+        if (p.compact) v *= neigh_mask(n, c, dl, p);
         return neigh_round(v, p);
     }
     }
@@ -521,6 +537,7 @@ __global__ void store_params_kernel(NeighParams p, NeighParams* __restrict__ dst
 // the build before) are done; the host alternates rsel from build to build, so no launch is spent on clearing.
 constexpr int LM_TILE = 32;     // rows of H per range entry
 constexpr int LM_KG = 8;        // columns per skipping decision: four MFMA k steps (a tile's range is rounded outwards to it)
+constexpr int LM_BK = 32;       // columns a workgroup of the GEMMs stages at a time (the k chunk)
 
 __host__ __device__ inline int band_tiles(int rows) { return (rows + LM_TILE - 1) / LM_TILE; }
 __host__ __device__ inline long band_entries(int X, int Y, int nt) { return (long)nt * (band_tiles(Y) + band_tiles(X)); }
@@ -542,10 +559,12 @@ __host__ __device__ inline void band_tile_range(int2 v, int segw, int& tlo, int&
 __host__ __device__ inline bool band_group_on(int k0, int tlo, int thi) { return k0 < thi && k0 + LM_KG > tlo; }
 // the columns a workgroup stages: the union over its ntiles tiles (entries tiles[t * nseg + sg]) and all segments, the
 // lower end rounded down to a chunk; every segment is walked over the same [lo, hi).  Nothing nonzero: lo = hi = 0.
-__host__ __device__ inline void band_union(const int2* tiles, int ntiles, int nseg, int segw, int chunk, int& lo, int& hi) {
+// (step: the entries' distance -- 2 for one piece of a toroidal table, below)
+__host__ __device__ inline void band_union(const int2* tiles, int ntiles, int nseg, int segw, int chunk, int& lo, int& hi,
+                                           int step = 1) {
     lo = segw; hi = 0;
     for (int i = 0; i < ntiles * nseg; ++i) {
-        const int2 v = tiles[i];
+        const int2 v = tiles[(long)i * step];
         if (v.y > 0) {
             const int l = ((segw - v.x) / chunk) * chunk, u = v.y < segw ? v.y : segw;
             lo = l < lo ? l : lo;
@@ -561,6 +580,21 @@ __host__ __device__ inline int2 band_entry_with(int2 v, int col, int segw) {
     v.y = v.y > col + 1 ? v.y : col + 1;
     return v;
 }
+
+// Toroidal tables.  The nonzeros of a tile that touches the seam lie in TWO runs of a row, [0, w) and [L - w, L), and one
+// range around both is the whole row.  So every segment is cut at band_wrap_mid(segw), the multiple of LM_KG nearest its
+// middle, into a LOW piece [0, mid) and a HIGH piece [mid, segw), and a tile has one entry per segment AND PIECE: entry
+// 2 e + piece where a rectangular table has entry e, the same {segw - first, last + 1} pair in SEGMENT coordinates, fed
+// only by the nonzeros of its own piece (so a low range ends at or before mid and a high one begins at or after it: mid
+// is a multiple of LM_KG, and rounding a range outwards to whole groups never crosses it).  A tile away from the seam
+// has two adjacent ranges or one empty piece; a seam tile has [0, w) low and [L - w, L) high.  A workgroup stages the
+// union per piece and walks low then high: ascending columns, no column twice (the pieces are disjoint -- the high union's
+// lower end is rounded down to LM_KG, not to a chunk, so that it cannot reach below mid).
+// The cut is the middle and not the nearest chunk boundary because a side of three tiles (96) has a seam tile on either
+// side of every chunk boundary: rows 0..31 reach columns [0, 32 + w) and rows 64..95 columns [64 - w, 96).
+// mid is 0 for a side below 8 (beside a long one): the low piece is empty and the high one is the old range.
+__host__ __device__ inline int band_wrap_mid(int segw) { return ((segw / 2 + LM_KG / 2) / LM_KG) * LM_KG; }
+__host__ __device__ inline int band_wrap_piece(int col, int segw) { return col >= band_wrap_mid(segw) ? 1 : 0; }
 
 // the ranges as a launch gets them: base == nullptr: none (walk everything); else buffer (p_dev ? p_dev->rsel : sel),
 // `stride` entries apart, `base` already advanced to the launch's first tile (a captured launch reads rsel where
@@ -615,7 +649,7 @@ __global__ __launch_bounds__(NT_THREADS) void neigh_tables_kernel(NeighParams p_
         return;
     }
     __shared__ int s_first[NT_THREADS / 64], s_end[NT_THREADS / 64];
-    const long nb = band_entries(p.X, p.Y, p.nt);
+    const long nb = band_entries(p.X, p.Y, p.nt) * (p.torus ? 2 : 1);   // (toroidal: an entry per piece, band_wrap_mid)
     if (bands != nullptr && id < nb) bands[(p.rsel ? 0 : nb) + id] = make_int2(0, 0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ty = band_tiles(p.Y), cy = (p.Y + NT_COLS - 1) / NT_COLS, cx = (p.X + NT_COLS - 1) / NT_COLS;
@@ -657,6 +691,31 @@ __global__ __launch_bounds__(NT_THREADS) void neigh_tables_kernel(NeighParams p_
         nz |= __ballot(in && stored != 0.0f);
     }
     if (bands == nullptr) return;
+    if (p.torus) {
+        // the same record once per piece, from the columns of this chunk that lie in it (mid need not be a multiple of 64)
+        const int nlow = min(max(band_wrap_mid(side) - chunk * NT_COLS, 0), NT_COLS);
+        const unsigned long long low = nlow >= 64 ? ~0ull : (1ull << nlow) - 1ull;
+        for (int piece = 0; piece < 2; ++piece) {
+            const unsigned long long m = piece ? nz & ~low : nz & low;
+            if (lane == 0) {
+                s_first[wave] = m != 0 ? chunk * NT_COLS + (int)__builtin_ctzll(m) : side;
+                s_end[wave] = m != 0 ? chunk * NT_COLS + 64 - (int)__builtin_clzll(m) : 0;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                int first = side, end = 0;
+                for (int w = 0; w < NT_THREADS / 64; ++w) { first = min(first, s_first[w]); end = max(end, s_end[w]); }
+                if (end > 0) {
+                    const long e = stage1 ? band_entry_stage1(t, tile * LM_TILE, p.Y) : band_entry_stage2(tile * LM_TILE, t, p.Y, p.nt);
+                    int* r = (int*)(bands + (p.rsel ? nb : 0) + 2 * e + piece);
+                    atomicMax(r, side - first);
+                    atomicMax(r + 1, end);
+                }
+            }
+            __syncthreads();
+        }
+        return;
+    }
     if (lane == 0) {
         s_first[wave] = nz != 0 ? chunk * NT_COLS + (int)__builtin_ctzll(nz) : side;
         s_end[wave] = nz != 0 ? chunk * NT_COLS + 64 - (int)__builtin_clzll(nz) : 0;
@@ -706,7 +765,7 @@ __global__ __launch_bounds__(256) void mask_rows_kernel(NeighParams p_val, const
 // for the LM_KG-column groups inside that tile's own range (a wave-uniform test; the k order of the steps that
 // remain is the ascending one of the full walk).  A skipped step would have added 0 * m = +0 to a float32
 // accumulator, so the result is bit-identical for finite data.
-constexpr int LM_BM = 128, LM_BN = 128, LM_BK = 32;
+constexpr int LM_BM = 128, LM_BN = 128;               // (LM_BK = 32, the k chunk: with the ranges, above)
 constexpr int LM_NARROW = 8;    // a last column tile this narrow goes to leftmul_narrow_f32_kernel (VALU) instead of a
                                 // mostly empty 128-wide MFMA tile (64x64x32: 32 columns as a partial MFMA tile 11 us, as VALU 14)
 
@@ -714,12 +773,15 @@ constexpr int LM_NARROW = 8;    // a last column tile this narrow goes to leftmu
 // 32-row tile, segment 0.  C columns are computed; rows of M are ld, rows of OUT ldo floats apart.
 // BM = rows of H per workgroup: 128 (waves 2 x 2, each 64 rows x 64 columns) or 64 (waves 1 x 4, each 64 rows x 32
 // columns; launch_leftmul in somhip.hip chooses).
+// WRAP: the ranges are a toroidal table's, two per tile and segment (band_wrap_mid); every segment is walked over the
+// union of the low pieces, then over the union of the high pieces.  The body of two kernels, below: WRAP is a compile-time
+// constant in each, so the rectangular / hexagonal kernel is the code it was.
 template <int A> using a_is = std::integral_constant<int, A>;
-template <int BM>
-__global__ __launch_bounds__(256, BM == 128 ? 3 : 5) void leftmul_f32_kernel(const float* __restrict__ H, int Ro, int Ri,
-                                                          const float* __restrict__ M, long m_batch_stride,
-                                                          float* __restrict__ OUT, long o_batch_stride, long C,
-                                                          long ld, long ldo, BandRanges br, int nseg, int segw) {
+template <int BM, bool WRAP>
+__device__ __forceinline__ void leftmul_f32_body(const float* __restrict__ H, int Ro, int Ri,
+                                                 const float* __restrict__ M, long m_batch_stride,
+                                                 float* __restrict__ OUT, long o_batch_stride, long C,
+                                                 long ld, long ldo, BandRanges br, int nseg, int segw) {
     static_assert(BM == 128 || BM == 64, "leftmul: 128- or 64-row tiles");
     static_assert(LM_BK % LM_KG == 0 && LM_KG % 2 == 0, "leftmul: whole MFMA steps per skipping group, whole groups per chunk");
     constexpr int NT = BM / LM_TILE;                     // range entries (32-row tiles) per workgroup
@@ -789,10 +851,25 @@ __global__ __launch_bounds__(256, BM == 128 ? 3 : 5) void leftmul_f32_kernel(con
 
     // the chunks to walk (uniform over the workgroup): every segment is walked over the union [lo, hi) of the
     // nonzero ranges of the workgroup's tiles and segments, LM_BK columns at a time, clipped to hi
+    // (WRAP: [lo, hi) is the union of the low pieces, [lo2, hi2) that of the high pieces, walked behind it)
     int lo = 0, hi = Ri, ns = 1, sw = Ri;
+    int lo2 = 0, hi2 = 0;
     const int my_tiles = min(NT, band_tiles(Ro - i0));   // (the entries of tiles past the last row do not exist)
     bool dense = true;                                   // every tile of the workgroup covers [lo, hi) in every segment
-    if (ranges != nullptr) {
+    if (WRAP) {                                          // (a WRAP launch always has ranges)
+        ns = nseg; sw = segw;
+        const int2* mine = ranges + (long)blockIdx.y * NT * nseg * 2;
+        band_union(mine, my_tiles, nseg, segw, LM_BK, lo, hi, 2);
+        band_union(mine + 1, my_tiles, nseg, segw, LM_KG, lo2, hi2, 2);   // (LM_KG: never below the cut, band_wrap_mid)
+        dense = my_tiles == NT;
+        for (int i = 0; i < my_tiles * nseg; ++i) {
+            int l, u;
+            band_tile_range(mine[2 * i], segw, l, u);
+            dense = dense && l <= lo && u >= hi;
+            band_tile_range(mine[2 * i + 1], segw, l, u);
+            dense = dense && l <= lo2 && u >= hi2;
+        }
+    } else if (ranges != nullptr) {
         ns = nseg; sw = segw;
         const int2* mine = ranges + (long)blockIdx.y * NT * nseg;
         band_union(mine, my_tiles, nseg, segw, LM_BK, lo, hi);
@@ -803,12 +880,19 @@ __global__ __launch_bounds__(256, BM == 128 ? 3 : 5) void leftmul_f32_kernel(con
             dense = dense && l <= lo && u >= hi;
         }
     }
-    const int per = (hi - lo + LM_BK - 1) / LM_BK;     // chunks per segment
-    const int total = per * ns;
+    const int per = (hi - lo + LM_BK - 1) / LM_BK;     // chunks per segment (WRAP: of its low piece)
+    const int per2 = WRAP ? (hi2 - lo2 + LM_BK - 1) / LM_BK : 0;   // ... of its high piece
+    const int pers = per + per2;
+    const int total = pers * ns;
     auto chunk_at = [&](int c, int& sg, int& j, int& r0, int& kend) __attribute__((always_inline)) {
-        sg = c / per; j = c - sg * per;
-        r0 = sg * sw + lo + j * LM_BK;
-        kend = sg * sw + hi;
+        sg = c / pers; j = c - sg * pers;
+        if (WRAP && j >= per) {
+            r0 = sg * sw + lo2 + (j - per) * LM_BK;
+            kend = sg * sw + hi2;
+        } else {
+            r0 = sg * sw + lo + j * LM_BK;
+            kend = sg * sw + hi;
+        }
     };
     // this wave's two a-tiles: their own ranges in the segment being walked (wave-uniform; no ranges: everything)
     const int wtile = __builtin_amdgcn_readfirstlane(wr) * 2;
@@ -857,12 +941,16 @@ __global__ __launch_bounds__(256, BM == 128 ? 3 : 5) void leftmul_f32_kernel(con
             __syncthreads();                            // everyone is done reading the previous chunk
             stash();
             __syncthreads();
-            const int kc = lo + j * LM_BK;              // the staged chunk's first column, in segment coordinates
-            if (!DENSE && j == 0) {                     // a new segment: this wave's tiles' ranges in it
+            const int piece = WRAP && j >= per;         // (per == 0: a segment begins with its high piece)
+            const int kc = piece ? lo2 + (j - per) * LM_BK : lo + j * LM_BK;   // the staged chunk's first column, in segment coordinates
+            if (!DENSE && (j == 0 || (WRAP && j == per))) {   // a new segment (or piece): this wave's tiles' ranges in it
 #pragma unroll
                 for (int a = 0; a < 2; ++a) {
                     int2 v = make_int2(0, 0);
-                    if (wtile + a < my_tiles) v = ranges[((long)blockIdx.y * NT + wtile + a) * nseg + sg];
+                    if (wtile + a < my_tiles) {
+                        const long e = ((long)blockIdx.y * NT + wtile + a) * nseg + sg;
+                        v = ranges[WRAP ? 2 * e + piece : e];
+                    }
                     int l, u;
                     band_tile_range(v, segw, l, u);
                     tlo[a] = __builtin_amdgcn_readfirstlane(l);
@@ -887,6 +975,22 @@ __global__ __launch_bounds__(256, BM == 128 ? 3 : 5) void leftmul_f32_kernel(con
     };
     if (dense) walk(std::integral_constant<bool, true>());
     else walk(std::integral_constant<bool, false>());
+}
+
+template <int BM>
+__global__ __launch_bounds__(256, BM == 128 ? 3 : 5) void leftmul_f32_kernel(const float* __restrict__ H, int Ro, int Ri,
+                                                          const float* __restrict__ M, long m_batch_stride,
+                                                          float* __restrict__ OUT, long o_batch_stride, long C,
+                                                          long ld, long ldo, BandRanges br, int nseg, int segw) {
+    leftmul_f32_body<BM, false>(H, Ro, Ri, M, m_batch_stride, OUT, o_batch_stride, C, ld, ldo, br, nseg, segw);
+}
+// the same product over a toroidal table's ranges (br.base != nullptr; launch_leftmul in somhip.hip takes it for those only)
+template <int BM>
+__global__ __launch_bounds__(256, BM == 128 ? 3 : 5) void leftmul_wrap_f32_kernel(const float* __restrict__ H, int Ro, int Ri,
+                                                          const float* __restrict__ M, long m_batch_stride,
+                                                          float* __restrict__ OUT, long o_batch_stride, long C,
+                                                          long ld, long ldo, BandRanges br, int nseg, int segw) {
+    leftmul_f32_body<BM, true>(H, Ro, Ri, M, m_batch_stride, OUT, o_batch_stride, C, ld, ldo, br, nseg, segw);
 }
 
 // The columns [c_begin, C) of the same product when they are too few for a 128-wide MFMA tile (the count

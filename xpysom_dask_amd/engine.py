@@ -404,6 +404,20 @@ class HipEngine:
                                                     p2.ctypes.data_as(fp)))
         return bool(info[0]), ent, p1, p2
 
+    def band_tables_wrap(self):
+        """band_tables() of a toroidal engine: entries [n][2 pieces][2], a low and a high range per 32-row tile and segment
+        (som_debug_band_tables_wrap, include/somhip_test.h)."""
+        info = (C.c_int32 * 4)()
+        self._check(self._lib.som_debug_band_tables_wrap(self._h, info, None, None, None))
+        nt, n = info[1], info[2]
+        ent = np.zeros((n // 2, 2, 2), dtype=np.int32)
+        p1 = np.zeros((nt, self.y, self.y), dtype=np.float32)
+        p2 = np.zeros((self.x, nt * self.x), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self._lib.som_debug_band_tables_wrap(self._h, info, ent.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                         p1.ctypes.data_as(fp), p2.ctypes.data_as(fp)))
+        return bool(info[0]), ent, p1, p2
+
     def exact_plan_stats(self):
         """precision 'exact': (plans of a screen pass that ran both levels and the lists in one launch, plans that ran them as
         launches of their own) so far."""

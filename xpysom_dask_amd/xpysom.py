@@ -16,7 +16,7 @@ import numpy as np
 from . import distributed as _dist
 from .decays import DECAY_FUNCTIONS
 
-TOPOLOGIES = ("hexagonal", "rectangular")
+TOPOLOGIES = ("hexagonal", "rectangular", "toroidal")
 # name -> implemented in the HIP engine?   (registry order follows xpysom.py:260-283)
 NEIGHBORHOODS = {"gaussian": True, "mexican_hat": True, "bubble": True, "triangle": True}
 # distances.py:162-170 registry; False = valid reference name the engine does not cover yet
@@ -135,6 +135,32 @@ def _host_rows(x, engine=None):
     return np.asarray(x, dtype=np.float32)
 
 
+def units_adjacent(b1, b2, X, Y, topology):
+    """Are the units with raveled ids b1 and b2 (arrays, id = i * Y + j) neighbours on an X x Y map?  topographic_error's
+    adjacency rule, a pure function of the ids and the lattice.
+      rectangular  |di| <= 1 and |dj| <= 1 (xpysom.py:709-746, rectangular branch)
+      toroidal     the same on the wrapped offsets: |d| taken as min(|d|, L - |d|) per axis
+      hexagonal    no farther apart than 1.5 in the hexagonal coordinates (xpysom.py:739-746).  The reference reads them
+                   as _xx[i, j], _yy[i, j] from its UNtransposed (Y, X) meshgrids, i.e. x = j - s(i)/2, y = i with s
+                   marking every second row from the last (xpysom.py:201-206) -- reproduced on square maps (pinned by
+                   tests/golden/g13); on a non-square map that indexing runs out of bounds in the reference, and the
+                   unit's own coordinates x = i - s(j)/2, y = j are used instead (deviations)."""
+    b1, b2 = np.asarray(b1), np.asarray(b2)
+    i1, j1, i2, j2 = b1 // Y, b1 % Y, b2 // Y, b2 % Y
+    if topology == 'hexagonal':
+        if X == Y:
+            x1, y1 = j1 - 0.5 * ((Y - 1 - i1) % 2 == 0), i1
+            x2, y2 = j2 - 0.5 * ((Y - 1 - i2) % 2 == 0), i2
+        else:
+            x1, y1 = i1 - 0.5 * ((Y - 1 - j1) % 2 == 0), j1
+            x2, y2 = i2 - 0.5 * ((Y - 1 - j2) % 2 == 0), j2
+        return ~(np.hypot(x1 - x2, (y1 - y2).astype(float)) > 1.5)
+    di, dj = np.abs(i1 - i2), np.abs(j1 - j2)
+    if topology == 'toroidal':
+        di, dj = np.minimum(di, X - di), np.minimum(dj, Y - dj)
+    return ~((di > 1) | (dj > 1))
+
+
 class XPySom:
     def __init__(self, x, y, input_len,
                  sigma=0, sigmaN=1,
@@ -226,6 +252,9 @@ class XPySom:
             # against px's (n, x), so NumPy refuses to broadcast it at the first _update.  Reproduced on square maps.
             raise ValueError('mexican_hat with compact_support needs a square map on the rectangular topology: '
                              'operands could not be broadcast together with shapes (n,%d) (n,%d)' % (x, y))
+        if neighborhood_function == 'mexican_hat' and compact_support and topology == 'toroidal':
+            # the rectangular form exists to reproduce the reference's double mask; the torus has no reference to reproduce
+            raise ValueError('mexican_hat with compact_support is not defined on the toroidal topology')
         if precision not in ('f32', 'exact') and activation_distance not in ('euclidean', 'cosine'):
             raise ValueError("precision '%s' implements the GEMM-form distances 'euclidean' and 'cosine'; "
                              "'%s' needs precision='f32'" % (precision, activation_distance))
@@ -320,10 +349,19 @@ class XPySom:
     def distance_map(self):
         """U-matrix: each unit's summed distance to its map neighbours, scaled to a maximum of 1
         (xpysom.py:788-817: 8 neighbours on the rectangular grid; 6 on the hexagonal one, whose offsets
-        depend on the parity of the unit's column index j).  One shifted difference per neighbour offset over
-        the whole codebook -- host-side, the codebook is tiny next to the data."""
+        depend on the parity of the unit's column index j; on the toroidal one the 8 offsets applied cyclically, so
+        every unit has all 8 -- on a side of 1 or 2 an offset may lead to the unit itself or to the same neighbour
+        twice, and counts as often).  One shifted difference per neighbour offset over the whole codebook --
+        host-side, the codebook is tiny next to the data."""
         w = np.asarray(self._weights, dtype=np.float64)
         X, Y = w.shape[:2]
+        if self.topology == 'toroidal':
+            um = np.zeros((X, Y))
+            for di in (-1, 0, 1):
+                for dj in (-1, 0, 1):
+                    if (di, dj) != (0, 0):      # np.roll(w, -d)[x] = w[(x + d) % L]
+                        um += np.linalg.norm(w - np.roll(w, (-di, -dj), axis=(0, 1)), axis=-1)
+            return um / um.max()
         if self.topology == 'hexagonal':
             offsets = {1: ((0, 1), (1, 0), (0, -1), (-1, -1), (-1, 0), (-1, 1)),      # even j
                        0: ((1, 1), (1, 0), (1, -1), (0, -1), (-1, 0), (0, 1))}        # odd j
@@ -573,7 +611,7 @@ class XPySom:
         if self._weights.shape[0] * self._weights.shape[1] == 1 and n_rows:
             # one unit, input_len > 1: argsort(...)[:, :2] holds one column and its diff none -- the reference's mean over
             # an empty axis is NaN (rectangular), its norm over one is 0 (hexagonal: 0 > 1.5 never)
-            return float('nan') if self.topology == 'rectangular' else 0.0
+            return 0.0 if self.topology == 'hexagonal' else float('nan')
         eng = q[0] if q is not None else self._upload_weights()   # (_device_query has uploaded the codebook)
         Y = self._weights.shape[1]
         bad, n = 0, 0
@@ -582,24 +620,7 @@ class XPySom:
         else:
             pairs = (eng.bmu_top2(data[s:s + self._n_parallel]) for s in range(0, n_rows, self._n_parallel))
         for b1, b2 in pairs:
-            i1, j1, i2, j2 = b1 // Y, b1 % Y, b2 // Y, b2 % Y
-            if self.topology == 'hexagonal':
-                # not adjacent = farther apart than 1.5 in the hexagonal coordinates (xpysom.py:739-746).  The
-                # reference reads them as _xx[i, j], _yy[i, j] from its UNtransposed (Y, X) meshgrids, i.e.
-                # x = j - s(i)/2, y = i with s marking every second row from the last (xpysom.py:201-206) --
-                # reproduced on square maps (pinned by tests/golden/g13); on a non-square map that indexing
-                # runs out of bounds in the reference, and the unit's own coordinates x = i - s(j)/2, y = j
-                # are used instead (deviations).
-                X = self._weights.shape[0]
-                if X == Y:
-                    x1, y1 = j1 - 0.5 * ((Y - 1 - i1) % 2 == 0), i1
-                    x2, y2 = j2 - 0.5 * ((Y - 1 - i2) % 2 == 0), i2
-                else:
-                    x1, y1 = i1 - 0.5 * ((Y - 1 - j1) % 2 == 0), j1
-                    x2, y2 = i2 - 0.5 * ((Y - 1 - j2) % 2 == 0), j2
-                bad += int((np.hypot(x1 - x2, (y1 - y2).astype(float)) > 1.5).sum())
-            else:
-                bad += int(((np.abs(i1 - i2) > 1) | (np.abs(j1 - j2) > 1)).sum())
+            bad += int((~units_adjacent(b1, b2, self._weights.shape[0], Y, self.topology)).sum())
             n += len(b1)
         return bad / n if n else float('nan')
 
