@@ -80,6 +80,28 @@ enum { SOM_PREC_F32 = 0, SOM_PREC_BF16 = 1,
        SOM_PREC_RETIRED_4 = 4,  /* was F16X3: refused likewise */
        SOM_PREC_EXACT = 5 };  /* F32's BMUs through an IEEE-half MFMA screen + float32 re-score (bmu_exact.hpp) */
 
+/* Missing values (som_config.missing; not in the reference).  SOM_MISSING_NAN: a NaN in a training, streamed or query row means
+ * "this feature was not observed" -- any NaN bit pattern (the test is x != x); +-inf is still a value.  With m_nd = 1 where x_nd is
+ * observed and 0 otherwise, and x~_nd = x_nd where observed and 0 otherwise:
+ *     BMU      b_n = the first minimum over k of s_nk = sum_d m_nd (x_nd - w_kd)^2, evaluated as fmaf(-2, c1, c2) with the two
+ *              float32 fma chains c1 = sum_d x~_nd w_kd and c2 = sum_d m_nd fl(w_kd w_kd) (csrc/bmu_masked_f32.hpp).  A row with
+ *              nothing observed scores 0 everywhere, takes unit 0 and adds nothing below.
+ *     update   num[k][d] = sum_n g(b_n, k) m_nd x~_nd,   den[k][d] = sum_n g(b_n, k) m_nd,   g = eta h(b_n -> k) as ever;
+ *              W[k][d] = num[k][d] / den[k][d] where den[k][d] != 0, otherwise W[k][d] stays bit for bit.  A denominator per
+ *              unit AND feature: the fused accumulator is [K][round_up(2 input_len + 1, 4)], a row = [num (input_len) |
+ *              den (input_len) | g-weighted row count | padding] -- som_accum_device_ptr, som_epoch_accumulate_block and
+ *              som_epoch_allreduce report and move that size.  Sample weights w_n multiply both m_nd x~_nd and m_nd.
+ *     QE       mean over ALL rows of sqrt(sum_d m_nd (x_nd - w_{b_n,d})^2), differences formed directly; a row with nothing
+ *              observed adds 0 and is counted.
+ * The codebook never receives a NaN from the data.  On complete rows num is the unmasked num bit for bit under the same BMUs
+ * and every column of den is the unmasked den up to float32 summation order.
+ * Scope: distance SOM_DIST_EUCLIDEAN; precision F32 or EXACT (both run the float32 masked kernel -- no screen applies);
+ * every neighbourhood and topology; resident, device, weighted and streamed rows.  som_create refuses other distances and
+ * BF16 / F16.  On such a handle som_epoch_fetch, som_epoch_accumulate_faithful, som_set_verify(n > 0), som_bmu_top2*,
+ * som_bmu_f64 and som_distance_matrix fail with a message; som_epoch_fetch_masked reads the accumulator.
+ * SOM_MISSING_NONE (the default): NaNs are ordinary values, every launch and result is what it is without this field. */
+enum { SOM_MISSING_NONE = 0, SOM_MISSING_NAN = 1 };
+
 /* which BMU rule som_bmu applies */
 enum { SOM_BMU_ACTIVATION = 0,   /* configured activation distance: XPySom._winner, xpysom.py:410-417 */
        SOM_BMU_QUANTIZATION = 1  /* full sqrt'd Euclidean + nan_to_num: _quantization, xpysom.py:640,670 */ };
@@ -101,6 +123,7 @@ typedef struct som_config {
     int32_t topology;            /* SOM_TOPO_* */
     int32_t norm_p;              /* exponent p of SOM_DIST_NORM_P* (activation_distance_kwargs={'p': ...}); 0 = default 2 */
     double  norm_p_real;         /* a non-integer exponent p > 0 (distances.py:61-75 takes any real p); 0 = norm_p holds it */
+    int32_t missing;             /* SOM_MISSING_* */
 } som_config;
 
 const char* som_version(void);
@@ -223,6 +246,9 @@ int som_get_stream(som_handle* h, void** stream_out);
 /* teacher-forced parity: copy the last accumulate's results to the host.
  * Any pointer may be NULL.  num [K][D], den [K], bmu [n_rows] (raveled ids). */
 int som_epoch_fetch(som_handle* h, float* num, float* den, int32_t* bmu);
+/* ... of a handle created with SOM_MISSING_NAN (som_epoch_fetch refuses those, and this call the others):
+ * num [K][input_len], den [K][input_len] -- a denominator per unit and feature --, bmu [n_rows].  Any pointer may be NULL. */
+int som_epoch_fetch_masked(som_handle* h, float* num, float* den, int32_t* bmu);
 /* teacher-forcing the other way: run the accumulate with these BMU ids instead
  * of computing them (isolates the update path in tests). */
 int som_epoch_accumulate_forced(som_handle* h, const int32_t* bmu_host, double sigma, double eta, int neigh_f64);

@@ -12,6 +12,7 @@ SOM_DIST = {"euclidean": 0, "euclidean_no_opt": 1, "cosine": 2, "manhattan": 3, 
 SOM_NEIGH = {"gaussian": 0, "mexican_hat": 1, "bubble": 2, "triangle": 3}
 SOM_PREC = {"f32": 0, "bf16": 1, "f16": 3, "exact": 5}      # (ids 2 and 4: the retired split-operand modes)
 SOM_TOPO = {"rectangular": 0, "hexagonal": 1, "toroidal": 2}
+SOM_MISSING = {None: 0, "nan": 1}
 SOM_BMU_ACTIVATION, SOM_BMU_QUANTIZATION = 0, 1
 SOM_KERNELS = {"bmu": 0, "segsum": 1, "kron": 2, "merge": 3, "prep": 4, "screen": 5}
 
@@ -21,7 +22,8 @@ class SomConfig(C.Structure):
                 ("distance", C.c_int32), ("neighborhood", C.c_int32),
                 ("compact_support", C.c_int32), ("precision", C.c_int32), ("device", C.c_int32),
                 ("std_coeff", C.c_double), ("stream", C.c_void_p),
-                ("topology", C.c_int32), ("norm_p", C.c_int32), ("norm_p_real", C.c_double)]
+                ("topology", C.c_int32), ("norm_p", C.c_int32), ("norm_p_real", C.c_double),
+                ("missing", C.c_int32)]
 
 
 _F = C.POINTER(C.c_float)
@@ -64,6 +66,7 @@ SIGNATURES = {
     "som_accum_device_ptr": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "som_get_stream": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
     "som_epoch_fetch": (C.c_int, [_H, _F, _F, _I]),
+    "som_epoch_fetch_masked": (C.c_int, [_H, _F, _F, _I]),
     "som_epoch_accumulate_forced": (C.c_int, [_H, _I, C.c_double, C.c_double, C.c_int]),
     "som_bmu": (C.c_int, [_H, _F, C.c_int64, C.c_int32, _I]),
     "som_bmu_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, _I]),

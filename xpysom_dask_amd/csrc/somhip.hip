@@ -32,6 +32,7 @@
 #include "bmu_f32.hpp"
 #include "bmu_f32_res.hpp"
 #include "bmu_f32_tiled.hpp"
+#include "bmu_masked_f32.hpp"
 #include "bmu_pairwise.hpp"
 #include "update.hpp"
 
@@ -128,6 +129,12 @@ struct som_handle {
     hipStream_t comm_stream = nullptr;   // the blockwise all-reduce runs here, under the transform of the next block
     hipEvent_t ev_block = nullptr, ev_comm = nullptr;
     int X = 0, Y = 0, K = 0, D = 0, D1p = 0;
+    // missing values (som_config.missing == SOM_MISSING_NAN): a NaN feature is "not observed".  The search is
+    // bmu_masked_f32_kernel, level 0 of the run sum keeps a count per feature, the merge divides per (unit, feature).
+    // UD: the features of an update row -- D, or masked 2 * D, [sums | per-feature counts] -- with the count in column UD;
+    // D1p = round_up(UD + 1, 4).  Everything between level 0 and the merge sees UD features and nothing else.
+    bool masked = false;
+    int UD = 0;
     int ks32 = 0;            // bf16, 16x16x32 shape: ceil(D/32)
     bool tiled = false;      // bf16, input_len > 128: two-sided tiling (bmu_bf16_tiled.hpp)
     bool f16 = false;        // precision f16: _Float16 operands instead of __bf16 (the same kernels, som_common.hpp)
@@ -718,6 +725,16 @@ int launch_bmu_f32_any(som_handle* h, const float* X, long N, const float* xsq, 
     return fail(h, "bmu_f32: bad k-group count");
 }
 
+// missing values: the masked search (bmu_masked_f32.hpp) reads the rows and the codebook as they are -- no operand image, no |w|^2
+int launch_bmu_masked(som_handle* h, const float* X, long N, int* out) {
+    const long grid = cdiv(N, F32_SB);
+    if (grid <= 0 || grid > 0x7fffffffL) return fail(h, "bmu_masked_f32: row count out of range");
+    bmu_masked_f32_kernel<<<dim3((unsigned)grid), dim3(256), MSK_LDS_BYTES, h->stream>>>(X, N, h->D, (int)round_up(h->D, F32_KC), h->W,
+                                                                                        h->K, out);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 // best AND second-best unit under the sqrt'd Euclidean distance (topographic error)
 int launch_bmu_top2(som_handle* h, const float* X, long N, const float* xsq, int* out, int* out2) {
     constexpr int M = SCORE_EUCLID_SQRT;
@@ -1053,6 +1070,10 @@ int verify_bmu_launch(som_handle* h, const Rows& r) {
 
 // BMU of a row set's device rows with the configured activation distance (xpysom.py:410-417)
 int run_activation_bmu_launch(som_handle* h, const Rows& r) {
+    if (h->masked) {                                     // missing values: one kernel, no codebook operands to refresh
+        Timed t(h, SOM_K_BMU);
+        return launch_bmu_masked(h, r.X, r.N, r.out);
+    }
     // (exact mode up to 128 features: the launch writes the codebook's 16-bit image itself, in one grid with its plan's centroid images)
     if (int rc = refresh_codebook_operands(h, operands::Request::Search, h->exact && h->ex.chain)) return rc;
     Timed t(h, SOM_K_BMU);
@@ -1131,6 +1152,14 @@ long launch_runsum(som_handle* h, const float* X, const int* keys, const int* sr
     const dim3 grid((unsigned)blocks), block(64 * nw);
     const size_t lds = nw > 1 ? (size_t)2 * nw * (h->D1p + 1) * sizeof(float) : 0;
     if constexpr (LEVEL0) {
+        if (h->masked) {                                 // missing values: the masked instances of level 0, with or without weights
+            const bool v2 = (h->D & 1) == 0;
+#define SOM_RUNSUM_MASKED(V, WG) runsum_kernel<true, V, WG, true><<<grid, block, lds, h->stream>>>(X, keys, srow, vin, n, chunk, h->D, h->D1p, accumulate, h->SC, h->SC + (size_t)h->K * h->D1p, kout, vout, wgt)
+            if (wgt != nullptr) { if (v2) SOM_RUNSUM_MASKED(true, true); else SOM_RUNSUM_MASKED(false, true); }
+            else { if (v2) SOM_RUNSUM_MASKED(true, false); else SOM_RUNSUM_MASKED(false, false); }
+#undef SOM_RUNSUM_MASKED
+            return blocks;
+        }
         if (wgt != nullptr) {                            // sample weights: the weighted instances of level 0
             if ((h->D & 1) == 0)
                 runsum_kernel<true, true, true><<<grid, block, lds, h->stream>>>(X, keys, srow, vin, n, chunk, h->D, h->D1p, accumulate, h->SC, h->SC + (size_t)h->K * h->D1p, kout, vout, wgt);
@@ -1139,10 +1168,11 @@ long launch_runsum(som_handle* h, const float* X, const int* keys, const int* sr
             return blocks;
         }
     }
-    if ((h->D & 1) == 0)
-        runsum_kernel<LEVEL0, true><<<grid, block, lds, h->stream>>>(X, keys, srow, vin, n, chunk, h->D, h->D1p, accumulate, h->SC, h->SC + (size_t)h->K * h->D1p, kout, vout);
+    // (UD: D, or -- the upper levels of a masked handle -- the 2 * D features of its lists)
+    if ((h->UD & 1) == 0)
+        runsum_kernel<LEVEL0, true><<<grid, block, lds, h->stream>>>(X, keys, srow, vin, n, chunk, h->UD, h->D1p, accumulate, h->SC, h->SC + (size_t)h->K * h->D1p, kout, vout);
     else
-        runsum_kernel<LEVEL0, false><<<grid, block, lds, h->stream>>>(X, keys, srow, vin, n, chunk, h->D, h->D1p, accumulate, h->SC, h->SC + (size_t)h->K * h->D1p, kout, vout);
+        runsum_kernel<LEVEL0, false><<<grid, block, lds, h->stream>>>(X, keys, srow, vin, n, chunk, h->UD, h->D1p, accumulate, h->SC, h->SC + (size_t)h->K * h->D1p, kout, vout);
     return blocks;
 }
 
@@ -1300,12 +1330,12 @@ int run_transform_stage1(som_handle* h, double sigma, double eta, int neigh_f64)
     }
     for (int t1 = 0; t1 < h->nt; ++t1)
         launch_leftmul(h, h->P1 + (long)t1 * h->Y * h->Y, h->Y, h->Y, h->SC, slab, h->T + (long)t1 * h->X * slab, slab,
-                       h->D, h->D1p, nyb, h->X, band_ranges_from(h, band_entry_stage1(t1, 0, h->Y)), 1, h->Y);
+                       h->UD, h->D1p, nyb, h->X, band_ranges_from(h, band_entry_stage1(t1, 0, h->Y)), 1, h->Y);
     // U_t[a][j] = sum_b C[a][b] Py_t[j][b] from the dense counts; stage 2 reads it densely (Ud) when it batches over
     // the map columns, or finds it where stage 1 would have put it, T_t[a][j][D], when it runs over whole rows
-    const bool per_column = h->D % LM_BN == 0;
+    const bool per_column = h->UD % LM_BN == 0;
     strided_gemm_f32_kernel<<<dim3((unsigned)cdiv(h->Y, SG_T), (unsigned)cdiv(h->X, SG_T), (unsigned)h->nt), dim3(256), 0, h->stream>>>(
-        h->SC + (size_t)h->K * h->D1p, h->Y, 1, h->P1, 1, h->Y, per_column ? h->Ud : h->T + h->D, per_column ? h->Y : slab,
+        h->SC + (size_t)h->K * h->D1p, h->Y, 1, h->P1, 1, h->Y, per_column ? h->Ud : h->T + h->UD, per_column ? h->Y : slab,
         per_column ? 1 : h->D1p, h->X, h->Y, h->Y, 0, (long)h->Y * h->Y, per_column ? (long)h->K : (long)h->X * slab);
     HIPCHK(h, hipGetLastError());
     return 0;
@@ -1330,12 +1360,12 @@ int run_transform_stage2(som_handle* h, int b0, int b1) {
     }
     const float* H = h->P2 + i0 * h->nt * h->X;
     const BandRanges ranges = band_ranges_from(h, band_entry_stage2((int)i0, 0, h->Y, h->nt));   // the block's first 32-row tile
-    if (h->D % LM_BN == 0) {
-        launch_leftmul(h, H, rows, h->nt * h->X, h->T, h->D1p, h->ACC + i0 * slab, h->D1p, h->D, slab, b1 - b0, h->Y, ranges,
+    if (h->UD % LM_BN == 0) {
+        launch_leftmul(h, H, rows, h->nt * h->X, h->T, h->D1p, h->ACC + i0 * slab, h->D1p, h->UD, slab, b1 - b0, h->Y, ranges,
                        h->nt, h->X);
         // den[i][j] = sum_k [Px_0 | Px_1 ...][i][k] U[k][j], U = [U_0; U_1; ...] dense (stage 1)
         strided_gemm_f32_kernel<<<dim3((unsigned)cdiv(h->Y, SG_T), (unsigned)cdiv(rows, SG_T), 1), dim3(256), 0, h->stream>>>(
-            H, (long)h->nt * h->X, 1, h->Ud, h->Y, 1, h->ACC + i0 * slab + h->D, slab, h->D1p, rows, h->Y, h->nt * h->X, 0, 0, 0);
+            H, (long)h->nt * h->X, 1, h->Ud, h->Y, 1, h->ACC + i0 * slab + h->UD, slab, h->D1p, rows, h->Y, h->nt * h->X, 0, 0, 0);
     } else {
         launch_leftmul(h, H, rows, h->nt * h->X, h->T, 0, h->ACC + i0 * slab, 0, slab, slab, b1 - b0, 1, ranges, h->nt, h->X);
     }
@@ -1449,6 +1479,15 @@ int som_create(const som_config* cfg, som_handle** out) {
             return fail(nullptr, "som_create: bf16 precision implements 'euclidean' and 'cosine' "
                                  "('euclidean_no_opt' has the same argmin as 'euclidean')");
     }
+    if (cfg->missing != SOM_MISSING_NONE && cfg->missing != SOM_MISSING_NAN) return fail(nullptr, "som_create: unknown missing-value mode");
+    if (cfg->missing == SOM_MISSING_NAN) {
+        if (cfg->distance != SOM_DIST_EUCLIDEAN)
+            return fail(nullptr, "som_create: missing values (SOM_MISSING_NAN) are defined for the 'euclidean' activation distance only");
+        if (cfg->precision == SOM_PREC_BF16 || cfg->precision == SOM_PREC_F16)
+            return fail(nullptr, "som_create: missing values (SOM_MISSING_NAN) run the float32 masked kernel: precision 'exact' or "
+                                 "'f32', not 'bf16' / 'f16'");
+        if ((long)cfg->input_len > (1L << 20)) return fail(nullptr, "som_create: missing values: input_len too large");
+    }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev < 1) return fail(nullptr, "som_create: no HIP device available");
@@ -1456,7 +1495,9 @@ int som_create(const som_config* cfg, som_handle** out) {
 
     som_handle* h = new som_handle();
     h->cfg = *cfg;
-    if (cfg->precision == SOM_PREC_EXACT) {
+    h->masked = cfg->missing == SOM_MISSING_NAN;
+    if (h->masked) h->cfg.precision = SOM_PREC_F32;      // no screen applies: the float32 masked kernel IS the exact mode
+    else if (cfg->precision == SOM_PREC_EXACT) {
         // the screen + re-score scheme covers the euclidean distance up to 128 features; everywhere else the
         // float32 kernels ARE the exact mode
         // (<= 128 features: the resident screen, euclidean; 129 .. 800 features on maps of >= 4096 units: the wide
@@ -1467,7 +1508,8 @@ int som_create(const som_config* cfg, som_handle** out) {
     }
     cfg = &h->cfg;
     h->X = cfg->x; h->Y = cfg->y; h->K = cfg->x * cfg->y; h->D = cfg->input_len;
-    h->D1p = (int)round_up(h->D + 1, 4);
+    h->UD = h->masked ? 2 * h->D : h->D;
+    h->D1p = (int)round_up(h->UD + 1, 4);
     h->norm_p = cfg->norm_p > 0 ? cfg->norm_p : 2;
     if (cfg->norm_p_real != 0.0 && (cfg->distance == SOM_DIST_NORM_P || cfg->distance == SOM_DIST_NORM_P_NO_OPT)) h->norm_pr = cfg->norm_p_real;
     h->ks32 = (int)cdiv(h->D, 32);
@@ -1559,6 +1601,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         if (const char* e = dev_env("SOM_F32_PARTS")) h->env_f32_parts = std::atoi(e);
         h->debug = std::getenv("SOM_DEBUG") != nullptr;
         if (const char* e = std::getenv("SOM_VERIFY")) h->verify_rows = std::max(0, std::atoi(e));
+        if (h->masked) h->verify_rows = 0;               // (the canary re-scores with the unmasked float32 kernel: not on these rows)
         if (const char* e = dev_env("SOM_EXACT_PASS_ROWS")) h->ex.pass_rows_override = std::atol(e);
         if (const char* e = dev_env("SOM_EXACT_DEBUG_REFUSE_ABOVE")) h->ex.hook_refuse_above = std::atol(e);
         if (const char* e = dev_env("SOM_EXACT_PAIRS")) h->ex.hook_pairs = std::max(1L, std::atol(e));
@@ -1596,12 +1639,13 @@ int som_create(const som_config* cfg, som_handle** out) {
         hipMemsetAsync(h->T, 0, KD1 * h->nt * sizeof(float), h->stream) != hipSuccess ||
         hipMemsetAsync(h->ACC, 0, KD1 * sizeof(float), h->stream) != hipSuccess)
         return bail(fail(h, "hipMemsetAsync failed"));
-    if (h->D > 128) {
+    // (a masked handle's search reads the codebook itself: no float32 operand image)
+    if (h->D > 128 && !h->masked) {
         h->ft_kchunks = (int)cdiv(h->D, FT_BK);
         h->ft_ublocks = (int)cdiv(h->K, FT_BN);
         if ((rc = h->Wfimg.alloc(h, (size_t)h->ft_ublocks * h->ft_kchunks * FT_WTILE))) return bail(rc);
     }
-    if (h->D <= 128) {
+    if (h->D <= 128 && !h->masked) {
         int kg = 1;
         while (kg * 8 < h->D) kg *= 2;                      // 8, 16, 32, 64 or 128 features per row image
         h->fr_kg = kg;
@@ -1839,6 +1883,8 @@ int som_epoch_accumulate_faithful(som_handle* h, double sigma, double eta, int n
     if (!r.X && r.N > 0) return fail(h, "som_epoch_accumulate_faithful: no resident data (call som_set_data)");
     if (h->swapped) return fail(h, "som_epoch_accumulate_faithful: mexican_hat with compact_support on the rectangular "
                                    "topology is not a sum of row factor x column factor terms");
+    if (h->masked) return fail(h, "som_epoch_accumulate_faithful: the handle was created with SOM_MISSING_NAN; the faithful form is "
+                                  "the cross-check of the update without missing values");
     if (r.wgt) return fail(h, "som_epoch_accumulate_faithful: sample weights are set; the faithful form is the cross-check of the "
                                "unweighted update (clear them with som_set_sample_weights(h, NULL, 0))");
     if (int rc = run_activation_bmu(h, r)) return rc;
@@ -2012,6 +2058,13 @@ int som_epoch_merge(som_handle* h) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
     Timed t(h, SOM_K_MERGE);
+    if (h->masked) {                                     // missing values: a denominator per unit and feature (update.hpp)
+        const long total = (long)h->K * h->D;
+        merge_masked_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, h->stream>>>(h->W, h->ACC, h->K, h->D, h->D1p);
+        HIPCHK(h, hipGetLastError());
+        h->ops.merged_plain();
+        return 0;
+    }
     // the exact mode up to 128 features (euclidean): the merge also writes the patch-order copy, |w|^2 and its maximum, the
     // float32 stage image and the plan's centroids -- everything of the next epoch's operands that does not wait for the
     // maximum (exact_merge_prep_kernel); the 16-bit images follow at the head of the BMU launch (they stay owed)
@@ -2228,6 +2281,8 @@ int som_get_stream(som_handle* h, void** stream_out) {
 int som_epoch_fetch(som_handle* h, float* num, float* den, int32_t* bmu) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
+    if (h->masked) return fail(h, "som_epoch_fetch: the handle was created with SOM_MISSING_NAN, its denominator is [K][input_len]: "
+                                  "call som_epoch_fetch_masked");
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (num || den) {
         std::vector<float> acc((size_t)h->K * h->D1p);
@@ -2235,6 +2290,23 @@ int som_epoch_fetch(som_handle* h, float* num, float* den, int32_t* bmu) {
         for (long k = 0; k < h->K; ++k) {
             if (num) std::memcpy(num + k * h->D, acc.data() + k * h->D1p, (size_t)h->D * sizeof(float));
             if (den) den[k] = acc[k * h->D1p + h->D];
+        }
+    }
+    if (bmu && h->res.N > 0) HIPCHK(h, hipMemcpy(bmu, h->res.bmu, (size_t)h->res.N * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int som_epoch_fetch_masked(som_handle* h, float* num, float* den, int32_t* bmu) {
+    DeviceGuard dev_guard(h);
+    if (!h) return 1;
+    if (!h->masked) return fail(h, "som_epoch_fetch_masked: the handle was not created with SOM_MISSING_NAN: call som_epoch_fetch");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (num || den) {
+        std::vector<float> acc((size_t)h->K * h->D1p);
+        HIPCHK(h, hipMemcpy(acc.data(), h->ACC, acc.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (long k = 0; k < h->K; ++k) {
+            if (num) std::memcpy(num + k * h->D, acc.data() + k * h->D1p, (size_t)h->D * sizeof(float));
+            if (den) std::memcpy(den + k * h->D, acc.data() + k * h->D1p + h->D, (size_t)h->D * sizeof(float));
         }
     }
     if (bmu && h->res.N > 0) HIPCHK(h, hipMemcpy(bmu, h->res.bmu, (size_t)h->res.N * sizeof(int), hipMemcpyDeviceToHost));
@@ -2253,6 +2325,8 @@ namespace {
 // no such tie can overturn; the others go through the float32 SQRT kernel, so the ids are float32's bit for bit.
 int run_quantization_bmu(som_handle* h, bool value_only = false) {
     RowSet& q = h->q; const float* X = q.X; const long n_rows = q.N;
+    // missing values: the sqrt is monotone, the masked search's first minimum IS the row's unit (include/somhip.h)
+    if (h->masked) return run_activation_bmu(h, q.view());
     if (h->cfg.precision != SOM_PREC_F32 && h->cfg.distance == SOM_DIST_EUCLIDEAN && (!h->exact || value_only)) {
         if (int rc = prepare(h, q, h->exact)) return rc;
         if (int rc = run_activation_bmu(h, q.view())) return rc;
@@ -2324,6 +2398,7 @@ int query_top2(som_handle* h, const std::string& who, const float* x_host, const
     if (!h || n_rows < 0 || (n_rows > 0 && ((!x_host && !x_dev) || !ids1_out || !ids2_out))) return fail(h, who + ": bad argument");
     if (n_rows == 0) return 0;
     if (x_dev && n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    if (h->masked) return fail(h, who + ": the top-2 search is not defined on a handle created with SOM_MISSING_NAN");
     if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
     if (int rc = run_top2(h)) return rc;
     const size_t bytes = (size_t)n_rows * sizeof(int);
@@ -2339,7 +2414,9 @@ int query_quantization_error(som_handle* h, const std::string& who, const float*
     if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
     if (int rc = run_quantization_bmu(h, true)) return rc;
     HIPCHK(h, hipMemsetAsync(h->dsum, 0, sizeof(double), h->stream));
-    qe_kernel<<<dim3((unsigned)std::min<long>(cdiv(n_rows, 4), 4096)), dim3(256), 0, h->stream>>>(h->q.X, h->q.bmu, h->W, n_rows, h->D, h->dsum);
+    const dim3 qe_grid((unsigned)std::min<long>(cdiv(n_rows, 4), 4096));
+    if (h->masked) qe_masked_kernel<<<qe_grid, dim3(256), 0, h->stream>>>(h->q.X, h->q.bmu, h->W, n_rows, h->D, h->dsum);
+    else qe_kernel<<<qe_grid, dim3(256), 0, h->stream>>>(h->q.X, h->q.bmu, h->W, n_rows, h->D, h->dsum);
     HIPCHK(h, hipGetLastError());
     double s = 0.0;
     if (int rc = d2h_blocking(h, &s, h->dsum, sizeof(double))) return rc;
@@ -2359,6 +2436,7 @@ int som_bmu_f64(som_handle* h, const double* x_host, int64_t n_rows, int32_t* id
     DeviceGuard dev_guard(h);
     if (!h || n_rows < 0 || (n_rows > 0 && (!x_host || !ids_out))) return fail(h, "som_bmu_f64: bad argument");
     if (h->cfg.distance != SOM_DIST_EUCLIDEAN) return fail(h, "som_bmu_f64: the float64 query path serves the 'euclidean' activation distance");
+    if (h->masked) return fail(h, "som_bmu_f64: not available on a handle created with SOM_MISSING_NAN (query with float32 rows)");
     if (n_rows == 0) return 0;
     const size_t w_bytes = (size_t)PW_UNITS * h->D * sizeof(float);
     if (w_bytes > 150 * 1024) return fail(h, "som_bmu_f64: input_len too large for the LDS unit tile");
@@ -2379,6 +2457,7 @@ int som_distance_matrix(som_handle* h, const float* x_host, int64_t n_rows, int3
     DeviceGuard dev_guard(h);
     if (!h || n_rows < 0 || (n_rows > 0 && (!x_host || !dist_out))) return fail(h, "som_distance_matrix: bad argument");
     if (mode != SOM_BMU_ACTIVATION && mode != SOM_BMU_QUANTIZATION) return fail(h, "som_distance_matrix: unknown mode");
+    if (h->masked) return fail(h, "som_distance_matrix: not available on a handle created with SOM_MISSING_NAN");
     if (mode == SOM_BMU_ACTIVATION && h->cfg.distance > SOM_DIST_COSINE)
         return fail(h, "som_distance_matrix: only the GEMM-form distances (euclidean, euclidean_no_opt, cosine)");
     if (n_rows == 0) return 0;
@@ -2399,6 +2478,8 @@ int som_distance_matrix(som_handle* h, const float* x_host, int64_t n_rows, int3
 
 int som_set_verify(som_handle* h, int32_t n_rows) {
     if (!h || n_rows < 0) return fail(h, "som_set_verify: bad argument");
+    if (h->masked && n_rows > 0)
+        return fail(h, "som_set_verify: the canary re-scores with the unmasked float32 kernel; not on a handle created with SOM_MISSING_NAN");
     h->verify_rows = n_rows;
     return 0;
 }

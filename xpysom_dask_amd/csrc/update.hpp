@@ -253,16 +253,24 @@ __host__ __device__ inline long seg_next_entries(long n, int c, int nw) { return
 // fmaf(w, x, acc) at the place and in the order the unweighted walk forms acc + x (fmaf(1, x, acc) rounds like acc + x:
 // weights of 1.0 give the unweighted sums bit for bit), and the count column carries the sum of the weights.  A row of
 // weight 0 is not loaded at all -- it is absent, not multiplied by 0, so its NaN / infinite features stay out of its unit.
-template <bool ROWS, bool VEC2, bool WEIGHTED = false>
+// MASKED (with ROWS only; missing values, SOM_MISSING_NAN): a NaN feature is "not observed".  A row enters as x~ (x where
+// observed, 0 otherwise) at the place and in the order the unmasked walk adds x -- complete rows give the unmasked sums bit
+// for bit -- and next to every feature sum the walk keeps the feature's COUNT, the sum of m (1 where observed, 0 otherwise;
+// WEIGHTED: of w m).  D is then the width of the rows; the row written is [S (D) | C (D) | total count] of width 2 D + 1
+// <= D1p, and everything above level 0 walks it as a list of 2 D features with the count in column 2 D.
+template <bool ROWS, bool VEC2, bool WEIGHTED = false, bool MASKED = false>
 __device__ __forceinline__ void seg_walk(const float* __restrict__ X, const float* list, int my_key, int my_row,
                                          float my_cnt, int cnt, bool open_left, bool open_right, int D, int D1p,
                                          int accumulate, float* __restrict__ SC, float* __restrict__ cnt_dense,
                                          float* slot0, float* slot1, int& key0, int& key1) {
+    static_assert(ROWS || !MASKED, "run sum: only the walk over rows sees missing values");
     const int lane = threadIdx.x & 63;
+    const int CD = MASKED ? 2 * D : D;                    // the count's column
     key0 = -1; key1 = -1;
     bool slot1_zero = false;
     for (int f0 = 0; f0 < D; f0 += 256) {                 // 4 features per lane per sweep
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        float cm[4] = {0.f, 0.f, 0.f, 0.f};              // MASKED: the features' counts (unused otherwise)
         int cur = __builtin_amdgcn_readfirstlane(my_key);
         int run_begin = 0;
         float run = 0.f;
@@ -276,18 +284,26 @@ __device__ __forceinline__ void seg_walk(const float* __restrict__ X, const floa
                         float2 t = make_float2(acc[2 * jj], acc[2 * jj + 1]);
                         if (add) { const float2 o = *(const float2*)(dst + d); t.x += o.x; t.y += o.y; }
                         *(float2*)(dst + d) = t;
+                        if (MASKED) {                        // (D even: D + d is 8-byte aligned as d is)
+                            float2 c = make_float2(cm[2 * jj], cm[2 * jj + 1]);
+                            if (add) { const float2 o = *(const float2*)(dst + D + d); c.x += o.x; c.y += o.y; }
+                            *(float2*)(dst + D + d) = c;
+                        }
                     }
                 }
             } else {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int d = f0 + lane + 64 * j;
-                    if (d < D) dst[d] = add ? dst[d] + acc[j] : acc[j];
+                    if (d < D) {
+                        dst[d] = add ? dst[d] + acc[j] : acc[j];
+                        if (MASKED) dst[D + d] = add ? dst[D + d] + cm[j] : cm[j];
+                    }
                 }
             }
             if (f0 == 0 && lane == 0) {
-                const float c = add ? dst[D] + run : run;
-                dst[D] = c;
+                const float c = add ? dst[CD] + run : run;
+                dst[CD] = c;
                 if (unit >= 0) cnt_dense[unit] = c;          // the counts once more, densely (the transform's count path)
             }
         };
@@ -306,7 +322,7 @@ __device__ __forceinline__ void seg_walk(const float* __restrict__ X, const floa
                 }
             }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = 0.f;
+            for (int j = 0; j < 4; ++j) { acc[j] = 0.f; if (MASKED) cm[j] = 0.f; }
             run = 0.f;
         };
         for (int i0 = 0; i0 < cnt; i0 += 8) {
@@ -341,8 +357,18 @@ __device__ __forceinline__ void seg_walk(const float* __restrict__ X, const floa
                     const int b = __builtin_amdgcn_readlane(my_key, i);
                     if (b != cur) { flush(i); cur = b; run_begin = i; }
                     const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_cnt), i));
+                    if (MASKED) {
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[j] = (ROWS && WEIGHTED) ? __builtin_fmaf(w, v[u][j], acc[j]) : acc[j] + v[u][j];
+                        for (int j = 0; j < 4; ++j) {
+                            const bool seen = v[u][j] == v[u][j];
+                            const float xt = seen ? v[u][j] : 0.f, m = seen ? 1.f : 0.f;
+                            acc[j] = WEIGHTED ? __builtin_fmaf(w, xt, acc[j]) : acc[j] + xt;
+                            cm[j] = WEIGHTED ? __builtin_fmaf(w, m, cm[j]) : cm[j] + m;
+                        }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[j] = (ROWS && WEIGHTED) ? __builtin_fmaf(w, v[u][j], acc[j]) : acc[j] + v[u][j];
+                    }
                     run += w;
                 }
             }
@@ -350,7 +376,7 @@ __device__ __forceinline__ void seg_walk(const float* __restrict__ X, const floa
         flush(cnt);
         if (slot1_zero) {                                 // one run, open on both sides: slot 1 = (key, 0)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = 0.f;
+            for (int j = 0; j < 4; ++j) { acc[j] = 0.f; if (MASKED) cm[j] = 0.f; }
             run = 0.f;
             put(slot1, false);
         }
@@ -361,11 +387,13 @@ __device__ __forceinline__ void seg_walk(const float* __restrict__ X, const floa
 // !LEVEL0: keys / vin = the previous level's partial list ([n] keys, [n][D1p] vectors, count in column D).
 // WEIGHTED (LEVEL0 only): wgt[row id] is the row's sample weight (float32, finite, >= 0) -- the count 1 of the row becomes
 // its weight, its features enter the sum times the weight (seg_walk); the upper levels do not know the difference.
+// MASKED (LEVEL0 only): NaN features are missing values -- D is the rows' width, the list written has 2 * D features (sums,
+// then per-feature counts) and the count in column 2 * D (seg_walk); D1p >= 2 * D + 1.
 // VEC2 (D even): a lane owns feature pairs (8-byte accesses, one instruction per 128 features of a row).
 // accumulate == 0: SC was zeroed and every unit is written at most once in the whole pass: plain stores.
 // Dynamic LDS: blockDim.x / 64 > 1 ? 2 * waves * (D1p + 1) floats : none (a one-wave block writes its slots
 // straight to the next list).
-template <bool LEVEL0, bool VEC2, bool WEIGHTED = false>
+template <bool LEVEL0, bool VEC2, bool WEIGHTED = false, bool MASKED = false>
 __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void runsum_kernel(const float* __restrict__ X,
                                                                    const int* __restrict__ keys,
                                                                    const int* __restrict__ srow,
@@ -375,6 +403,8 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void runsum_kernel(const float*
                                                                    float* __restrict__ vout,
                                                                    const float* __restrict__ wgt = nullptr) {
     static_assert(LEVEL0 || !WEIGHTED, "run sum: only level 0 reads rows, so only level 0 is weighted");
+    static_assert(LEVEL0 || !MASKED, "run sum: only level 0 reads rows, so only level 0 sees missing values");
+    const int LD = MASKED ? 2 * D : D;                    // features of a list entry, = the column of its count
     extern __shared__ __attribute__((aligned(16))) float seg_lds[];
     const int C = LEVEL0 ? SEG_CHUNK : chunk;             // <= 64: lane i holds entry i
     const int lane = threadIdx.x & 63;
@@ -400,7 +430,7 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void runsum_kernel(const float*
         const bool open_right = last_key >= 0 && __builtin_amdgcn_readfirstlane(next_key) == last_key;
         float* s0 = direct ? vout + (2 * blk) * (long)D1p : slots + (long)(2 * wave) * D1p;
         float* s1 = direct ? vout + (2 * blk + 1) * (long)D1p : slots + (long)(2 * wave + 1) * D1p;
-        seg_walk<LEVEL0, VEC2, WEIGHTED>(X, LEVEL0 ? nullptr : vin + p0 * (long)D1p, my_key, my_row, my_cnt, cnt, open_left,
+        seg_walk<LEVEL0, VEC2, WEIGHTED, MASKED>(X, LEVEL0 ? nullptr : vin + p0 * (long)D1p, my_key, my_row, my_cnt, cnt, open_left,
                                open_right, D, D1p, accumulate, SC, cnt_dense, s0, s1, k0, k1);
     }
     if (direct) {
@@ -414,11 +444,11 @@ __global__ __launch_bounds__(64 * SEG_MAX_WAVES) void runsum_kernel(const float*
     // block by construction, a filled slot 1 of the last wave is continued by the next one.
     const int cnt2 = 2 * nw;
     const int my_key2 = lane < cnt2 ? slot_keys[lane] : -1;
-    const float my_cnt2 = (lane < cnt2 && my_key2 >= 0) ? slots[(long)lane * D1p + D] : 0.0f;
+    const float my_cnt2 = (lane < cnt2 && my_key2 >= 0) ? slots[(long)lane * D1p + LD] : 0.0f;
     const bool open_left2 = __builtin_amdgcn_readfirstlane(my_key2) >= 0;
     const bool open_right2 = __builtin_amdgcn_readlane(my_key2, cnt2 - 1) >= 0;
     int g0 = -1, g1 = -1;
-    seg_walk<false, VEC2>(nullptr, slots, my_key2, 0, my_cnt2, cnt2, open_left2, open_right2, D, D1p, accumulate, SC,
+    seg_walk<false, VEC2>(nullptr, slots, my_key2, 0, my_cnt2, cnt2, open_left2, open_right2, LD, D1p, accumulate, SC,
                           cnt_dense, vout + (2 * blk) * (long)D1p, vout + (2 * blk + 1) * (long)D1p, g0, g1);
     if (lane == 0) { kout[2 * blk] = g0; kout[2 * blk + 1] = g1; }
 }
@@ -1229,6 +1259,18 @@ __global__ __launch_bounds__(256) void merge_kernel(float* __restrict__ W, const
             Wp[(long)inv[k] * D + d] = v;
         }
     }
+}
+
+// ---- merge of a handle with missing values (SOM_MISSING_NAN): a denominator per unit AND feature ----
+// ACC row k = [num (D) | den (D) | total]: W[k][d] = num[k][d] / den[k][d] where den[k][d] != 0, else W[k][d] stays bit for bit
+__global__ __launch_bounds__(256) void merge_masked_kernel(float* __restrict__ W, const float* __restrict__ ACC, long K, int D,
+                                                           int D1p) {
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= K * D) return;
+    long k = i / D;
+    int d = (int)(i - k * D);
+    const float den = ACC[k * D1p + D + d];
+    if (den != 0.0f) W[i] = ACC[k * D1p + d] / den;
 }
 
 // ---- quantization error: sum_n |x_n - W[bmu_n]|  (xpysom.py:703-705) -----------------------------

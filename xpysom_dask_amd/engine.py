@@ -22,7 +22,9 @@ def _f32(a):
 class HipEngine:
     def __init__(self, x, y, input_len, *, distance="euclidean", neighborhood="gaussian",
                  std_coeff=0.5, compact_support=False, precision="exact", device=0, stream=None,
-                 topology="rectangular", norm_p=0, norm_p_real=0.0):
+                 topology="rectangular", norm_p=0, norm_p_real=0.0, missing=None):
+        if missing not in _lib.SOM_MISSING:
+            raise ValueError("missing must be None or 'nan', got %r" % (missing,))
         self._lib = _lib.load()
         self._h = None
         self.K, self.D = int(x) * int(y), int(input_len)
@@ -33,7 +35,8 @@ class HipEngine:
         cfg = _lib.SomConfig(int(x), int(y), int(input_len), _lib.SOM_DIST[distance],
                              _lib.SOM_NEIGH[neighborhood], int(bool(compact_support)),
                              _lib.SOM_PREC[precision], int(device), float(std_coeff),
-                             C.c_void_p(stream) if stream else None, _lib.SOM_TOPO[topology], int(norm_p), float(norm_p_real))
+                             C.c_void_p(stream) if stream else None, _lib.SOM_TOPO[topology], int(norm_p), float(norm_p_real),
+                             _lib.SOM_MISSING[missing])
         h = C.c_void_p()
         if self._lib.som_create(C.byref(cfg), C.byref(h)) != 0:
             raise SomHipError(self._lib.som_last_error(None).decode())
@@ -41,6 +44,7 @@ class HipEngine:
         self.has_comm = False
         self.device = int(device)
         self.precision = precision
+        self.missing = missing
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc):
@@ -234,6 +238,16 @@ class HipEngine:
         bmu = np.empty((self.n_rows,), dtype=np.int32) if want_bmu else None
         self._check(self._lib.som_epoch_fetch(self._h, self._fp(num), self._fp(den),
                                               self._ip(bmu) if want_bmu else None))
+        return num, den, bmu
+
+    def epoch_fetch_masked(self, want_bmu=True):
+        """(num (K,D), den (K,D), bmu (n,) or None) of the last accumulate of an engine created with missing='nan': a
+        denominator per unit and feature."""
+        num = np.empty((self.K, self.D), dtype=np.float32)
+        den = np.empty((self.K, self.D), dtype=np.float32)
+        bmu = np.empty((self.n_rows,), dtype=np.int32) if want_bmu else None
+        self._check(self._lib.som_epoch_fetch_masked(self._h, self._fp(num), self._fp(den),
+                                                     self._ip(bmu) if want_bmu else None))
         return num, den, bmu
 
     def accum_device_ptr(self):

@@ -172,7 +172,7 @@ class XPySom:
                  random_seed=None, n_parallel=0, compact_support=False,
                  xp=None,
                  use_dask=False, dask_chunks='auto',
-                 *, precision='exact', device=None, sharded_input=False, shard='contiguous'):
+                 *, precision='exact', device=None, sharded_input=False, shard='contiguous', missing=None):
         """Same positional/keyword surface as the reference constructor (xpysom.py:73-82).
 
         ``xp``, ``use_dask`` and ``dask_chunks`` are accepted for source compatibility and
@@ -192,6 +192,17 @@ class XPySom:
                          or 'strided' (rows rank, rank + world, ...: every rank a sample of the whole file, so that an
                          order in the input cannot become rank skew under block skipping); the same map either way, to
                          float32 summation order
+          missing        None (the default: a NaN is a value like any other, and poisons what it touches) or 'nan': a NaN
+                         in training, streamed or query rows means "not observed".  The BMU of a row is the first minimum
+                         of the squared distance over its observed features (a row with none takes unit 0 and teaches
+                         nothing); the batch update keeps a numerator and a denominator per unit AND feature,
+                         W[k, d] = sum_n g m_nd x_nd / sum_n g m_nd, and leaves W[k, d] untouched where no observed value
+                         reached it; quantization_error is the mean over all rows of the distance over the observed
+                         features.  The codebook never receives a NaN from the data.  'euclidean' only, precision 'exact'
+                         or 'f32' (both run the float32 masked kernel); every neighbourhood and topology; train (with
+                         sample_weight, device rows), train_streaming, winner, predict, quantization, quantization_error,
+                         activation_response, win_map, labels_map.  topographic_error, activate and
+                         distance_from_weights raise NotImplementedError; the initialisers refuse data with a NaN
         """
         if sigma >= x or sigma >= y:
             warn('Warning: sigma is too high for the dimension of the map.')
@@ -276,6 +287,14 @@ class XPySom:
             n_parallel = DEFAULT_BATCH_ROWS
         self._n_parallel = n_parallel
 
+        if missing not in (None, 'nan'):
+            raise ValueError("missing must be None or 'nan', got %r" % (missing,))
+        if missing == 'nan':
+            if activation_distance != 'euclidean':
+                raise ValueError("missing='nan' is defined for activation_distance='euclidean' only, got '%s'" % activation_distance)
+            if precision not in ('f32', 'exact'):
+                raise ValueError("missing='nan' runs the float32 masked kernel: precision 'exact' or 'f32', not '%s'" % precision)
+        self._missing = missing
         self._precision = precision
         self._device = device
         self._sharded_input = sharded_input
@@ -291,6 +310,8 @@ class XPySom:
             kw = dict(distance=self._activation_distance_name, neighborhood=self.neighborhood_func_name,
                       std_coeff=self._std_coeff, compact_support=self.compact_support,
                       precision=self._precision, topology=self.topology)
+            if getattr(self, '_missing', None) is not None:
+                kw['missing'] = self._missing
             if self._activation_distance_name.startswith('norm_p'):
                 p = self._activation_distance_kwargs.get('p', 2)
                 if isinstance(p, (float, np.floating)) and not float(p).is_integer():
@@ -331,6 +352,7 @@ class XPySom:
     def activate(self, x):
         """Activation map of x: its distance to every unit under the configured distance, shape (n, K)
         (xpysom.py:323-354).  An analysis call: training never materialises this matrix."""
+        self._refuse_missing('activate')
         x = _host_rows(x, self._engine)
         if x.ndim == 0:
             x = x.reshape(1, 1)
@@ -343,6 +365,7 @@ class XPySom:
 
     def distance_from_weights(self, data, weights_gpu=None):
         """d[i, j] = euclidean distance between data[i] and the j-th unit (xpysom.py:647-671)."""
+        self._refuse_missing('distance_from_weights')
         data = _host_rows(data, self._engine)
         return self._upload_weights().distance_matrix(data, quantization=True)
 
@@ -380,6 +403,15 @@ class XPySom:
                 d = np.linalg.norm(w[xs, ys] - w[xn, yn], axis=-1)
                 um[xs, ys] += d * (even[:, ys] == bool(parity))
         return um / um.max()
+
+    def _refuse_missing(self, what):
+        if getattr(self, '_missing', None) is not None:
+            raise NotImplementedError("%s() is not defined with missing='%s': a distance over a row's observed features has no "
+                                      "common scale across rows" % (what, self._missing))
+
+    def _refuse_nan_init(self, what, data):
+        if getattr(self, '_missing', None) is not None and np.isnan(np.asarray(data, dtype=np.float64)).any():
+            raise ValueError("%s: the data holds NaN (missing values); initialise from complete rows" % what)
 
     def _check_input_len(self, data):
         """Checks that the data in input is of the correct shape (xpysom.py:360-366)."""
@@ -546,7 +578,8 @@ class XPySom:
         # float64 by NumPy.  Served for the 'euclidean' distance in the float32-exact modes; elsewhere x is taken as float32
         x64 = None
         if (isinstance(x, np.ndarray) and x.dtype == np.float64 and np.asarray(self._weights).dtype == np.float32
-                and self._activation_distance_name == 'euclidean' and self._precision in ('f32', 'exact')):
+                and self._activation_distance_name == 'euclidean' and self._precision in ('f32', 'exact')
+                and getattr(self, '_missing', None) is None):
             x64 = x
         if self._device_query(x) is not None:               # rows in HBM: searched there
             ids = self._ids_of(x).astype(np.int64)
@@ -598,6 +631,7 @@ class XPySom:
         """Share of samples whose best and second-best matching units are not adjacent on the map
         (xpysom.py:709-746, rectangular branch: |di| > 1 or |dj| > 1).  The reference sorts the whole
         (n, K) distance matrix; here a fused top-2 variant of the BMU kernel returns the pair."""
+        self._refuse_missing('topographic_error')
         # rows in HBM are searched where they are, whole (som_bmu_top2_device); host rows in n_parallel chunks
         q = self._device_query(data)                        # (checks the feature count of device rows itself)
         if q is None:
@@ -673,6 +707,7 @@ class XPySom:
     def random_weights_init(self, data):
         """Initializes the weights picking random samples from data (xpysom.py:749-759)."""
         self._check_input_len(data)
+        self._refuse_nan_init('random_weights_init', data)
         x, y, _ = self._weights.shape
         for i in range(x):
             for j in range(y):
@@ -683,6 +718,7 @@ class XPySom:
         if self._input_len == 1:
             raise ValueError('The data needs at least 2 features for pca initialization')
         self._check_input_len(data)
+        self._refuse_nan_init('pca_weights_init', data)
         if len(self._neigx) == 1 or len(self._neigy) == 1:
             warn('PCA initialization inappropriate:One of the dimensions of the map is 1.')
         pc_length, pc = np.linalg.eig(np.cov(np.transpose(data)))
@@ -699,3 +735,4 @@ class XPySom:
 
     def __setstate__(self, state):
         self.__dict__.update(state)
+        self.__dict__.setdefault('_missing', None)        # (a pickle from before the keyword)
