@@ -294,6 +294,25 @@ int som_quantization_error(som_handle* h, const float* x_host, int64_t n_rows, d
  * clamps to 0, units at DIFFERENT distances tie under the sqrt, and the lowest id wins.  Every row whose pick such a tie
  * could overturn is searched again by the float32 SQRT kernel, so the ids -- and the value -- are F32 precision's. */
 int som_quantization_error_device(som_handle* h, const void* x_dev, int64_t n_rows, double* qe_out);
+/* Map diagnostics: the per-row terms of that mean, and how they spread over the map (not in the reference).
+ *   b_n   the unit som_bmu(QUANTIZATION) names for row n on this handle: the Euclidean first minimum (SOM_MISSING_NAN: the masked
+ *         search's), found as som_quantization_error finds it -- in EXACT precision through the screen and its tie window
+ *   d_n   float32: |x_n - W[b_n]| exactly as som_quantization_error forms it before it widens and adds (SOM_MISSING_NAN: over the
+ *         row's observed features; a row with nothing observed has b_n = 0, d_n = 0).  The novelty / outlier score of the row.
+ * som_bmu_distances*: ids_out [n_rows] = b_n, dist_out [n_rows] = d_n, host memory; one of the two may be NULL, not both.
+ * n_rows == 0 writes nothing.
+ * som_unit_stats*: for every unit k (K = x * y entries per array, host memory; none may be NULL)
+ *   count[k] = #{n : b_n = k}   sum[k] = sum d_n   sumsq[k] = sum d_n^2 (both in double; each square is exact)   max[k] = max d_n
+ * and all four are 0 for a unit without rows (n_rows == 0: K zeros each).  The mean distance per unit -- the quantization-error
+ * map -- is sum / count, the variance sumsq / count - mean^2; the raw quantities add across shards.  The sums run over a unit's
+ * rows in ascending row index in a fixed reduction tree, without floating-point atomics: two calls on the same rows, and the host
+ * and the device entry point on the same rows, return the same bits.  On a handle without SOM_MISSING_NAN a row holding a NaN
+ * has d_n = NaN, and its unit's sum and sumsq are NaN; the counts stay exact and max ignores the NaN.
+ * The *_device forms read rows that already live in HBM (see som_bmu_device: borrowed for the call, at most 2^31-1 rows). */
+int som_bmu_distances(som_handle* h, const float* x_host, int64_t n_rows, int32_t* ids_out, float* dist_out);
+int som_bmu_distances_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids_out, float* dist_out);
+int som_unit_stats(som_handle* h, const float* x_host, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max);
+int som_unit_stats_device(som_handle* h, const void* x_dev, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max);
 
 /* The canary.  n_rows > 0: after every BMU launch (epochs, streamed chunks, som_bmu) n_rows strided rows are scored
  * again by the float32 parity kernel and the launch's own picks must be the float32 picks (F32, EXACT) or within the

@@ -1,4 +1,4 @@
 """MI355X-native batch-SOM engine behind the XPySom class surface of jcfaracco/xpysom-dask."""
-from .xpysom import XPySom
+from .xpysom import UnitStatistics, XPySom
 
-__all__ = ["XPySom"]
+__all__ = ["XPySom", "UnitStatistics"]

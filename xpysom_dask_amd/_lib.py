@@ -76,6 +76,10 @@ SIGNATURES = {
     "som_distance_matrix": (C.c_int, [_H, _F, C.c_int64, C.c_int32, _F]),
     "som_quantization_error": (C.c_int, [_H, _F, C.c_int64, C.POINTER(C.c_double)]),
     "som_quantization_error_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.POINTER(C.c_double)]),
+    "som_bmu_distances": (C.c_int, [_H, _F, C.c_int64, _I, _F]),
+    "som_bmu_distances_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _I, _F]),
+    "som_unit_stats": (C.c_int, [_H, _F, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
+    "som_unit_stats_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
     "som_set_verify": (C.c_int, [_H, C.c_int32]),
     "som_verify_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_debug_corrupt_operands": (C.c_int, [_H, C.c_int32]),

@@ -35,6 +35,7 @@
 #include "bmu_masked_f32.hpp"
 #include "bmu_pairwise.hpp"
 #include "update.hpp"
+#include "diag.hpp"
 
 using namespace somhip;
 
@@ -116,6 +117,20 @@ struct RowSet {
     float* xmax2 = nullptr;      // max_n |x~_n|^2: this set's float of som_handle::xmax2 ([0] resident, [1] every transient set)
     bool err_half = false;       // precision 'exact'
     bool ids_valid = false;      // bmu holds the ids of a completed BMU pass over THESE rows (resident set only: a transient set's never outlive the call)
+    // map diagnostics (diag.hpp; the query set only): the rows' distances to their BMUs, the rows sorted by BMU, the segment starts
+    // and the per-unit results.  Grown with the set's `cap` (diag_reserve), so nothing is allocated once a size has been seen.
+    struct Diag {
+        DevBuf<float> dist;                      // [cap] d_n
+        DevBuf<int> skey, srow;                  // [sort_cap] the stable sort's (unit, row) pairs
+        DevBuf<int> tmp;                         // radix_sort_rows' scratch
+        DevBuf<int> cs_table;                    // counting sort (small maps), as SegScratch's
+        long cs_blocks = 0;
+        long sort_cap = 0;                       // rows the sort's buffers serve
+        DevBuf<int> start;                       // [K] first sorted position of every unit that has rows, else -1
+        DevBuf<long long> count;                 // [K]
+        DevBuf<double> sums;                     // [2 K] sum | sum of squares
+        DevBuf<float> max;                       // [K]
+    } diag;
     bool resident() const { return kind == rowset::Kind::Resident; }
     // precision 'exact': the rows' measured operand rounding errors (bmu_exact.hpp) live in the second half of xsq.  The only place that knows.
     float* xerr() const { return err_half && xsq.p != nullptr ? xsq.p + cap : nullptr; }
@@ -1176,6 +1191,23 @@ long launch_runsum(som_handle* h, const float* X, const int* keys, const int* sr
     return blocks;
 }
 
+// (skey, srow) = the N rows sorted by their unit `bmu`, rows ascending inside a unit (stable): the counting sort where the caller
+// holds its table (cs_table: [cs_blocks + 1][K] ints) and the rows fill two blocks, else the radix sort (tmp: radix_scratch_ints)
+int sort_rows_by_unit(som_handle* h, const int* bmu, long N, int bits, int* skey, int* srow, int* tmp, int* cs_table, long cs_blocks) {
+    const int B = (int)cdiv(N, CS_BLOCK);
+    if (cs_table != nullptr && B <= cs_blocks && N >= 2 * CS_BLOCK) {
+        // few units: a stable counting sort in three launches (same order as the radix sort: unit, then row)
+        int* tot = cs_table + (long)B * h->K;
+        const size_t lds = (size_t)h->K * sizeof(int);
+        cs_hist_kernel<<<dim3((unsigned)B), dim3(256), lds, h->stream>>>(bmu, N, h->K, B, cs_table);
+        cs_scan_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(cs_table, h->K, B, tot);
+        cs_scatter_kernel<<<dim3((unsigned)B), dim3(CS_BLOCK), lds, h->stream>>>(bmu, N, h->K, B, bits, cs_table, tot, skey, srow);
+        HIPCHK(h, hipGetLastError());
+        return 0;
+    }
+    return radix_sort_rows(h, bmu, N, bits, skey, srow, tmp);
+}
+
 // SC[b] += sum of the rows whose BMU is b (and their count): sort by BMU, then the levels of update.hpp's
 // run sum (rows -> partial lists) until one workgroup holds the whole list.  zero_first: SC starts from zero and
 // every unit is written once (plain stores); otherwise the chunk's sums are added to what SC holds.
@@ -1189,19 +1221,7 @@ int segsum_rows(som_handle* h, const Rows& r, som_handle::SegScratch& sg, bool z
         if (N > sg.cap) return fail(h, "segment sum: scratch smaller than the row set");
         int bits = 1;
         while ((1L << bits) < h->K) ++bits;
-        const int B = (int)cdiv(N, CS_BLOCK);
-        if (sg.cs_table != nullptr && B <= sg.cs_blocks && N >= 2 * CS_BLOCK) {
-            // few units: a stable counting sort in three launches (same order as the radix sort: unit, then row)
-            int* tot = sg.cs_table + (long)B * h->K;
-            const size_t lds = (size_t)h->K * sizeof(int);
-            cs_hist_kernel<<<dim3((unsigned)B), dim3(256), lds, h->stream>>>(bmu, N, h->K, B, sg.cs_table);
-            cs_scan_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(sg.cs_table, h->K, B, tot);
-            cs_scatter_kernel<<<dim3((unsigned)B), dim3(CS_BLOCK), lds, h->stream>>>(bmu, N, h->K, B, bits, sg.cs_table, tot, sg.skey,
-                                                                                    sg.srow);
-            HIPCHK(h, hipGetLastError());
-        } else {
-            if (int rc = radix_sort_rows(h, bmu, N, bits, sg.skey, sg.srow, sg.tmp)) return rc;
-        }
+        if (int rc = sort_rows_by_unit(h, bmu, N, bits, sg.skey, sg.srow, sg.tmp, sg.cs_table, sg.cs_blocks)) return rc;
         const int acc = zero_first ? 0 : 1;
         long blocks = launch_runsum<true>(h, X, sg.skey, sg.srow, nullptr, N, acc, sg.kA, sg.vA, r.wgt);
         int *kin = sg.kA, *kout = sg.kB;
@@ -2423,6 +2443,85 @@ int query_quantization_error(som_handle* h, const std::string& who, const float*
     *qe_out = s / (double)n_rows;
     return 0;
 }
+
+// ---- map diagnostics (diag.hpp): every row's distance to its BMU, and the per-unit statistics of those distances ----
+// the query set's rows are on the device: their units into q.bmu -- quantization_error's own search, so in EXACT precision
+// the screen and its tie window serve it -- and q.diag.dist[n] = the float32 qe_kernel would add for row n
+int run_bmu_distances(som_handle* h) {
+    RowSet& q = h->q;
+    if (int rc = q.diag.dist.reserve(h, (size_t)q.cap)) return rc;
+    if (int rc = run_quantization_bmu(h, true)) return rc;
+    const dim3 grid((unsigned)std::min<long>(cdiv(q.N, 4), 4096));      // (qe_kernel's geometry)
+    if (h->masked) bmu_dist_kernel<true><<<grid, dim3(256), 0, h->stream>>>(q.X, q.bmu, h->W, q.N, h->D, q.diag.dist);
+    else bmu_dist_kernel<false><<<grid, dim3(256), 0, h->stream>>>(q.X, q.bmu, h->W, q.N, h->D, q.diag.dist);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+// the sort's buffers for the rows `s` holds (its cap: they grow with it), the per-unit buffers once
+int diag_reserve_stats(som_handle* h, RowSet& s) {
+    auto& g = s.diag;
+    if (int rc = g.start.reserve(h, (size_t)h->K)) return rc;
+    if (int rc = g.count.reserve(h, (size_t)h->K)) return rc;
+    if (int rc = g.sums.reserve(h, 2 * (size_t)h->K)) return rc;
+    if (int rc = g.max.reserve(h, (size_t)h->K)) return rc;
+    if (s.N > 0x7fffffffL) return fail(h, "more than 2^31-1 rows per GPU in one row set");   // (the sort holds row indices as ints)
+    if (s.cap <= g.sort_cap) return 0;
+    g.skey.reset(); g.srow.reset(); g.tmp.reset(); g.cs_table.reset(); g.cs_blocks = 0; g.sort_cap = 0;
+    if (int rc = g.skey.alloc(h, (size_t)s.cap)) return rc;
+    if (int rc = g.srow.alloc(h, (size_t)s.cap)) return rc;
+    if (int rc = g.tmp.alloc(h, radix_scratch_ints(s.cap))) return rc;
+    const long csb = cdiv(s.cap, CS_BLOCK);                            // (seg_reserve's rule for the counting sort's table)
+    if (h->counting_sort && h->K <= CS_MAX_K && s.cap >= 2 * CS_BLOCK && csb * h->K <= (1L << 21)) {
+        if (int rc = g.cs_table.alloc(h, (size_t)(csb + 1) * h->K)) return rc;
+        g.cs_blocks = csb;
+    }
+    g.sort_cap = s.cap;
+    return 0;
+}
+int query_bmu_distances(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, int32_t* ids_out,
+                        float* dist_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || n_rows < 0 || (n_rows > 0 && ((!x_host && !x_dev) || (!ids_out && !dist_out)))) return fail(h, who + ": bad argument");
+    if (n_rows == 0) return 0;
+    if (x_dev && n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
+    if (int rc = run_bmu_distances(h)) return rc;
+    if (ids_out) if (int rc = d2h_blocking(h, ids_out, h->q.bmu, (size_t)n_rows * sizeof(int))) return rc;
+    if (dist_out) if (int rc = d2h_blocking(h, dist_out, h->q.diag.dist, (size_t)n_rows * sizeof(float))) return rc;
+    return 0;
+}
+int query_unit_stats(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, int64_t* count,
+                     double* sum, double* sumsq, float* max) {
+    DeviceGuard dev_guard(h);
+    if (!h || !count || !sum || !sumsq || !max || n_rows < 0 || (n_rows > 0 && !x_host && !x_dev)) return fail(h, who + ": bad argument");
+    const size_t K = (size_t)h->K;
+    if (n_rows == 0) {
+        std::memset(count, 0, K * sizeof(int64_t)); std::memset(sum, 0, K * sizeof(double));
+        std::memset(sumsq, 0, K * sizeof(double)); std::memset(max, 0, K * sizeof(float));
+        return 0;
+    }
+    if (x_dev && n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
+    RowSet& q = h->q; auto& g = q.diag;
+    if (int rc = diag_reserve_stats(h, q)) return rc;
+    if (int rc = run_bmu_distances(h)) return rc;
+    {
+        Timed t(h, SOM_K_SEGSUM);                                       // (the sort by unit and the reduction over its segments)
+        int bits = 1;
+        while ((1L << bits) < h->K) ++bits;
+        if (int rc = sort_rows_by_unit(h, q.bmu, q.N, bits, g.skey, g.srow, g.tmp, g.cs_table, g.cs_blocks)) return rc;
+        HIPCHK(h, hipMemsetAsync(g.start, 0xff, K * sizeof(int), h->stream));       // -1: the unit has no rows
+        unit_heads_kernel<<<dim3((unsigned)cdiv(q.N, 256)), dim3(256), 0, h->stream>>>(g.skey, q.N, h->K, g.start);
+        unit_stats_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(g.start, g.skey, g.srow, g.dist, q.N, h->K, g.count,
+                                                                                     g.sums, g.sums + K, g.max);
+        HIPCHK(h, hipGetLastError());
+    }
+    static_assert(sizeof(long long) == sizeof(int64_t), "the per-unit counts are copied out as int64_t");
+    if (int rc = d2h_blocking(h, count, g.count, K * sizeof(int64_t))) return rc;
+    if (int rc = d2h_blocking(h, sum, g.sums, K * sizeof(double))) return rc;
+    if (int rc = d2h_blocking(h, sumsq, g.sums + K, K * sizeof(double))) return rc;
+    return d2h_blocking(h, max, g.max, K * sizeof(float));
+}
 }  // namespace
 
 int som_bmu(som_handle* h, const float* x_host, int64_t n_rows, int32_t mode, int32_t* ids_out) { return query_bmu(h, "som_bmu", x_host, nullptr, n_rows, mode, ids_out); }
@@ -2431,6 +2530,10 @@ int som_bmu_top2(som_handle* h, const float* x_host, int64_t n_rows, int32_t* id
 int som_bmu_top2_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids1_out, int32_t* ids2_out) { return query_top2(h, "som_bmu_top2_device", nullptr, x_dev, n_rows, ids1_out, ids2_out); }
 int som_quantization_error(som_handle* h, const float* x_host, int64_t n_rows, double* qe_out) { return query_quantization_error(h, "som_quantization_error", x_host, nullptr, n_rows, qe_out); }
 int som_quantization_error_device(som_handle* h, const void* x_dev, int64_t n_rows, double* qe_out) { return query_quantization_error(h, "som_quantization_error_device", nullptr, x_dev, n_rows, qe_out); }
+int som_bmu_distances(som_handle* h, const float* x_host, int64_t n_rows, int32_t* ids_out, float* dist_out) { return query_bmu_distances(h, "som_bmu_distances", x_host, nullptr, n_rows, ids_out, dist_out); }
+int som_bmu_distances_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids_out, float* dist_out) { return query_bmu_distances(h, "som_bmu_distances_device", nullptr, x_dev, n_rows, ids_out, dist_out); }
+int som_unit_stats(som_handle* h, const float* x_host, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max) { return query_unit_stats(h, "som_unit_stats", x_host, nullptr, n_rows, count, sum, sumsq, max); }
+int som_unit_stats_device(som_handle* h, const void* x_dev, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max) { return query_unit_stats(h, "som_unit_stats_device", nullptr, x_dev, n_rows, count, sum, sumsq, max); }
 
 int som_bmu_f64(som_handle* h, const double* x_host, int64_t n_rows, int32_t* ids_out) {
     DeviceGuard dev_guard(h);

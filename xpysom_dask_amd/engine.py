@@ -336,6 +336,49 @@ class HipEngine:
         self._check(self._lib.som_quantization_error(self._h, self._fp(x), x.shape[0], C.byref(out)))
         return out.value
 
+    # -- map diagnostics (include/somhip.h, som_bmu_distances / som_unit_stats) --------------
+    def _rows_arg(self, x):
+        x = _f32(x)
+        if x.ndim != 2 or x.shape[1] != self.D:
+            raise ValueError("x must be (n, %d), got %r" % (self.D, x.shape))
+        return x
+
+    def bmu_distances(self, x):
+        """(ids int32, dist float32): every row's unit under the full Euclidean distance and its distance to it, the
+        per-row terms of quantization_error."""
+        x = self._rows_arg(x)
+        ids = np.empty((x.shape[0],), dtype=np.int32)
+        dist = np.empty((x.shape[0],), dtype=np.float32)
+        self._check(self._lib.som_bmu_distances(self._h, self._fp(x), x.shape[0], self._ip(ids), self._fp(dist)))
+        return ids, dist
+
+    def bmu_distances_device(self, dev_ptr, n_rows):
+        """bmu_distances of float32 rows that already live in HBM (`dev_ptr`: [n_rows][D], borrowed for the call)."""
+        ids = np.empty((int(n_rows),), dtype=np.int32)
+        dist = np.empty((int(n_rows),), dtype=np.float32)
+        self._check(self._lib.som_bmu_distances_device(self._h, C.c_void_p(dev_ptr), int(n_rows), self._ip(ids), self._fp(dist)))
+        return ids, dist
+
+    def _unit_stats_out(self):
+        out = (np.empty((self.K,), dtype=np.int64), np.empty((self.K,), dtype=np.float64), np.empty((self.K,), dtype=np.float64),
+               np.empty((self.K,), dtype=np.float32))
+        d = C.POINTER(C.c_double)
+        return out, (out[0].ctypes.data_as(C.POINTER(C.c_int64)), out[1].ctypes.data_as(d), out[2].ctypes.data_as(d), self._fp(out[3]))
+
+    def unit_stats(self, x):
+        """(count int64, sum float64, sumsq float64, max float32), K entries each: per unit, the rows it wins and the sum, the
+        sum of squares and the maximum of their distances to it.  Deterministic: the same rows give the same bits."""
+        x = self._rows_arg(x)
+        out, ptrs = self._unit_stats_out()
+        self._check(self._lib.som_unit_stats(self._h, self._fp(x), x.shape[0], *ptrs))
+        return out
+
+    def unit_stats_device(self, dev_ptr, n_rows):
+        """unit_stats of float32 rows that already live in HBM (`dev_ptr`: [n_rows][D], borrowed for the call)."""
+        out, ptrs = self._unit_stats_out()
+        self._check(self._lib.som_unit_stats_device(self._h, C.c_void_p(dev_ptr), int(n_rows), *ptrs))
+        return out
+
     def set_verify(self, n_rows):
         """The canary: re-score `n_rows` strided rows of every BMU launch with the float32 kernel (0 = off)."""
         self._check(self._lib.som_set_verify(self._h, int(n_rows)))

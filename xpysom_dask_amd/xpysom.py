@@ -161,6 +161,33 @@ def units_adjacent(b1, b2, X, Y, topology):
     return ~((di > 1) | (dj > 1))
 
 
+class UnitStatistics:
+    """What ``XPySom.unit_statistics`` returns: per unit of an ``(x, y)`` map, over the samples the unit wins,
+    ``hits`` (int64), ``sum`` and ``sumsq`` of their distances to it (float64) and ``max`` (float32; 0 for a unit without
+    samples).  ``hits``, ``sum`` and ``sumsq`` are the raw additive quantities: shards or ranks add them (``max``: the
+    elementwise maximum) and derive ``mean`` and ``std`` afterwards."""
+
+    def __init__(self, hits, sum, sumsq, max):
+        self.hits, self.sum, self.sumsq, self.max = hits, sum, sumsq, max
+
+    @property
+    def mean(self):
+        """Mean distance per unit, the quantization-error map; NaN where the unit has no samples."""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.where(self.hits == 0, np.nan, self.sum / self.hits)
+
+    @property
+    def std(self):
+        """Population standard deviation of the distances per unit, sqrt(max(sumsq / hits - mean^2, 0)); NaN where the unit
+        has no samples."""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            var = self.sumsq / self.hits - self.mean ** 2
+            return np.where(self.hits == 0, np.nan, np.sqrt(np.maximum(var, 0.0)))
+
+    def __repr__(self):
+        return "UnitStatistics(%d x %d units, %d samples)" % (self.hits.shape + (int(self.hits.sum()),))
+
+
 class XPySom:
     def __init__(self, x, y, input_len,
                  sigma=0, sigmaN=1,
@@ -626,6 +653,54 @@ class XPySom:
             total += eng.quantization_error(chunk) * len(chunk)
             n += len(chunk)
         return total / n if n else float('nan')
+
+    def _diag_query(self, data):
+        """(engine, device query or None, host rows or None) for the map diagnostics: device rows stay where they are, host
+        rows are coerced (a 1-D row is one sample) and their feature count is checked; the codebook is uploaded once."""
+        q = self._device_query(data)
+        if q is not None:
+            return q[0], q, None
+        data = _host_rows(data, self._engine)
+        if data.ndim == 1:
+            data = data[None, :]
+        if len(data):
+            self._check_input_len(data)
+        return self._upload_weights(), None, data
+
+    def quantization_distances(self, data):
+        """``(ids, dist)``: every sample's best matching unit under the Euclidean distance (int64, raveled as in
+        ``predict``) and its distance to it (float32) -- the per-sample terms ``quantization_error`` averages, and the usual
+        novelty score of a sample.  Rows in HBM are searched where they are, whole; host rows in ``n_parallel`` chunks.
+        With ``missing='nan'`` the distance runs over a row's observed features (a row with none: unit 0, distance 0)."""
+        eng, q, data = self._diag_query(data)
+        if q is not None:
+            ids, dist = eng.bmu_distances_device(q[1], q[2]) if q[2] else (np.zeros(0, np.int32), np.zeros(0, np.float32))
+            return ids.astype(np.int64), dist
+        parts = [eng.bmu_distances(data[s:s + self._n_parallel]) for s in range(0, len(data), self._n_parallel)]
+        if not parts:
+            return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32)
+        return np.concatenate([p[0] for p in parts]).astype(np.int64), np.concatenate([p[1] for p in parts])
+
+    def unit_statistics(self, data):
+        """Per-unit statistics of the samples' distances to their best matching units, a ``UnitStatistics`` of ``(x, y)``
+        arrays: ``hits`` (samples the unit wins), ``sum`` and ``sumsq`` of their distances (float64), ``max`` (float32), with
+        ``mean`` -- the quantization-error map -- and ``std`` derived.  Computed on the device without floating-point
+        atomics: the same rows give the same bits.  Host rows go in ``n_parallel`` chunks whose results are added on the
+        host in chunk order (float64; ``max`` by ``np.maximum``)."""
+        eng, q, data = self._diag_query(data)
+        X, Y = self._weights.shape[:2]
+        hits, tot = np.zeros(X * Y, dtype=np.int64), np.zeros(X * Y, dtype=np.float64)
+        sq, mx = np.zeros(X * Y, dtype=np.float64), np.zeros(X * Y, dtype=np.float32)
+        if q is not None:
+            parts = [eng.unit_stats_device(q[1], q[2])] if q[2] else []
+        else:
+            parts = (eng.unit_stats(data[s:s + self._n_parallel]) for s in range(0, len(data), self._n_parallel))
+        for c, s, s2, m in parts:
+            hits += c
+            tot += s
+            sq += s2
+            mx = np.maximum(mx, m)
+        return UnitStatistics(hits.reshape(X, Y), tot.reshape(X, Y), sq.reshape(X, Y), mx.reshape(X, Y))
 
     def topographic_error(self, data):
         """Share of samples whose best and second-best matching units are not adjacent on the map
