@@ -23,7 +23,10 @@ data = (raw - raw.mean(axis=0)) / raw.std(axis=0)
 for decay in ("linear", "exponential"):
     som = XPySom(6, 6, 4, random_seed=10, decay_function=decay)
     print("%-12s quantization error before training: %.5f" % (decay, som.quantization_error(data)))
-    som.train(data, 100)
+    som.train(data, 100, monitor=True)      # the learning curve comes with the training: one EpochRecord per epoch in som.history
+    for r in som.history[::20] + som.history[-1:]:
+        print("%-12s epoch %3d  sigma %.3f  QE %.5f  BMU changes %s  codebook shift %.5f"
+              % (decay, r.iteration, r.sigma, r.quantization_error, r.bmu_changed, r.codebook_shift))
     qe = som.quantization_error(data)
     print("%-12s after 100 epochs: %.5f   (reference: %.5f)   topographic error %.4f"
           % (decay, qe, float(g[decay + "_default_qe"]), som.topographic_error(data)))

@@ -314,6 +314,43 @@ int som_bmu_distances_device(som_handle* h, const void* x_dev, int64_t n_rows, i
 int som_unit_stats(som_handle* h, const float* x_host, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max);
 int som_unit_stats_device(som_handle* h, const void* x_dev, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max);
 
+/* Training monitor (not in the reference): what an epoch did, measured from what the epoch itself left on the device -- the rows,
+ * this epoch's BMU ids, the codebook W_t the epoch ran with (unchanged until som_epoch_merge) and the final accumulator.  No
+ * second BMU search, no copy of the rows.  The epoch runs with W_t and produces W_{t+1}:
+ *   sum_wd, sum_w   sum_n w_n d_n and sum_n w_n in double, over the rows of weight w_n > 0 (w_n = 1 without sample weights; a row
+ *                   of weight 0 is not read).  d_n = the float32 |x_n - W_t[b_n]| exactly as som_bmu_distances forms it (SOM_MISSING_NAN:
+ *                   over the observed features; a row with nothing observed has d_n = 0 and is counted), b_n = the unit THIS
+ *                   EPOCH'S search found under the configured distance and precision.  The epoch's quantization error is
+ *                   sum_wd / sum_w.  It is not som_quantization_error bit for bit: that call searches under the sqrt'd Euclidean
+ *                   distance (other tie windows), and for the cosine, Manhattan and norm_p distances b_n is another unit.
+ *   rows            rows measured (weight > 0)
+ *   changed         rows whose b_n differs from the id the previous measured epoch left for the same resident row set; -1 = unknown:
+ *                   the first measured epoch after som_set_data*, and every streamed epoch
+ *   shift_sumsq     sum_{k,d} (W_{t+1}[k][d] - W_t[k][d])^2, differences and squares in double
+ *   shift_max       max_{k,d} |W_{t+1}[k][d] - W_t[k][d]| in float32
+ *                   W_{t+1}[k][d] is the float32 the merge will write: num / den where den != 0, else W_t[k][d] (SOM_MISSING_NAN: the
+ *                   denominator of the feature).  Formed from the FINAL accumulator -- after the all-reduce --, so every rank
+ *                   holds the same two values without a collective; the four row sums are this rank's and add across ranks.
+ * Sums without floating-point atomics, in fixed trees over grids that depend on the row count and the map alone: two monitored
+ * runs return the same bits.  A monitored schedule trains the codebook of the unmonitored one bit for bit.
+ *   som_monitor(h, 1)           switches the monitor on: allocates its buffers and keeps a copy of every measured epoch's ids
+ *                               beside the resident rows (som_set_data* invalidates it); som_monitor(h, 0) frees them.  While it
+ *                               is off no call launches or allocates anything for it.
+ *   som_epoch_measure_rows      launch; the resident rows, after any som_epoch_accumulate* form and before the next search
+ *   som_epoch_measure_shift     launch; the accumulator must be final (after the all-reduce / the last staged block), before
+ *                               som_epoch_merge
+ *   som_epoch_metrics           ONE blocking read-back of the struct
+ * Every launch is eager on the handle's stream (a replayed epoch graph is followed by them).  Streamed epochs: som_stream_begin
+ * zeroes the row sums, every som_stream_rows* adds its chunk's in chunk order (som_epoch_measure_rows is implicit), and
+ * som_epoch_metrics after som_stream_end (+ som_epoch_measure_shift) returns the totals.  som_epoch, the fused call, is not
+ * monitored.  Errors (som_last_error): a measure call on a handle without som_monitor(h, 1); som_epoch_measure_rows with no
+ * search since the last merge; som_epoch_measure_shift while staged blocks are outstanding. */
+typedef struct { double sum_wd, sum_w, shift_sumsq; int64_t rows, changed /* -1: unknown */; float shift_max; } som_epoch_metrics_t;
+int som_monitor(som_handle* h, int32_t on);
+int som_epoch_measure_rows(som_handle* h);
+int som_epoch_measure_shift(som_handle* h);
+int som_epoch_metrics(som_handle* h, som_epoch_metrics_t* out);
+
 /* The canary.  n_rows > 0: after every BMU launch (epochs, streamed chunks, som_bmu) n_rows strided rows are scored
  * again by the float32 parity kernel and the launch's own picks must be the float32 picks (F32, EXACT) or within the
  * precision mode's operand-rounding bound of them; otherwise the call fails with a message naming a row.  Costs one

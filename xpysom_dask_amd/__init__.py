@@ -1,4 +1,4 @@
 """MI355X-native batch-SOM engine behind the XPySom class surface of jcfaracco/xpysom-dask."""
-from .xpysom import UnitStatistics, XPySom
+from .xpysom import EpochRecord, UnitStatistics, XPySom
 
-__all__ = ["XPySom", "UnitStatistics"]
+__all__ = ["XPySom", "UnitStatistics", "EpochRecord"]

@@ -26,6 +26,12 @@ class SomConfig(C.Structure):
                 ("missing", C.c_int32)]
 
 
+class EpochMetrics(C.Structure):
+    """som_epoch_metrics_t (include/somhip.h): the training monitor's record of one epoch as the device holds it."""
+    _fields_ = [("sum_wd", C.c_double), ("sum_w", C.c_double), ("shift_sumsq", C.c_double),
+                ("rows", C.c_int64), ("changed", C.c_int64), ("shift_max", C.c_float)]
+
+
 _F = C.POINTER(C.c_float)
 _I = C.POINTER(C.c_int32)
 _H = C.c_void_p
@@ -80,6 +86,10 @@ SIGNATURES = {
     "som_bmu_distances_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _I, _F]),
     "som_unit_stats": (C.c_int, [_H, _F, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
     "som_unit_stats_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
+    "som_monitor": (C.c_int, [_H, C.c_int32]),
+    "som_epoch_measure_rows": (C.c_int, [_H]),
+    "som_epoch_measure_shift": (C.c_int, [_H]),
+    "som_epoch_metrics": (C.c_int, [_H, C.POINTER(EpochMetrics)]),
     "som_set_verify": (C.c_int, [_H, C.c_int32]),
     "som_verify_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_debug_corrupt_operands": (C.c_int, [_H, C.c_int32]),

@@ -36,6 +36,7 @@
 #include "bmu_pairwise.hpp"
 #include "update.hpp"
 #include "diag.hpp"
+#include "monitor.hpp"
 
 using namespace somhip;
 
@@ -371,6 +372,18 @@ struct som_handle {
     struct KernelSlots { const void* fn; size_t lds; int per_cu; };
     std::vector<KernelSlots> kernel_slots;
     int staged_blocks_done = -1; // som_epoch_accumulate_begin / _block: next block expected, -1 = none pending
+    // training monitor (monitor.hpp; som_monitor): everything here is allocated when it is switched on and freed when it is
+    // switched off -- `prev`, last measured epoch's ids of the resident rows, beside the row set but not of rowset::sizes
+    struct Monitor {
+        bool on = false;
+        DevBuf<int> prev;                        // [res.N] the ids the last som_epoch_measure_rows saw
+        bool prev_valid = false;                 // ... of THESE resident rows (som_set_data* clears it)
+        DevBuf<MonitorRowPartial> rpart;         // [4096] one per workgroup of the row kernel
+        DevBuf<MonitorShiftPartial> spart;       // [2048] ... of the shift kernel
+        DevBuf<som_epoch_metrics_t> m;           // the metrics of the epoch in flight
+        som_epoch_metrics_t* m_host = nullptr;   // pinned: som_epoch_metrics' one read-back
+    } mon;
+    bool searched = false;       // the resident ids are those of a search since the last som_epoch_merge
     bool async_copies = false;   // SOM_ASYNC_COPIES=1: round 1's original copy path (fresh_process_stress.py)
     int prof = 0;            // som_profile_enable: 0 off, 1 every kernel family, 2 the BMU family only
     std::vector<EventPair> pending, pool;
@@ -1711,6 +1724,7 @@ void som_destroy(som_handle* h) {
         if (sl.consumed) (void)hipEventDestroy(sl.consumed);
     }
     if (h->ex.pass_host) (void)hipHostFree(h->ex.pass_host);
+    if (h->mon.m_host) (void)hipHostFree(h->mon.m_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;                                            // (the device buffers free themselves, on the handle's device: dev_guard)
@@ -1760,6 +1774,8 @@ static int adopt_rows(som_handle* h, const std::string& who, const void* x, int6
     clear_sample_weights(h);                             // (weights belong to the rows they were set for)
     if (!host) s.X_owned.reset();
     s.ids_valid = false;
+    h->mon.prev_valid = false;                           // (the monitor's last ids belong to the rows they were found for)
+    h->searched = false;
     h->ex.plan.order_lost();                             // (the resident sorted pass belongs to the rows it was sorted from)
     h->ex.srt[0].lastpos_valid = false;
     h->seg = som_handle::SegScratch{};
@@ -1822,6 +1838,39 @@ int epoch_accumulate_eager(som_handle* h, double sigma, double eta, int neigh_f6
     return rc;
 }
 
+// ---- training monitor (monitor.hpp): eager launches on the handle's stream, never inside a captured graph -----
+// the row metrics of `r` under its own ids: the partials, then their sum into the metrics struct (add: onto a streamed epoch's
+// running sums).  prev: the id buffer to refresh, and with have_prev to compare with (nullptr: a streamed chunk, or no rows).
+int monitor_launch_rows(som_handle* h, const Rows& r, int* prev, bool have_prev, bool add) {
+    auto& mon = h->mon;
+    const int grid = (int)monitor_rows_grid(r.N);
+    if (grid > 0) {
+        const dim3 g((unsigned)grid), b(256);
+        const int hp = have_prev ? 1 : 0;
+        if (h->masked) {
+            if (r.wgt) monitor_rows_kernel<true, true><<<g, b, 0, h->stream>>>(r.X, r.out, h->W, r.wgt, prev, hp, r.N, h->D, mon.rpart);
+            else monitor_rows_kernel<true, false><<<g, b, 0, h->stream>>>(r.X, r.out, h->W, nullptr, prev, hp, r.N, h->D, mon.rpart);
+        } else {
+            if (r.wgt) monitor_rows_kernel<false, true><<<g, b, 0, h->stream>>>(r.X, r.out, h->W, r.wgt, prev, hp, r.N, h->D, mon.rpart);
+            else monitor_rows_kernel<false, false><<<g, b, 0, h->stream>>>(r.X, r.out, h->W, nullptr, prev, hp, r.N, h->D, mon.rpart);
+        }
+        HIPCHK(h, hipGetLastError());
+    }
+    monitor_rows_reduce_kernel<<<dim3(1), dim3(MON_REDUCE_THREADS), 0, h->stream>>>(mon.rpart, grid, add ? 1 : 0,
+                                                                                  have_prev ? 1 : 0, mon.m);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+void monitor_free(som_handle* h) {
+    auto& mon = h->mon;
+    mon.on = false;
+    mon.prev_valid = false;
+    mon.prev.reset(); mon.rpart.reset(); mon.spart.reset(); mon.m.reset();
+    if (mon.m_host) (void)hipHostFree(mon.m_host);
+    mon.m_host = nullptr;
+}
+
 void drop_graph(som_handle* h) {
     if (h->gexec) (void)hipGraphExecDestroy(h->gexec);
     h->gexec = nullptr;
@@ -1869,6 +1918,7 @@ int som_epoch_accumulate(som_handle* h, double sigma, double eta, int neigh_f64)
     if (!h) return 1;
     const RowSet& res = h->res;
     if (!res.X && res.N > 0) return fail(h, "som_epoch_accumulate: no resident data (call som_set_data)");
+    h->searched = true;
     // launch-bound maps (many short kernels per epoch) replay a captured graph; profiling needs the
     // per-kernel events of the eager path
     if (h->use_graph && !h->prof && res.N > 0 && !h->exact) {
@@ -1907,6 +1957,7 @@ int som_epoch_accumulate_faithful(som_handle* h, double sigma, double eta, int n
                                   "the cross-check of the update without missing values");
     if (r.wgt) return fail(h, "som_epoch_accumulate_faithful: sample weights are set; the faithful form is the cross-check of the "
                                "unweighted update (clear them with som_set_sample_weights(h, NULL, 0))");
+    h->searched = true;
     if (int rc = run_activation_bmu(h, r)) return rc;
     Timed t(h, SOM_K_KRON);
     if (int rc = build_tables(h, sigma, eta, neigh_f64, h->stream)) return rc;
@@ -1924,6 +1975,7 @@ int som_epoch_accumulate_forced(som_handle* h, const int32_t* bmu_host, double s
     for (long i = 0; i < h->res.N; ++i)
         if (bmu_host[i] < 0 || bmu_host[i] >= h->K) return fail(h, "som_epoch_accumulate_forced: id out of range");
     h->ex.srt[0].lastpos_valid = false;                  // (ids from outside: the sorted rows' carried positions are not theirs)
+    h->searched = true;                                  // (... and the monitor measures the rows against them)
     if (h->res.N > 0)
         if (int rc = h2d_blocking(h, h->res.bmu, bmu_host, (size_t)h->res.N * sizeof(int))) return rc;
     return run_update(h, sigma, eta, neigh_f64);
@@ -1976,6 +2028,10 @@ int som_stream_begin(som_handle* h) {
     if (!h) return 1;
     if (int rc = refresh_codebook_operands(h, operands::Request::Search)) return rc;
     HIPCHK(h, hipMemsetAsync(h->SC, 0, (size_t)h->K * (h->D1p + 1) * sizeof(float), h->stream));
+    if (h->mon.on) {                                     // the epoch's running row sums start at zero, `changed` unknown
+        monitor_rows_reduce_kernel<<<dim3(1), dim3(MON_REDUCE_THREADS), 0, h->stream>>>(h->mon.rpart, 0, 0, 0, h->mon.m);
+        HIPCHK(h, hipGetLastError());
+    }
     h->streaming = true;
     return 0;
 }
@@ -2034,6 +2090,9 @@ static int stream_rows(som_handle* h, const float* x_host, const float* w_host, 
     const Rows r = s.view();
     if (int rc = run_activation_bmu(h, r)) return rc;
     if (int rc = segsum_rows(h, r, h->st_seg, false)) return rc;
+    // the monitor reads the chunk where it lies, behind its search and before the slot is given back
+    if (h->mon.on)
+        if (int rc = monitor_launch_rows(h, r, nullptr, false, true)) return rc;
     // a slot is free again behind this event; a pageable chunk's buffer -- the caller's and ours -- on return
     if (!pinned) { HIPCHK(h, hipStreamSynchronize(h->stream)); return 0; }
     HIPCHK(h, hipEventRecord(sl->consumed, h->stream));
@@ -2077,6 +2136,7 @@ int som_stream_end(som_handle* h, double sigma, double eta, int neigh_f64) {
 int som_epoch_merge(som_handle* h) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
+    h->searched = false;
     Timed t(h, SOM_K_MERGE);
     if (h->masked) {                                     // missing values: a denominator per unit and feature (update.hpp)
         const long total = (long)h->K * h->D;
@@ -2254,6 +2314,7 @@ int som_epoch_accumulate_begin(som_handle* h, double sigma, double eta, int neig
     if (!h) return 1;
     const Rows r = h->res.view();
     if (!r.X && r.N > 0) return fail(h, "som_epoch_accumulate_begin: no resident data (call som_set_data)");
+    h->searched = true;
     if (int rc = run_activation_bmu(h, r)) return rc;
     if (int rc = segsum_rows(h, r, h->seg, true)) return rc;
     Timed t(h, SOM_K_KRON);
@@ -2330,6 +2391,82 @@ int som_epoch_fetch_masked(som_handle* h, float* num, float* den, int32_t* bmu) 
         }
     }
     if (bmu && h->res.N > 0) HIPCHK(h, hipMemcpy(bmu, h->res.bmu, (size_t)h->res.N * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- training monitor (include/somhip.h; csrc/monitor.hpp) -----------------------------------------------------
+int som_monitor(som_handle* h, int32_t on) {
+    DeviceGuard dev_guard(h);
+    if (!h) return 1;
+    auto& mon = h->mon;
+    if (!on) {
+        if (mon.on) HIPCHK(h, hipStreamSynchronize(h->stream));   // (its launches may still be reading what goes)
+        monitor_free(h);
+        return 0;
+    }
+    if (mon.on) return 0;
+    int rc = mon.rpart.alloc(h, (size_t)monitor_rows_grid(0x7fffffffL));
+    if (rc == 0) rc = mon.spart.alloc(h, (size_t)monitor_shift_grid((long)h->K * h->D));
+    if (rc == 0) rc = mon.m.alloc(h, 1);
+    if (rc == 0 && h->res.N > 0) rc = mon.prev.alloc(h, (size_t)h->res.N);
+    if (rc == 0 && hipHostMalloc((void**)&mon.m_host, sizeof(som_epoch_metrics_t), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        mon.m_host = nullptr;
+        rc = fail(h, "som_monitor: no pinned host memory for the metrics");
+    }
+    if (rc == 0) {
+        hipError_t e = hipMemsetAsync(mon.m, 0, sizeof(som_epoch_metrics_t), h->stream);
+        if (e != hipSuccess) rc = fail_hip(h, "som_monitor: hipMemsetAsync", e);
+    }
+    if (rc != 0) { const std::string why = h->err; monitor_free(h); h->err = why; return rc; }
+    mon.on = true;
+    mon.prev_valid = false;
+    return 0;
+}
+
+int som_epoch_measure_rows(som_handle* h) {
+    DeviceGuard dev_guard(h);
+    if (!h) return 1;
+    auto& mon = h->mon;
+    if (!mon.on) return fail(h, "som_epoch_measure_rows: the monitor is off (call som_monitor(h, 1))");
+    if (!h->searched) return fail(h, "som_epoch_measure_rows: no search over the resident rows since the last som_epoch_merge "
+                                     "(call a som_epoch_accumulate* form first)");
+    const Rows r = h->res.view();
+    if (r.N > 0 && (size_t)r.N > mon.prev.cap) {         // rows adopted after som_monitor: the ids' copy grows with them
+        if (int rc = mon.prev.alloc(h, (size_t)r.N)) return rc;
+        mon.prev_valid = false;
+    }
+    if (int rc = monitor_launch_rows(h, r, mon.prev, mon.prev_valid, false)) return rc;
+    mon.prev_valid = true;
+    return 0;
+}
+
+int som_epoch_measure_shift(som_handle* h) {
+    DeviceGuard dev_guard(h);
+    if (!h) return 1;
+    auto& mon = h->mon;
+    if (!mon.on) return fail(h, "som_epoch_measure_shift: the monitor is off (call som_monitor(h, 1))");
+    if (h->staged_blocks_done >= 0)
+        return fail(h, "som_epoch_measure_shift: staged blocks are outstanding: the accumulator is final after the last "
+                       "som_epoch_accumulate_block");
+    if (h->streaming) return fail(h, "som_epoch_measure_shift: a streamed epoch is open: call som_stream_end first");
+    const int grid = (int)monitor_shift_grid((long)h->K * h->D);
+    if (h->masked) monitor_shift_kernel<true><<<dim3((unsigned)grid), dim3(256), 0, h->stream>>>(h->ACC, h->W, h->K, h->D, h->D1p, mon.spart);
+    else monitor_shift_kernel<false><<<dim3((unsigned)grid), dim3(256), 0, h->stream>>>(h->ACC, h->W, h->K, h->D, h->D1p, mon.spart);
+    HIPCHK(h, hipGetLastError());
+    monitor_shift_reduce_kernel<<<dim3(1), dim3(MON_REDUCE_THREADS), 0, h->stream>>>(mon.spart, grid, mon.m);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int som_epoch_metrics(som_handle* h, som_epoch_metrics_t* out) {
+    DeviceGuard dev_guard(h);
+    if (!h || !out) return fail(h, "som_epoch_metrics: NULL argument");
+    auto& mon = h->mon;
+    if (!mon.on) return fail(h, "som_epoch_metrics: the monitor is off (call som_monitor(h, 1))");
+    HIPCHK(h, hipMemcpyAsync(mon.m_host, mon.m, sizeof(som_epoch_metrics_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *out = *mon.m_host;
     return 0;
 }
 

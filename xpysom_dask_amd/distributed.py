@@ -130,12 +130,14 @@ def _overlap_wanted(engine, world):
     return dist.get_backend() == "nccl" and engine.epoch_block_count() > 2
 
 
-def _epoch_overlapped(engine, sigma, eta, neigh_f64):
+def _epoch_overlapped(engine, sigma, eta, neigh_f64, monitored=False):
     """accumulate -> [stage 2 of block b  ||  all-reduce of block b-1] ... -> merge.  The slices of the fused
     accumulator are disjoint, so the result equals the monolithic all-reduce element for element."""
     import torch
     import torch.distributed as dist
     engine.epoch_accumulate_begin(sigma, eta, neigh_f64)
+    if monitored:
+        engine.epoch_measure_rows()                    # the search is done; the blocks below do not touch the rows
     t = engine.accum_tensor()
     nb = engine.epoch_block_count()
     stream_ordered = t.is_cuda and dist.get_backend() == "nccl"
@@ -164,6 +166,8 @@ def _epoch_overlapped(engine, sigma, eta, neigh_f64):
                 torch.cuda.current_stream(t.device).synchronize()
     if stream_ordered:
         ext.wait_stream(comm)                          # the merge queued next waits for the last collective
+    if monitored:
+        engine.epoch_measure_shift()                   # every block is reduced: the accumulator is final
     engine.epoch_merge()
 
 
@@ -181,8 +185,60 @@ def _native_comm(engine, rank, world):
     engine.comm_init(world, rank, ids[0])
 
 
-def epoch(engine, sigma, eta, neigh_f64, chunks=None):
-    """One data-parallel epoch on this rank's shard (resident rows, or `chunks` streamed through)."""
+def _allreduce_row_sums(engine, m, world):
+    """The four row sums of a monitored epoch added over the ranks, as one small float64 tensor (counts below 2^53 are exact in
+    it): every rank then holds the same record.  `changed` is unknown (-1) on every rank at once -- the first measured epoch
+    after the rows were set, and streamed epochs -- and stays so."""
+    if world == 1:
+        return
+    import torch
+    import torch.distributed as dist
+    dev = torch.device("cuda", engine.device) if dist.get_backend() == "nccl" else torch.device("cpu")
+    known = m["changed"] >= 0
+    t = torch.tensor([m["sum_wd"], m["sum_w"], float(m["rows"]), float(max(m["changed"], 0))], dtype=torch.float64, device=dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    wd, w, rows, changed = t.tolist()
+    m.update(sum_wd=wd, sum_w=w, rows=int(rows), changed=int(changed) if known else -1)
+
+
+def _epoch_monitored(engine, sigma, eta, neigh_f64, chunks, metrics):
+    """`epoch` in its three-call form on every path, with the monitor's two launches in it:
+    accumulate -> measure_rows -> all-reduce -> measure_shift -> merge -> ONE read-back, after the merge is queued."""
+    rank, world = dist_info()
+    multi = world > 1 or bool(os.environ.get("SOM_FORCE_ALLREDUCE"))
+    native = os.environ.get("SOM_COMM") == "native" and hasattr(engine, "comm_init") and multi
+    if native:
+        _native_comm(engine, rank, world)
+    if chunks is None and not native and multi and _overlap_wanted(engine, world):
+        _epoch_overlapped(engine, sigma, eta, neigh_f64, monitored=True)
+    else:
+        if chunks is None:
+            engine.epoch_accumulate(sigma, eta, neigh_f64)
+            engine.epoch_measure_rows()
+        else:
+            engine.stream_epoch_accumulate(chunks, sigma, eta, neigh_f64)   # (every chunk measured behind its search)
+        if native:
+            engine.epoch_allreduce()
+        else:
+            allreduce_accumulator(engine)
+        engine.epoch_measure_shift()
+        engine.epoch_merge()
+    m = engine.epoch_metrics()
+    _allreduce_row_sums(engine, m, world)
+    metrics.update(m)
+
+
+def epoch(engine, sigma, eta, neigh_f64, chunks=None, metrics=None):
+    """One data-parallel epoch on this rank's shard (resident rows, or `chunks` streamed through).
+
+    `metrics`: a dict to fill with the training monitor's record of the epoch (the engine's monitor must be on:
+    `engine.monitor(True)`) -- sum_wd, sum_w, rows, changed (-1: unknown), shift_sumsq, shift_max as
+    include/somhip.h defines them, the four row sums added over the ranks, so that every rank holds the same values.  The
+    monitored epoch costs two small launches, one host synchronisation (the read-back, after the merge is queued) and, under a
+    process group, one collective of four doubles.  Under SOM_COMM=native it runs accumulate / all-reduce / merge as three calls
+    and so loses the library's blockwise overlap of the all-reduce with the transform while it is monitored."""
+    if metrics is not None:
+        return _epoch_monitored(engine, sigma, eta, neigh_f64, chunks, metrics)
     rank, world = dist_info()
     if os.environ.get("SOM_COMM") == "native" and hasattr(engine, "comm_init") and \
             (world > 1 or os.environ.get("SOM_FORCE_ALLREDUCE")):

@@ -42,6 +42,7 @@ class HipEngine:
             raise SomHipError(self._lib.som_last_error(None).decode())
         self._h = h
         self.has_comm = False
+        self.monitoring = False
         self.device = int(device)
         self.precision = precision
         self.missing = missing
@@ -378,6 +379,31 @@ class HipEngine:
         out, ptrs = self._unit_stats_out()
         self._check(self._lib.som_unit_stats_device(self._h, C.c_void_p(dev_ptr), int(n_rows), *ptrs))
         return out
+
+    # -- training monitor (include/somhip.h, som_monitor / som_epoch_measure_* / som_epoch_metrics) --
+    def monitor(self, on=True):
+        """Switch the training monitor on (the engine keeps every measured epoch's BMU ids beside the resident rows) or off
+        (frees them).  While it is off nothing is launched or allocated for it."""
+        self._check(self._lib.som_monitor(self._h, int(bool(on))))
+        self.monitoring = bool(on)
+
+    def epoch_measure_rows(self):
+        """Queue the row metrics of the resident rows under this epoch's own BMUs: after any epoch_accumulate* form, before
+        the next search."""
+        self._check(self._lib.som_epoch_measure_rows(self._h))
+
+    def epoch_measure_shift(self):
+        """Queue the codebook shift the merge is about to make: the accumulator must be final (after the all-reduce, or the
+        last staged block), before epoch_merge."""
+        self._check(self._lib.som_epoch_measure_shift(self._h))
+
+    def epoch_metrics(self):
+        """The one blocking read-back: a dict of sum_wd, sum_w, shift_sumsq (float), rows, changed (int; -1 = unknown) and
+        shift_max (float)."""
+        m = _lib.EpochMetrics()
+        self._check(self._lib.som_epoch_metrics(self._h, C.byref(m)))
+        return {"sum_wd": m.sum_wd, "sum_w": m.sum_w, "shift_sumsq": m.shift_sumsq, "rows": int(m.rows),
+                "changed": int(m.changed), "shift_max": float(m.shift_max)}
 
     def set_verify(self, n_rows):
         """The canary: re-score `n_rows` strided rows of every BMU launch with the float32 kernel (0 = off)."""

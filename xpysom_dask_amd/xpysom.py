@@ -8,7 +8,7 @@ formatting, pickling -- and hands everything below ``_update``/``_winner``/``_me
 to libsomhip through ctypes.  There is no ``xp=`` dispatch and no CPU path: without the HIP
 library (or a GPU) the compute methods raise.
 """
-from collections import Counter, defaultdict
+from collections import Counter, defaultdict, namedtuple
 from warnings import warn
 
 import numpy as np
@@ -159,6 +159,40 @@ def units_adjacent(b1, b2, X, Y, topology):
     if topology == 'toroidal':
         di, dj = np.minimum(di, X - di), np.minimum(dj, Y - dj)
     return ~((di > 1) | (dj > 1))
+
+
+EpochRecord = namedtuple('EpochRecord', ['iteration', 'sigma', 'learning_rate', 'quantization_error', 'rows', 'weight',
+                                         'bmu_changed', 'codebook_shift', 'codebook_shift_max'])
+EpochRecord.__doc__ = """What a monitored epoch of ``XPySom.train`` / ``train_streaming`` appends to ``XPySom.history``: plain Python
+numbers.  The epoch ran with codebook W_t and produced W_t+1.
+  iteration, sigma, learning_rate   what the epoch was run with
+  quantization_error   sum_n w_n d_n / sum_n w_n over the rows of weight > 0 (all rows, w_n = 1, without sample weights): d_n the
+                       float32 Euclidean distance of row n to W_t[b_n], b_n the BMU the epoch's OWN search found under the
+                       configured distance and precision; with missing='nan' over the observed features.  NaN when the weights
+                       sum to 0 (no rows).  Not ``quantization_error(data)`` bit for bit: that call searches under the sqrt'd
+                       Euclidean distance (ties can fall differently), and under the cosine, Manhattan and norm_p distances the
+                       epoch's unit is a different unit altogether
+  rows, weight         rows measured (weight > 0) and the sum of their weights, over all ranks
+  bmu_changed          rows whose BMU differs from the previous monitored epoch's over the same resident rows; None for the first
+                       monitored epoch of a ``train`` call and for every streamed epoch
+  codebook_shift       sqrt(sum (W_t+1 - W_t)^2) over all units and features; codebook_shift_max the largest |W_t+1 - W_t|"""
+
+
+def _check_monitor(monitor, callback):
+    """``train``'s ``monitor`` / ``callback`` validated before any engine exists; returns whether the schedule is monitored."""
+    if not isinstance(monitor, (bool, np.bool_)):
+        raise TypeError('monitor must be a bool, got %r' % (monitor,))
+    if callback is not None and not callable(callback):
+        raise TypeError('callback must be callable or None, got %r' % (callback,))
+    return bool(monitor) or callback is not None
+
+
+def _epoch_record(iteration, sig, eta, m):
+    """The EpochRecord of one monitored epoch from the metrics ``distributed.epoch`` filled in."""
+    qe = m['sum_wd'] / m['sum_w'] if m['sum_w'] != 0 else float('nan')
+    return EpochRecord(int(iteration), float(sig), float(eta), float(qe), int(m['rows']), float(m['sum_w']),
+                       int(m['changed']) if m['changed'] >= 0 else None, float(np.sqrt(m['shift_sumsq'])),
+                       float(m['shift_max']))
 
 
 class UnitStatistics:
@@ -329,6 +363,7 @@ class XPySom:
             raise ValueError("shard must be one of %s" % ", ".join(_dist.SHARDS))
         self._shard = shard
         self._engine_obj = None
+        self.history = []                    # EpochRecords of the monitored epochs so far (train(..., monitor=True)); never cleared here
 
     # ------------------------------------------------------------------ engine plumbing
     def _engine(self):
@@ -448,7 +483,8 @@ class XPySom:
             raise ValueError(msg)
 
     # ------------------------------------------------------------------ training
-    def train(self, data, num_epochs, iter_beg=0, iter_end=None, verbose=False, *, sample_weight=None):
+    def train(self, data, num_epochs, iter_beg=0, iter_end=None, verbose=False, *, sample_weight=None, monitor=False,
+              callback=None):
         """Trains the SOM (batch algorithm); same contract as xpysom.py:458-594.
 
         ``sample_weight`` (keyword-only; not in the reference) gives the rows unequal importance: one finite value >= 0
@@ -458,12 +494,21 @@ class XPySom:
         device.  Under a process group the weights are cut like the rows.  An argument of this call, not state: a later
         ``train`` without it is unweighted.
 
+        ``monitor=True`` (keyword-only; not in the reference) appends an ``EpochRecord`` per epoch to ``self.history`` (a plain
+        list the library never clears): the epoch's quantization error under its own BMUs, how many rows changed BMU, how far
+        the codebook moved -- measured on the device from what the epoch itself left there, for two small launches and one
+        host synchronisation per epoch; the trained codebook is the unmonitored one bit for bit.  ``callback(record)`` (implies
+        ``monitor``) runs after each epoch's merge; a truthy return ends the schedule there, with the codebook and the records
+        of the epochs that completed.  Under a process group every rank holds the same record, so a callback that is a pure
+        function of the record stops every rank at the same epoch.
+
         ``iter_beg``/``iter_end`` resume the schedule mid-run (decays are pure functions of
         (iteration, num_epochs)).  Under an initialised torch.distributed group the rows are
         sharded contiguously over the ranks and the per-epoch numerator/denominator are
         all-reduced before the merge.  Returns ``self``; ``_weights`` is float32 afterwards."""
         if iter_end is None:
             iter_end = num_epochs
+        monitored = _check_monitor(monitor, callback)    # (refused before an engine exists)
 
         rank, world = _dist.dist_info()
         on_device = _device_rows(data) is not None
@@ -503,6 +548,10 @@ class XPySom:
             eng.set_sample_weights_device(wptr, eng.n_rows, keepalive=wowner)
         elif weights is not None:
             eng.set_sample_weights(weights)
+        if monitored:
+            eng.monitor(True)
+        elif getattr(eng, 'monitoring', False):          # an earlier monitored call's: an unmonitored schedule launches nothing for it
+            eng.monitor(False)
 
         try:
             for iteration in range(iter_beg, iter_end):
@@ -512,10 +561,18 @@ class XPySom:
                 # NumPy >= 2: a numpy scalar sigma makes the reference's neighbourhood float64
                 neigh_f64 = isinstance(sig, np.generic)
                 self._check_sigma(sig)
-                _dist.epoch(eng, sig, eta, neigh_f64)
+                if monitored:
+                    m = {}
+                    _dist.epoch(eng, sig, eta, neigh_f64, metrics=m)
+                    record = _epoch_record(iteration, sig, eta, m)
+                    self.history.append(record)
+                else:
+                    _dist.epoch(eng, sig, eta, neigh_f64)
                 if verbose:
                     print('\r [ %d / %d ] %3.0f%%' % (iteration + 1, num_epochs, 100 * (iteration + 1) / num_epochs),
                           end='')
+                if callback is not None and callback(record):
+                    break
         finally:
             # also on the way out of an exception (mexican_hat's ZeroDivisionError at sigma 0): the object holds
             # the codebook of the epochs that completed, as the reference's does
@@ -533,7 +590,7 @@ class XPySom:
                 and 2 * self._std_coeff ** 2 * sig ** 2 == 0:    # d, associated as neighborhoods.py:59 writes it
             raise ZeroDivisionError('float division by zero')
 
-    def train_streaming(self, chunks, num_epochs, iter_beg=0, iter_end=None):
+    def train_streaming(self, chunks, num_epochs, iter_beg=0, iter_end=None, *, monitor=False, callback=None):
         """``train`` for data that does not stay resident in HBM (or in host memory as one array).
 
         ``chunks`` is a callable returning a fresh iterable of ``(n_i, input_len)`` row blocks for each
@@ -541,16 +598,32 @@ class XPySom:
         (xpysom.py:545-556).  A block may also be a ``(rows, weights)`` pair with one sample weight per row
         (``train``'s ``sample_weight``); an epoch's blocks are all of one form or all of the other (``ValueError``).  Every block goes host -> HBM, through the BMU kernel and into the same
         segment sums; the epoch ends with the usual transform, all-reduce and merge.  Under a process
-        group each rank streams its own blocks."""
+        group each rank streams its own blocks.
+
+        ``monitor`` and ``callback`` as in ``train``: every block is measured behind its own BMU search, an epoch's sums are
+        added in block order; ``bmu_changed`` is always None (no rows stay to compare)."""
         if iter_end is None:
             iter_end = num_epochs
+        monitored = _check_monitor(monitor, callback)
         eng = self._upload_weights()
+        if monitored:
+            eng.monitor(True)
+        elif getattr(eng, 'monitoring', False):          # an earlier monitored call's: an unmonitored schedule launches nothing for it
+            eng.monitor(False)
         try:
             for iteration in range(iter_beg, iter_end):
                 eta = self._decay_function(self._learning_rate, self._learning_rateN, iteration, num_epochs)
                 sig = self._decay_function(self._sigma, self._sigmaN, iteration, num_epochs)
                 self._check_sigma(sig)
-                _dist.epoch(eng, sig, eta, isinstance(sig, np.generic), chunks=chunks())
+                if monitored:
+                    m = {}
+                    _dist.epoch(eng, sig, eta, isinstance(sig, np.generic), chunks=chunks(), metrics=m)
+                    record = _epoch_record(iteration, sig, eta, m)
+                    self.history.append(record)
+                    if callback is not None and callback(record):
+                        break
+                else:
+                    _dist.epoch(eng, sig, eta, isinstance(sig, np.generic), chunks=chunks())
         finally:
             self._weights = eng.get_weights().reshape(self._weights.shape)
         return self
@@ -811,3 +884,4 @@ class XPySom:
     def __setstate__(self, state):
         self.__dict__.update(state)
         self.__dict__.setdefault('_missing', None)        # (a pickle from before the keyword)
+        self.__dict__.setdefault('history', [])
