@@ -34,3 +34,12 @@ for decay in ("linear", "exponential"):
     print("%-12s first five winners: %s" % (decay, wins[:5]))
     hits = som.activation_response(data)
     print("%-12s busiest unit holds %d of 150 samples; %d of 36 units win at least one" % (decay, hits.max(), (hits > 0).sum()))
+    # the label map: iris.csv lists 50 setosa, 50 versicolor, 50 virginica in that order (class codes 0, 1, 2)
+    species = np.repeat(np.arange(3), 50)
+    counts = som.label_counts(data, species)                # (6, 6, 3): how many samples of each species every unit wins
+    print("%-12s label map (majority species per unit, . = no sample):" % decay)
+    for row in np.where(counts.sum(axis=2) > 0, counts.argmax(axis=2), -1):
+        print("%-12s   %s" % ("", " ".join("." if c < 0 else str(c) for c in row)))
+    print("%-12s classify on the training samples: accuracy %.3f" % (decay, (som.classify(data, counts) == species).mean()))
+    petal = som.unit_means(data, raw[:, 2])                 # a component plane: the mean raw petal length per unit
+    print("%-12s mean petal length per unit: %.2f ... %.2f cm" % (decay, np.nanmin(petal.mean), np.nanmax(petal.mean)))

@@ -313,6 +313,25 @@ int som_bmu_distances(som_handle* h, const float* x_host, int64_t n_rows, int32_
 int som_bmu_distances_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids_out, float* dist_out);
 int som_unit_stats(som_handle* h, const float* x_host, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max);
 int som_unit_stats_device(som_handle* h, const void* x_dev, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max);
+/* Label and value maps (not in the reference): what the rows a unit wins carry -- class labels, or columns of numbers the map was
+ * not trained on.  a_n = the unit som_bmu(ACTIVATION) names for row n on this handle: the configured distance and precision
+ * (SOM_MISSING_NAN: the masked search), the ids XPySom.predict / labels_map use -- not b_n above.  Outputs are host arrays
+ * [K][C] with K = x * y, k = i * y + j; none may be NULL; n_rows == 0 writes zeros.
+ * som_unit_label_counts*: labels [n_rows] int32 class codes, C = n_classes:
+ *   counts[k][c] = #{n : a_n = k and labels[n] = c}      a label outside [0, C) (-1 by convention) is "unlabelled": counted nowhere
+ * som_unit_value_sums*: values [n_rows][C] float32, row-major, C = n_cols; a NaN is "not observed" for that column only (whatever
+ * the handle's missing mode), +-Inf is a value:
+ *   count[k][c] = #{n : a_n = k, values[n][c] not NaN}   sum[k][c], sumsq[k][c] = the sums of those values and of their squares, in
+ *   double (a float32 and its square are exact in double).  The mean of column c in unit k is sum / count; the raw quantities add
+ *   across shards and ranks (each call reports the rows it was given).
+ * Integer counts; the sums without atomics, over a unit's rows in an order that is a function of the unit's row count and C alone
+ * (csrc/project.hpp): two calls on the same rows, and the host and the device entry point on the same rows, return the same bits.
+ * Refused: a NULL argument with n_rows > 0, n_rows < 0 or > 2^31-1, C < 1 or > 4096, K * C > 2^26.
+ * The *_device forms read rows, labels and values that already live in HBM (see som_bmu_device: borrowed for the call). */
+int som_unit_label_counts(som_handle* h, const float* x_host, const int32_t* labels_host, int64_t n_rows, int32_t n_classes, int64_t* counts);
+int som_unit_label_counts_device(som_handle* h, const void* x_dev, const void* labels_dev, int64_t n_rows, int32_t n_classes, int64_t* counts);
+int som_unit_value_sums(som_handle* h, const float* x_host, const float* v_host, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq);
+int som_unit_value_sums_device(som_handle* h, const void* x_dev, const void* v_dev, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq);
 
 /* Training monitor (not in the reference): what an epoch did, measured from what the epoch itself left on the device -- the rows,
  * this epoch's BMU ids, the codebook W_t the epoch ran with (unchanged until som_epoch_merge) and the final accumulator.  No

@@ -1,4 +1,4 @@
 """MI355X-native batch-SOM engine behind the XPySom class surface of jcfaracco/xpysom-dask."""
-from .xpysom import EpochRecord, UnitStatistics, XPySom
+from .xpysom import EpochRecord, UnitMeans, UnitStatistics, XPySom
 
-__all__ = ["XPySom", "UnitStatistics", "EpochRecord"]
+__all__ = ["XPySom", "UnitStatistics", "UnitMeans", "EpochRecord"]

@@ -86,6 +86,11 @@ SIGNATURES = {
     "som_bmu_distances_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _I, _F]),
     "som_unit_stats": (C.c_int, [_H, _F, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
     "som_unit_stats_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
+    "som_unit_label_counts": (C.c_int, [_H, _F, _I, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "som_unit_label_counts_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "som_unit_value_sums": (C.c_int, [_H, _F, _F, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "som_unit_value_sums_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double)]),
     "som_monitor": (C.c_int, [_H, C.c_int32]),
     "som_epoch_measure_rows": (C.c_int, [_H]),
     "som_epoch_measure_shift": (C.c_int, [_H]),

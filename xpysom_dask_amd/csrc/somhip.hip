@@ -37,6 +37,7 @@
 #include "update.hpp"
 #include "diag.hpp"
 #include "monitor.hpp"
+#include "project.hpp"
 
 using namespace somhip;
 
@@ -131,6 +132,11 @@ struct RowSet {
         DevBuf<long long> count;                 // [K]
         DevBuf<double> sums;                     // [2 K] sum | sum of squares
         DevBuf<float> max;                       // [K]
+        // label and value maps (project.hpp): the host entry points' labels and values beside the rows, the [K][C] results
+        DevBuf<int> labels;                      // [cap]
+        DevBuf<float> values;                    // [cap][C]
+        DevBuf<long long> pcount;                // [K][C]
+        DevBuf<double> psums;                    // [2][K][C] sum | sum of squares
     } diag;
     bool resident() const { return kind == rowset::Kind::Resident; }
     // precision 'exact': the rows' measured operand rounding errors (bmu_exact.hpp) live in the second half of xsq.  The only place that knows.
@@ -2659,6 +2665,87 @@ int query_unit_stats(som_handle* h, const std::string& who, const float* x_host,
     if (int rc = d2h_blocking(h, sumsq, g.sums + K, K * sizeof(double))) return rc;
     return d2h_blocking(h, max, g.max, K * sizeof(float));
 }
+
+// ---- label and value maps (project.hpp): what the rows a unit wins under the ACTIVATION search carry ----
+// the checks the four entry points share; `what` names the column count in the messages
+int project_check(som_handle* h, const std::string& who, const char* what, bool null_arg, int64_t n_rows, int32_t C) {
+    if (!h || null_arg || n_rows < 0) return fail(h, who + ": bad argument");
+    if (C < 1 || C > 4096) return fail(h, who + ": " + what + " must be between 1 and 4096");
+    if ((int64_t)h->K * C > (1L << 26)) return fail(h, who + ": x * y * " + what + " exceeds 2^26 (analysis call: fewer columns at a time)");
+    if (n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    return 0;
+}
+// the query set's rows are on the device: their units under the configured distance (som_bmu ACTIVATION's own steps), the rows
+// sorted by unit and every segment's start -- in diag_reserve_stats's buffers, which som_unit_stats* shares
+int project_segments(som_handle* h) {
+    RowSet& q = h->q; auto& g = q.diag;
+    if (int rc = diag_reserve_stats(h, q)) return rc;
+    if (int rc = prepare(h, q, needs_xsq(h))) return rc;
+    if (int rc = run_activation_bmu(h, q.view())) return rc;
+    Timed t(h, SOM_K_SEGSUM);                                           // (the sort by unit; the caller's reduction joins it)
+    int bits = 1;
+    while ((1L << bits) < h->K) ++bits;
+    if (int rc = sort_rows_by_unit(h, q.bmu, q.N, bits, g.skey, g.srow, g.tmp, g.cs_table, g.cs_blocks)) return rc;
+    HIPCHK(h, hipMemsetAsync(g.start, 0xff, (size_t)h->K * sizeof(int), h->stream));       // -1: the unit has no rows
+    unit_heads_kernel<<<dim3((unsigned)cdiv(q.N, 256)), dim3(256), 0, h->stream>>>(g.skey, q.N, h->K, g.start);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int query_unit_label_counts(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, const void* labels,
+                            int64_t n_rows, int32_t n_classes, int64_t* counts) {
+    DeviceGuard dev_guard(h);
+    if (int rc = project_check(h, who, "n_classes", !counts || (n_rows > 0 && ((!x_host && !x_dev) || !labels)), n_rows, n_classes)) return rc;
+    const size_t KC = (size_t)h->K * n_classes;
+    if (n_rows == 0) { std::memset(counts, 0, KC * sizeof(int64_t)); return 0; }
+    if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
+    RowSet& q = h->q; auto& g = q.diag;
+    if (int rc = g.pcount.reserve(h, KC)) return rc;
+    const int* lab = (const int*)labels;
+    if (x_host) {
+        if (int rc = g.labels.reserve(h, (size_t)q.cap)) return rc;
+        if (int rc = h2d_blocking(h, g.labels, labels, (size_t)n_rows * sizeof(int))) return rc;
+        lab = g.labels;
+    }
+    if (int rc = project_segments(h)) return rc;
+    {
+        Timed t(h, SOM_K_SEGSUM);
+        unit_label_counts_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(g.start, g.skey, g.srow, lab, q.N, h->K,
+                                                                                            n_classes, g.pcount);
+        HIPCHK(h, hipGetLastError());
+    }
+    static_assert(sizeof(long long) == sizeof(int64_t), "the per-unit counts are copied out as int64_t");
+    return d2h_blocking(h, counts, g.pcount, KC * sizeof(int64_t));
+}
+int query_unit_value_sums(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, const void* values,
+                          int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq) {
+    DeviceGuard dev_guard(h);
+    if (int rc = project_check(h, who, "n_cols", !count || !sum || !sumsq || (n_rows > 0 && ((!x_host && !x_dev) || !values)), n_rows, n_cols)) return rc;
+    const size_t KC = (size_t)h->K * n_cols;
+    if (n_rows == 0) {
+        std::memset(count, 0, KC * sizeof(int64_t)); std::memset(sum, 0, KC * sizeof(double)); std::memset(sumsq, 0, KC * sizeof(double));
+        return 0;
+    }
+    if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
+    RowSet& q = h->q; auto& g = q.diag;
+    if (int rc = g.pcount.reserve(h, KC)) return rc;
+    if (int rc = g.psums.reserve(h, 2 * KC)) return rc;
+    const float* val = (const float*)values;
+    if (x_host) {
+        if (int rc = g.values.reserve(h, (size_t)q.cap * n_cols)) return rc;
+        if (int rc = h2d_blocking(h, g.values, values, (size_t)n_rows * n_cols * sizeof(float))) return rc;
+        val = g.values;
+    }
+    if (int rc = project_segments(h)) return rc;
+    {
+        Timed t(h, SOM_K_SEGSUM);
+        unit_value_sums_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(g.start, g.skey, g.srow, val, q.N, h->K, n_cols,
+                                                                                          g.pcount, g.psums, g.psums + KC);
+        HIPCHK(h, hipGetLastError());
+    }
+    if (int rc = d2h_blocking(h, count, g.pcount, KC * sizeof(int64_t))) return rc;
+    if (int rc = d2h_blocking(h, sum, g.psums, KC * sizeof(double))) return rc;
+    return d2h_blocking(h, sumsq, g.psums + KC, KC * sizeof(double));
+}
 }  // namespace
 
 int som_bmu(som_handle* h, const float* x_host, int64_t n_rows, int32_t mode, int32_t* ids_out) { return query_bmu(h, "som_bmu", x_host, nullptr, n_rows, mode, ids_out); }
@@ -2671,6 +2758,10 @@ int som_bmu_distances(som_handle* h, const float* x_host, int64_t n_rows, int32_
 int som_bmu_distances_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids_out, float* dist_out) { return query_bmu_distances(h, "som_bmu_distances_device", nullptr, x_dev, n_rows, ids_out, dist_out); }
 int som_unit_stats(som_handle* h, const float* x_host, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max) { return query_unit_stats(h, "som_unit_stats", x_host, nullptr, n_rows, count, sum, sumsq, max); }
 int som_unit_stats_device(som_handle* h, const void* x_dev, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max) { return query_unit_stats(h, "som_unit_stats_device", nullptr, x_dev, n_rows, count, sum, sumsq, max); }
+int som_unit_label_counts(som_handle* h, const float* x_host, const int32_t* labels_host, int64_t n_rows, int32_t n_classes, int64_t* counts) { return query_unit_label_counts(h, "som_unit_label_counts", x_host, nullptr, labels_host, n_rows, n_classes, counts); }
+int som_unit_label_counts_device(som_handle* h, const void* x_dev, const void* labels_dev, int64_t n_rows, int32_t n_classes, int64_t* counts) { return query_unit_label_counts(h, "som_unit_label_counts_device", nullptr, x_dev, labels_dev, n_rows, n_classes, counts); }
+int som_unit_value_sums(som_handle* h, const float* x_host, const float* v_host, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq) { return query_unit_value_sums(h, "som_unit_value_sums", x_host, nullptr, v_host, n_rows, n_cols, count, sum, sumsq); }
+int som_unit_value_sums_device(som_handle* h, const void* x_dev, const void* v_dev, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq) { return query_unit_value_sums(h, "som_unit_value_sums_device", nullptr, x_dev, v_dev, n_rows, n_cols, count, sum, sumsq); }
 
 int som_bmu_f64(som_handle* h, const double* x_host, int64_t n_rows, int32_t* ids_out) {
     DeviceGuard dev_guard(h);

@@ -380,6 +380,62 @@ class HipEngine:
         self._check(self._lib.som_unit_stats_device(self._h, C.c_void_p(dev_ptr), int(n_rows), *ptrs))
         return out
 
+    # -- label and value maps (include/somhip.h, som_unit_label_counts / som_unit_value_sums) --
+    def _check_columns(self, what, n):
+        n = int(n)
+        if not 1 <= n <= 4096:
+            raise ValueError("%s must be between 1 and 4096, got %d" % (what, n))
+        return n
+
+    def _value_sums_out(self, n_cols):
+        out = (np.empty((self.K, n_cols), dtype=np.int64), np.empty((self.K, n_cols), dtype=np.float64),
+               np.empty((self.K, n_cols), dtype=np.float64))
+        d = C.POINTER(C.c_double)
+        return out, (out[0].ctypes.data_as(C.POINTER(C.c_int64)), out[1].ctypes.data_as(d), out[2].ctypes.data_as(d))
+
+    def label_counts(self, x, labels, n_classes):
+        """int64 (K, n_classes): per unit, how many of the rows it wins under the configured distance (the ids of bmu(x)) carry
+        each class code of `labels` (one int32 per row); a code outside [0, n_classes) is unlabelled and counted nowhere."""
+        x = self._rows_arg(x)
+        n_classes = self._check_columns("n_classes", n_classes)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.shape != (x.shape[0],):
+            raise ValueError("labels must have one value per row, got %r for %d rows" % (labels.shape, x.shape[0]))
+        out = np.empty((self.K, n_classes), dtype=np.int64)
+        self._check(self._lib.som_unit_label_counts(self._h, self._fp(x), self._ip(labels), x.shape[0], n_classes,
+                                                    out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def label_counts_device(self, dev_ptr, labels_ptr, n_rows, n_classes):
+        """label_counts of float32 rows and int32 labels that already live in HBM (`dev_ptr`: [n_rows][D], `labels_ptr`:
+        [n_rows]; both borrowed for the call)."""
+        n_classes = self._check_columns("n_classes", n_classes)
+        out = np.empty((self.K, n_classes), dtype=np.int64)
+        self._check(self._lib.som_unit_label_counts_device(self._h, C.c_void_p(dev_ptr), C.c_void_p(labels_ptr), int(n_rows), n_classes,
+                                                           out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def value_sums(self, x, values):
+        """(count int64, sum float64, sumsq float64), (K, n_cols) each: per unit and column of `values` ((n, n_cols) float32),
+        over the rows the unit wins under the configured distance whose value in the column is not NaN.  Deterministic: the
+        same rows give the same bits."""
+        x = self._rows_arg(x)
+        values = _f32(values)
+        if values.ndim != 2 or values.shape[0] != x.shape[0]:
+            raise ValueError("values must be (%d, n_cols), got %r" % (x.shape[0], values.shape))
+        n_cols = self._check_columns("n_cols", values.shape[1])
+        out, ptrs = self._value_sums_out(n_cols)
+        self._check(self._lib.som_unit_value_sums(self._h, self._fp(x), self._fp(values), x.shape[0], n_cols, *ptrs))
+        return out
+
+    def value_sums_device(self, dev_ptr, values_ptr, n_rows, n_cols):
+        """value_sums of float32 rows and values that already live in HBM (`dev_ptr`: [n_rows][D], `values_ptr`:
+        [n_rows][n_cols]; both borrowed for the call)."""
+        n_cols = self._check_columns("n_cols", n_cols)
+        out, ptrs = self._value_sums_out(n_cols)
+        self._check(self._lib.som_unit_value_sums_device(self._h, C.c_void_p(dev_ptr), C.c_void_p(values_ptr), int(n_rows), n_cols, *ptrs))
+        return out
+
     # -- training monitor (include/somhip.h, som_monitor / som_epoch_measure_* / som_epoch_metrics) --
     def monitor(self, on=True):
         """Switch the training monitor on (the engine keeps every measured epoch's BMU ids beside the resident rows) or off

@@ -62,6 +62,12 @@ def _n_rows(data):
     return int(shape[0]) if shape is not None and len(shape) > 0 else len(data)
 
 
+def _n_shape(a):
+    """Shape of a device array without touching it."""
+    shape = getattr(a, "shape", None)
+    return tuple(shape) if shape is not None else tuple(a.__cuda_array_interface__["shape"])
+
+
 def _is_device_array(a):
     if type(a).__module__.split(".")[0] == "torch":
         return bool(getattr(a, "is_cuda", False))
@@ -220,6 +226,55 @@ class UnitStatistics:
 
     def __repr__(self):
         return "UnitStatistics(%d x %d units, %d samples)" % (self.hits.shape + (int(self.hits.sum()),))
+
+
+class UnitMeans:
+    """What ``XPySom.unit_means`` returns: per unit of an ``(x, y)`` map and column of the values, over the samples the unit
+    wins whose value in the column is not NaN, ``count`` (int64), ``sum`` and ``sumsq`` (float64), ``(x, y, n_cols)`` arrays.
+    They are the raw additive quantities: shards or ranks add them and derive ``mean`` and ``std`` afterwards."""
+
+    def __init__(self, count, sum, sumsq):
+        self.count, self.sum, self.sumsq = count, sum, sumsq
+
+    @property
+    def mean(self):
+        """Mean of every column per unit, the component plane of a variable the map was not trained on; NaN where the unit
+        observed no value of the column."""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.where(self.count == 0, np.nan, self.sum / self.count)
+
+    @property
+    def std(self):
+        """Population standard deviation per unit and column, sqrt(max(sumsq / count - mean^2, 0)); NaN where the unit
+        observed no value of the column."""
+        with np.errstate(divide='ignore', invalid='ignore'):
+            var = self.sumsq / self.count - self.mean ** 2
+            return np.where(self.count == 0, np.nan, np.sqrt(np.maximum(var, 0.0)))
+
+    def __repr__(self):
+        return "UnitMeans(%d x %d units, %d columns)" % self.count.shape
+
+
+def _device_column(a, dtype_name, typestr):
+    """(pointer, shape, device_index, owner, stream) of labels or values that live in HBM next to device rows, as a contiguous
+    array of the dtype the engine reads (see _device_rows)."""
+    if type(a).__module__.split(".")[0] == "torch":
+        import torch
+        t, want = a.detach(), getattr(torch, dtype_name)
+        if t.dtype != want or not t.is_contiguous():
+            t = t.to(want).contiguous()
+        torch.cuda.current_stream(t.device).synchronize()
+        return t.data_ptr(), tuple(t.shape), t.device.index, t, "done"
+    cai = a.__cuda_array_interface__
+    if cai["typestr"] != typestr or cai.get("strides") is not None:
+        raise ValueError('device %s must be a C-contiguous %s array' % ('labels' if dtype_name == 'int32' else 'values', dtype_name))
+    return int(cai["data"][0]), tuple(cai["shape"]), None, a, cai.get("stream")
+
+
+def _to_device(host, device_index):
+    """A host array copied next to device rows (torch is the plumbing for device memory here)."""
+    import torch
+    return torch.from_numpy(host).to(torch.device("cuda", device_index))
 
 
 class XPySom:
@@ -774,6 +829,137 @@ class XPySom:
             sq += s2
             mx = np.maximum(mx, m)
         return UnitStatistics(hits.reshape(X, Y), tot.reshape(X, Y), sq.reshape(X, Y), mx.reshape(X, Y))
+
+    def _column_query(self, eng, col, what, dtype_name, typestr, host):
+        """(pointer, owner) of the labels or values that go with device rows: a device array is read where it is (its
+        producer waited for), the checked host array `host` is copied next to the rows."""
+        if host is not None:
+            owner = _to_device(host, eng.device)
+            return owner.data_ptr(), owner
+        ptr, _shape, dev_index, owner, stream = _device_column(col, dtype_name, typestr)
+        if dev_index is not None and dev_index != eng.device:
+            raise ValueError('device %s live on cuda:%d, the engine on cuda:%d' % (what, dev_index, eng.device))
+        if stream != "done":
+            eng.sync_producer(stream)
+        return ptr, owner
+
+    def label_counts(self, data, labels, n_classes=None):
+        """The label map as an array: int64 ``(x, y, n_classes)``, element ``[i, j, c]`` the number of samples whose best
+        matching unit is ``(i, j)`` (the units of ``predict`` / ``labels_map``: the configured distance) and whose label is
+        ``c`` -- ``labels_map``'s Counters, counted on the device.  ``labels`` holds one integer class code per sample: a
+        host array-like, or for rows in HBM a 1-D device int32 tensor next to them (a host array is copied there); any
+        negative code means unlabelled and is counted nowhere.  ``n_classes`` defaults to ``max(labels) + 1`` and is required
+        for device labels (codes ``>= n_classes`` there are counted nowhere); host codes ``>= n_classes`` raise
+        ``ValueError``.  Rows in HBM go whole; host rows in ``n_parallel`` chunks whose counts are added on the host.  No
+        sample weights, no neighbourhood smoothing, no cross-rank reduction: each rank reports its own rows, and the counts
+        add."""
+        eng, q, data = self._diag_query(data)
+        X, Y = self._weights.shape[:2]
+        n = q[2] if q is not None else len(data)
+        lab32 = None
+        if n_classes is not None:
+            if isinstance(n_classes, (bool, np.bool_)) or int(n_classes) != n_classes or not 1 <= n_classes <= 4096:
+                raise ValueError('n_classes must be an integer between 1 and 4096, got %r' % (n_classes,))
+            n_classes = int(n_classes)
+        if _is_device_array(labels):
+            if q is None:
+                raise ValueError('labels in device memory need data in device memory')
+            if n_classes is None:
+                raise ValueError('n_classes is required for labels in device memory')
+            if tuple(_n_shape(labels)) != (n,):
+                raise ValueError('data and labels must have the same length.')
+        else:
+            lab = np.asarray(labels)
+            if lab.ndim != 1 or len(lab) != n:
+                raise ValueError('data and labels must have the same length.')
+            if len(lab) and (lab.dtype == np.bool_ or not np.issubdtype(lab.dtype, np.integer)):
+                raise ValueError('labels must be integer class codes, got dtype %s' % (lab.dtype,))
+            top = int(lab.max()) if len(lab) else -1
+            if n_classes is None:
+                if top < 0:
+                    raise ValueError('n_classes cannot be inferred: no sample is labelled')
+                n_classes = top + 1
+                if n_classes > 4096:
+                    raise ValueError('labels hold codes up to %d: at most 4096 classes' % top)
+            if top >= n_classes:
+                raise ValueError('labels must be < n_classes = %d, got %d' % (n_classes, top))
+            lab32 = np.where(lab < 0, -1, lab).astype(np.int32) if len(lab) else np.zeros(0, np.int32)
+        counts = np.zeros((X * Y, n_classes), dtype=np.int64)
+        if q is not None:
+            if n:
+                ptr, _owner = self._column_query(eng, labels, 'labels', 'int32', '<i4', lab32)
+                counts += eng.label_counts_device(q[1], ptr, n, n_classes)
+        else:
+            for s in range(0, n, self._n_parallel):
+                counts += eng.label_counts(data[s:s + self._n_parallel], lab32[s:s + self._n_parallel], n_classes)
+        return counts.reshape(X, Y, n_classes)
+
+    def unit_means(self, data, values):
+        """Per-unit statistics of ``values`` -- one or more columns of numbers the map was not trained on, ``(n,)`` or
+        ``(n, n_cols)`` float32 -- over the samples each unit wins (the units of ``predict``): a ``UnitMeans`` of
+        ``(x, y, n_cols)`` arrays ``count``, ``sum``, ``sumsq`` (float64 sums) with ``mean`` -- the component planes -- and
+        ``std`` derived.  A NaN value is "not observed" for its column only, whatever ``missing`` is; +-Inf is a value.  For
+        rows in HBM ``values`` is a device float32 tensor next to them (a host array is copied there).  Computed on the
+        device without atomics: the same rows give the same bits.  Rows in HBM go whole; host rows in ``n_parallel`` chunks
+        whose results are added on the host in chunk order (float64).  No sample weights, no neighbourhood smoothing, no
+        cross-rank reduction: each rank reports its own rows, and the three raw arrays add."""
+        eng, q, data = self._diag_query(data)
+        X, Y = self._weights.shape[:2]
+        n = q[2] if q is not None else len(data)
+        val = None
+        if _is_device_array(values):
+            if q is None:
+                raise ValueError('values in device memory need data in device memory')
+            shape = tuple(_n_shape(values))
+        else:
+            val = np.asarray(values)
+            if val.dtype == np.bool_ or not (np.issubdtype(val.dtype, np.integer) or np.issubdtype(val.dtype, np.floating)):
+                raise ValueError('values must have a real dtype, got %s' % (val.dtype,))
+            val = np.ascontiguousarray(val, dtype=np.float32)
+            if val.ndim == 1:
+                val = val[:, None]
+            shape = val.shape
+        if len(shape) not in (1, 2) or shape[0] != n:
+            raise ValueError('data and values must have the same length.')
+        n_cols = shape[1] if len(shape) == 2 else 1
+        if not 1 <= n_cols <= 4096:
+            raise ValueError('values must have between 1 and 4096 columns, got %d' % n_cols)
+        count = np.zeros((X * Y, n_cols), dtype=np.int64)
+        tot, sq = np.zeros((X * Y, n_cols), dtype=np.float64), np.zeros((X * Y, n_cols), dtype=np.float64)
+        if q is not None:
+            parts = []
+            if n:
+                ptr, _owner = self._column_query(eng, values, 'values', 'float32', '<f4', val)
+                parts = [eng.value_sums_device(q[1], ptr, n, n_cols)]
+        else:
+            parts = (eng.value_sums(data[s:s + self._n_parallel], val[s:s + self._n_parallel]) for s in range(0, n, self._n_parallel))
+        for c, s, s2 in parts:
+            count += c
+            tot += s
+            sq += s2
+        return UnitMeans(count.reshape(X, Y, n_cols), tot.reshape(X, Y, n_cols), sq.reshape(X, Y, n_cols))
+
+    def classify(self, data, counts, default=None):
+        """Class code (int64) of every sample from a label map ``counts`` (``label_counts`` of labelled samples,
+        ``(x, y, n_classes)``): the most frequent class of the sample's best matching unit, the lowest code on a tie.  A unit
+        without a labelled sample gives ``default``; ``None`` means the class with the largest total over the map (the
+        lowest code on a tie).  The rule of MiniSom's classification example without its per-sample ``winner`` loop; the
+        map is taken as it is (no smoothing over neighbouring units)."""
+        X, Y = self._weights.shape[:2]
+        counts = np.asarray(counts)
+        if counts.ndim != 3 or counts.shape[:2] != (X, Y) or counts.shape[2] < 1:
+            raise ValueError('counts must be (%d, %d, n_classes), got %r' % (X, Y, counts.shape))
+        flat = counts.reshape(X * Y, -1)
+        if default is None:
+            default = int(np.argmax(flat.sum(axis=0)))
+        per_unit = np.where(flat.sum(axis=1) > 0, np.argmax(flat, axis=1), default).astype(np.int64)
+        if self._device_query(data) is None:
+            data = _host_rows(data, self._engine)
+            if data.ndim == 1:
+                data = data[None, :]
+            if len(data):
+                self._check_input_len(data)
+        return per_unit[self.predict(data)]
 
     def topographic_error(self, data):
         """Share of samples whose best and second-best matching units are not adjacent on the map
