@@ -1,6 +1,7 @@
 """A float64 model of the engine with missing values (`XPySom(..., missing='nan')`, SOM_MISSING_NAN).
 
-Shared by tests/test_missing_cpu.py and tests/test_gpu_missing.py (not a conftest).
+Shared by tests/test_missing_cpu.py, tests/test_gpu_missing.py and tests/test_gpu_missing_large.py (not a conftest); the
+last one's forced-update grid, LARGE_FORCED, lives here so that the CPU coverage test reads the same table.
 
 A NaN in a row means "not observed".  With m_nd = 1 where x_nd is observed and 0 otherwise, x~_nd = x_nd where observed and
 0 otherwise:
@@ -193,6 +194,107 @@ def check_merge(w_old, w_new, num, den, ref, mexican=False, what=""):
     i = int(np.argmax(r))
     assert r.flat[i] <= 1.0, "%s merge vs reference: err/bound %.3g at unit %d feature %d" % (what, r.flat[i], i // D, i % D)
     return float(r.flat[i])
+
+
+# ------------------------------------------------------------------------------------------------------ the large grid
+# The forced-update grid of tests/test_gpu_missing_large.py, kept here so that the GPU module and the coverage test of
+# tests/test_missing_cpu.py read one table.  A masked handle's rows are UD = 2 D wide, so these are the smallest shapes at
+# which every width the host's dispatch decides on (update_ref.update_paths(..., masked=True)) crosses its boundary.
+# family (update_ref.FAMILIES or "torus_gaussian"), X, Y, D, N, BMU pattern, missing pattern, sigma, wide
+LARGE_FORCED = [
+    ("gaussian", 129, 5, 64, 1000, "spread", "random30", 2.0, False),     # two row blocks, one-row last block, UD = 128 per column
+    ("gaussian", 257, 3, 65, 2100, "skewed", "payload", 1.2, True),       # three blocks, UD = 130 narrow2, counting sort, odd D
+    ("gaussian", 5, 130, 128, 1000, "spread", "halves", 2.0, False),      # stage 1 over two blocks, UD = 256: two column tiles
+    ("gaussian", 1, 300, 3, 2047, "spread", "row", 1.5, True),            # degenerate axis, three stage-1 blocks, UD = 6: narrow only
+    ("mexican_hat_compact", 66, 66, 3, 5000, "spread", "random30", 3.0, True),   # swapped order, 128-row tile without ranges, D1p = 8
+    # (the swapped order's column stage is D1p wide: at D1p = 8 it is a narrow tile alone, and only D1p = 132 gives it a
+    #  128-row MFMA tile AND a narrow tile of 4 columns -- no other row reaches s2.tile128 or s2.narrow2)
+    ("mexican_hat_compact", 66, 66, 64, 5000, "spread", "random30", 3.0, False),
+    ("mexican_hat", 129, 5, 6, 300, "spread", "random30", 2.0, True),     # two terms, two blocks
+    ("hex_mexican_hat_compact", 40, 34, 6, 2047, "spread", "random30", 2.0, False),   # sixteen term copies
+    ("hex_gaussian", 129, 34, 33, 5000, "spread", "feature", 1.5, False),  # three classes, an unobserved feature stays bit for bit
+    ("bubble", 129, 40, 1, 5200, "spread", "random30", 3.0, False),       # UD = 2, whole tiles of a table zero
+    ("triangle_compact", 40, 129, 4, 5200, "spread", "random30", 3.5, False),    # UD = 8
+    ("torus_gaussian", 129, 40, 67, 5200, "spread", "random30", 1.2, False),     # wrap kernel, band across the seam, UD = 134 narrow4
+    ("torus_gaussian", 40, 129, 64, 5200, "spread", "payload", 4.0, True),       # wrap kernel, per-column stage 2
+    ("gaussian", 5, 7, 600, 300, "skewed", "random30", 2.0, True),        # 4 waves
+    ("gaussian", 5, 7, 1100, 300, "spread", "random30", 2.0, False),      # 2 waves
+    ("gaussian", 5, 7, 2046, 300, "skewed", "random30", 2.0, True),       # 1 wave (direct slots), even D
+    ("gaussian", 5, 7, 2047, 129, "spread", "halves", 2.0, False),        # 1 wave, odd D
+    ("gaussian", 8, 8, 2, 300000, "skewed", "random30", 1.5, True),       # three run-sum levels
+    ("gaussian", 129, 64, 4, 8300, "spread", "random30", 2.0, False),     # K = 8256 > CS_MAX_K: radix sort
+]
+LARGE_ETA, LARGE_STD = 0.5, 0.5
+MIN_MERGE_SHARE = 0.95      # of the (unit, feature) elements: what merge_bound must cover on every row of the grid
+_large_cache = {}
+
+
+def family_of(fam):
+    """(neighbourhood, topology, compact) of a family of the grids."""
+    return ("gaussian", "toroidal", False) if fam == "torus_gaussian" else U.FAMILIES[fam]
+
+
+def large_id(row):
+    return "%s-%dx%dx%d-n%d-%s-%s" % row[:7]
+
+
+def large_forced_case(row, missing=None, weighted=False):
+    """{data, bmu, weights, w0, ref, kw, mexican} of a LARGE_FORCED row, computed once and never changed.  `missing`
+    replaces the row's missing pattern; `weighted` adds weights_ref.make_weights and sets one row of weight 0 to inf
+    (a row of weight 0 is not read)."""
+    key = (row, missing, weighted)
+    if key not in _large_cache:
+        fam, X, Y, D, N, bpat, mpat, sigma, wide = row
+        neigh, topo, compact = family_of(fam)
+        rs = np.random.RandomState(X * Y + D + N)
+        bmu = U.make_bmu(bpat, X, Y, N, rs)
+        data = punch(U.make_data(N, D, 1.0, 70 + D), missing or mpat, 9, bmu)
+        w = None
+        if weighted:
+            w = R.make_weights(N, 5 + D)
+            data[np.flatnonzero(w == 0)[0]] = np.inf
+        ref = reference_update_masked(data, bmu, X, Y, LARGE_ETA, sigma, wide=wide, weights=w, neighbourhood=neigh,
+                                      topology=topo, compact=compact, std_coeff=LARGE_STD)
+        for a in (data, bmu, *ref):
+            a.setflags(write=False)
+        _large_cache[key] = dict(
+            data=data, bmu=bmu, weights=w, ref=ref, mexican=neigh == "mexican_hat",
+            w0=O.default_codebook(X, Y, D, 3).astype(F32).reshape(X * Y, D),
+            kw=dict(neighborhood=neigh, topology=topo, compact_support=compact, std_coeff=LARGE_STD))
+    return _large_cache[key]
+
+
+def merge_share(ref, mexican=False):
+    """The share of the (unit, feature) elements merge_bound checks against the reference (from the reference alone)."""
+    ok, _, _ = merge_bound(ref, mexican)
+    return float(ok.mean()) if ok.size else 1.0
+
+
+def update_from_unit_rows(rows, X, Y, eta, sigma, *, wide, neighbourhood="gaussian", topology="rectangular", compact=False,
+                          std_coeff=0.5):
+    """(num, den), each float64 (K, D): the masked update from the per-unit rows [S (D) | C (D)] (K, 2 D) that level 0 hands
+    to the transform, H^T rows with the neighbourhood rows update_ref.reference_update builds (rectangular and hexagonal
+    topologies).  With the rows of the true segment sums this is reference_update_masked; the named mutants of
+    tests/test_missing_cpu.py feed it rows a wrong kernel would have left."""
+    rows = np.asarray(rows, F64)
+    K, D = X * Y, rows.shape[1] // 2
+    fn = O.NEIGHBOURHOODS[U.oracle_key(neighbourhood, topology)]
+    eta_t = F64(eta) if wide else float(eta)
+
+    def h_of(u):
+        return fn(X, Y, std_coeff, compact, u // Y, u % Y, sigma, wide) * eta_t
+
+    num, _, _, _ = U.accumulate(rows, np.abs(rows), np.zeros(K), np.arange(K), K, h_of)
+    return num[:, :D], num[:, D:]
+
+
+def unit_rows(data, bmu, K):
+    """The dense per-unit rows [S | C | count] (K, 2 D + 1), float64, of the augmented rows: what level 0 leaves in SC."""
+    units, S, _, c = U.segment_sums(augmented(data), bmu)
+    out = np.zeros((K, S.shape[1] + 1))
+    out[units, :-1] = S
+    out[units, -1] = c
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------ data

@@ -10,7 +10,7 @@ Every forced case goes through epoch_accumulate_forced, so the BMUs are the test
                 bitwise the monolithic accumulate
 The grid's axes: map shapes past the 64-row tile, several 128-row blocks with a one-row last block, bands on, square
 maps for the swapped stage order, one stage on each tile size, degenerate axes; D on every narrow tile, per-column
-stage 2 and segment-sum workgroup width (16, 8, 4, 2 waves, odd and even); all twelve neighbourhood families at two
+stage 2 and segment-sum workgroup width (16, 8, 4, 2 waves and 1, odd and even); all twelve neighbourhood families at two
 shapes with a side > 128, one of them with bands; rows 1 .. 400 000; BMU patterns spread / edges / skewed / sparse.
 tests/test_update_ref_cpu.py checks that the grid reaches every branch update_ref.update_paths names."""
 import numpy as np
@@ -63,6 +63,9 @@ _ROWS = [  # family, X, Y, D, N, pattern, sigma, std, wide, scale
     ("mexican_hat_compact", 252, 252, 136, 2048, "edges", np.nextafter(126.0, 200.0), 0.25, False, 1e3),
     ("mexican_hat_compact", 139, 139, 256, 5000, "edges", np.nextafter(69.5, 0.0), 0.25, True, 1e3),
     ("hex_mexican_hat_compact", 271, 198, 136, 2048, "edges", np.nextafter(1.5, 2.0), 0.25, False, 1.0),
+    # (rows are appended, never inserted: a row's eta and seed come from its position)
+    # D1p = 4096: the run sum's one-wave workgroup, its slots written straight into the next list
+    ("gaussian", 5, 7, 4092, 300, "skewed", 2.0, 0.5, True, 1.0),
 ]
 CASES = []
 for _i, (_f, _X, _Y, _D, _N, _p, _s, _std, _w, _sc) in enumerate(_ROWS):

@@ -191,6 +191,94 @@ def test_score_model_against_the_definition(X, Y, D, pattern):
     assert Q.check_picks(M.masked_bmu(x, w), s, E, pattern) == 0.0
 
 
+# ------------------------------------------------------------------------------------------------------ the large grid
+def test_masked_grid_reaches_every_update_branch():
+    """The rows of tests/test_gpu_missing_large.py reach, with UD = 2 D wide rows, every transform tile, both stage-2
+    forms, the bands, the swapped order, the hexagonal class copies, the toroidal wrap kernels, the run sum's 16-, 4-,
+    2- and 1-wave workgroups (8 waves: tests/test_gpu_missing.py at D = 260), both parities and both sorts; and on every
+    row the merge check covers at least MIN_MERGE_SHARE of the (unit, feature) elements -- from the reference alone."""
+    reached = set()
+    for row in M.LARGE_FORCED:
+        fam, X, Y, D, N = row[:5]
+        neigh, topo, compact = M.family_of(fam)
+        reached |= U.update_paths(X, Y, D, neigh, topo, compact, N, masked=True)
+    want = ({"%s.%s" % (s, b) for s in ("s1", "s2")
+             for b in ("tile64", "tile128", "narrow2", "narrow4", "narrow_none", "rows1", "rows2", "rows3+", "last1", "wrap")}
+            | {"s2.per_column", "s2.whole_rows", "bands.on", "bands.off", "swapped.on", "swapped.off", "hex.classes0",
+               "hex.classes3", "hex.classes4", "seg.waves16", "seg.waves4", "seg.waves2", "seg.waves1", "seg.vec2", "seg.vec1",
+               "sort.counting", "sort.radix", "runsum.upper", "runsum.single"})
+    assert want - reached == set()
+    assert reached <= U.ALL_LABELS | U.TORUS_LABELS
+    assert len(set(M.LARGE_FORCED)) == len(M.LARGE_FORCED)
+    for row in M.LARGE_FORCED:
+        c = M.large_forced_case(row)
+        share = M.merge_share(c["ref"], c["mexican"])
+        print("%s: the merge check covers %.4f of the elements" % (M.large_id(row), share))
+        assert share >= M.MIN_MERGE_SHARE, M.large_id(row)
+        assert np.isnan(c["data"]).any() and all(np.isfinite(a).all() for a in c["ref"])
+
+
+def _f32_case(row):
+    """(case, num, den): a LARGE_FORCED row and its reference rounded to float32 -- what a correct kernel may return."""
+    c = M.large_forced_case(row)
+    return c, c["ref"][0].astype(F32), c["ref"][1].astype(F32)
+
+
+def _row(X, Y, D):
+    return next(r for r in M.LARGE_FORCED if r[1:4] == (X, Y, D))
+
+
+def test_large_grid_control_the_model_from_the_unit_rows_passes():
+    """the control of the two mutants below: the true per-unit rows give the reference, and its float32 rounding passes"""
+    for row in (_row(5, 7, 600), _row(129, 5, 64)):
+        fam, X, Y, D, N, _, _, sigma, wide = row
+        c, num, den = _f32_case(row)
+        assert M.check_accumulators(num, den, c["ref"]) < 0.1
+        assert M.check_merge(c["w0"], M.merge(c["w0"], num, den), num, den, c["ref"]) < 0.1
+        sc = M.unit_rows(c["data"], c["bmu"], X * Y)
+        assert (sc[:, -1] == np.bincount(c["bmu"], minlength=X * Y)).all()
+        mnum, mden = M.update_from_unit_rows(sc[:, :-1], X, Y, M.LARGE_ETA, sigma, wide=wide, std_coeff=M.LARGE_STD)
+        assert M.check_accumulators(mnum.astype(F32), mden.astype(F32), c["ref"]) < 0.1
+
+
+def test_checker_rejects_rows_laid_out_with_the_unmasked_row_pitch():
+    """The per-unit rows [S | C | count] of a masked handle written D1p = round_up(D + 1, 4) floats apart -- the pitch of
+    a handle without missing values -- instead of round_up(2 D + 1, 4): every row's counts are overwritten by the next
+    row's sums before the transform reads them."""
+    row = _row(5, 7, 600)
+    fam, X, Y, D, N, _, _, sigma, wide = row
+    c = M.large_forced_case(row)
+    K, width = X * Y, 2 * D + 1
+    sc = M.unit_rows(c["data"], c["bmu"], K)
+    for pitch, good in ((-(-(2 * D + 1) // 4) * 4, True), (-(-(D + 1) // 4) * 4, False)):
+        flat = np.zeros(K * pitch + width)
+        for k in range(K):                                   # unit by unit, as the run sum stores them
+            flat[k * pitch:k * pitch + width] = sc[k]
+        read = np.stack([flat[k * pitch:k * pitch + width] for k in range(K)])
+        num, den = M.update_from_unit_rows(read[:, :-1], X, Y, M.LARGE_ETA, sigma, wide=wide, std_coeff=M.LARGE_STD)
+        if good:
+            M.check_accumulators(num.astype(F32), den.astype(F32), c["ref"])
+        else:
+            with pytest.raises(AssertionError):
+                M.check_accumulators(num.astype(F32), den.astype(F32), c["ref"])
+
+
+def test_checker_rejects_a_second_block_without_its_count_columns():
+    """Stage 2 of the second 128-row block (one map row at 129 x 5) leaves the counts C -- the columns a masked handle
+    divides by -- as the accumulator was zeroed: five units out of 645.  The accumulator check sees the denominators; the
+    merge check sees the rows that kept their old values."""
+    row = _row(129, 5, 64)
+    fam, X, Y, D, N = row[:5]
+    c, num, den = _f32_case(row)
+    bad = den.copy()
+    bad[128 * Y:] = 0
+    assert (den[128 * Y:] != 0).all() and (bad != den).sum() == Y * D
+    with pytest.raises(AssertionError, match="den"):
+        M.check_accumulators(num, bad, c["ref"])
+    with pytest.raises(AssertionError, match="merge vs reference"):
+        M.check_merge(c["w0"], M.merge(c["w0"], num, bad), num, bad, c["ref"])
+
+
 def test_exact_case_is_exact_in_float32_and_has_ties():
     x, w = M.exact_case(300, 77, 33, seed=1)
     s, _ = M.masked_scores(x, w)

@@ -183,15 +183,47 @@ def test_grid_covers_every_family_on_large_maps():
 
 
 def test_update_paths_follows_the_dispatch_rules():
-    p = update_paths(300, 260, 3, "gaussian", "rectangular", False, 2047)
+    def paths(X, Y, D, N, neigh="gaussian", topo="rectangular", compact=False, **kw):
+        return update_paths(X, Y, D, neigh, topo, compact, N, **kw)
+
+    def waves(D, **kw):
+        return [x for x in paths(4, 4, D, 1, **kw) if x.startswith("seg.waves")]
+
+    p = paths(300, 260, 3, 2047)
     assert {"s1.narrow2", "s1.rows3+", "s2.rows3+", "bands.on", "s2.whole_rows", "sort.radix", "seg.waves16",
             "seg.vec1", "runsum.upper"} <= p
-    p = update_paths(40, 200, 128, "gaussian", "rectangular", False, 1)
-    assert {"s2.per_column", "s2.tile64", "s1.tile128", "runsum.single", "bands.off", "seg.vec2"} <= p
+    # ranges on (a side > 32): the 64-row tile whatever the stage's height
+    p = paths(40, 200, 128, 1)
+    assert {"s2.per_column", "s2.tile64", "s1.tile64", "runsum.single", "bands.on", "seg.vec2"} <= p
+    assert not {"s1.tile128", "s2.tile128", "s1.wrap", "s2.wrap"} & p
+    # bands: on iff a side exceeds the 32-row range tile, and never for the swapped order
+    assert "bands.off" in paths(32, 32, 24, 10) and "bands.on" in paths(33, 32, 24, 10) and "bands.on" in paths(32, 33, 24, 10)
+    assert "bands.on" in paths(1, 33, 24, 10) and "bands.off" in paths(1, 32, 24, 10)
+    p = paths(130, 130, 24, 10, "mexican_hat", compact=True)
+    assert {"swapped.on", "bands.off", "s1.tile128", "s2.tile128"} <= p and not {"s1.tile64", "s2.tile64"} & p
+    assert {"s1.tile64", "s2.tile64"} <= paths(64, 64, 24, 10, "mexican_hat", compact=True)       # no ranges, Ro <= 64
+    assert "s2.tile128" not in paths(66, 66, 3, 10, "mexican_hat", compact=True)                  # D1p = 4: a narrow tile alone
+    # a toroidal handle with ranges launches the wrap kernels (its narrow tile is the ordinary one)
+    p = paths(129, 40, 24, 10, topo="toroidal")
+    assert {"s1.wrap", "s2.wrap", "s1.tile64", "s2.tile64", "bands.on", "hex.classes0"} <= p
+    assert not {"s1.wrap", "s2.wrap"} & paths(32, 32, 24, 10, topo="toroidal")
+    assert "s1.wrap" not in paths(129, 40, 3, 10, topo="toroidal") and "s1.narrow2" in paths(129, 40, 3, 10, topo="toroidal")
     assert "swapped.on" in update_paths(130, 130, 6, "mexican_hat", "rectangular", True, 10)
     assert "hex.classes4" in update_paths(130, 130, 6, "mexican_hat", "hexagonal", True, 10)
     assert "hex.classes0" in update_paths(130, 130, 6, "bubble", "hexagonal", True, 10)
-    assert [min(x for x in update_paths(4, 4, D, "gaussian", "rectangular", False, 1) if x.startswith("seg.waves"))
-            for D in (507, 508, 1020, 2044)] == ["seg.waves16", "seg.waves8", "seg.waves4", "seg.waves2"]
+    assert [waves(D) for D in (507, 508, 1020, 2044, 4091, 4092)] == [
+        ["seg.waves16"], ["seg.waves8"], ["seg.waves4"], ["seg.waves2"], ["seg.waves2"], ["seg.waves1"]]
+    # a masked handle: rows of 2 D features, D1p = round_up(2 D + 1, 4); level 0 keeps D's parity
+    assert [waves(D, masked=True) for D in (253, 254, 510, 1022, 2046)] == [
+        ["seg.waves16"], ["seg.waves8"], ["seg.waves4"], ["seg.waves2"], ["seg.waves1"]]
+    assert [waves(D, masked=True) for D in (509, 1021, 2045)] == [["seg.waves8"], ["seg.waves4"], ["seg.waves2"]]
+    assert "seg.vec1" in paths(4, 4, 3, 1, masked=True) and "seg.vec2" in paths(4, 4, 2, 1, masked=True)
+    p = paths(129, 5, 64, 1000, masked=True)                                    # UD = 128: per column, no narrow tile
+    assert {"s2.per_column", "s1.narrow_none", "s2.narrow_none", "s2.last1", "s2.rows2"} <= p
+    assert "s2.whole_rows" in paths(129, 5, 64, 1000)
+    p = paths(257, 3, 65, 2100, masked=True)                                    # UD = 130: a narrow tile of 2 columns
+    assert {"s1.narrow2", "s1.tile64", "s2.whole_rows", "s2.rows3+", "s2.last1"} <= p
+    assert {"s1.narrow4", "s2.narrow_none"} <= paths(1, 300, 3, 10, masked=True) and \
+        "s1.tile64" not in paths(1, 300, 3, 10, masked=True)                    # UD = 6: stage 1 is a narrow tile alone
     assert "sort.counting" in update_paths(64, 64, 3, "gaussian", "rectangular", False, 2048)
     assert "sort.radix" in update_paths(64, 128, 3, "gaussian", "rectangular", False, 1 << 20)     # 1024 blocks x 8192

@@ -8,7 +8,8 @@ reference's float32 / float64 evaluation, the hexagonal coordinates and the mexi
 num = H^T S and den = H^T c in float64.  It shares no table, term or class offset with csrc/update.hpp.
 
 `update_paths` returns the kernel instances one epoch of the library reaches (csrc/somhip.hip and csrc/update.hpp,
-lines cited below), so the GPU module can show that its case list reaches every one of them.
+functions named below), on an ordinary handle or one with missing values, so the GPU modules can show that their case
+lists reach every one of them.
 """
 import numpy as np
 
@@ -201,24 +202,32 @@ def seg_waves_per_block(D1p):
     return nw
 
 
-def update_paths(X, Y, D, neighbourhood, topology, compact, N):
-    """The branches one epoch of N rows reaches on an X x Y x D map, as labels:
+def update_paths(X, Y, D, neighbourhood, topology, compact, N, masked=False):
+    """The branches one epoch of N rows reaches on an X x Y x D map, as labels (somhip.hip: launch_leftmul,
+    run_transform_stage1 / run_transform_stage2, band_ranges_from, som_create, seg_reserve, launch_runsum, segsum_rows;
+    update.hpp: seg_waves_per_block).  The SOM_LM_ROWS / SOM_NO_BANDS hooks are not modelled here:
+    tests/test_gpu_transform_bands.py owns them.
 
-      s1.* / s2.*        stage 1 / stage 2 of the transform (launch_leftmul, somhip.hip:1147-1171): tile64 / tile128
-                         (leftmul_f32_kernel<64> when the stage has <= 64 output rows, else <128>), narrow2 / narrow4 /
-                         narrow_none (leftmul_narrow_f32_kernel on a last column tile of 1..4 / 5..8 columns),
-                         rows1 / rows2 / rows3+ (128-row blocks), last1 (the last block holds one row)
-      s2.per_column / s2.whole_rows   stage 2 batched over map columns when D % 128 == 0 (somhip.hip:1228-1236)
-      bands.on / off     nonzero bands of the tables, a side > 256 (somhip.hip:1480)
-      swapped.on / off   mexican hat + compact support, rectangular: the row stage first (somhip.hip:1401, 1185-1199)
-      hex.classes0/3/4   parity classes of the hexagonal terms (somhip.hip:1404-1405)
-      seg.waves{16,8,4,2,1}, seg.vec2 / seg.vec1   the run sum's workgroup (update.hpp:239) and D's parity
-                         (launch_runsum, somhip.hip:1057-1066)
-      sort.counting / sort.radix      seg_reserve + segsum_rows (somhip.hip:1041-1043, 1077-1089)
-      runsum.upper / runsum.single    whether level 0 leaves more than one workgroup (somhip.hip:1092-1097)
+      s1.* / s2.*        stage 1 / stage 2 of the transform (launch_leftmul): tile64 / tile128 (the 64-row tile when the
+                         stage has <= 64 output rows or the launch carries band ranges, else the 128-row tile), wrap
+                         (a toroidal handle with ranges: leftmul_wrap_f32_kernel in place of leftmul_f32_kernel),
+                         narrow2 / narrow4 / narrow_none (leftmul_narrow_f32_kernel on a last column tile of 1..4 / 5..8
+                         columns), rows1 / rows2 / rows3+ (128-row blocks), last1 (the last block holds one row)
+      s2.per_column / s2.whole_rows   stage 2 batched over map columns when the row width UD % 128 == 0
+      bands.on / off     nonzero bands of the tables: a side > 32 (LM_TILE), and never for the swapped order
+      swapped.on / off   mexican hat + compact support, rectangular: the row stage first
+      hex.classes0/3/4   parity classes of the hexagonal terms
+      seg.waves{16,8,4,2,1}, seg.vec2 / seg.vec1   the run sum's workgroup (seg_waves_per_block(D1p)) and D's parity
+                         at level 0 (launch_runsum)
+      sort.counting / sort.radix      seg_reserve + sort_rows_by_unit
+      runsum.upper / runsum.single    whether level 0 leaves more than one workgroup (segsum_rows)
+
+    masked: a handle created with SOM_MISSING_NAN.  Its rows are [S | C | count], UD = 2 D wide, through the whole chain
+    (h->UD, h->D1p = round_up(UD + 1, 4)); only level 0 of the run sum, which reads the data's rows, still sees D.
     """
     out = set()
-    D1p = _cdiv(D + 1, 4) * 4
+    UD = 2 * D if masked else D
+    D1p = _cdiv(UD + 1, 4) * 4
     mex = neighbourhood == "mexican_hat"
     nt = (4 if compact else 2) if mex else 1
     classes = 0
@@ -226,9 +235,11 @@ def update_paths(X, Y, D, neighbourhood, topology, compact, N):
         classes = 4 if compact else 3
         nt *= classes
     swapped = mex and compact and topology == "rectangular"
+    torus = topology == "toroidal"
+    bands = (X > 32 or Y > 32) and not swapped
     nyb, nxb = _cdiv(Y, 128), _cdiv(X, 128)
 
-    def leftmul(stage, Ro, C, row_blocks):
+    def leftmul(stage, Ro, C, row_blocks, ranges):
         rem = C % 128
         wide = _cdiv(C, 128)
         if 0 < rem <= 8:
@@ -237,20 +248,22 @@ def update_paths(X, Y, D, neighbourhood, topology, compact, N):
         else:
             out.add(stage + ".narrow_none")
         if wide > 0:
-            out.add(stage + (".tile64" if Ro <= 64 else ".tile128"))
+            out.add(stage + (".tile64" if Ro <= 64 or ranges else ".tile128"))
+            if torus and ranges:
+                out.add(stage + ".wrap")
         out.add(stage + (".rows1" if row_blocks == 1 else ".rows2" if row_blocks == 2 else ".rows3+"))
         if Ro > 128 and Ro % 128 == 1:
             out.add(stage + ".last1")
 
     if swapped:
-        leftmul("s1", X, Y * D1p, nxb)
-        leftmul("s2", Y, D1p, nyb)
+        leftmul("s1", X, Y * D1p, nxb, False)
+        leftmul("s2", Y, D1p, nyb, False)
     else:
-        leftmul("s1", Y, D, nyb)
-        per_column = D % 128 == 0
+        leftmul("s1", Y, UD, nyb, bands)
+        per_column = UD % 128 == 0
         out.add("s2.per_column" if per_column else "s2.whole_rows")
-        leftmul("s2", X, D if per_column else Y * D1p, nxb)
-    out.add("bands.on" if (X > 256 or Y > 256) else "bands.off")
+        leftmul("s2", X, UD if per_column else Y * D1p, nxb, bands)
+    out.add("bands.on" if bands else "bands.off")
     out.add("swapped.on" if swapped else "swapped.off")
     out.add("hex.classes%d" % classes)
     if N > 0:
@@ -264,12 +277,14 @@ def update_paths(X, Y, D, neighbourhood, topology, compact, N):
     return out
 
 
-# every label the GPU case list must reach (seg.waves1 needs D > 4090: not asked for)
+# every label the GPU case list of tests/test_gpu_update_ref.py must reach
 ALL_LABELS = ({"%s.%s" % (s, b) for s in ("s1", "s2")
                for b in ("tile64", "tile128", "narrow2", "narrow4", "narrow_none", "rows1", "rows2", "rows3+", "last1")}
               | {"s2.per_column", "s2.whole_rows", "bands.on", "bands.off", "swapped.on", "swapped.off",
                  "hex.classes0", "hex.classes3", "hex.classes4", "seg.waves16", "seg.waves8", "seg.waves4", "seg.waves2",
-                 "seg.vec2", "seg.vec1", "sort.counting", "sort.radix", "runsum.upper", "runsum.single"})
+                 "seg.waves1", "seg.vec2", "seg.vec1", "sort.counting", "sort.radix", "runsum.upper", "runsum.single"})
+# what a toroidal handle adds (that grid has no toroidal family: tests/test_gpu_torus.py and the masked grid reach them)
+TORUS_LABELS = {"s1.wrap", "s2.wrap"}
 
 
 # ------------------------------------------------------------------------------------------ case construction
