@@ -203,7 +203,23 @@ CASES = (
     + [_case(64, 64, 32, 5000, data="three")]              # three segments of > 1000 rows, 4093 empty units
     + [_case(X, Y, D, n, prec=prec, missing="nan")         # 30 % NaN, one all-NaN row, one feature nobody observes
        for (X, Y, D, n) in ((12, 11, 33, 300), (5, 7, 3, 127)) for prec in ("f32", "exact")]
+    # past one turn of bmu_dist_kernel's persistent loop (16 384 waves), and the per-unit kernels behind both sorts at scale
+    + [_case(5, 7, 3, 40003)]                              # three turns, the last partial
+    + [_case(12, 11, 130, 16389, prec=prec, missing="nan") for prec in ("f32", "exact")]   # just past the grid cap; the mask on
+    #                                                        the second and third fma steps of a lane
+    + [_case(12, 11, 65, 300, missing="nan")]              # the mask on lane 0's second step alone
+    + [_case(128, 64, 4, 5000)]                            # K = 8 192 = CS_MAX_K: the counting sort at its ceiling
+    + [_case(129, 64, 4, 5000)]                            # K = 8 256: the radix sort, 14 key bits, > 3 000 empty units
 )
+DIST_WAVES = 4 * 4096                                      # bmu_dist_kernel's grid cap: a wave takes rows r, r + 16 384, ...
+
+
+def sort_path(c):
+    """The sort sort_rows_by_unit takes for a case's query (somhip.hip, diag_reserve_stats: seg_reserve's rule on the rows of a
+    first query): counting up to CS_MAX_K = 8 192 units with at least 2 CS_BLOCK = 2 048 rows and a table of at most 2^21
+    entries, else radix."""
+    K, n = c["X"] * c["Y"], c["n"]
+    return "counting" if K <= 8192 and n >= 2048 and -(-n // 1024) * K <= (1 << 21) else "radix"
 
 
 def case_seed(c):

@@ -44,9 +44,12 @@ def test_model_equals_brute_force_on_the_case_list(c):
     d = ref.astype(F32)                                    # a float32 rounding of the reference is within the bound
     R.check_distances(d, x, w, ids, masked=bool(c["missing"]), what=c["id"])
     got = R.unit_stats_model(ids, d, K)
-    bf = R.brute_force_unit_stats(ids, d, K)
-    for a, b in zip(got, bf):
-        assert np.array_equal(a, b)                        # (fsum is the correctly rounded exact sum)
+    if n < 20000:                                          # the exact-rational loop: too slow beyond; the float64 model runs on all
+        bf = R.brute_force_unit_stats(ids, d, K)
+        for a, b in zip(got, bf):
+            assert np.array_equal(a, b)                    # (fsum is the correctly rounded exact sum)
+    else:
+        assert np.array_equal(got[0], np.bincount(ids, minlength=K)) and np.allclose(got[1].sum(), d.astype(F64).sum(), rtol=1e-12)
     assert R.check_unit_stats(got, ids, d, K, what=c["id"]) == 0.0
     assert got[0].sum() == n
     if c["data"] == "weights":
@@ -63,14 +66,40 @@ def test_model_equals_brute_force_on_the_case_list(c):
 
 def test_case_list_covers_the_issue_table():
     ids = {c["id"] for c in R.CASES}
-    assert len(ids) == len(R.CASES) == 7 + 8 + 1 + 4
+    assert len(ids) == len(R.CASES) == 7 + 8 + 1 + 4 + 6
     assert {(c["X"], c["Y"], c["D"], c["n"]) for c in R.CASES} == {
         (5, 7, 1, 1), (5, 7, 3, 127), (5, 7, 64, 129), (12, 11, 65, 300), (12, 11, 130, 1031), (16, 16, 260, 257),
-        (64, 64, 32, 5000), (12, 11, 33, 300)}
+        (64, 64, 32, 5000), (12, 11, 33, 300),
+        (5, 7, 3, 40003), (12, 11, 130, 16389), (128, 64, 4, 5000), (129, 64, 4, 5000)}
     exact = [c for c in R.CASES if c["prec"] == "exact" and not c["missing"]]
     assert {c["data"] for c in exact} == {"blobs", "offset30", "offset300", "weights"}
     assert {c["env"].get("SOM_EXACT_SKIP") for c in exact} == {None, "2"}
-    assert {(c["prec"], c["D"]) for c in R.CASES if c["missing"]} == {("f32", 33), ("exact", 33), ("f32", 3), ("exact", 3)}
+    assert {(c["prec"], c["D"]) for c in R.CASES if c["missing"]} == {("f32", 33), ("exact", 33), ("f32", 3), ("exact", 3),
+                                                                      ("f32", 130), ("exact", 130), ("f32", 65)}
+    assert sorted((c["X"], c["D"], c["n"]) for c in R.CASES if c["missing"] and c["D"] >= 65) == [(12, 65, 300), (12, 130, 16389),
+                                                                                                 (12, 130, 16389)]
+
+
+def test_case_list_goes_past_one_turn_and_behind_both_sorts():
+    """What the cases added for the persistent loop and the sorts reach, restated from the launch code: bmu_dist_kernel's waves
+    take rows r, r + 16 384, ...; the sort is update_ref.update_paths' rule (and diag_ref.sort_path's)."""
+    from tests import update_ref as U
+    turns = {c["id"]: -(-c["n"] // R.DIST_WAVES) for c in R.CASES}
+    assert max(turns.values()) == 3 and turns["5x7x3-n40003-f32-blobs"] == 3 and 40003 % R.DIST_WAVES not in (0, R.DIST_WAVES - 1)
+    assert {c["prec"] for c in R.CASES if c["missing"] and c["n"] > R.DIST_WAVES} == {"f32", "exact"}
+    assert {c["D"] for c in R.CASES if c["missing"] and c["n"] > R.DIST_WAVES} == {130}          # three fma steps on lanes 0 and 1
+    assert all(c["n"] - R.DIST_WAVES == 5 for c in R.CASES if c["missing"] and c["n"] > R.DIST_WAVES)   # waves 0 ... 4 turn twice
+    for c in R.CASES:
+        label = "sort." + R.sort_path(c)
+        assert label in U.update_paths(c["X"], c["Y"], c["D"], "gaussian", "rectangular", False, c["n"]), c["id"]
+    by_units = {}
+    for c in R.CASES:
+        by_units.setdefault(R.sort_path(c), set()).add(c["X"] * c["Y"])
+    assert max(by_units["counting"]) == 8192 and max(by_units["radix"]) == 8256          # the ceiling, and just past it
+    big = [c for c in R.CASES if c["X"] * c["Y"] > 8192]
+    assert len(big) == 1 and big[0]["n"] >= 2048                            # (enough rows for the counting sort: only K decides)
+    assert R.sort_path(dict(big[0], X=128)) == "counting"
+    assert (8256 - 1).bit_length() == 14                                    # the radix sort's key bits
 
 
 # ------------------------------------------------------------------------------------------------------ the bounds

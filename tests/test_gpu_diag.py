@@ -4,7 +4,8 @@ against the float64 model and the bounds of tests/diag_ref.py.  GPU only (`-m gp
 Every case is teacher-forced: set a codebook, query rows, compare with the model computed from the codebook the engine holds.
 For every case of diag_ref.CASES (the smallest shapes that cross each boundary of the kernels: one lane, odd widths, one and two
 fma steps a lane, beyond 128 features, the 16-bit searches, the exact mode's screen + window path on >= 4096 units, segments of
-more than a thousand rows, missing values):
+more than a thousand rows, missing values; and past one turn: three turns of the persistent row loop, the mask on a lane's second
+and third fma step, the per-unit kernels behind the counting sort at its ceiling of 8 192 units and behind the radix sort above it):
   (a) the ids are e.bmu(x, quantization=True)'s of the same handle bit for bit (exact handles: also a float32 handle's)
   (b) the distances, counts, maxima and sums are within diag_ref's bounds
   (c) the device entry point returns the host entry point's bits
@@ -91,7 +92,7 @@ def test_diag_case(c, env_of):
             finally:
                 f.close()
         # (b) the distances
-        R.check_distances(d, x, w, ids, masked=masked, what=what)
+        worst_d = R.check_distances(d, x, w, ids, masked=masked, what=what)
         if c["data"] == "weights":
             assert (d == 0).all(), "%s: rows that are units must be at distance 0 exactly" % what
         if c["data"] == "int":
@@ -104,9 +105,12 @@ def test_diag_case(c, env_of):
         # (b) the per-unit statistics
         st = e.unit_stats(x)
         advanced("unit_stats")
-        R.check_unit_stats(st, ids, d, K, what=what)
+        print("%s: worst err / bound of the distances %.3g, of the unit sums %.3g" % (
+            what, worst_d, R.check_unit_stats(st, ids, d, K, what=what)))
         if c["data"] == "three":
             assert (st[0] > 1000).sum() == 3 and (st[0] == 0).sum() == K - 3
+        if K >= 8192:                                       # both sorts at scale: thousands of segments beside thousands of empty units
+            assert (st[0] > 0).sum() > 1000 and (st[0] == 0).sum() > 3000, "%s: %d units with rows" % (what, (st[0] > 0).sum())
         # (c)
         ids_dev, d_dev = e.bmu_distances_device(t.data_ptr(), n)
         advanced("bmu_distances_device")

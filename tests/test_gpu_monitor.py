@@ -8,8 +8,12 @@ tests/monitor_ref.py's float64 model on those ids and codebooks:
   QE              within gamma(D + 10) ref (query_ref.check_qe's bound)
   shift_max       exactly float32's max |W' - W|
   shift_sumsq     within K D 2^-52 relative of the float64 sum of the squares
-Shapes: the smallest that reach each path (named at the case list).  Then three equalities bit for bit -- two monitored runs, the
-XPySom history against the stage-by-stage replay, the monitored against the unmonitored codebook -- and the state errors."""
+Shapes: the smallest that reach each path (named at the case list).  monitor_ref.BIG_CASES are the shapes past one turn of the
+kernels' loops -- the all-live instance of the unrolled row chains, a second turn, a zero-weight row inside a full turn, the
+capped shift grid, a ragged reduction --; there the Euclidean record's sum_wd is also held to the float32 distances
+bmu_distances returns for the same rows, within 2 rows 2^-53 (monitor_ref.check_rows_tight): one misread row fails it.  Then
+three equalities bit for bit -- two monitored runs, the XPySom history against the stage-by-stage replay, the monitored against
+the unmonitored codebook -- and the state errors."""
 import contextlib
 import math
 import os
@@ -18,7 +22,6 @@ import numpy as np
 import pytest
 
 from oracle import som_oracle as O
-from tests import missing_ref as M
 from tests import monitor_ref as R
 from tests import query_ref as Q
 
@@ -62,8 +65,9 @@ def record_bits(m):
             np.array([m["shift_max"]], F32).tobytes())
 
 
-def replay(e, x, w0, epochs=4, weights=None, masked=False, check=True, monitored=True, what=""):
-    """`epochs` epochs stage by stage on engine `e`; every record checked against the model.  Returns (records, final codebook)."""
+def replay(e, x, w0, epochs=4, weights=None, masked=False, check=True, monitored=True, tight=False, what=""):
+    """`epochs` epochs stage by stage on engine `e`; every record checked against the model.  tight: also against the float32
+    distances e.bmu_distances(x) returns under the epoch's codebook (distances_under).  Returns (records, final codebook)."""
     e.set_weights(w0)
     e.set_data(x)
     if weights is not None:
@@ -74,6 +78,8 @@ def replay(e, x, w0, epochs=4, weights=None, masked=False, check=True, monitored
     for t in range(epochs):
         sigma, eta, f64 = SCHEDULE[t]
         w_old = e.get_weights()
+        if tight and check and monitored:
+            q_ids, q_d = e.bmu_distances(x)                  # (the query's own row set: the resident rows are untouched)
         e.epoch_accumulate(sigma, eta, f64)
         if not monitored:
             e.epoch_merge()
@@ -93,17 +99,40 @@ def replay(e, x, w0, epochs=4, weights=None, masked=False, check=True, monitored
             sr = R.check_shift(m, w_old, w_new, tag)
             print("%s: rows %d changed %d QE %.9g (err/bound %.3g) shift %.9g max %.9g (err/bound %.3g)"
                   % (tag, m["rows"], m["changed"], R.qe_of(m), qr, math.sqrt(m["shift_sumsq"]), m["shift_max"], sr))
+            if tight:
+                d32, ties = distances_under(x, w_old, ids, q_ids, q_d, masked, tag)
+                print("%s: sum_wd against the float32 distances: err/bound %.3g (%d rows re-scored at the epoch's unit)"
+                      % (tag, R.check_rows_tight(m, d32, weights, tag), ties))
             assert m["shift_sumsq"] > 0 or len(x) == 0
         prev = ids
     return out, e.get_weights()
 
 
+def distances_under(x, w, ids, q_ids, q_d, masked, what):
+    """bmu_dist_kernel's float32 distance of every row to the unit the EPOCH gave it.  bmu_distances names the quantization
+    search's unit (the differences themselves), the epoch the training search's (|w|^2 - 2 x.w): on a tie at float32's
+    resolution the two may differ.  Such a row is held to be a tie (monitor_ref.check_near_ties) and its distance is taken
+    again from the same kernel on a 5 x 4 handle whose every unit is the epoch's unit -- the float32 depends on the row, the unit
+    and D alone.  Returns (distances, rows re-scored)."""
+    diff = np.flatnonzero(q_ids != ids)
+    if len(diff) == 0:
+        return q_d, 0
+    R.check_near_ties(x, w, ids, q_ids, diff, masked, what)
+    d32 = q_d.copy()
+    D = x.shape[1]
+    f = engine(5, 4, D, precision="f32", **({"missing": "nan"} if masked else {}))
+    try:
+        for k in np.unique(ids[diff]):
+            rows = diff[ids[diff] == k]
+            f.set_weights(np.repeat(w[k][None, :], 20, axis=0))
+            d32[rows] = f.bmu_distances(x[rows])[1]
+    finally:
+        f.close()
+    return d32, len(diff)
+
+
 def _masked_case(n=500, D=9, seed=5):
-    x = M.punch(Q.make_rows("blobs", n, D, 11), "random30", seed)
-    x[7] = np.nan                                            # one row with nothing observed
-    w = np.random.RandomState(2).randint(0, 3, n).astype(F32)   # weights 0, 1, 2
-    w[7] = 1.0
-    return x, w
+    return R.masked_rows(n, D, seed)                         # 30 % missing, row 7 entirely; weights 0, 1, 2
 
 
 # name: (X, Y, D, n, engine keywords, environment)
@@ -137,6 +166,33 @@ def test_records_against_the_model(name):
     assert all(m["rows"] == n and m["sum_w"] == float(n) for m in recs)
     if n > 100:
         assert any(m["changed"] > 0 for m in recs[1:])
+
+
+@pytest.mark.parametrize("name", list(R.BIG_CASES))
+def test_records_past_one_turn(name):
+    """monitor_ref.BIG_CASES: what each reaches is pinned by tests/test_monitor_cpu.py.  Every epoch holds check_rows, check_shift,
+    exact rows and changed, the merge, and sum_wd against the float32 distances of bmu_distances."""
+    c = R.BIG_CASES[name]
+    X, Y, D, n, epochs = c["X"], c["Y"], c["D"], c["n"], c["epochs"]
+    x, wt = R.big_case_data(name)
+    assert x.shape == (n, D)
+    e = engine(X, Y, D, c["env"], **c["kw"])
+    try:
+        recs, _ = replay(e, x, codebook(X, Y, D), epochs=epochs, weights=wt, masked=c["masked"], tight=True, what=name)
+        if name.startswith("exact-skip"):
+            planned, sorts = e.exact_resident_stats()
+            run, total = e.exact_skip_stats()
+            assert planned >= 3 and sorts >= 1 and run < total, (planned, sorts, run, total)
+    finally:
+        e.close()
+    assert len(recs) == epochs and [m["changed"] >= 0 for m in recs] == [False] + [True] * (epochs - 1)
+    if wt is None:
+        assert all(m["rows"] == n and m["sum_w"] == float(n) for m in recs)
+    else:
+        assert all(m["rows"] == int((wt != 0).sum()) for m in recs)          # the non-zero weights, exactly
+        if c["weights"] == "012":                            # small integers: their double sum is exact in any order
+            assert all(m["sum_w"] == float(wt.sum(dtype=F64)) for m in recs)
+    assert any(m["changed"] > 0 for m in recs[1:])
 
 
 def test_missing_values_with_weights():
@@ -246,6 +302,8 @@ EQ_CASES = {
     "f32": (CASES["f32"], False),
     "exact": (CASES["exact-skip"], False),
     "masked": ((16, 16, 9, 500, dict(precision="exact", missing="nan"), {}), True),
+    # the all-live chains and a second turn: their tree, run twice
+    "f32-n81925": (tuple(R.BIG_CASES["f32-n81925"][k] for k in ("X", "Y", "D", "n", "kw", "env")), False),
 }
 
 
@@ -258,14 +316,15 @@ def test_two_monitored_runs_and_the_unmonitored_codebook(name):
     else:
         x, wt = (O.gaussian_blobs(n, D, seed=11) if name == "exact" else Q.make_rows("blobs", n, D, 11 + D)), None
     w0 = codebook(X, Y, D)
+    epochs = R.BIG_CASES[name]["epochs"] if name in R.BIG_CASES else 4
     runs = []
     for monitored in (True, True, False):
         e = engine(X, Y, D, env, **kw)
         try:
-            runs.append(replay(e, x, w0, weights=wt, masked=masked, check=False, monitored=monitored))
+            runs.append(replay(e, x, w0, epochs=epochs, weights=wt, masked=masked, check=False, monitored=monitored))
         finally:
             e.close()
-    assert len(runs[0][0]) == 4 and [record_bits(m) for m in runs[0][0]] == [record_bits(m) for m in runs[1][0]]
+    assert len(runs[0][0]) == epochs and [record_bits(m) for m in runs[0][0]] == [record_bits(m) for m in runs[1][0]]
     assert np.array_equal(bits(runs[0][1]), bits(runs[1][1]))
     assert np.array_equal(bits(runs[0][1]), bits(runs[2][1])), "the monitor changed the trained codebook"
 

@@ -18,6 +18,7 @@ import pytest
 from tests import diag_ref as R
 from tests import project_ref as P
 from tests import query_ref as Q
+from tests import update_ref as U
 
 pytestmark = pytest.mark.gpu
 
@@ -64,7 +65,12 @@ CASES = (
     + [_case(12, 11, 33, 300, 6, prec=prec, missing="nan") for prec in ("f32", "exact")]
     + [_case(12, 11, 65, 300, 5, prec="bf16")]
     + [_case(5, 7, 3, 127, 4, data="blobs", tag="-holes")]  # values: 30 % NaN, an all-NaN column, an all-NaN row, a +Inf
-)                                                           # labels: -1 and >= C mixed in
+    #                                                         labels: -1 and >= C mixed in
+    # behind both sorts at scale: K = 8 256 (radix, 14 key bits) and K = 8 192 = CS_MAX_K (the counting sort's ceiling)
+    + [_case(129, 64, 4, 5000, 3), _case(128, 64, 4, 5000, 3)]
+    + [_case(5, 7, 3, 70000, 2, data="one")]                # one segment of 70 000 rows, 32 row slots x 2 columns: the longest walk
+)
+HOLES = next(c for c in CASES if c["id"].endswith("-holes"))
 
 
 def case_data(c):
@@ -92,16 +98,21 @@ def case_data(c):
 
 
 def test_case_list_covers_the_issue_table():
-    assert len({c["id"] for c in CASES}) == len(CASES) == 2 + 4 + 2 + 1 + 2 + 1 + 2 + 1 + 1
+    assert len({c["id"] for c in CASES}) == len(CASES) == 2 + 4 + 2 + 1 + 2 + 1 + 2 + 1 + 1 + 2 + 1
     assert {(c["X"], c["Y"], c["D"], c["n"], c["C"]) for c in CASES} >= {
         (5, 7, 3, 1, 1), (5, 7, 3, 127, 3), (12, 11, 65, 300, 63), (12, 11, 65, 300, 64), (12, 11, 65, 300, 65),
         (12, 11, 65, 300, 130), (12, 11, 65, 300, 1), (12, 11, 65, 300, 2), (64, 64, 32, 5000, 5), (5, 7, 3, 20000, 1),
-        (5, 7, 3, 20000, 7)}
+        (5, 7, 3, 20000, 7), (129, 64, 4, 5000, 3), (128, 64, 4, 5000, 3), (5, 7, 3, 70000, 2)}
+    sorts = {c["X"] * c["Y"]: R.sort_path(c) for c in CASES if c["n"] == 5000 and c["D"] == 4}
+    assert sorts == {8256: "radix", 8192: "counting"}       # (the threshold cannot move the cases quietly)
+    for c in CASES:
+        assert "sort." + R.sort_path(c) in U.update_paths(c["X"], c["Y"], c["D"], "gaussian", "rectangular", False, c["n"]), c["id"]
+    assert [c["data"] for c in CASES if c["n"] == 70000] == ["one"]
     assert {c["prec"] for c in CASES if c["missing"]} == {"f32", "exact"}
     assert any(c["prec"] == "bf16" for c in CASES) and any(c["distance"] == "cosine" for c in CASES)
-    x, _w, labels, values = case_data(CASES[-1])
+    x, _w, labels, values = case_data(HOLES)
     assert np.isnan(values[:, 1]).all() and np.isnan(values[6]).all() and np.isinf(values).sum() == 1
-    assert 0.2 < np.isnan(values).mean() < 0.6 and (labels < 0).any() and (labels >= CASES[-1]["C"]).any()
+    assert 0.2 < np.isnan(values).mean() < 0.6 and (labels < 0).any() and (labels >= HOLES["C"]).any()
 
 
 @pytest.mark.parametrize("c", CASES, ids=[c["id"] for c in CASES])
@@ -124,6 +135,9 @@ def test_project_case(c, monkeypatch):
         if c["data"] == "three":
             seg = np.bincount(ids, minlength=K)
             assert (seg > 1000).sum() == 3 and (seg == 0).sum() == K - 3
+        if K >= 8192:                                       # both sorts at scale: thousands of segments, thousands of empty units
+            seg = np.bincount(ids, minlength=K)
+            assert (seg > 0).sum() > 1000 and (seg == 0).sum() > 3000, "%s: %d units with rows" % (what, (seg > 0).sum())
         if c["missing"]:
             assert np.isnan(x[0]).all() and 0.25 < np.isnan(x).mean()
         tx, tl, tv = _dev(x), _dev(labels, np.int32), _dev(values)
