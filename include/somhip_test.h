@@ -109,6 +109,27 @@ int som_debug_band_tables_wrap(som_handle* h, int32_t* info4, int32_t* entries_o
  *   out8 = [0] skip  [1] resort  [2] scout  [3] level 2  [4] estimate  [5] sample_tiles  [6] refine  [7] time_phases */
 int som_debug_exact_last_plan(som_handle* h, int32_t* out8);
 
+/* precision EXACT, read-only: what the last BMU launch learned from its samples before it committed to a plan (the default
+ * switches' forecast: launch_bmu_exact, exact_sample_tiles, csrc/exact_host.hpp) -- plain numbers the host stored where it
+ * computed them; nothing is launched.
+ *   out12 = [0] need: the share of the groups a sampled row needs (-1: the row sample was not asked)  [1] rows sampled
+ *           [2] est, [3] est1: the share of their blocks the sample tiles would run after both levels / after level 1
+ *           [4] n_st: sample tiles  [5] st: their stride in tiles of the pass   ([2..5]: -1 where the tiles were not asked)
+ *           [6] blocks_run, [7] groups_run: the sample's raw counters (-1: not asked)
+ *           [8] scout_declined: launches of this handle so far whose estimate declined the plan (policy::PlanState::stats())
+ *           [9] the sample was planned with level 2 (-1: not asked)
+ *           [10] full_total, [11] full_screen: the policy's costs of the last launch WITHOUT a plan as they stand now (ms per row;
+ *           0: none on record) -- to be printed, never asserted on
+ * tests/test_gpu_default_plan.py compares them with a float64 model (tests/scout_ref.py). */
+int som_debug_exact_forecast(som_handle* h, double* out12);
+
+/* precision EXACT up to 128 features, read-only: the tiles' lists of the LAST PASS of the last BMU launch as its screen walked
+ * them -- blocks_out[t] the 16-unit blocks on tile t's list (tcnt), groups_out[t] the groups level 1 kept (the two numbers
+ * exact_list_totals_body sums into the pass's blocks_run and groups_run).  info2 = {tiles of that pass (0: it ran without a plan),
+ * its plan ran level 2}; written first, and alone when n_tiles == 0 or both arrays are NULL.  Returns non-zero where n_tiles
+ * exceeds the pass's tiles. */
+int som_debug_exact_tile_blocks(som_handle* h, int32_t* blocks_out, int32_t* groups_out, int64_t n_tiles, int32_t* info2);
+
 /* diagnostic builds only (-DSOM_STAMPS, tools/stamps.py builds one on demand): out_host == NULL attaches a buffer of n_pairs
  * (shader-clock ticks, 100 MHz ticks) pairs, one per workgroup of the next BMU launches (n_pairs == 0 detaches);
  * out_host != NULL reads n_pairs pairs back.  The product build refuses both. */

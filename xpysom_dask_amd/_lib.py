@@ -114,6 +114,8 @@ SIGNATURES = {
     "som_debug_band_tables_wrap": (C.c_int, [_H, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "som_debug_band_walk_wrap": (C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, _I]),
     "som_debug_exact_last_plan": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "som_debug_exact_forecast": (C.c_int, [_H, C.POINTER(C.c_double)]),
+    "som_debug_exact_tile_blocks": (C.c_int, [_H, _I, _I, C.c_int64, _I]),
     "som_policy_eval": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "som_policy_replay": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "som_operands_replay": (C.c_int, [_I, C.c_int32, _I, _I]),

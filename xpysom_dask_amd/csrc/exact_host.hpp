@@ -835,6 +835,9 @@ int exact_sample_tiles(som_handle* h, const ExactLaunch& L, som_handle::ExactScr
     HIPCHK(h, hipMemsetAsync(&pc.tail()->scout_wins, 0, sizeof(int), h->stream));
     const double est = (double)ex.pass_host->blocks_run / (double)(n_st * L.n_groups * K16_T);
     const double est1 = (double)ex.pass_host->groups_run / (double)(n_st * L.n_groups);
+    ex.fc.est = est; ex.fc.est1 = est1; ex.fc.n_st = (double)n_st; ex.fc.st = (double)st;
+    ex.fc.blocks_run = (double)ex.pass_host->blocks_run; ex.fc.groups_run = (double)ex.pass_host->groups_run;
+    ex.fc.level2 = lp.level2 ? 1.0 : 0.0;
     const bool decline = ex.plan.tiles_sampled(est, est1, L.f, lp);
     if (h->debug) {
         const policy::Costs& c = ex.plan.costs();
@@ -1030,6 +1033,8 @@ int exact_pass(som_handle* h, ExactLaunch& L, som_handle::ExactScratch::SortedRo
     ex.rows_total += n; ex.rows_fallback += n_fb; ex.chunks += 1;
     // (counted in 16-unit blocks: four per (256-row tile, group))
     ex.blocks_total += cdiv(n, SK_TILE) * n_groups * K16_T;
+    ex.last_plan_tiles = lp.skip && !h->wide ? cdiv(n, SK_TILE) : 0;   // (som_debug_exact_tile_blocks: the lists as this pass's screen walked them)
+    ex.last_plan_l2 = lp.skip && lp.level2;
     ex.blocks_run += lp.skip ? got.blocks_run : cdiv(n, SK_TILE) * n_groups * K16_T;
     L.o.groups_run += lp.skip ? got.groups_run : cdiv(n, SK_TILE) * n_groups;
     L.o.pairs_in += got.pairs_in;
@@ -1095,6 +1100,8 @@ int launch_bmu_exact(som_handle* h, const Rows& R) {
     f.skip_mode = ex.skip_mode; f.refine_on = ex.refine_on; f.sub_blocks = ex.sub_blocks; f.res_every = ex.res_every;
 
     lp = ex.plan.begin(f);
+    ex.fc = som_handle::ExactScratch::Forecast{};
+    ex.last_plan_tiles = 0; ex.last_plan_l2 = false;
     auto& sr = ex.srt[f.resident ? 0 : 1];
     // (the resident rows' carried positions: this launch's to use, and stale from here on unless its own finalize renews them;
     //  a launch over other rows works in srt[1] and writes other ids: it leaves them alone)
@@ -1127,6 +1134,7 @@ int launch_bmu_exact(som_handle* h, const Rows& R) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         const double need = (double)need_host->need / std::max(1.0, (double)need_host->rows * n_groups);
         if (h->debug) std::fprintf(stderr, "[somhip] exact scout: a sampled row needs %.4f of the groups\n", need);
+        ex.fc.need = need; ex.fc.rows = (double)need_host->rows;
         ex.plan.rows_sampled(need, lp);
     }
     if (lp.sample_tiles && exact_skip_reserve(h, ex.srt[1], 128 * SK_TILE, ex.stride) != 0) { (void)hipGetLastError(); h->err.clear(); lp.sample_tiles = false; }

@@ -232,6 +232,16 @@ struct som_handle {
         DevBuf<int> scout_g;              // [stride] nearest group centroid of every row of the pass
         DevBuf<float> tq;                 // [stride] wide plan: the float32 score of every sorted row's last BMU under the current codebook
         double share_forecast = 1.0;      // executed share expected of the launch about to run (the screen sizes its codebook parts by it)
+        // what the last launch learned from its samples, as plain numbers (-1: not asked), and the geometry of its last planned
+        // pass up to 128 features (read-only test accessors: som_debug_exact_forecast, som_debug_exact_tile_blocks)
+        struct Forecast {
+            double need = -1.0, rows = 0.0;                           // the row sample: share of the groups a row needs; rows sampled
+            double est = -1.0, est1 = -1.0, n_st = -1.0, st = -1.0;   // the sample tiles: shares after both levels / level 1; tiles; stride
+            double blocks_run = -1.0, groups_run = -1.0;              // ... their raw counters
+            double level2 = -1.0;                                     // ... planned with level 2?
+        } fc;
+        long last_plan_tiles = 0;         // tiles of the last pass of the last launch, where it ran under a plan (else 0)
+        bool last_plan_l2 = false;        // ... whether that pass's plan ran level 2
         // MEASURED COSTS (hipEvents on the handle's stream; per ROW, in ms, so that launches of different sizes compare): what the
         // policy decides from -- is a plan worth its launches, does level 2 pay, did a sort pay, is the plan idle.  The launch as
         // a whole is timed every time (two records); its phases under a plan -- screen, level 2, sort + gather -- in the first
@@ -3148,6 +3158,38 @@ int som_debug_exact_last_plan(som_handle* h, int32_t* out8) {
     const policy::LaunchPlan& p = h->ex.lp;
     out8[0] = p.skip; out8[1] = p.resort; out8[2] = p.scout; out8[3] = p.level2; out8[4] = p.estimate; out8[5] = p.sample_tiles;
     out8[6] = p.refine; out8[7] = p.time_phases;
+    return 0;
+}
+
+// TEST HOOK, read-only: what the last launch_bmu_exact learned from its samples (plain numbers the host stored where it computed
+// them: launch_bmu_exact, exact_sample_tiles) and the handle's running count of declined estimates.  Layout: include/somhip_test.h.
+int som_debug_exact_forecast(som_handle* h, double* out12) {
+    if (!h || !out12) return fail(h, "som_debug_exact_forecast: NULL argument");
+    const auto& fc = h->ex.fc;
+    out12[0] = fc.need; out12[1] = fc.rows; out12[2] = fc.est; out12[3] = fc.est1; out12[4] = fc.n_st; out12[5] = fc.st;
+    out12[6] = fc.blocks_run; out12[7] = fc.groups_run; out12[8] = (double)h->ex.plan.stats().scout_declined; out12[9] = fc.level2;
+    out12[10] = h->ex.plan.costs().full_total; out12[11] = h->ex.plan.costs().full_screen;
+    return 0;
+}
+
+// TEST HOOK, read-only: the lengths of the tiles' lists as the screen of the last pass of the last launch walked them -- tcnt (16-unit
+// blocks) and tile_counts (groups level 1 kept), the numbers exact_list_totals_body sums into the pass's counters.  Nothing is
+// launched, no state changed.  Layout: include/somhip_test.h.
+int som_debug_exact_tile_blocks(som_handle* h, int32_t* blocks_out, int32_t* groups_out, int64_t n_tiles, int32_t* info2) {
+    DeviceGuard dev_guard(h);
+    if (!h || !info2 || n_tiles < 0) return fail(h, "som_debug_exact_tile_blocks: bad argument");
+    const auto& ex = h->ex;
+    info2[0] = (int32_t)ex.last_plan_tiles; info2[1] = ex.last_plan_l2 ? 1 : 0;
+    if (n_tiles == 0 || (!blocks_out && !groups_out)) return 0;
+    if (ex.last_plan_tiles <= 0) return fail(h, "som_debug_exact_tile_blocks: the last launch ran no planned pass (up to 128 features)");
+    if (n_tiles > ex.last_plan_tiles || n_tiles * SK_TILE > ex.sk_stride) return fail(h, "som_debug_exact_tile_blocks: the last planned pass had fewer tiles");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (blocks_out) if (int rc = d2h_blocking(h, blocks_out, ex.tcnt, (size_t)n_tiles * sizeof(int32_t))) return rc;
+    if (groups_out) {
+        std::vector<int2> tc((size_t)n_tiles);
+        if (int rc = d2h_blocking(h, tc.data(), ex.tile_counts, (size_t)n_tiles * sizeof(int2))) return rc;
+        for (int64_t t = 0; t < n_tiles; ++t) groups_out[t] = tc[(size_t)t].y;
+    }
     return 0;
 }
 

@@ -577,6 +577,31 @@ class HipEngine:
         self._check(self._lib.som_debug_exact_last_plan(self._h, out))
         return dict(zip(("skip", "resort", "scout", "level2", "estimate", "sample_tiles", "refine", "time_phases"), (bool(v) for v in out)))
 
+    def exact_forecast(self):
+        """precision 'exact': what the last BMU launch learned from its samples, a dict -- need (share of the groups a sampled row
+        needs; -1: the row sample was not asked), rows (rows sampled), est / est1 (share of their blocks the sample tiles would run
+        after both levels / level 1; -1: not asked), n_st, st (sample tiles, their stride in tiles), blocks_run, groups_run (the
+        sample's raw counters), level2 (the sample was planned with level 2; -1: not asked), scout_declined (launches of this
+        handle so far whose estimate declined the plan), full_total / full_screen (the policy's measured costs of the last
+        launch without a plan, ms per row; 0: none yet)."""
+        out = (C.c_double * 12)()
+        self._check(self._lib.som_debug_exact_forecast(self._h, out))
+        d = dict(zip(("need", "rows", "est", "est1", "n_st", "st", "blocks_run", "groups_run", "scout_declined", "level2", "full_total", "full_screen"),
+                     (float(v) for v in out)))
+        for k in ("rows", "n_st", "st", "blocks_run", "groups_run", "scout_declined", "level2"):
+            d[k] = int(d[k])
+        return d
+
+    def exact_tile_blocks(self):
+        """precision 'exact', up to 128 features: (16-unit blocks on each tile's list, groups level 1 kept per tile, level 2 ran) of
+        the last pass of the last BMU launch as its screen walked them; raises where that launch ran without a plan."""
+        info = (C.c_int32 * 2)()
+        self._check(self._lib.som_debug_exact_tile_blocks(self._h, None, None, 0, info))
+        blocks = np.empty((max(int(info[0]), 0),), dtype=np.int32)
+        groups = np.empty_like(blocks)
+        self._check(self._lib.som_debug_exact_tile_blocks(self._h, self._ip(blocks), self._ip(groups), blocks.size, info))
+        return blocks, groups, bool(info[1])
+
     def exact_skip_stats(self):
         """precision 'exact': (blocks the screens ran, blocks of full scans) so far -- block skipping's executed share."""
         a, b = C.c_int64(), C.c_int64()
