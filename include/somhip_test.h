@@ -201,6 +201,16 @@ int som_operands_replay(const int32_t* config, int32_t n_events, const int32_t* 
  *          a buffer that exists holds at least one element).  Returns non-zero for a NULL or out-of-range argument. */
 int som_debug_row_set_sizes(int32_t kind, int64_t n, int32_t input_len, int32_t dp, int32_t flags, int64_t* out5);
 
+/* The SORT BY UNIT's rule (csrc/unit_sort.hpp, unitsort::sizes and unitsort::counting: what a sort scratch of capacity rows_cap
+ * allocates on a map of K units, and which sort n rows then take) on caller-supplied numbers -- pure host arithmetic, NO device
+ * needed (tests/test_unit_sort_cpu.py).  counting_on: the handle's SOM_COUNTING_SORT switch.
+ *   out6 = {skey, srow, radix scratch, counting table (elements; 0: no table), cs_blocks, 1 if n rows take the counting sort else 0}.
+ *   Returns non-zero for a NULL out6, negative rows or K < 1. */
+int som_debug_unit_sort_sizes(int64_t rows_cap, int32_t K, int32_t counting_on, int64_t n, int64_t* out6);
+/* The sorts by unit the handle ran since som_create, by kind (segment sums of resident rows and streamed chunks, the per-unit
+ * queries): the path the rule above PREDICTS, observed.  Counted where the host launches a sort: a replayed graph's are not. */
+int som_debug_unit_sort_stats(som_handle* h, int64_t* counting, int64_t* radix);
+
 #ifdef __cplusplus
 }
 #endif

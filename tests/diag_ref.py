@@ -28,6 +28,7 @@ import math
 import numpy as np
 
 from tests import query_ref as Q
+from tests import update_ref as U
 
 F32, F64 = np.float32, np.float64
 U64 = 2.0 ** -53
@@ -215,11 +216,8 @@ DIST_WAVES = 4 * 4096                                      # bmu_dist_kernel's g
 
 
 def sort_path(c):
-    """The sort sort_rows_by_unit takes for a case's query (somhip.hip, diag_reserve_stats: seg_reserve's rule on the rows of a
-    first query): counting up to CS_MAX_K = 8 192 units with at least 2 CS_BLOCK = 2 048 rows and a table of at most 2^21
-    entries, else radix."""
-    K, n = c["X"] * c["Y"], c["n"]
-    return "counting" if K <= 8192 and n >= 2048 and -(-n // 1024) * K <= (1 << 21) else "radix"
+    """The sort sort_rows_by_unit takes for a case's query, the first of its handle: update_ref.sort_path, the rule's one restatement."""
+    return U.sort_path(c["X"] * c["Y"], c["n"])
 
 
 def case_seed(c):

@@ -128,6 +128,7 @@ def test_diag_case(c, env_of):
         for name, a, b in zip(("count", "sum", "sumsq", "max"), e.unit_stats_device(t.data_ptr(), n), st):
             _same_bits(a, b, "%s second call %s" % (what, name))
         advanced("unit_stats_device again")
+        assert e.unit_sort_stats() == ((3, 0) if R.sort_path(c) == "counting" else (0, 3)), "%s: not the sort the rule names" % what
         # (e)
         R.check_qe_agreement(st[1], n, e.quantization_error(x), what)
     finally:

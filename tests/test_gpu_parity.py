@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import som_oracle as O
+from tests import update_ref
 from tests.conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -1015,9 +1016,10 @@ def test_banded_transform_is_bit_identical(monkeypatch, X, Y, neigh, topo, sigma
 @pytest.mark.parametrize("X,Y,n", [(64, 64, 100000), (90, 91, 5000), (8, 8, 2048), (30, 30, 70001)])
 def test_counting_sort_by_bmu_equals_the_library_sort(monkeypatch, X, Y, n):
     """Maps of <= 8192 units bucket the rows of an epoch by BMU with the in-tree stable counting sort
-    (cs_hist / cs_scan / cs_scatter, update.hpp) instead of rocPRIM's radix sort (SOM_COUNTING_SORT=0).
-    Both are stable, the segment sum adds a unit's rows in list order: numerator, denominator and BMUs
-    must be bitwise equal -- on clustered rows too, where a handful of units own every row."""
+    (cs_hist / cs_scan / cs_scatter, update.hpp) instead of the in-tree stable radix sort (rs_hist / rs_scan /
+    rs_scatter; SOM_COUNTING_SORT=0 keeps it on small maps too).  Both are stable, the segment sum adds a unit's rows in
+    list order: numerator, denominator and BMUs must be bitwise equal -- on clustered rows too, where a handful of units
+    own every row.  The handle's counters say which sort ran: the one csrc/unit_sort.hpp's rule names, in both modes."""
     D = 7
     data = O.gaussian_blobs(n, D, seed=X + n % 97)
     data[: n // 3] = data[0]                                  # a third of the rows on one unit
@@ -1031,6 +1033,9 @@ def test_counting_sort_by_bmu_equals_the_library_sort(monkeypatch, X, Y, n):
         e.epoch_accumulate(3.0, 0.4, True)
         num, den, bmu = e.epoch_fetch()
         outs[mode] = (num.copy(), den.copy(), bmu.copy())
+        ran = {"counting": (1, 0), "radix": (0, 1)}[update_ref.sort_path(X * Y, n) if mode == "1" else "radix"]
+        assert e.unit_sort_stats() == ran, "SOM_COUNTING_SORT=%s: (counting, radix) sorts %r" % (mode, e.unit_sort_stats())
+    assert update_ref.sort_path(X * Y, n) == "counting"      # (every parametrisation is one the two sorts differ on)
     for a, b in zip(outs["0"], outs["1"]):
         assert np.array_equal(a, b)
 

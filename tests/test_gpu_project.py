@@ -161,6 +161,7 @@ def test_project_case(c, monkeypatch):
         for second in (e.value_sums(x, values), e.value_sums_device(tx.data_ptr(), tv.data_ptr(), n, Cc)):
             for name, a, b in zip(("count", "sum", "sumsq"), second, sums):
                 _same_bits(a, b, "%s second call %s" % (what, name))
+        assert e.unit_sort_stats() == ((8, 0) if R.sort_path(c) == "counting" else (0, 8)), "%s: not the sort the rule names" % what
     finally:
         e.close()
 

@@ -97,6 +97,7 @@ def test_forced_weighted_update_against_the_float64_model(cid, X, Y, D, N, make_
         e.set_sample_weights(w)
         e.epoch_accumulate_forced(bmu, sigma, 0.5, wide)
         num, den, _ = e.epoch_fetch(want_bmu=False)
+        assert e.unit_sort_stats() == ((1, 0) if U.sort_path(X * Y, N) == "counting" else (0, 1)), "%s: not the sort the rule names" % cid
     finally:
         e.close()
     ref = R.reference_update_weighted(data, bmu, w, X, Y, 0.5, sigma, wide=wide)

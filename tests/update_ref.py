@@ -202,6 +202,15 @@ def seg_waves_per_block(D1p):
     return nw
 
 
+def sort_path(K, n):
+    """'counting' or 'radix': the sort by unit that n rows take on a map of K units in a scratch that was sized for them (a fresh
+    resident set, a first query, a first streamed chunk) -- the suite's ONE restatement of csrc/unit_sort.hpp's rule (sizes +
+    counting), pinned against the library by tests/test_unit_sort_cpu.py: counting up to CS_MAX_K = 8 192 units with at least
+    2 CS_BLOCK = 2 048 rows and a table of at most 2^21 counts, else radix.  A scratch grown by earlier, larger calls holds the
+    table its capacity allowed; the clauses on n then decide alone."""
+    return "counting" if K <= 8192 and n >= 2048 and _cdiv(n, 1024) * K <= (1 << 21) else "radix"
+
+
 def update_paths(X, Y, D, neighbourhood, topology, compact, N, masked=False):
     """The branches one epoch of N rows reaches on an X x Y x D map, as labels (somhip.hip: launch_leftmul,
     run_transform_stage1 / run_transform_stage2, band_ranges_from, som_create, seg_reserve, launch_runsum, segsum_rows;
@@ -219,7 +228,7 @@ def update_paths(X, Y, D, neighbourhood, topology, compact, N, masked=False):
       hex.classes0/3/4   parity classes of the hexagonal terms
       seg.waves{16,8,4,2,1}, seg.vec2 / seg.vec1   the run sum's workgroup (seg_waves_per_block(D1p)) and D's parity
                          at level 0 (launch_runsum)
-      sort.counting / sort.radix      seg_reserve + sort_rows_by_unit
+      sort.counting / sort.radix      sort_path: unit_sort.hpp's rule (seg_reserve, sort_rows_by_unit)
       runsum.upper / runsum.single    whether level 0 leaves more than one workgroup (segsum_rows)
 
     masked: a handle created with SOM_MISSING_NAN.  Its rows are [S | C | count], UD = 2 D wide, through the whole chain
@@ -271,8 +280,7 @@ def update_paths(X, Y, D, neighbourhood, topology, compact, N, masked=False):
         nw = seg_waves_per_block(D1p)
         out.add("seg.waves%d" % nw)
         out.add("seg.vec2" if D % 2 == 0 else "seg.vec1")
-        counting = K <= 8192 and N >= 2048 and _cdiv(N, 1024) * K <= (1 << 21)
-        out.add("sort.counting" if counting else "sort.radix")
+        out.add("sort." + sort_path(K, N))
         out.add("runsum.upper" if _cdiv(N, nw * 32) > 1 else "runsum.single")
     return out
 

@@ -120,6 +120,8 @@ SIGNATURES = {
     "som_policy_replay": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "som_operands_replay": (C.c_int, [_I, C.c_int32, _I, _I]),
     "som_debug_row_set_sizes": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "som_debug_unit_sort_sizes": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "som_debug_unit_sort_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_patch_order": (C.c_int, [C.c_int32, C.c_int32, _I]),
     "som_exact_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_exact_top2_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -241,31 +241,6 @@ int exact_screen_ks(som_handle* h, const __bf16* Xb, long n, unsigned long long*
         return exact_screen<decltype(k)::value>(h, Xb, n, best64, xsq, xerr, xmax2, eb, seed, glist, gcnt, sel, selected); });
 }
 
-
-// The stable radix sort of update.hpp: (keys_in, row index) -> (keys_out, vals_out), `bits` key bits, 8 a pass.  scratch: two
-// pairs of n ints + the 256 x blocks table (radix_scratch_ints).  keys_in is left intact.
-inline size_t radix_scratch_ints(long n) { return 4 * (size_t)n + 256 * (size_t)cdiv(std::max<long>(n, 1), RS_BLOCK) + 256; }
-int radix_sort_rows(som_handle* h, const int* keys_in, long n, int bits, int* keys_out, int* vals_out, int* scratch) {
-    if (n <= 0) return 0;
-    const int B = (int)cdiv(n, RS_BLOCK);
-    int* ka = scratch; int* va = scratch + n; int* kb = scratch + 2 * n; int* vb = scratch + 3 * n;
-    int* table = scratch + 4 * n;
-    int* tot = table + 256L * B;
-    const int passes = std::max(1, (int)cdiv(bits, 8));
-    const int* kin = keys_in; const int* vin = nullptr;
-    for (int p = 0; p < passes; ++p) {
-        const bool last = p == passes - 1;
-        int* ko = last ? keys_out : (p & 1) ? kb : ka;
-        int* vo = last ? vals_out : (p & 1) ? vb : va;
-        rs_hist_kernel<<<dim3((unsigned)B), dim3(256), 0, h->stream>>>(kin, n, 8 * p, B, table);
-        rs_scan_kernel<<<dim3(64), dim3(256), 0, h->stream>>>(table, B, tot);
-        rs_scatter_kernel<<<dim3((unsigned)B), dim3(256), 0, h->stream>>>(kin, vin, n, 8 * p, B, table, tot, ko, vo);
-        kin = ko; vin = vo;
-    }
-    HIPCHK(h, hipGetLastError());
-    return 0;
-}
-
 // ---- block skipping (exact_skip.hpp): buffers, the centroid images, the sorted pass, the scout, a pass's plan -----------------
 // sr: the sorted copies to (re)size for `rows` positions; stride: rows of one pass (the plan's own buffers)
 int exact_skip_reserve(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long rows, long stride) {
@@ -400,9 +375,7 @@ int exact_skip_sortkeys(som_handle* h, som_handle::ExactScratch::SortedRows& sr,
         exact_groupkey_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(scout_g, n, n_groups, ex.sk_keys, ex.sk_vals);
     else
         exact_sortkey_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(prev, h->ex_inv, n, h->K, ex.sk_keys, ex.sk_vals);
-    int bits = 1;
-    while ((1L << bits) < n_groups) ++bits;
-    return radix_sort_rows(h, ex.sk_keys, n, bits, ex.sk_keys2, sr.order + s0, ex.sk_tmp);
+    return radix_sort_rows(h, ex.sk_keys, n, unitsort::key_bits(n_groups), ex.sk_keys2, sr.order + s0, ex.sk_tmp);
 }
 // ... and the operands gathered in that order (`order`: n positions -> rows of the pass) into sr at positions s0 ...
 int exact_skip_gather(som_handle* h, som_handle::ExactScratch::SortedRows& sr, long s0, const int* order, const float* X, const __bf16* Xb, long n,

@@ -103,6 +103,17 @@ struct Rows {
     const float* wgt; bool resident; bool ids_valid;
 };
 
+// The sort by unit (unit_sort.hpp) and its buffers: the one owner.  The handle holds three -- the resident rows' and the streamed
+// chunks' (SegScratch), the query scratch's (RowSet::Diag).  reserve and sort_rows_by_unit take it whole; neither
+// synchronises: a caller whose earlier launches may still read the buffers does that before it lets them grow.
+struct UnitSort {
+    DevBuf<int> skey, srow;      // [cap] the sorted (unit, row) pairs
+    DevBuf<int> tmp;             // radix_sort_rows' scratch
+    DevBuf<int> cs_table;        // counting sort (small maps): [K][blocks of 1 024 rows] counts, then [K] totals
+    long cs_blocks = 0;          // ... the blocks the table was sized for (0: no table)
+    long cap = 0;                // rows the buffers serve
+};
+
 // One row set (row_set.hpp) and everything derived from its rows: the one owner of these buffers.  The handle holds three --
 // `res` the resident training rows, `q` the query scratch (also the pageable streamed chunks), Slot::rows the pinned chunks.
 struct RowSet {
@@ -123,11 +134,7 @@ struct RowSet {
     // and the per-unit results.  Grown with the set's `cap` (diag_reserve), so nothing is allocated once a size has been seen.
     struct Diag {
         DevBuf<float> dist;                      // [cap] d_n
-        DevBuf<int> skey, srow;                  // [sort_cap] the stable sort's (unit, row) pairs
-        DevBuf<int> tmp;                         // radix_sort_rows' scratch
-        DevBuf<int> cs_table;                    // counting sort (small maps), as SegScratch's
-        long cs_blocks = 0;
-        long sort_cap = 0;                       // rows the sort's buffers serve
+        UnitSort sort;                           // the rows sorted by unit (grown with `cap` by the first per-unit query: diag_reserve_stats)
         DevBuf<int> start;                       // [K] first sorted position of every unit that has rows, else -1
         DevBuf<long long> count;                 // [K]
         DevBuf<double> sums;                     // [2 K] sum | sum of squares
@@ -312,13 +319,9 @@ struct som_handle {
     int n_cus = 0;
     // BMU-ordered view of a row set + the partial lists of the segment sum's upper levels (update.hpp)
     struct SegScratch {
-        DevBuf<int> skey, srow;
-        DevBuf<int> tmp;                         // radix_sort_rows' scratch
+        UnitSort sort;                           // (its cap: the rows this scratch serves)
         DevBuf<int> kA, kB;                      // keys of the level-1 / level-2 lists (ping-pong from there on)
         DevBuf<float> vA, vB;                    // their vectors [entries][D1p]
-        long cap = 0;                            // rows this scratch serves
-        DevBuf<int> cs_table;                    // counting sort (small maps): [K][blocks of 1 024 rows] counts, then [K] totals
-        long cs_blocks = 0;
     };
     SegScratch seg;                              // resident rows
     DevBuf<float> xmax2;     // [0] resident rows, [1] every transient row set: max_n |x~_n|^2 (RowSet::xmax2)
@@ -379,7 +382,8 @@ struct som_handle {
     int vf_cap = 0;
     int64_t verify_launches = 0, verify_rows_checked = 0;
     bool fuse_merge_prep = true; // SOM_FUSE_MERGE=0: separate merge and operand-preparation launches (A/B)
-    bool counting_sort = true;   // SOM_COUNTING_SORT=0: rocPRIM's sort on small maps too (A/B)
+    bool counting_sort = true;   // SOM_COUNTING_SORT=0: the radix sort on small maps too (A/B)
+    int64_t sorts_counting = 0, sorts_radix = 0;   // sorts by unit of each kind since som_create (som_debug_unit_sort_stats)
     // read once in som_create (experiments / A-B runs): forced part counts, launch-geometry printing
     int env_bf16_parts = 0;
     int env_f32_parts = 0;   // SOM_F32_PARTS: the float32 resident kernel's part count (clamped to [1, fr_stages])
@@ -1058,6 +1062,66 @@ int launch_bmu_pairwise(som_handle* h, const float* X, long N, int p, bool even,
     return 0;
 }
 
+// ---- the sort by unit (unit_sort.hpp: the rule; update.hpp: the kernels) ----------------------------------------------------
+// The stable radix sort of update.hpp: (keys_in, row index) -> (keys_out, vals_out), `bits` key bits, 8 a pass.  scratch: two
+// pairs of n ints + the 256 x blocks table (radix_scratch_ints).  keys_in is left intact.
+int radix_sort_rows(som_handle* h, const int* keys_in, long n, int bits, int* keys_out, int* vals_out, int* scratch) {
+    if (n <= 0) return 0;
+    const int B = (int)cdiv(n, RS_BLOCK);
+    int* ka = scratch; int* va = scratch + n; int* kb = scratch + 2 * n; int* vb = scratch + 3 * n;
+    int* table = scratch + 4 * n;
+    int* tot = table + 256L * B;
+    const int passes = std::max(1, (int)cdiv(bits, 8));
+    const int* kin = keys_in; const int* vin = nullptr;
+    for (int p = 0; p < passes; ++p) {
+        const bool last = p == passes - 1;
+        int* ko = last ? keys_out : (p & 1) ? kb : ka;
+        int* vo = last ? vals_out : (p & 1) ? vb : va;
+        rs_hist_kernel<<<dim3((unsigned)B), dim3(256), 0, h->stream>>>(kin, n, 8 * p, B, table);
+        rs_scan_kernel<<<dim3(64), dim3(256), 0, h->stream>>>(table, B, tot);
+        rs_scatter_kernel<<<dim3((unsigned)B), dim3(256), 0, h->stream>>>(kin, vin, n, 8 * p, B, table, tot, ko, vo);
+        kin = ko; vin = vo;
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// the buffers for up to `rows` rows, as unitsort::sizes says: they only grow (free first, then allocate)
+int reserve(som_handle* h, UnitSort& u, long rows) {
+    if (rows <= u.cap) return 0;
+    u.skey.reset(); u.srow.reset(); u.tmp.reset(); u.cs_table.reset(); u.cs_blocks = 0; u.cap = 0;
+    if (rows > 0x7fffffffL) return fail(h, "more than 2^31-1 rows per GPU in one row set");   // (the sort holds row indices as ints)
+    const unitsort::Sizes z = unitsort::sizes(rows, h->K, h->counting_sort);
+    if (int rc = u.skey.alloc(h, z.skey)) return rc;
+    if (int rc = u.srow.alloc(h, z.srow)) return rc;
+    if (int rc = u.tmp.alloc(h, z.scratch)) return rc;
+    if (z.table) if (int rc = u.cs_table.alloc(h, z.table)) return rc;
+    u.cs_blocks = z.cs_blocks;
+    u.cap = rows;
+    return 0;
+}
+
+// (skey, srow) = the N rows sorted by their unit `bmu`, rows ascending inside a unit (stable): the counting sort where
+// unitsort::counting says so -- the table is held, the rows fit it and fill two blocks --, else the radix sort
+int sort_rows_by_unit(som_handle* h, UnitSort& u, const int* bmu, long N) {
+    if (N <= 0) return 0;
+    const int bits = unitsort::key_bits(h->K);
+    if (!unitsort::counting(u.cs_blocks, N)) {
+        h->sorts_radix += 1;
+        return radix_sort_rows(h, bmu, N, bits, u.skey, u.srow, u.tmp);
+    }
+    // few units: a stable counting sort in three launches (same order as the radix sort: unit, then row)
+    const int B = (int)cdiv(N, CS_BLOCK);
+    int* tot = u.cs_table + (long)B * h->K;             // (the totals behind THESE rows' blocks, not behind the table's)
+    const size_t lds = (size_t)h->K * sizeof(int);
+    cs_hist_kernel<<<dim3((unsigned)B), dim3(256), lds, h->stream>>>(bmu, N, h->K, B, u.cs_table);
+    cs_scan_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(u.cs_table, h->K, B, tot);
+    cs_scatter_kernel<<<dim3((unsigned)B), dim3(CS_BLOCK), lds, h->stream>>>(bmu, N, h->K, B, bits, u.cs_table, tot, u.skey, u.srow);
+    HIPCHK(h, hipGetLastError());
+    h->sorts_counting += 1;
+    return 0;
+}
+
 #include "exact_host.hpp"   // launch_bmu_exact and everything it drives (precision 'exact'): same translation unit
 
 // ---- canary: re-score a strided sample of a BMU launch's rows with the float32 kernel (bmu_exact.hpp) -------------
@@ -1164,26 +1228,17 @@ int reserve(som_handle* h, RowSet& s, long n, bool with_rows) {
 // scratch for the segment sum of up to `rows` rows (sort buffers + the partial lists of levels 1 and 2;
 // level 3 reuses level 1's, and so on)
 int seg_reserve(som_handle* h, som_handle::SegScratch& sg, long rows) {
-    if (rows <= sg.cap) return 0;
-    sg = som_handle::SegScratch{};
-    if (rows > 0x7fffffffL) return fail(h, "more than 2^31-1 rows per GPU in one row set");
-    if (int rc = sg.skey.alloc(h, (size_t)rows)) return rc;
-    if (int rc = sg.srow.alloc(h, (size_t)rows)) return rc;
-    if (int rc = sg.tmp.alloc(h, radix_scratch_ints(rows))) return rc;
+    if (rows <= sg.sort.cap) return 0;
+    sg.kA.reset(); sg.vA.reset(); sg.kB.reset(); sg.vB.reset();
     const int nw = seg_waves_per_block(h->D1p);
     const long n1 = seg_next_entries(rows, SEG_CHUNK, nw), n2 = seg_next_entries(n1, SEG_CHUNK_UP, nw);
-    if (int rc = sg.kA.alloc(h, (size_t)n1)) return rc;
-    if (int rc = sg.vA.alloc(h, (size_t)n1 * h->D1p)) return rc;
-    if (int rc = sg.kB.alloc(h, (size_t)n2)) return rc;
-    if (int rc = sg.vB.alloc(h, (size_t)n2 * h->D1p)) return rc;
-    // small maps: the counting sort's table (update.hpp); SOM_COUNTING_SORT=0 keeps rocPRIM's sort (A/B)
-    const long csb = cdiv(rows, CS_BLOCK);
-    if (h->counting_sort && h->K <= CS_MAX_K && rows >= 2 * CS_BLOCK && csb * h->K <= (1L << 21)) {
-        if (int rc = sg.cs_table.alloc(h, (size_t)(csb + 1) * h->K)) return rc;
-        sg.cs_blocks = csb;
-    }
-    sg.cap = rows;
-    return 0;
+    int rc = reserve(h, sg.sort, rows);
+    if (!rc) rc = sg.kA.alloc(h, (size_t)n1);
+    if (!rc) rc = sg.vA.alloc(h, (size_t)n1 * h->D1p);
+    if (!rc) rc = sg.kB.alloc(h, (size_t)n2);
+    if (!rc) rc = sg.vB.alloc(h, (size_t)n2 * h->D1p);
+    if (rc) sg = som_handle::SegScratch{};               // (refused part of the way: nothing half allocated is used, the next call tries again)
+    return rc;
 }
 
 // one level of the run sum over n entries; returns the number of workgroups it used
@@ -1220,23 +1275,6 @@ long launch_runsum(som_handle* h, const float* X, const int* keys, const int* sr
     return blocks;
 }
 
-// (skey, srow) = the N rows sorted by their unit `bmu`, rows ascending inside a unit (stable): the counting sort where the caller
-// holds its table (cs_table: [cs_blocks + 1][K] ints) and the rows fill two blocks, else the radix sort (tmp: radix_scratch_ints)
-int sort_rows_by_unit(som_handle* h, const int* bmu, long N, int bits, int* skey, int* srow, int* tmp, int* cs_table, long cs_blocks) {
-    const int B = (int)cdiv(N, CS_BLOCK);
-    if (cs_table != nullptr && B <= cs_blocks && N >= 2 * CS_BLOCK) {
-        // few units: a stable counting sort in three launches (same order as the radix sort: unit, then row)
-        int* tot = cs_table + (long)B * h->K;
-        const size_t lds = (size_t)h->K * sizeof(int);
-        cs_hist_kernel<<<dim3((unsigned)B), dim3(256), lds, h->stream>>>(bmu, N, h->K, B, cs_table);
-        cs_scan_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(cs_table, h->K, B, tot);
-        cs_scatter_kernel<<<dim3((unsigned)B), dim3(CS_BLOCK), lds, h->stream>>>(bmu, N, h->K, B, bits, cs_table, tot, skey, srow);
-        HIPCHK(h, hipGetLastError());
-        return 0;
-    }
-    return radix_sort_rows(h, bmu, N, bits, skey, srow, tmp);
-}
-
 // SC[b] += sum of the rows whose BMU is b (and their count): sort by BMU, then the levels of update.hpp's
 // run sum (rows -> partial lists) until one workgroup holds the whole list.  zero_first: SC starts from zero and
 // every unit is written once (plain stores); otherwise the chunk's sums are added to what SC holds.
@@ -1247,12 +1285,10 @@ int segsum_rows(som_handle* h, const Rows& r, som_handle::SegScratch& sg, bool z
     if (zero_first && !(h->early.done && r.resident))   // (exact mode: already zeroed before the pass's read-back)
         HIPCHK(h, hipMemsetAsync(h->SC, 0, (size_t)h->K * (h->D1p + 1) * sizeof(float), h->stream));
     if (N > 0) {
-        if (N > sg.cap) return fail(h, "segment sum: scratch smaller than the row set");
-        int bits = 1;
-        while ((1L << bits) < h->K) ++bits;
-        if (int rc = sort_rows_by_unit(h, bmu, N, bits, sg.skey, sg.srow, sg.tmp, sg.cs_table, sg.cs_blocks)) return rc;
+        if (N > sg.sort.cap) return fail(h, "segment sum: scratch smaller than the row set");
+        if (int rc = sort_rows_by_unit(h, sg.sort, bmu, N)) return rc;
         const int acc = zero_first ? 0 : 1;
-        long blocks = launch_runsum<true>(h, X, sg.skey, sg.srow, nullptr, N, acc, sg.kA, sg.vA, r.wgt);
+        long blocks = launch_runsum<true>(h, X, sg.sort.skey, sg.sort.srow, nullptr, N, acc, sg.kA, sg.vA, r.wgt);
         int *kin = sg.kA, *kout = sg.kB;
         float *vin = sg.vA, *vout = sg.vB;
         while (blocks > 1) {                             // 2 * blocks entries are waiting in (kin, vin)
@@ -2064,7 +2100,7 @@ static int stream_rows(som_handle* h, const float* x_host, const float* w_host, 
     if (n_rows == 0) return 0;
     if (n_rows > 0x7fffffffL) return fail(h, "som_stream_rows: more than 2^31-1 rows in one chunk");
     const bool pinned = is_pinned_host(x_host);
-    if (n_rows > h->st_seg.cap) {
+    if (n_rows > h->st_seg.sort.cap) {
         HIPCHK(h, hipStreamSynchronize(h->stream));       // earlier chunks' kernels still read the old scratch
         if (int rc = seg_reserve(h, h->st_seg, round_up(n_rows, 1024))) return rc;
     }
@@ -2617,18 +2653,15 @@ int diag_reserve_stats(som_handle* h, RowSet& s) {
     if (int rc = g.count.reserve(h, (size_t)h->K)) return rc;
     if (int rc = g.sums.reserve(h, 2 * (size_t)h->K)) return rc;
     if (int rc = g.max.reserve(h, (size_t)h->K)) return rc;
-    if (s.N > 0x7fffffffL) return fail(h, "more than 2^31-1 rows per GPU in one row set");   // (the sort holds row indices as ints)
-    if (s.cap <= g.sort_cap) return 0;
-    g.skey.reset(); g.srow.reset(); g.tmp.reset(); g.cs_table.reset(); g.cs_blocks = 0; g.sort_cap = 0;
-    if (int rc = g.skey.alloc(h, (size_t)s.cap)) return rc;
-    if (int rc = g.srow.alloc(h, (size_t)s.cap)) return rc;
-    if (int rc = g.tmp.alloc(h, radix_scratch_ints(s.cap))) return rc;
-    const long csb = cdiv(s.cap, CS_BLOCK);                            // (seg_reserve's rule for the counting sort's table)
-    if (h->counting_sort && h->K <= CS_MAX_K && s.cap >= 2 * CS_BLOCK && csb * h->K <= (1L << 21)) {
-        if (int rc = g.cs_table.alloc(h, (size_t)(csb + 1) * h->K)) return rc;
-        g.cs_blocks = csb;
-    }
-    g.sort_cap = s.cap;
+    return reserve(h, g.sort, s.cap);
+}
+// the set's rows sorted by unit (diag.sort) and every unit's first sorted position (diag.start; -1: the unit has no rows)
+int sort_rows_with_heads(som_handle* h, RowSet& s) {
+    auto& g = s.diag;
+    if (int rc = sort_rows_by_unit(h, g.sort, s.bmu, s.N)) return rc;
+    HIPCHK(h, hipMemsetAsync(g.start, 0xff, (size_t)h->K * sizeof(int), h->stream));
+    unit_heads_kernel<<<dim3((unsigned)cdiv(s.N, 256)), dim3(256), 0, h->stream>>>(g.sort.skey, s.N, h->K, g.start);
+    HIPCHK(h, hipGetLastError());
     return 0;
 }
 int query_bmu_distances(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, int32_t* ids_out,
@@ -2660,12 +2693,8 @@ int query_unit_stats(som_handle* h, const std::string& who, const float* x_host,
     if (int rc = run_bmu_distances(h)) return rc;
     {
         Timed t(h, SOM_K_SEGSUM);                                       // (the sort by unit and the reduction over its segments)
-        int bits = 1;
-        while ((1L << bits) < h->K) ++bits;
-        if (int rc = sort_rows_by_unit(h, q.bmu, q.N, bits, g.skey, g.srow, g.tmp, g.cs_table, g.cs_blocks)) return rc;
-        HIPCHK(h, hipMemsetAsync(g.start, 0xff, K * sizeof(int), h->stream));       // -1: the unit has no rows
-        unit_heads_kernel<<<dim3((unsigned)cdiv(q.N, 256)), dim3(256), 0, h->stream>>>(g.skey, q.N, h->K, g.start);
-        unit_stats_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(g.start, g.skey, g.srow, g.dist, q.N, h->K, g.count,
+        if (int rc = sort_rows_with_heads(h, q)) return rc;
+        unit_stats_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(g.start, g.sort.skey, g.sort.srow, g.dist, q.N, h->K, g.count,
                                                                                      g.sums, g.sums + K, g.max);
         HIPCHK(h, hipGetLastError());
     }
@@ -2688,18 +2717,12 @@ int project_check(som_handle* h, const std::string& who, const char* what, bool 
 // the query set's rows are on the device: their units under the configured distance (som_bmu ACTIVATION's own steps), the rows
 // sorted by unit and every segment's start -- in diag_reserve_stats's buffers, which som_unit_stats* shares
 int project_segments(som_handle* h) {
-    RowSet& q = h->q; auto& g = q.diag;
+    RowSet& q = h->q;
     if (int rc = diag_reserve_stats(h, q)) return rc;
     if (int rc = prepare(h, q, needs_xsq(h))) return rc;
     if (int rc = run_activation_bmu(h, q.view())) return rc;
     Timed t(h, SOM_K_SEGSUM);                                           // (the sort by unit; the caller's reduction joins it)
-    int bits = 1;
-    while ((1L << bits) < h->K) ++bits;
-    if (int rc = sort_rows_by_unit(h, q.bmu, q.N, bits, g.skey, g.srow, g.tmp, g.cs_table, g.cs_blocks)) return rc;
-    HIPCHK(h, hipMemsetAsync(g.start, 0xff, (size_t)h->K * sizeof(int), h->stream));       // -1: the unit has no rows
-    unit_heads_kernel<<<dim3((unsigned)cdiv(q.N, 256)), dim3(256), 0, h->stream>>>(g.skey, q.N, h->K, g.start);
-    HIPCHK(h, hipGetLastError());
-    return 0;
+    return sort_rows_with_heads(h, q);
 }
 int query_unit_label_counts(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, const void* labels,
                             int64_t n_rows, int32_t n_classes, int64_t* counts) {
@@ -2719,7 +2742,7 @@ int query_unit_label_counts(som_handle* h, const std::string& who, const float* 
     if (int rc = project_segments(h)) return rc;
     {
         Timed t(h, SOM_K_SEGSUM);
-        unit_label_counts_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(g.start, g.skey, g.srow, lab, q.N, h->K,
+        unit_label_counts_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(g.start, g.sort.skey, g.sort.srow, lab, q.N, h->K,
                                                                                             n_classes, g.pcount);
         HIPCHK(h, hipGetLastError());
     }
@@ -2748,7 +2771,7 @@ int query_unit_value_sums(som_handle* h, const std::string& who, const float* x_
     if (int rc = project_segments(h)) return rc;
     {
         Timed t(h, SOM_K_SEGSUM);
-        unit_value_sums_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(g.start, g.skey, g.srow, val, q.N, h->K, n_cols,
+        unit_value_sums_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(g.start, g.sort.skey, g.sort.srow, val, q.N, h->K, n_cols,
                                                                                           g.pcount, g.psums, g.psums + KC);
         HIPCHK(h, hipGetLastError());
     }
@@ -3009,6 +3032,21 @@ int som_debug_row_set_sizes(int32_t kind, int64_t n, int32_t input_len, int32_t 
     if (kind < 0 || kind > 2 || n < 0 || input_len < 1 || dp < 0 || !out5) return 1;
     const rowset::Sizes z = rowset::sizes((rowset::Kind)kind, (long)n, input_len, dp, {(flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, (flags & 8) != 0});
     out5[0] = z.cap; out5[1] = (int64_t)z.X; out5[2] = (int64_t)z.xsq; out5[3] = (int64_t)z.Xb; out5[4] = (int64_t)z.ids;
+    return 0;
+}
+
+int som_debug_unit_sort_sizes(int64_t rows_cap, int32_t K, int32_t counting_on, int64_t n, int64_t* out6) {
+    if (rows_cap < 0 || n < 0 || K < 1 || !out6) return 1;
+    const unitsort::Sizes z = unitsort::sizes((long)rows_cap, K, counting_on != 0);
+    out6[0] = (int64_t)z.skey; out6[1] = (int64_t)z.srow; out6[2] = (int64_t)z.scratch; out6[3] = (int64_t)z.table;
+    out6[4] = z.cs_blocks; out6[5] = unitsort::counting(z, (long)n) ? 1 : 0;
+    return 0;
+}
+
+int som_debug_unit_sort_stats(som_handle* h, int64_t* counting, int64_t* radix) {
+    if (!h || !counting || !radix) return fail(h, "som_debug_unit_sort_stats: NULL argument");
+    *counting = h->sorts_counting;
+    *radix = h->sorts_radix;
     return 0;
 }
 

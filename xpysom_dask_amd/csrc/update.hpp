@@ -22,11 +22,12 @@
 #pragma once
 #include <type_traits>
 #include "som_common.hpp"
+#include "unit_sort.hpp"   // RS_BLOCK, CS_MAX_K, CS_BLOCK: the sorts' block sizes, beside the rule that sizes their buffers
 
 namespace somhip {
 
 // ---- segment sum: SC[b][0..D-1] = sum_{bmu_n = b} x_n ; SC[b][D] = #{bmu_n = b} ------------------
-// The rows are first ordered by BMU (stable radix sort of (bmu_n, n) pairs, rocPRIM: the sorted order is a
+// The rows are first ordered by BMU (stable sort of (bmu_n, n) pairs, below: the sorted order is a
 // function of the BMUs alone).  A unit's rows are then ONE run of the sorted order, and the sum of a run is
 // formed by a tree whose shape depends on N only -- no atomics, one fixed order:
 //   wave   walks a chunk of consecutive entries (level 0: SEG_CHUNK sorted rows, gathered as whole 4*D-byte rows,
@@ -58,8 +59,6 @@ constexpr int SEG_MAX_WAVES = 16;  // waves per workgroup (fewer when 2 * waves 
 //                      destination = its run's cursor + its rank among the wave's items of the same digit: the order of equal
 //                      digits is the order of the items -- STABLE, and the same order on every run (no atomics decide a place)
 // vin == nullptr: the values are the items' own indices (first pass of a sort of row ids).
-constexpr int RS_BLOCK = 2048;
-
 __global__ __launch_bounds__(256) void rs_hist_kernel(const int* __restrict__ keys, long n, int shift, int B, int* __restrict__ table) {
     __shared__ int hist[256];
     hist[threadIdx.x] = 0;
@@ -143,16 +142,13 @@ __global__ __launch_bounds__(256) void rs_scatter_kernel(const int* __restrict__
 
 // ---- stable counting sort of the rows by BMU for maps of at most CS_MAX_K units ------------------------------------
 // (sorted by unit, rows ascending inside a unit: exactly what the stable radix sort returns, so the run sum adds in the same
-// fixed order.)  rocPRIM's merge sort takes six to seven launches at 100 000 rows (55 us of a 0.4 ms epoch at 64 x 64 x 32);
+// fixed order.)  The library merge sort used before took six to seven launches at 100 000 rows (55 us of a 0.4 ms epoch at 64 x 64 x 32);
 // with few units a histogram per 1 024-row block is small: table[unit][block], three launches.
 //   cs_hist_kernel     block = 1 024 rows: LDS histogram of its units -> table[k * B + block]
 //   cs_scan_kernel     wave per unit: exclusive scan of its B block counts in place, the unit's total -> tot[k]
 //   cs_scatter_kernel  block = 1 024 rows: first destination of every (unit, block) = scan of tot over the units + the block's
 //                      prefix; the block's 16 waves take their turns in order, a wave ranks its rows among equal units by
 //                      ballots over the unit's bits (lower lane = lower row first)
-constexpr int CS_MAX_K = 8192;        // units (LDS: 4 bytes per unit)
-constexpr int CS_BLOCK = 1024;        // rows per block
-
 __global__ __launch_bounds__(256) void cs_hist_kernel(const int* __restrict__ bmu, long N, int K, int B, int* __restrict__ table) {
     extern __shared__ int cs_lds[];
     for (int k = threadIdx.x; k < K; k += 256) cs_lds[k] = 0;

@@ -529,6 +529,13 @@ class HipEngine:
         self._check(self._lib.som_debug_exact_select_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def unit_sort_stats(self):
+        """(counting sorts, radix sorts) of rows by their unit the engine ran so far: the segment sums of resident rows and
+        streamed chunks, the per-unit queries (csrc/unit_sort.hpp holds the rule that chooses)."""
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self._lib.som_debug_unit_sort_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def band_tables(self):
         """(bands on, entries [n][2], P1 [nt][Y][Y], P2 [X][nt * X]): the neighbourhood tables of the last build and the nonzero
         column ranges recorded with them, read back from the device (som_debug_band_tables, include/somhip_test.h)."""
