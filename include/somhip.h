@@ -333,6 +333,30 @@ int som_unit_label_counts_device(som_handle* h, const void* x_dev, const void* l
 int som_unit_value_sums(som_handle* h, const float* x_host, const float* v_host, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq);
 int som_unit_value_sums_device(som_handle* h, const void* x_dev, const void* v_dev, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq);
 
+/* Row moments, for the codebook initialisers (not in the reference; csrc/moments.hpp).  With d_n = x_n - pivot formed in float32
+ * (pivot: input_len host floats, NULL = 0) and w_n the row's weight (NULL = 1):
+ *   *wsum = sum_n w_n      s1[a] = sum_n w_n d_na      gram[a][b] = sum_n w_n d_na d_nb      (host arrays: s1 [input_len], gram
+ *   [input_len][input_len], full and symmetric -- gram[a][b] and gram[b][a] are the same bits; gram == NULL: only the sums, the
+ *   cheap memory-bound pass).  Any pivot is exact for the covariance: cov = (gram - s1 s1^T / wsum) / divisor.
+ * wsum and s1 add exact double products in double.  gram: fl(w_n d_na) * d_nb on v_mfma_f32_32x32x2_f32, a float32 chain per chunk
+ * of SOM_MOMENTS_CHUNK_ROWS rows (include/somhip_test.h), the chunks' results added in double.  A row of weight 0 is left out as in
+ * training: its features reach no sum, whatever they hold.  Weights of 1.0 give the unweighted call bit for bit.  There is no NaN
+ * handling: a NaN or Inf in a contributing row makes s1 non-finite, which the caller tests.
+ * No floating-point atomics; every order of addition is a function of (n_rows, input_len) alone: the same rows give the same bits
+ * twice, and the device entry returns the host entry's bits (the host entry stages rows and weights and runs the same kernels).
+ * A query: the handle's resident rows, their weights and ids and the exact mode's plans stay as they were.  Scratch is the
+ * handle's, grown on demand, freed by som_destroy.
+ * Refused: input_len > SOM_MOMENTS_MAX_FEATURES (before any launch), n_rows < 0 or > 2^31-1, a NULL wsum / s1 / rows pointer, a
+ * negative or non-finite HOST weight (device weights are unchecked, as in som_set_sample_weights_device).  n_rows == 0 writes zeros.
+ * The *_device form reads float32 rows [n_rows][input_len] and weights [n_rows] that already live in HBM (borrowed for the call;
+ * see som_bmu_device).
+ * som_gather_rows_device: out_host[i][:] = row idx_host[i] of the device block x_dev [n_rows][input_len], i < k; an index outside
+ * [0, n_rows) is refused. */
+#define SOM_MOMENTS_MAX_FEATURES 2048
+int som_row_moments(som_handle* h, const float* x_host, const float* w_host, int64_t n_rows, const float* pivot, double* wsum, double* s1, double* gram);
+int som_row_moments_device(som_handle* h, const void* x_dev, const void* w_dev, int64_t n_rows, const float* pivot, double* wsum, double* s1, double* gram);
+int som_gather_rows_device(som_handle* h, const void* x_dev, int64_t n_rows, const int64_t* idx_host, int64_t k, float* out_host);
+
 /* Training monitor (not in the reference): what an epoch did, measured from what the epoch itself left on the device -- the rows,
  * this epoch's BMU ids, the codebook W_t the epoch ran with (unchanged until som_epoch_merge) and the final accumulator.  No
  * second BMU search, no copy of the rows.  The epoch runs with W_t and produces W_{t+1}:

@@ -211,6 +211,14 @@ int som_debug_unit_sort_sizes(int64_t rows_cap, int32_t K, int32_t counting_on, 
  * queries): the path the rule above PREDICTS, observed.  Counted where the host launches a sort: a replayed graph's are not. */
 int som_debug_unit_sort_stats(som_handle* h, int64_t* counting, int64_t* radix);
 
+/* The ROW MOMENTS' launch geometry (csrc/moments.hpp) for n_rows rows of input_len features -- pure host arithmetic, NO device
+ * needed (tests/moments_ref.py mirrors the chunk length into its bound; tests/test_gpu_moments.py takes its boundary shapes from it).
+ *   out6 = {SOM_MOMENTS_CHUNK_ROWS: rows per float32 chain of the Gram kernel, 32 x 32 tiles with a-block <= b-block, row splits,
+ *           chunks in one round of the row split, workgroups of the sums kernel, SOM_MOMENTS_MAX_FEATURES}
+ *   Returns non-zero for a NULL out6, negative rows or input_len < 1. */
+#define SOM_MOMENTS_CHUNK_ROWS 256
+int som_debug_moments_plan(int64_t n_rows, int32_t input_len, int64_t* out6);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,11 @@ SIGNATURES = {
     "som_unit_value_sums": (C.c_int, [_H, _F, _F, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "som_unit_value_sums_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                              C.POINTER(C.c_double)]),
+    "som_row_moments": (C.c_int, [_H, _F, _F, C.c_int64, _F, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "som_row_moments_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, _F, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double)]),
+    "som_gather_rows_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int64, _F]),
+    "som_debug_moments_plan": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "som_monitor": (C.c_int, [_H, C.c_int32]),
     "som_epoch_measure_rows": (C.c_int, [_H]),
     "som_epoch_measure_shift": (C.c_int, [_H]),

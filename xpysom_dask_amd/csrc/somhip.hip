@@ -38,6 +38,7 @@
 #include "diag.hpp"
 #include "monitor.hpp"
 #include "project.hpp"
+#include "moments.hpp"
 
 using namespace somhip;
 
@@ -403,6 +404,17 @@ struct som_handle {
         DevBuf<som_epoch_metrics_t> m;           // the metrics of the epoch in flight
         som_epoch_metrics_t* m_host = nullptr;   // pinned: som_epoch_metrics' one read-back
     } mon;
+    // row moments and the row gather (moments.hpp; som_row_moments*, som_gather_rows_device): the one owner of their scratch, grown
+    // on demand and freed with the handle.  Size rule, for n rows of D features (moments_plan): X n * D and w n floats (the host
+    // entry's staged rows and weights), pivot D floats, spart mom_sum_grid(n) * (D + 1) and sums D + 1 doubles, gpart
+    // mom_splits(n, D) * mom_tiles(D) * 1024 and gram D * D doubles (only where the Gram matrix is asked for); the gather: idx k
+    // int64 and rows k * D floats
+    struct MomentsScratch {
+        DevBuf<float> X, w, pivot;
+        DevBuf<double> spart, sums, gpart, gram;
+        DevBuf<long long> idx;
+        DevBuf<float> rows;
+    } mom;
     bool searched = false;       // the resident ids are those of a search since the last som_epoch_merge
     bool async_copies = false;   // SOM_ASYNC_COPIES=1: round 1's original copy path (fresh_process_stress.py)
     int prof = 0;            // som_profile_enable: 0 off, 1 every kernel family, 2 the BMU family only
@@ -2795,6 +2807,96 @@ int som_unit_label_counts(som_handle* h, const float* x_host, const int32_t* lab
 int som_unit_label_counts_device(som_handle* h, const void* x_dev, const void* labels_dev, int64_t n_rows, int32_t n_classes, int64_t* counts) { return query_unit_label_counts(h, "som_unit_label_counts_device", nullptr, x_dev, labels_dev, n_rows, n_classes, counts); }
 int som_unit_value_sums(som_handle* h, const float* x_host, const float* v_host, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq) { return query_unit_value_sums(h, "som_unit_value_sums", x_host, nullptr, v_host, n_rows, n_cols, count, sum, sumsq); }
 int som_unit_value_sums_device(som_handle* h, const void* x_dev, const void* v_dev, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq) { return query_unit_value_sums(h, "som_unit_value_sums_device", nullptr, x_dev, v_dev, n_rows, n_cols, count, sum, sumsq); }
+
+// ---- row moments and the row gather (moments.hpp): queries that touch nothing of the engine's row sets, weights, ids or plans ----
+namespace {
+int row_moments(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, const void* w, int64_t n_rows,
+                const float* pivot, double* wsum, double* s1, double* gram) {
+    DeviceGuard dev_guard(h);
+    if (!h) return fail(h, who + ": NULL handle");
+    if (h->D > MOM_MAX_D)
+        return fail(h, who + ": input_len " + std::to_string(h->D) + " exceeds SOM_MOMENTS_MAX_FEATURES (" + std::to_string(MOM_MAX_D) + ")");
+    if (!wsum || !s1 || n_rows < 0 || (n_rows > 0 && !x_host && !x_dev)) return fail(h, who + ": bad argument");
+    if (n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows");
+    const int D = h->D;
+    if (x_host && w)
+        if (const int64_t bad = first_bad_weight((const float*)w, n_rows); bad >= 0) return fail_bad_weight(h, who.c_str(), (const float*)w, bad);
+    if (n_rows == 0) {
+        *wsum = 0.0;
+        std::memset(s1, 0, (size_t)D * sizeof(double));
+        if (gram) std::memset(gram, 0, (size_t)D * D * sizeof(double));
+        return 0;
+    }
+    auto& m = h->mom;
+    const long N = n_rows;
+    const float* X = (const float*)x_dev;
+    const float* wd = (const float*)w;
+    if (x_host) {
+        if (int rc = m.X.reserve(h, (size_t)N * D)) return rc;
+        if (int rc = h2d_blocking(h, m.X, x_host, (size_t)N * D * sizeof(float))) return rc;
+        X = m.X;
+        if (w) {
+            if (int rc = m.w.reserve(h, (size_t)N)) return rc;
+            if (int rc = h2d_blocking(h, m.w, w, (size_t)N * sizeof(float))) return rc;
+            wd = m.w;
+        }
+    }
+    if (int rc = m.pivot.reserve(h, (size_t)D)) return rc;
+    if (pivot) { if (int rc = h2d_blocking(h, m.pivot, pivot, (size_t)D * sizeof(float))) return rc; }
+    else HIPCHK(h, hipMemsetAsync(m.pivot, 0, (size_t)D * sizeof(float), h->stream));
+    const long sg = mom_sum_grid(N);
+    if (int rc = m.spart.reserve(h, (size_t)sg * (D + 1))) return rc;
+    if (int rc = m.sums.reserve(h, (size_t)D + 1)) return rc;
+    if (wd) moments_sums_kernel<true><<<dim3((unsigned)sg), dim3(256), 0, h->stream>>>(X, wd, m.pivot, N, D, m.spart);
+    else moments_sums_kernel<false><<<dim3((unsigned)sg), dim3(256), 0, h->stream>>>(X, nullptr, m.pivot, N, D, m.spart);
+    moments_sums_reduce_kernel<<<dim3((unsigned)cdiv(D + 1, 64)), dim3(64 * MOM_RED_WAVES), 0, h->stream>>>(m.spart, (int)sg, D, m.sums);
+    HIPCHK(h, hipGetLastError());
+    if (gram) {
+        const long T = mom_tiles(D), S = mom_splits(N, D);
+        if (int rc = m.gpart.reserve(h, (size_t)S * T * MOM_TILE)) return rc;
+        if (int rc = m.gram.reserve(h, (size_t)D * D)) return rc;
+        const dim3 grid((unsigned)mom_tile_groups(D), (unsigned)S);
+        if (wd) moments_gram_kernel<true><<<grid, dim3(256), 0, h->stream>>>(X, wd, m.pivot, N, D, m.gpart);
+        else moments_gram_kernel<false><<<grid, dim3(256), 0, h->stream>>>(X, nullptr, m.pivot, N, D, m.gpart);
+        moments_gram_reduce_kernel<<<dim3((unsigned)T, 16), dim3(64 * MOM_RED_WAVES), 0, h->stream>>>(m.gpart, S, D, m.gram);
+        HIPCHK(h, hipGetLastError());
+    }
+    if (int rc = d2h_blocking(h, s1, m.sums, (size_t)D * sizeof(double))) return rc;
+    if (int rc = d2h_blocking(h, wsum, m.sums + D, sizeof(double))) return rc;
+    if (gram) return d2h_blocking(h, gram, m.gram, (size_t)D * D * sizeof(double));
+    return 0;
+}
+}  // namespace
+
+int som_row_moments(som_handle* h, const float* x_host, const float* w_host, int64_t n_rows, const float* pivot, double* wsum, double* s1, double* gram) { return row_moments(h, "som_row_moments", x_host, nullptr, w_host, n_rows, pivot, wsum, s1, gram); }
+int som_row_moments_device(som_handle* h, const void* x_dev, const void* w_dev, int64_t n_rows, const float* pivot, double* wsum, double* s1, double* gram) { return row_moments(h, "som_row_moments_device", nullptr, x_dev, w_dev, n_rows, pivot, wsum, s1, gram); }
+
+int som_gather_rows_device(som_handle* h, const void* x_dev, int64_t n_rows, const int64_t* idx_host, int64_t k, float* out_host) {
+    DeviceGuard dev_guard(h);
+    if (!h || n_rows < 0 || k < 0 || (k > 0 && (!x_dev || !idx_host || !out_host))) return fail(h, "som_gather_rows_device: bad argument");
+    if (k > 0x7fffffffL) return fail(h, "som_gather_rows_device: more than 2^31-1 rows asked for");
+    for (int64_t i = 0; i < k; ++i)
+        if (idx_host[i] < 0 || idx_host[i] >= n_rows)
+            return fail(h, "som_gather_rows_device: index " + std::to_string(idx_host[i]) + " (entry " + std::to_string(i) + ") is outside the block of " + std::to_string(n_rows) + " rows");
+    if (k == 0) return 0;
+    auto& m = h->mom;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the indices are copied in as int64_t");
+    if (int rc = m.idx.reserve(h, (size_t)k)) return rc;
+    if (int rc = m.rows.reserve(h, (size_t)k * h->D)) return rc;
+    if (int rc = h2d_blocking(h, m.idx, idx_host, (size_t)k * sizeof(int64_t))) return rc;
+    const long g = std::min<long>(cdiv((long)k * h->D, 256), 4096);
+    gather_rows_kernel<<<dim3((unsigned)g), dim3(256), 0, h->stream>>>((const float*)x_dev, m.idx, (long)k, h->D, m.rows);
+    HIPCHK(h, hipGetLastError());
+    return d2h_blocking(h, out_host, m.rows, (size_t)k * h->D * sizeof(float));
+}
+
+int som_debug_moments_plan(int64_t n_rows, int32_t input_len, int64_t* out6) {
+    static_assert(MOM_R == SOM_MOMENTS_CHUNK_ROWS && MOM_MAX_D == SOM_MOMENTS_MAX_FEATURES, "the headers state the kernels' constants");
+    if (!out6 || n_rows < 0 || input_len < 1) return 1;
+    out6[0] = MOM_R; out6[1] = mom_tiles(input_len); out6[2] = mom_splits(n_rows, input_len); out6[3] = mom_split_cap(input_len);
+    out6[4] = mom_sum_grid(n_rows); out6[5] = MOM_MAX_D;
+    return 0;
+}
 
 int som_bmu_f64(som_handle* h, const double* x_host, int64_t n_rows, int32_t* ids_out) {
     DeviceGuard dev_guard(h);

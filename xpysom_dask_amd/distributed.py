@@ -201,6 +201,29 @@ def _allreduce_row_sums(engine, m, world):
     m.update(sum_wd=wd, sum_w=w, rows=int(rows), changed=int(changed) if known else -1)
 
 
+def allreduce_moments(engine, world, *parts):
+    """The initialisers' row moments (a float and float64 arrays: wsum, s1, the Gram matrix) added over the ranks as ONE float64
+    tensor, the way _allreduce_row_sums does it -- on the device under nccl, on the CPU under gloo.  Returns them in the shapes they
+    came in; every rank then holds the same bits.  world == 1: returned as they are."""
+    if world == 1:
+        return parts
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    dev = torch.device("cuda", engine.device) if dist.get_backend() == "nccl" else torch.device("cpu")
+    flat = np.concatenate([np.asarray(p, dtype=np.float64).ravel() for p in parts])
+    t = torch.from_numpy(flat).to(dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    flat = t.cpu().numpy()
+    out, at = [], 0
+    for p in parts:
+        shape = np.shape(p)
+        n = int(np.prod(shape)) if shape else 1
+        out.append(flat[at:at + n].reshape(shape).copy() if shape else float(flat[at]))
+        at += n
+    return tuple(out)
+
+
 def _epoch_monitored(engine, sigma, eta, neigh_f64, chunks, metrics):
     """`epoch` in its three-call form on every path, with the monitor's two launches in it:
     accumulate -> measure_rows -> all-reduce -> measure_shift -> merge -> ONE read-back, after the merge is queued."""

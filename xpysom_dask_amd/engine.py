@@ -436,6 +436,47 @@ class HipEngine:
         self._check(self._lib.som_unit_value_sums_device(self._h, C.c_void_p(dev_ptr), C.c_void_p(values_ptr), int(n_rows), n_cols, *ptrs))
         return out
 
+    # -- row moments and the row gather (include/somhip.h, som_row_moments / som_gather_rows_device) --
+    MOMENTS_MAX_FEATURES = 2048
+
+    def _moments_out(self, pivot, gram):
+        if pivot is not None:
+            pivot = _f32(pivot)
+            if pivot.shape != (self.D,):
+                raise ValueError("pivot must have one value per feature, got %r" % (pivot.shape,))
+        out = (C.c_double(), np.empty((self.D,), dtype=np.float64), np.empty((self.D, self.D), dtype=np.float64) if gram else None)
+        d = C.POINTER(C.c_double)
+        return pivot, out, (self._fp(pivot) if pivot is not None else None, C.byref(out[0]), out[1].ctypes.data_as(d),
+                            out[2].ctypes.data_as(d) if gram else None)
+
+    def row_moments(self, x, weights=None, pivot=None, gram=True):
+        """(wsum float, s1 float64 (D,), gram float64 (D, D) or None) of host rows about `pivot` (None: 0): sum w, sum w d and
+        sum w d d^T with d = x - pivot in float32.  A query: nothing of the engine's rows, weights or plans changes.  Deterministic."""
+        x = self._rows_arg(x)
+        if weights is not None:
+            weights = _f32(weights)
+            if weights.shape != (x.shape[0],):
+                raise ValueError("weights must have one value per row, got %r for %d rows" % (weights.shape, x.shape[0]))
+        pivot, out, ptrs = self._moments_out(pivot, gram)
+        self._check(self._lib.som_row_moments(self._h, self._fp(x), self._fp(weights) if weights is not None else None, x.shape[0], *ptrs))
+        return out[0].value, out[1], out[2]
+
+    def row_moments_device(self, dev_ptr, n_rows, weights_ptr=None, pivot=None, gram=True):
+        """row_moments of float32 rows (and weights, unchecked) that already live in HBM (`dev_ptr`: [n_rows][D], `weights_ptr`:
+        [n_rows] or None; both borrowed for the call): the host entry's bits."""
+        pivot, out, ptrs = self._moments_out(pivot, gram)
+        self._check(self._lib.som_row_moments_device(self._h, C.c_void_p(dev_ptr), C.c_void_p(weights_ptr) if weights_ptr else None,
+                                                     int(n_rows), *ptrs))
+        return out[0].value, out[1], out[2]
+
+    def gather_rows_device(self, dev_ptr, n_rows, idx):
+        """Rows idx[i] of a float32 device block [n_rows][D] as a host array (len(idx), D); an index outside the block is refused."""
+        idx = np.ascontiguousarray(idx, dtype=np.int64).ravel()
+        out = np.empty((idx.shape[0], self.D), dtype=np.float32)
+        self._check(self._lib.som_gather_rows_device(self._h, C.c_void_p(dev_ptr), int(n_rows), idx.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                     idx.shape[0], self._fp(out)))
+        return out
+
     # -- training monitor (include/somhip.h, som_monitor / som_epoch_measure_* / som_epoch_metrics) --
     def monitor(self, on=True):
         """Switch the training monitor on (the engine keeps every measured epoch's BMU ids beside the resident rows) or off

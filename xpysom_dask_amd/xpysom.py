@@ -277,6 +277,46 @@ def _to_device(host, device_index):
     return torch.from_numpy(host).to(torch.device("cuda", device_index))
 
 
+def _nan_init_message(what):
+    return "%s: the data holds NaN (missing values); initialise from complete rows" % what
+
+
+def _pca_codebook(cov, x, y):
+    """The reference's PCA codebook (xpysom.py:779-785) of a covariance matrix, (x, y, D): its own ``np.linalg.eig``, its own
+    formula -- ROWS of the eigenvector matrix, no mean, no scale --, one broadcast over the grid in place of the loop over the
+    units: the same elementwise arithmetic, hence the same bits."""
+    pc_length, pc = np.linalg.eig(cov)
+    order = np.argsort(-pc_length)
+    c1 = np.linspace(-1, 1, x)[:, None, None]
+    c2 = np.linspace(-1, 1, y)[None, :, None]
+    return c1 * pc[order[0]][None, None, :] + c2 * pc[order[1]][None, None, :]
+
+
+def _linear_codebook(wsum, mean, cov, x, y):
+    """The linear initialisation (the SOM Toolbox's ``lininit``) of an x * y map from weighted moments, (x, y, D) float64:
+    ``W[i, j] = mean + c_i sqrt(l1) v1 + c_j sqrt(l2) v2``, (l, v) the two leading eigenpairs of ``np.linalg.eigh(cov)`` (l clipped at
+    0), the FIRST axis along the longer side of the map (a tie: along x), coordinates ``linspace(-1, 1, side)`` (a side of 1: 0), and
+    every vector's sign fixed so that its first largest-magnitude component is positive.  ``wsum``: the weights' sum the moments
+    were divided by, which must be positive."""
+    mean = np.asarray(mean, dtype=np.float64)
+    cov = np.asarray(cov, dtype=np.float64)
+    if not wsum > 0:
+        raise ValueError('linear_weights_init: the sample weights sum to 0')
+    if not (np.isfinite(mean).all() and np.isfinite(cov).all()):
+        raise ValueError(_nan_init_message('linear_weights_init'))
+    lam, vec = np.linalg.eigh(cov)                       # ascending
+    axes = []
+    for k in (-1, -2):
+        v = vec[:, k]
+        if v[np.argmax(np.abs(v))] < 0:                  # (argmax: the first of equal magnitudes)
+            v = -v
+        axes.append(np.sqrt(max(lam[k], 0.0)) * v)
+    cx = np.linspace(-1, 1, x) if x > 1 else np.zeros(1)
+    cy = np.linspace(-1, 1, y) if y > 1 else np.zeros(1)
+    ax, ay = (axes[0], axes[1]) if x >= y else (axes[1], axes[0])
+    return mean[None, None, :] + cx[:, None, None] * ax[None, None, :] + cy[None, :, None] * ay[None, None, :]
+
+
 class XPySom:
     def __init__(self, x, y, input_len,
                  sigma=0, sigmaN=1,
@@ -528,7 +568,7 @@ class XPySom:
 
     def _refuse_nan_init(self, what, data):
         if getattr(self, '_missing', None) is not None and np.isnan(np.asarray(data, dtype=np.float64)).any():
-            raise ValueError("%s: the data holds NaN (missing values); initialise from complete rows" % what)
+            raise ValueError(_nan_init_message(what))
 
     def _check_input_len(self, data):
         """Checks that the data in input is of the correct shape (xpysom.py:360-366)."""
@@ -1038,28 +1078,149 @@ class XPySom:
         return winmap
 
     # ------------------------------------------------------------------ host-side initialisers
+    def _init_device_rows(self, dev, what):
+        """(pointer, n_rows, engine, owner) of device rows handed to an initialiser -- `dev`: what ``_device_rows`` returned for
+        them, resolved ONCE per call (each resolution waits for torch's stream and, for a tensor that is not contiguous float32,
+        makes a converted copy) --, checked and waited for.  The caller holds `owner` for as long as the pointer is in use: for a
+        converted tensor it is the only reference to the copy the pointer points into."""
+        ptr, n, d, dev_index, owner, stream = dev
+        if d != self._input_len:
+            raise ValueError('Received %d features, expected %d.' % (d, self._input_len))
+        if self._input_len > 2048 and what != 'random_weights_init':
+            raise ValueError('%s: the device moments take up to 2048 features, got %d' % (what, self._input_len))
+        eng = self._engine()
+        if dev_index is not None and dev_index != eng.device:
+            raise ValueError('device data lives on cuda:%d, the engine on cuda:%d' % (dev_index, eng.device))
+        if stream != "done":
+            eng.sync_producer(stream)
+        return ptr, n, eng, owner
+
+    def _row_moments(self, data, weights=None, what='linear_weights_init', grouped=False):
+        """``(wsum, mean, M)`` in float64 from the device moments (include/somhip.h, som_row_moments): ``wsum = sum w``, the weighted
+        mean, and ``M = sum w (x - mean)(x - mean)^T`` -- divide by ``wsum`` or ``n - 1`` for a covariance.  Two passes: the sums
+        give the mean, the Gram matrix is taken about ``float32(mean)`` and shifted exactly in float64, so the pivot's rounding costs
+        nothing.  Device rows in one call per pass; host rows in ``n_parallel`` chunks, every chunk's result added in chunk order.
+        ``grouped``: under a process group the rows (and weights) are cut as ``train`` cuts them and both passes are all-reduced, so
+        every rank returns the same bits.  ``weights``: what ``_check_sample_weight`` returned, or None."""
+        rank, world = _dist.dist_info() if grouped else (0, 1)
+        if world > 1 and not self._sharded_input:
+            shard = getattr(self, '_shard', 'contiguous')
+            data = _dist.shard_rows(data, rank, world, shard)
+            if weights is not None:
+                weights = _dist.shard_rows(weights, rank, world, shard)
+        dev = _device_rows(data)                         # (once, after the cut: see _init_device_rows)
+        if dev is not None:
+            # owner / wowner: whatever owns the rows and the weights behind ptr / wptr, held by `passes` until both passes are done
+            ptr, n, eng, owner = self._init_device_rows(dev, what)
+            wptr = wowner = None
+            if weights is not None:
+                if not _is_device_array(weights):        # host weights beside device rows: they join them on the device
+                    weights = _to_device(np.ascontiguousarray(weights, dtype=np.float32), eng.device)
+                wptr, wdev, wowner, wstream = _device_weights(weights)
+                if wdev is not None and wdev != eng.device:
+                    raise ValueError('sample_weight lives on cuda:%d, the engine on cuda:%d' % (wdev, eng.device))
+                if wstream != "done":
+                    eng.sync_producer(wstream)
+
+            def passes(pivot, gram, _keepalive=(owner, wowner)):
+                yield eng.row_moments_device(ptr, n, wptr, pivot, gram)
+        else:
+            data = np.asarray(data, dtype=np.float32)
+            if data.ndim != 2:
+                raise ValueError('data must be 2-dimensional (n_samples, input_len)')
+            if self._input_len > 2048:
+                raise ValueError('%s: the device moments take up to 2048 features, got %d' % (what, self._input_len))
+            eng = self._engine()
+            step = max(1, int(self._n_parallel))
+
+            def passes(pivot, gram):
+                for lo in range(0, len(data), step):
+                    yield eng.row_moments(data[lo:lo + step], None if weights is None else weights[lo:lo + step], pivot, gram)
+        D = self._input_len
+        wsum, s1 = 0.0, np.zeros(D)
+        for w_, s_, _ in passes(None, False):
+            wsum += w_
+            s1 += s_
+        wsum, s1 = _dist.allreduce_moments(eng, world, wsum, s1)
+        if not (np.isfinite(wsum) and np.isfinite(s1).all()):
+            raise ValueError(_nan_init_message(what))
+        if not wsum > 0:
+            raise ValueError('%s: the sample weights sum to 0' % what)
+        pivot = (s1 / wsum).astype(np.float32)
+        wsum, s1, G = 0.0, np.zeros(D), np.zeros((D, D))
+        for w_, s_, g_ in passes(pivot, True):
+            wsum += w_
+            s1 += s_
+            G += g_
+        wsum, s1, G = _dist.allreduce_moments(eng, world, wsum, s1, G)
+        if not (np.isfinite(s1).all() and np.isfinite(G).all()):
+            raise ValueError(_nan_init_message(what))
+        return wsum, pivot.astype(np.float64) + s1 / wsum, G - np.outer(s1, s1) / wsum
+
     def random_weights_init(self, data):
-        """Initializes the weights picking random samples from data (xpysom.py:749-759)."""
+        """Initializes the weights picking random samples from data (xpysom.py:749-759).  Rows that live in HBM are picked by the
+        same stream of indices and gathered on the device: the host path's codebook for the same seed, bit for bit."""
+        x, y, _ = self._weights.shape
+        dev = _device_rows(data)
+        if dev is not None:
+            ptr, n, eng, owner = self._init_device_rows(dev, 'random_weights_init')     # (owner: held until the gather is done)
+            if getattr(self, '_missing', None) is not None:
+                # as on the host path: any NaN in the data is refused BEFORE an index is drawn, so a refusal leaves the generator alone
+                import torch
+                if bool(torch.isnan(torch.as_tensor(owner, device=torch.device("cuda", eng.device))).any()):
+                    raise ValueError(_nan_init_message('random_weights_init'))
+            # (one call draws the stream of x * y scalar calls: tests/test_init_cpu.py pins it)
+            rows = eng.gather_rows_device(ptr, n, self._random_generator.randint(n, size=x * y))
+            del owner
+            self._weights[...] = rows.reshape(x, y, -1)
+            return
         self._check_input_len(data)
         self._refuse_nan_init('random_weights_init', data)
-        x, y, _ = self._weights.shape
         for i in range(x):
             for j in range(y):
                 self._weights[i, j] = data[self._random_generator.randint(len(data))]
 
     def pca_weights_init(self, data):
-        """Initializes the weights to span the first two principal components (xpysom.py:762-785)."""
+        """Initializes the weights to span the first two principal components (xpysom.py:762-785).  Rows that live in HBM: the
+        covariance (divisor n - 1, as ``np.cov``) comes from the device moments, then the same ``eig`` and formula."""
         if self._input_len == 1:
             raise ValueError('The data needs at least 2 features for pca initialization')
-        self._check_input_len(data)
-        self._refuse_nan_init('pca_weights_init', data)
+        on_device = _is_device_array(data)
+        if not on_device:
+            self._check_input_len(data)
+            self._refuse_nan_init('pca_weights_init', data)
+        elif _n_rows(data) < 2:                          # (np.cov's divisor n - 1)
+            raise ValueError('pca_weights_init: the data needs at least 2 rows, got %d' % _n_rows(data))
         if len(self._neigx) == 1 or len(self._neigy) == 1:
             warn('PCA initialization inappropriate:One of the dimensions of the map is 1.')
-        pc_length, pc = np.linalg.eig(np.cov(np.transpose(data)))
-        order = np.argsort(-pc_length)
-        for i, c1 in enumerate(np.linspace(-1, 1, len(self._neigx))):
-            for j, c2 in enumerate(np.linspace(-1, 1, len(self._neigy))):
-                self._weights[i, j] = c1 * pc[order[0]] + c2 * pc[order[1]]
+        if on_device:
+            wsum, _, M = self._row_moments(data, None, 'pca_weights_init')
+            cov = M / (wsum - 1.0)
+        else:
+            cov = np.cov(np.transpose(data))
+        self._weights[...] = _pca_codebook(cov, len(self._neigx), len(self._neigy))
+
+    def linear_weights_init(self, data, *, sample_weight=None):
+        """Places the map in the data (not in the reference; the SOM Toolbox's ``lininit``): the weighted mean plus the two leading
+        principal axes scaled by their standard deviations -- ``_linear_codebook`` of the weighted moments with divisor ``sum w``, so
+        an integer weight is the row repeated.  Host rows or rows that live in HBM; ``sample_weight`` as ``train`` takes it.  The
+        moments are computed on the device either way (``_row_moments``).  Under a process group the rows are cut as ``train`` cuts
+        them and every rank ends with the same codebook."""
+        if self._input_len == 1:
+            raise ValueError('The data needs at least 2 features for linear initialization')
+        on_device = _is_device_array(data)
+        if not on_device:
+            data = np.asarray(data, dtype=np.float32)
+            if data.ndim != 2:
+                raise ValueError('data must be 2-dimensional (n_samples, input_len)')
+            if len(data) > 0:
+                self._check_input_len(data)
+        weights = None
+        if sample_weight is not None:
+            weights = _check_sample_weight(sample_weight, _n_rows(data), on_device)
+        wsum, mean, M = self._row_moments(data, weights, 'linear_weights_init', grouped=True)
+        x, y, _ = self._weights.shape
+        self._weights = _linear_codebook(wsum, mean, M / wsum, x, y).astype(np.float32)
 
     # ------------------------------------------------------------------ pickling (xpysom.py:868-892)
     def __getstate__(self):
