@@ -211,6 +211,26 @@ int som_debug_unit_sort_sizes(int64_t rows_cap, int32_t K, int32_t counting_on, 
  * queries): the path the rule above PREDICTS, observed.  Counted where the host launches a sort: a replayed graph's are not. */
 int som_debug_unit_sort_stats(som_handle* h, int64_t* counting, int64_t* radix);
 
+/* The EXACT MODE'S SCRATCH rule (csrc/exact_scratch.hpp) on caller-supplied numbers -- pure host arithmetic, NO device and no
+ * handle needed (tests/test_exact_scratch_cpu.py).
+ *   geometry8 = {K, input_len, dp, stage_bytes, wide (0 | 1), item_slots, SOM_EXACT_PASS_ROWS (0: none), SOM_EXACT_PAIRS (0: none)}
+ *   out[0 .. 16): the stride ladder for `rows` rows -- first_stride without a cap, then next_stride of each -- zero from its end on
+ *   out[16 .. 75): one BLOCK at the ladder's first stride;  out[75 .. 134): one BLOCK at first_stride(rows, stride_cap).
+ * A BLOCK is 59 values, counts in elements of each buffer's own type:
+ *   [0]  pass:   stride, pairs, max_tiles, too_large, gmin, gflags, rowcnt, rowarg, seed, plist, fb_list, tile_tab, ctr
+ *   [13] centroid levels of the geometry (1 beyond 128 features, else 2)
+ *   [14] level 0, [23] level 1 (zeros where there is none): n_slots, n_cstages, n_img_stages, Cc, rg, csq, cmax2, Cst, Cst_plain
+ *   [32] a sorted pass of `rows` rows: cap, order, Xb_s, Xl_s, Xf_s, xsq_s, xerr_s, seed_s, sU_s, lastpos_s
+ *   [42] plan:   stride, tiles, sk_keys, sk_keys2, sk_vals, sk_tmp, scout_g, tq, need, need2, glist, gcnt, tlist, tcnt, tile_counts,
+ *                tile_ticket, items
+ * Returns non-zero for a NULL argument, rows < 1, a negative stride_cap, K < 1 or input_len < 1. */
+int som_debug_exact_scratch_sizes(const int64_t* geometry8, int64_t rows, int64_t stride_cap, int64_t* out);
+/* ... and what the handle's four owners HOLD now, read-only (nothing is launched or allocated): out[0 .. 59) one BLOCK in the order
+ * above -- capacities in elements, 0 for a buffer that is not held; levels 0 while no centroid set is held; the sorted pass is the
+ * resident rows' --, out[59 .. 69) the transient rows' sorted pass, out[69 .. 77) the geometry8 the handle sizes by,
+ * out[77 .. 79) the float32 fallback's dense rows and ids (fbX, fb_ids). */
+int som_debug_exact_scratch_held(som_handle* h, int64_t* out);
+
 /* The ROW MOMENTS' launch geometry (csrc/moments.hpp) for n_rows rows of input_len features -- pure host arithmetic, NO device
  * needed (tests/moments_ref.py mirrors the chunk length into its bound; tests/test_gpu_moments.py takes its boundary shapes from it).
  *   out6 = {SOM_MOMENTS_CHUNK_ROWS: rows per float32 chain of the Gram kernel, 32 x 32 tiles with a-block <= b-block, row splits,

@@ -127,6 +127,8 @@ SIGNATURES = {
     "som_debug_row_set_sizes": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "som_debug_unit_sort_sizes": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
     "som_debug_unit_sort_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "som_debug_exact_scratch_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "som_debug_exact_scratch_held": (C.c_int, [_H, C.POINTER(C.c_int64)]),
     "som_patch_order": (C.c_int, [C.c_int32, C.c_int32, _I]),
     "som_exact_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_exact_top2_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

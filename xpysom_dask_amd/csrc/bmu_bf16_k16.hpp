@@ -18,11 +18,10 @@
 // (4096 blocks on 768 slots would idle 11 % in the last round; 4096 x 3 parts is exactly 16).
 #pragma once
 #include "bmu_bf16.hpp"
+#include "exact_scratch.hpp"   // K16_T, K16_STAGE_UNITS (16-unit tiles per stage, units per stage): beside the rule that sizes the exact mode's buffers by them
 
 namespace somhip {
 
-constexpr int K16_T = 4;              // 16-unit tiles per stage
-constexpr int K16_STAGE_UNITS = 16 * K16_T;
 constexpr int K16_SB = 4;             // 16-sample blocks per wave
 constexpr int K16_NW = 4;             // waves per workgroup (they share one LDS ring)
 constexpr int K16_WG_SAMPLES = K16_NW * 16 * K16_SB;

@@ -19,11 +19,10 @@
 #include <type_traits>
 #include "bmu_bf16.hpp"
 #include "bmu_bf16_tiled.hpp"
+#include "exact_scratch.hpp"   // WD_T, WD_STAGE_UNITS (16-unit tiles per stage, units per stage)
 
 namespace somhip {
 
-constexpr int WD_T = 2;                          // 16-unit tiles per stage
-constexpr int WD_STAGE_UNITS = 16 * WD_T;
 constexpr int WD_SB = 2;                         // 16-sample blocks per wave
 constexpr int WD_NW = 8;                         // waves per workgroup
 constexpr int WD_WG_SAMPLES = WD_NW * WD_SB * 16;

@@ -87,11 +87,9 @@ namespace somhip {
 // exact_top2_host.hpp, the exact operand preparation in somhip.hip) instantiates every kernel it launches with ExactEl.
 using ExactEl = F16;
 
-constexpr int EX_GROUP = 64;          // units per group = one stage of the float32 stage image = one stage of the screen
-constexpr int EX_PAIRS = 64;          // least capacity of a pass in (row, group) pairs per row ON AVERAGE (exact_reserve sizes it)
+// (EX_GROUP, EX_PAIRS, EX_TR -- units per group, least pairs per row of a pass, rows per re-score tile: exact_scratch.hpp)
 constexpr int EX_SCAN_SPLIT = 4;      // waves that share a row's groups in the scan
 constexpr int EX_WERR_UNITS = 16;     // units per wave in exact_werr_kernel
-constexpr int EX_TR = 128;            // rows per re-score tile (4 waves x 32 rows against one 64-unit group)
 
 // Small per-pass counters, one allocation [n_groups gcount][n_groups gstart][PassCounters], zeroed by one memset before the scan:
 //   gcount: (row, group) pairs per group = fill cursor of the group's row list
@@ -111,6 +109,7 @@ struct PassCounters {
     int lists_done;   // exact_lists_totals_kernel: its workgroups' tickets (the last one sets it back to zero)
     int ticket_tiles; // the listed screen's select tail (bmu_bf16_k16.hpp): tiles cut into parts, selected by the last part to arrive
 };
+static_assert(sizeof(PassCounters) == EX_PASS_COUNTERS * sizeof(int), "PassCounters: exact_scratch.hpp sizes the counter block by it");
 // The row-need estimate (exact_scout_rowneed_kernel, exact_skip.hpp) runs before a launch's first pass and borrows the head of the block.
 struct RowNeed {
     int need;         // groups the sampled rows need, summed

@@ -37,7 +37,7 @@
 
 namespace somhip {
 
-constexpr int SK_TILE = K16_WG_SAMPLES;   // rows per plan / screen workgroup tile
+static_assert(SK_TILE == K16_WG_SAMPLES, "block skipping: a plan / screen tile (exact_scratch.hpp) is the resident screen's workgroup of rows");
 static_assert(K16_STAGE_UNITS == 64 && K16_T == 4, "block skipping: a stage of the resident screen is one 64-unit group of four 16-unit tiles");
 
 // Centroids and radii of the blocks of W (patch order), both levels in one launch: workgroup g holds group g's 64

@@ -30,7 +30,7 @@ int exact_top2_screen(som_handle* h, const __bf16* Xb, long n, unsigned long lon
         std::fprintf(stderr, "[somhip] exact top-2 screen: blocks=%ld per_cu=%d slots=%ld parts=%d groups=%d\n", blocks, per_cu, slots,
                      parts, (int)cdiv(h->K, EX_GROUP));
     bmu_bf16_k16_kernel<KS32, ExactEl, true, false, true><<<dim3((unsigned)blocks, (unsigned)parts), dim3(64 * K16_NW), lds, h->stream>>>(
-        Xb, n, h->Wst, h->n_stages, h->K, best64, h->ex.gmin, h->ex.stride, h->ex.gflags, xsq, xerr, xmax2, h->wmax2, h->wmax2 + 1, eb,
+        Xb, n, h->Wst, h->n_stages, h->K, best64, h->ex.pass.gmin, h->ex.pass.stride, h->ex.pass.gflags, xsq, xerr, xmax2, h->wmax2, h->wmax2 + 1, eb,
         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, h->t2.m, pitch);
     *parts_out = parts; *pitch_out = pitch;
     return 0;
@@ -49,8 +49,8 @@ int exact_top2_rescore_kg(som_handle* h, const float* X, unsigned long long* bes
     const size_t lds = (size_t)fr_stage_bytes(KG);
     int per_cu = 1;
     if (int rc = kernel_per_cu(h, (const void*)kern, 256, lds, &per_cu)) return rc;
-    const long grid = std::min<long>(ex.max_tiles, ex.grid_mult * resident_slots(h, per_cu));
-    kern<<<dim3((unsigned)grid), dim3(256), lds, h->stream>>>(X, h->D, h->Wfst, h->K, ex.tile_tab, &pass_ctr(h).tail()->n_tiles, ex.plist,
+    const long grid = std::min<long>(ex.pass.max_tiles, ex.sw.grid_mult * resident_slots(h, per_cu));
+    kern<<<dim3((unsigned)grid), dim3(256), lds, h->stream>>>(X, h->D, h->Wfst, h->K, ex.pass.tile_tab, &pass_ctr(h).tail()->n_tiles, ex.pass.plist,
                                                              best64, h->ex_perm, nullptr, h->ex_sub44 ? 1 : 0, 0, excl);
     return 0;
 }
@@ -101,15 +101,15 @@ int exact_top2_pass(som_handle* h, const Rows& R, const ExactBound& eb, long r0,
         if (int rc = exact_top2_screen_ks(h, Xb + r0 * h->dp, n, best1, xsq + r0, xerr + r0, xmax2, eb, &parts, &pitch)) return rc;
     }
     exact_select_kernel<false, true><<<dim3((unsigned)cdiv(n, 64)), dim3(64 * EX_SCAN_SPLIT), 0, h->stream>>>(
-        ex.gmin, ex.gflags, ex.stride, n_groups, n, best1, xsq + r0, h->wmax2, xmax2, eb, xerr + r0, h->wmax2 + 1, ex.plist, pc.gcount(),
-        ex.rowcnt, nullptr, nullptr, nullptr, nullptr, 0, h->t2.m, parts, pitch);
+        ex.pass.gmin, ex.pass.gflags, ex.pass.stride, n_groups, n, best1, xsq + r0, h->wmax2, xmax2, eb, xerr + r0, h->wmax2 + 1, ex.pass.plist, pc.gcount(),
+        ex.pass.rowcnt, nullptr, nullptr, nullptr, nullptr, 0, h->t2.m, parts, pitch);
     // round 1: the tiles, the float32 first minimum k1; round 2: the same tiles without k1
     if (int rc = exact_rescore_round(h, X + r0 * h->D, xsq + r0, best1, nullptr, nullptr, false, true)) return rc;
     exact_top2_first_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(best1, n, h->K, h->ex_patch ? h->ex_inv.p : nullptr,
                                                                                      h->t2.excl);
     if (int rc = exact_top2_rescore(h, X + r0 * h->D, best2, h->t2.excl)) return rc;
     exact_top2_settle_kernel<<<dim3((unsigned)cdiv(std::max<long>(n, h->K), 256)), dim3(256), 0, h->stream>>>(
-        best1, best2, n, h->K, xsq + r0, h->wsq, &pc.tail()->overflow, out1 + r0, out2 + r0, ex.fb_list, &pc.tail()->fallback,
+        best1, best2, n, h->K, xsq + r0, h->wsq, &pc.tail()->overflow, out1 + r0, out2 + r0, ex.pass.fb_list, &pc.tail()->fallback,
         &pc.tail()->bad_w);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(ex.pass_host, pc.tail(), sizeof(PassCounters), hipMemcpyDeviceToHost, h->stream));
@@ -122,7 +122,7 @@ int exact_top2_pass(som_handle* h, const Rows& R, const ExactBound& eb, long r0,
     if (h->debug)
         std::fprintf(stderr, "[somhip] exact top-2 pass: %ld rows, %d pairs (%.2f a row), %d rows to the float32 kernel%s\n", n, got.pairs_in,
                      (double)got.pairs_in / (double)n, n_list, got.overflow ? " (overflow)" : "");
-    if (n_list > 0) return exact_top2_list_rows(h, X + r0 * h->D, ex.fb_list, n_list, out1 + r0, out2 + r0);
+    if (n_list > 0) return exact_top2_list_rows(h, X + r0 * h->D, ex.pass.fb_list, n_list, out1 + r0, out2 + r0);
     return 0;
 }
 
@@ -133,9 +133,9 @@ int launch_top2_exact(som_handle* h, const Rows& R) {
     const long N = R.N;
     auto& ex = h->ex;
     // the pass scratch: what there is, unless there is none -- or too little and no resident order that growing it would forget
-    if (ex.stride == 0 || (ex.stride < round_up(std::min(N, exact_chunk_rows(h)), 256) && !ex.plan.order_valid()))
+    if (ex.pass.stride == 0 || (ex.pass.stride < exscratch::first_stride(exact_geometry(h), N, 0) && !ex.plan.order_valid()))
         if (int rc = exact_reserve(h, N)) return rc;
-    const long chunk = std::min(exact_chunk_rows(h), ex.stride);
+    const long chunk = std::min(exscratch::pass_rows(exact_geometry(h)), ex.pass.stride);
     const long off2 = round_up(N, 1024);                         // (round 2's merge keys behind round 1's)
     if (int rc = h->best64.reserve(h, (size_t)(off2 + N), 1024)) return rc;
     if (int rc = h->t2.excl.reserve(h, (size_t)std::min(N, chunk), 1024)) return rc;

@@ -152,6 +152,67 @@ struct RowSet {
     Rows view() const { return Rows{X, N, xsq, xerr(), Xb, xmax2, bmu, bmu2, wgt, resident(), ids_valid}; }
 };
 
+// THE EXACT MODE'S SCRATCH (exact_scratch.hpp: how large; exact_host.hpp: reserve, one overload each): four owners.  Each holds its buffers
+// and the numbers that say what they were sized for; reserve allocates what the rule's sizes struct says, in a fixed order, and a
+// refusal part of the way releases the WHOLE group before the error goes back: nothing half allocated is ever held or used.
+// (a pass's screen, select, refinement and re-score; the float32 fallback's dense rows, grown on demand)
+struct PassScratch {
+    DevBuf<uint32_t> gmin;               // [n_groups][stride] group minima of the chunk being screened (sparse: see gflags)
+    DevBuf<unsigned long long> gflags;   // [stride / 64][n_groups] which rows' minima the screen stored
+    DevBuf<int> rowcnt;                  // [stride] candidate groups of every row of the last pass (som_exact_last_counts)
+    DevBuf<int> rowarg;                  // [stride] the group round 1 scored for the row (-1: none)
+    DevBuf<float> seed;                  // [stride] exact_seed_kernel: the cap on the screen's keep threshold
+    DevBuf<int> plist;                   // [n_groups][stride] rows bucketed by candidate group
+    DevBuf<int> fb_list;                 // [stride] the rows the pass hands to the float32 kernel
+    DevBuf<int4> tile_tab;               // [max_tiles] re-score tiles: (group, first list entry, rows)
+    DevBuf<int> ctr;                     // [n_groups gcount][n_groups gstart of round 2][PassCounters] (bmu_exact.hpp; zeroed per pass; PassCtr names the parts)
+    DevBuf<float> fbX; DevBuf<int> fb_ids;   // fallback rows, dense, for the float32 kernel, and its ids (exact_fallback_rows grows them)
+    long stride = 0, pairs = 64, max_tiles = 0;   // rows per group line (0: nothing held); (row, group) pairs per row on average; [tile_tab]
+    void release() { *this = PassScratch{}; }
+};
+// (a pass's plan: the sort's keys, the scout's groups, the tiles' need words, lists and counts, the listed screen's work queue)
+struct PlanScratch {
+    DevBuf<int> sk_keys, sk_keys2, sk_vals, sk_tmp;   // [stride] the sort's keys and values; radix_sort_rows' scratch
+    DevBuf<int> scout_g;              // [stride] nearest group centroid of every row of the pass
+    DevBuf<float> tq;                 // [stride] wide plan: the float32 score of every sorted row's last BMU under the current codebook
+    DevBuf<unsigned long long> need, need2;
+    DevBuf<int> glist, gcnt;          // per tile: (group << 4 | sub-block mask) items: what the select kernel walks
+    DevBuf<int2> tile_counts;
+    DevBuf<int> tlist, tcnt;          // per tile: the same blocks as a dense list of 16-unit tiles: what the screen walks
+    DevBuf<int> tile_ticket;          // per tile: arrivals of its parts in the listed screen's select tail (zeroed by the lists kernels)
+    DevBuf<int2> items;               // the listed screen's work queue: [0] = (items, counter), from [8] on (tile, part | parts << 16)
+    long stride = 0; int item_slots = 0;   // rows per pass the buffers hold; resident workgroups the queue was sized for
+    void release() { *this = PlanScratch{}; }
+};
+// (the centroid sets of the plan: [0] the 64-unit groups, [1] their 16-unit sub-blocks -- exact_centroid_kernel's slot order)
+struct CentroidSet {
+    struct Level { DevBuf<float> Cc, rg, csq, cmax2; DevBuf<char> Cst;
+                   DevBuf<char> Cst_plain;      // level 0 only: the scout's copy (plain initial accumulators)
+                   int n_slots = 0, n_cstages = 0, n_img_stages = 0; } lv[2];
+    bool ready = false;               // every level of the geometry is allocated
+    void release() { *this = CentroidSet{}; }
+};
+// THE SORTED PASS: rows in the order of their (pseudo) last BMU's patch (position -> row: `order`), with sorted copies of the half
+// image, its second half, the float32 rows and the norms.  The handle holds two: the RESIDENT rows' (all passes; valid for one row
+// set, re-sorted when the order has gone stale -- policy::PlanState --, not every epoch) and ONE pass of a TRANSIENT row set
+// (query rows, streamed chunks: sorted by the scout of exact_skip.hpp, used once).
+struct SortedRows {
+    bool resident = false;        // the resident rows' pass (fixed at construction): replacing its buffers loses the resident order
+    long cap = 0;                 // positions the buffers hold (each pass padded to the tile)
+    DevBuf<int> order;
+    DevBuf<__bf16> Xb_s;
+    DevBuf<__bf16> Xl_s;          // ... the rows' second half image (the refinement pass): reserve_second_half, when it first engages
+    bool xl_filled = false;       //     ... and written by a gather since
+    DevBuf<float> Xf_s, xsq_s, xerr_s, seed_s, sU_s;
+    DevBuf<int> lastpos_s;        // position (patch order) of every sorted row's (pseudo) last BMU
+    // lastpos_s[p] == inv[bmu[order[p]]] for every position of the resident rows: the last epoch's finalize stored them
+    // pass by pass and no row fell back.  Taken (and cleared) by the next resident launch; cleared by whatever else writes
+    // the resident ids or replaces these buffers (launch_bmu_exact, exact_pass)
+    bool lastpos_valid = false;
+    explicit SortedRows(bool resident_rows = false) : resident(resident_rows) {}
+    void release() { *this = SortedRows{resident}; }
+};
+
 struct som_handle {
     som_config cfg{};
     void* comm = nullptr;        // ncclComm_t of som_comm_init (NULL: single GPU, or the host does the all-reduce)
@@ -179,66 +240,64 @@ struct som_handle {
     DevBuf<float> Wp;        // [K][D] codebook in patch order
     DevBuf<float> wsq_p;     // [K]   its |w|^2 (the float32 kernel's own values, permuted)
     struct ExactScratch {
-        DevBuf<uint32_t> gmin;               // [n_groups][stride] group minima of the chunk being screened (sparse: see gflags)
-        DevBuf<unsigned long long> gflags;   // [stride / 64][n_groups] which rows' minima the screen stored
-        long stride = 0;                     //   rows per group line (a chunk of the row set, padded)
-        DevBuf<int> rowcnt;                  // [stride] candidate groups of every row of the last pass (som_exact_last_counts)
-        DevBuf<int> rowarg;                  // [stride] the group round 1 scored for the row (-1: none)
-        DevBuf<float> seed;                  // [stride] exact_seed_kernel: the cap on the screen's keep threshold
-        bool seed_on = true;                 // SOM_EXACT_SEED=0: no seed (A/B)
-        bool seed_live = false;              // this pass's screen reads the seed
-        int two_round = -1;                  // SOM_EXACT_TWO_ROUND=0|1 forces the one- / two-round re-score (default: two rounds beyond 128 features)
-        DevBuf<int> fb_list, fb_ids;
-        DevBuf<int> ctr;                     // [n_groups gcount][n_groups gstart of round 2][PassCounters] (bmu_exact.hpp; zeroed per pass; PassCtr names the parts)
-        DevBuf<int> plist;                   // [n_groups][stride] rows bucketed by candidate group
-        DevBuf<int4> tile_tab;               // re-score tiles: (group, first list entry, rows)
-        long max_tiles = 0;
-        DevBuf<float> fbX;                   // fallback rows, dense, for the float32 kernel
+        PassScratch pass;                 // the buffers: four owners (above), sized by exact_scratch.hpp
+        PlanScratch pbuf;
+        CentroidSet cen;
+        SortedRows srt[2] = {SortedRows{true}, SortedRows{false}};   // [0] the resident rows, [1] one pass of a transient row set
+        long stride_cap = 0;              // rows per pass the device had memory for (0: no allocation was ever refused)
         PassCounters* pass_host = nullptr;   // pinned: the pass's counter tail, read back once per pass
         hipEvent_t fb_ready = nullptr;       // recorded behind the counter's copy
-        int64_t rows_total = 0, rows_fallback = 0, chunks = 0;   // som_exact_stats
-        int64_t blocks_run = 0, blocks_total = 0;                // som_exact_skip_stats: (256-row tile, 16-unit block) blocks of the screens
-        long pass_rows_override = 0;
-        long hook_refuse_above = 0, hook_pairs = 0; bool hook_refuse_skip = false;   // test hooks, read once in som_create (SOM_TEST_HOOKS=1)
-        long stride_cap = 0;              // rows per pass the device had memory for (0: no allocation was ever refused)
-        long pairs = 64;                  // capacity of a pass: (row, group) pairs per row on average (exact_reserve)
-        // block skipping (exact_skip.hpp): resident rows from their second epoch on, input_len <= 128
-        int skip_mode = 1;                // SOM_EXACT_SKIP: 0 off, 1 on for maps of >= 4096 units (default), 2 on for every map of >= 2 groups (tests), 3: plan, keep everything
+        struct Switches {                 // between kernel sequences (A/B; read once in som_create: read_env)
+            bool seed_on = true;              // SOM_EXACT_SEED=0: no seed
+            int two_round = -1;               // SOM_EXACT_TWO_ROUND=0|1 forces the one- / two-round re-score (default: two rounds beyond 128 features)
+            int skip_mode = 1;                // SOM_EXACT_SKIP: 0 off, 1 on for maps of >= 4096 units (default), 2 on for every map of >= 2 groups (tests), 3: plan, keep everything
+            bool sub_blocks = true;           // SOM_EXACT_SUBBLOCKS=0: the plan stops at the groups
+            bool chain = true;                // SOM_EXACT_CHAIN=0: the planned epoch's small launches as separate kernels and fills
+            int res_every = 0;                // SOM_EXACT_RESORT=n: re-sort every n-th planned epoch (0: when the order has gone stale)
+            bool refine_on = true;            // SOM_EXACT_REFINE=0: no refinement pass
+            int grid_mult = 2;                // persistent re-score / refinement kernels: workgroups per resident slot (SOM_EXACT_GRID_MULT)
+            bool scout_on = true;             // SOM_EXACT_SCOUT=0: no scout (exact_skip.hpp: pseudo last BMUs for rows that have none, or whose last BMUs say little)
+            bool fuse_select = true;          // SOM_EXACT_FUSE_SELECT=0: exact_select_kernel in a launch of its own, not the listed screen's select tail (bmu_bf16_k16.hpp)
+            bool fuse_plan = true;            // SOM_EXACT_FUSE_PLAN=0: a pass's plan always as three launches, not exact_plan_fused_kernel's one where the launch allows it
+            bool plan_fold = true;            // SOM_EXACT_PLAN_FOLD=0: the plan kernels compare against P as before instead of folding it into the extra MFMA step
+            bool item_queue = true;           // SOM_EXACT_QUEUE=0: one workgroup per tile (and part) instead of the work queue
+            int item_len_pct = 125;           // ... =<pct >= 25>: an item's length in per cent of the mean list
+        } sw;
+        struct Hooks {                    // the tests' (SOM_TEST_HOOKS=1): SOM_EXACT_PASS_ROWS, _DEBUG_REFUSE_ABOVE, _PAIRS, _DEBUG_REFUSE_SKIP, _PLAN_PARTS
+            long pass_rows_override = 0, refuse_above = 0, pairs = 0; bool refuse_skip = false; int plan_parts = 0;
+        } hook;
+        void read_env() {
+            if (const char* e = dev_env("SOM_EXACT_PASS_ROWS")) hook.pass_rows_override = std::atol(e);
+            if (const char* e = dev_env("SOM_EXACT_DEBUG_REFUSE_ABOVE")) hook.refuse_above = std::atol(e);
+            if (const char* e = dev_env("SOM_EXACT_PAIRS")) hook.pairs = std::max(1L, std::atol(e));
+            hook.refuse_skip = dev_env("SOM_EXACT_DEBUG_REFUSE_SKIP") != nullptr;
+            if (const char* e = dev_env("SOM_EXACT_TWO_ROUND")) sw.two_round = std::atoi(e) != 0 ? 1 : 0;
+            if (const char* e = dev_env("SOM_EXACT_SEED")) sw.seed_on = std::atoi(e) != 0;
+            if (const char* e = std::getenv("SOM_EXACT_SKIP")) sw.skip_mode = std::atoi(e);
+            if (const char* e = dev_env("SOM_EXACT_SUBBLOCKS")) sw.sub_blocks = std::atoi(e) != 0;
+            if (const char* e = dev_env("SOM_EXACT_REFINE")) sw.refine_on = std::atoi(e) != 0;
+            if (const char* e = dev_env("SOM_EXACT_QUEUE")) { sw.item_queue = std::atoi(e) != 0; if (std::atoi(e) >= 25) sw.item_len_pct = std::atoi(e); }
+            if (const char* e = dev_env("SOM_EXACT_SCOUT")) sw.scout_on = std::atoi(e) != 0;
+            if (const char* e = dev_env("SOM_EXACT_GRID_MULT")) sw.grid_mult = std::max(1, std::atoi(e));
+            if (const char* e = dev_env("SOM_EXACT_RESORT")) sw.res_every = std::max(0, std::atoi(e));
+            if (const char* e = dev_env("SOM_EXACT_CHAIN")) sw.chain = std::atoi(e) != 0;
+            if (const char* e = dev_env("SOM_EXACT_FUSE_SELECT")) sw.fuse_select = std::atoi(e) != 0;
+            if (const char* e = dev_env("SOM_EXACT_FUSE_PLAN")) sw.fuse_plan = std::atoi(e) != 0;
+            if (const char* e = dev_env("SOM_EXACT_PLAN_FOLD")) sw.plan_fold = std::atoi(e) != 0;
+            if (const char* e = dev_env("SOM_EXACT_PLAN_PARTS")) hook.plan_parts = std::max(0, std::atoi(e));
+        }
+        struct Stats {                    // what the som_exact_*_stats / som_debug_exact_*_stats entries return
+            int64_t rows_total = 0, rows_fallback = 0, chunks = 0;   // som_exact_stats
+            int64_t blocks_run = 0, blocks_total = 0;                // som_exact_skip_stats: (256-row tile, 16-unit block) blocks of the screens
+            int64_t lastpos_carried_epochs = 0;   // planned resident epochs that skipped exact_lastpos_kernel (som_debug_exact_chain_stats)
+            int64_t sel_fused_passes = 0, sel_launched_passes = 0, sel_ticket_tiles = 0;   // som_debug_exact_select_stats
+            int64_t plan_fused_launches = 0, plan_split_launches = 0, plan_folded = 0, plan_compared = 0;   // som_debug_exact_plan_stats, _plan_fold_stats
+        } stats;
+        bool seed_live = false; int screen_slots = 0;   // this pass's screen reads the seed; the listed screen's last grid (what the next plan cuts its lists for)
         // what a launch decides -- plan at all, re-sort, scout, level 2, refine -- and the state those decisions move from
         // launch to launch (pause ladder, re-sort schedule, level-2 probe, measured costs): exact_policy.hpp
         policy::PlanState plan;
         policy::LaunchPlan lp;            // ... of the launch in flight (launch_bmu_exact)
-        bool sub_blocks = true;           // SOM_EXACT_SUBBLOCKS=0: the plan stops at the groups (A/B)
-        // the SORTED PASS: rows in the order of their (pseudo) last BMU's patch (position -> row: `order`), with sorted copies of
-        // the half image, its second half, the float32 rows and the norms.  srt[0]: the RESIDENT rows (all passes; valid for
-        // one row set, re-sorted when the order has gone stale -- policy::PlanState --, not every epoch); srt[1]: ONE pass of
-        // a TRANSIENT row set (query rows, streamed chunks: sorted by the scout of exact_skip.hpp, used once).
-        struct SortedRows {
-            long cap = 0;                 // positions the buffers hold (each pass padded to the tile)
-            DevBuf<int> order;
-            DevBuf<__bf16> Xb_s;
-            DevBuf<__bf16> Xl_s;          // ... the rows' second half image (the refinement pass): allocated when it first engages
-            bool xl_filled = false;       //     ... and written by a gather since
-            DevBuf<float> Xf_s, xsq_s, xerr_s, seed_s, sU_s;
-            DevBuf<int> lastpos_s;        // position (patch order) of every sorted row's (pseudo) last BMU
-            // lastpos_s[p] == inv[bmu[order[p]]] for every position of the resident rows: the last epoch's finalize stored them
-            // pass by pass and no row fell back.  Taken (and cleared) by the next resident launch; cleared by whatever else writes
-            // the resident ids or replaces these buffers (launch_bmu_exact, exact_pass)
-            bool lastpos_valid = false;
-        } srt[2];
-        int64_t lastpos_carried_epochs = 0;   // planned resident epochs that skipped exact_lastpos_kernel (som_debug_exact_chain_stats)
-        bool chain = true;                // SOM_EXACT_CHAIN=0: the planned epoch's small launches as separate kernels and fills (A/B)
-        bool cen_ready = false;           // both centroid levels are allocated
-        long sk_stride = 0;               // rows per pass the per-pass plan buffers hold
-        int res_every = 0;                // SOM_EXACT_RESORT=n: re-sort every n-th planned epoch (0: when the order has gone stale)
-        DevBuf<int> sk_keys, sk_keys2, sk_vals;
-        DevBuf<int> sk_tmp;               // radix_sort_rows' scratch
-        bool refine_on = true;            // SOM_EXACT_REFINE=0: no refinement pass (A/B)
-        // the SCOUT (exact_skip.hpp): pseudo last BMUs for rows that have none, or whose last BMUs say little
-        int grid_mult = 2;                // persistent re-score / refinement kernels: workgroups per resident slot (SOM_EXACT_GRID_MULT: A/B)
-        bool scout_on = true;             // SOM_EXACT_SCOUT=0: plans only from last epoch's BMUs (A/B)
-        DevBuf<int> scout_g;              // [stride] nearest group centroid of every row of the pass
-        DevBuf<float> tq;                 // [stride] wide plan: the float32 score of every sorted row's last BMU under the current codebook
         double share_forecast = 1.0;      // executed share expected of the launch about to run (the screen sizes its codebook parts by it)
         // what the last launch learned from its samples, as plain numbers (-1: not asked), and the geometry of its last planned
         // pass up to 128 features (read-only test accessors: som_debug_exact_forecast, som_debug_exact_tile_blocks)
@@ -259,29 +318,6 @@ struct som_handle {
             hipEvent_t ev[8] = {};            // [0] launch / pass start, [1, 2] screen, [3, 4] level 2, [5, 6] sort + gather, [7] pass end
             bool have = false;
         } cost;
-        // the centroid sets of the plan: [0] the 64-unit groups, [1] their 16-unit sub-blocks (exact_centroid_kernel's slot order)
-        struct Centroids { DevBuf<float> Cc, rg, csq, cmax2; DevBuf<char> Cst;
-                           DevBuf<char> Cst_plain;      // level 1 only: the scout's copy (plain initial accumulators)
-                           int n_slots = 0, n_cstages = 0, n_img_stages = 0; } cen[2];
-        DevBuf<unsigned long long> need, need2;
-        DevBuf<int> glist, gcnt;          // per tile: (group << 4 | sub-block mask) items: what the select kernel walks
-        DevBuf<int> tlist, tcnt;          // per tile: the same blocks as a dense list of 16-unit tiles: what the screen walks
-        DevBuf<int2> tile_counts;
-        DevBuf<int> tile_ticket;          // per tile: arrivals of its parts in the listed screen's select tail (zeroed by the lists kernels)
-        // the listed screen's SELECT TAIL (bmu_bf16_k16.hpp): the queue's workgroups select the candidates behind their walks
-        bool fuse_select = true;          // SOM_EXACT_FUSE_SELECT=0: exact_select_kernel in a launch of its own behind the screen (A/B)
-        int64_t sel_fused_passes = 0, sel_launched_passes = 0, sel_ticket_tiles = 0;   // som_debug_exact_select_stats
-        // a pass's PLAN (exact_skip_plan): levels 1 and 2 and the lists in one launch (exact_plan_fused_kernel) where the launch allows it
-        bool fuse_plan = true;            // SOM_EXACT_FUSE_PLAN=0: always level 1, level 2 and the lists as launches of their own (A/B)
-        int hook_plan_parts = 0;          // SOM_EXACT_PLAN_PARTS=n: at most n workgroups per tile in the plan's grids (0: four)
-        int64_t plan_fused_launches = 0, plan_split_launches = 0;   // som_debug_exact_plan_stats
-        bool plan_fold = true;            // SOM_EXACT_PLAN_FOLD=0: the plan kernels compare against P as before instead of folding it into the extra MFMA step (A/B)
-        int64_t plan_folded = 0, plan_compared = 0;                 // som_debug_exact_plan_fold_stats
-        DevBuf<int2> items;               // the listed screen's work queue: [0] = (items, counter), from [8] on (tile, part | parts << 16)
-        int item_slots = 0;               // ... sized for this many resident workgroups
-        int screen_slots = 0;             // ... the listed screen's last grid (what the next plan cuts its lists for)
-        bool item_queue = true;           // SOM_EXACT_QUEUE=0: one workgroup per tile (and part) instead (A/B)
-        int item_len_pct = 125;           // ... =<pct >= 25>: an item's length in per cent of the mean list
     } ex;
     int n_kchunks = 0;       // tiled: 64-feature chunks
     int n_ublocks = 0;       // tiled: unit blocks of tl_bn
@@ -586,8 +622,8 @@ int for_kchunks(som_handle* h, const char* none, F&& f) {
 // (operands::State), and the launch -- or, should it not get there, the next refresh -- pays it
 int launch_prep_w_exact(som_handle* h, bool cm) {
     const float* Wex = h->ex_patch ? h->Wp : h->W;
-    float* cm1 = cm ? (float*)h->ex.cen[0].cmax2 : nullptr;
-    float* cm2 = cm ? (float*)h->ex.cen[1].cmax2 : nullptr;
+    float* cm1 = cm ? (float*)h->ex.cen.lv[0].cmax2 : nullptr;
+    float* cm2 = cm ? (float*)h->ex.cen.lv[1].cmax2 : nullptr;
     const dim3 tgrid((unsigned)cdiv((long)h->n_stages * K16_T, 4)), block(256);
     switch (h->ks32) {
 #define SOM_PREPX_CASE(k) case k: prep_w_exact_k16_kernel<k, ExactEl><<<tgrid, block, 0, h->stream>>>(Wex, h->K, h->D, h->Wst, h->n_stages, h->wmax2, h->wmax2 + 1, h->Wst_lo, cm1, cm2); break;
@@ -1195,7 +1231,7 @@ int run_activation_bmu_launch(som_handle* h, const Rows& r) {
         return launch_bmu_masked(h, r.X, r.N, r.out);
     }
     // (exact mode up to 128 features: the launch writes the codebook's 16-bit image itself, in one grid with its plan's centroid images)
-    if (int rc = refresh_codebook_operands(h, operands::Request::Search, h->exact && h->ex.chain)) return rc;
+    if (int rc = refresh_codebook_operands(h, operands::Request::Search, h->exact && h->ex.sw.chain)) return rc;
     Timed t(h, SOM_K_BMU);
     if (h->exact) return launch_bmu_exact(h, r);
     if (h->cfg.precision != SOM_PREC_F32) return launch_bmu_bf16(h, r);
@@ -1699,27 +1735,10 @@ int som_create(const som_config* cfg, som_handle** out) {
         h->debug = std::getenv("SOM_DEBUG") != nullptr;
         if (const char* e = std::getenv("SOM_VERIFY")) h->verify_rows = std::max(0, std::atoi(e));
         if (h->masked) h->verify_rows = 0;               // (the canary re-scores with the unmasked float32 kernel: not on these rows)
-        if (const char* e = dev_env("SOM_EXACT_PASS_ROWS")) h->ex.pass_rows_override = std::atol(e);
-        if (const char* e = dev_env("SOM_EXACT_DEBUG_REFUSE_ABOVE")) h->ex.hook_refuse_above = std::atol(e);
-        if (const char* e = dev_env("SOM_EXACT_PAIRS")) h->ex.hook_pairs = std::max(1L, std::atol(e));
-        h->ex.hook_refuse_skip = dev_env("SOM_EXACT_DEBUG_REFUSE_SKIP") != nullptr;
-        if (const char* e = dev_env("SOM_EXACT_TWO_ROUND")) h->ex.two_round = std::atoi(e) != 0 ? 1 : 0;
-        if (const char* e = dev_env("SOM_EXACT_SEED")) h->ex.seed_on = std::atoi(e) != 0;
-        if (const char* e = std::getenv("SOM_EXACT_SKIP")) h->ex.skip_mode = std::atoi(e);
+        h->ex.read_env();
         if (const char* e = std::getenv("SOM_EXACT_TOP2")) h->t2.on = std::atoi(e) != 0;
-        if (const char* e = dev_env("SOM_EXACT_SUBBLOCKS")) h->ex.sub_blocks = std::atoi(e) != 0;
-        if (const char* e = dev_env("SOM_EXACT_REFINE")) h->ex.refine_on = std::atoi(e) != 0;
-        if (const char* e = dev_env("SOM_EXACT_QUEUE")) { h->ex.item_queue = std::atoi(e) != 0; if (std::atoi(e) >= 25) h->ex.item_len_pct = std::atoi(e); }
-        if (const char* e = dev_env("SOM_EXACT_SCOUT")) h->ex.scout_on = std::atoi(e) != 0;
-        if (const char* e = dev_env("SOM_EXACT_GRID_MULT")) h->ex.grid_mult = std::max(1, std::atoi(e));
-        if (const char* e = dev_env("SOM_EXACT_RESORT")) h->ex.res_every = std::max(0, std::atoi(e));
         if (const char* e = dev_env("SOM_ASYNC_COPIES")) h->async_copies = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_FUSE_MERGE")) h->fuse_merge_prep = std::atoi(e) != 0;
-        if (const char* e = dev_env("SOM_EXACT_CHAIN")) h->ex.chain = std::atoi(e) != 0;
-        if (const char* e = dev_env("SOM_EXACT_FUSE_SELECT")) h->ex.fuse_select = std::atoi(e) != 0;
-        if (const char* e = dev_env("SOM_EXACT_FUSE_PLAN")) h->ex.fuse_plan = std::atoi(e) != 0;
-        if (const char* e = dev_env("SOM_EXACT_PLAN_FOLD")) h->ex.plan_fold = std::atoi(e) != 0;
-        if (const char* e = dev_env("SOM_EXACT_PLAN_PARTS")) h->ex.hook_plan_parts = std::max(0, std::atoi(e));
         if (const char* e = dev_env("SOM_COUNTING_SORT")) h->counting_sort = std::atoi(e) != 0;
         // the ranges are kept per 32-row tile of a table (update.hpp): a tile can have a zero column, and an MFMA step to
         // skip, as soon as the table has more columns than the tile has rows -- a map side above 32.  They cost no launch.
@@ -1861,7 +1880,7 @@ static int adopt_rows(som_handle* h, const std::string& who, const void* x, int6
         // milliseconds).  A refusal here is not an error: launch_bmu_exact asks again and settles it (smaller passes, no plan).
         bool ok = exact_reserve(h, n_rows) == 0;
         if (ok && exact_skip_wanted(h) && !h->wide)
-            ok = exact_skip_reserve(h, h->ex.srt[0], n_rows, h->ex.stride) == 0;
+            ok = exact_skip_reserve(h, h->ex.srt[0], n_rows, h->ex.pass.stride) == 0;
         if (!ok) { (void)hipGetLastError(); h->err.clear(); }
     }
     return 0;
@@ -2214,14 +2233,14 @@ int som_epoch_merge(som_handle* h) {
     // maximum (exact_merge_prep_kernel); the 16-bit images follow at the head of the BMU launch (they stay owed)
     if (h->fuse_merge_prep && h->exact && !h->tiled) {
         const int n_groups = (int)cdiv(h->K, EX_GROUP);
-        const bool cen = h->ex.cen_ready;
+        const bool cen = h->ex.cen.ready;
         HIPCHK(h, hipMemsetAsync(h->wmax2, 0, 2 * sizeof(float), h->stream));     // [0]: max |w|^2, [1]: max_k |w^_k - w~_k|^2
         const MergePrepOut o{h->W, h->ex_patch ? (float*)h->Wp : nullptr, h->ex_patch ? (const int*)h->ex_perm : nullptr,
                              h->wsq, h->ex_patch ? (float*)h->wsq_p : nullptr, h->wn, h->wmax2, h->Wfst, h->fr_kg};
         CentroidLevel l1{nullptr, nullptr, nullptr, nullptr, 0}, l2 = l1;
         if (cen) {
-            auto& c0 = h->ex.cen[0];
-            auto& c1 = h->ex.cen[1];
+            auto& c0 = h->ex.cen.lv[0];
+            auto& c1 = h->ex.cen.lv[1];
             l1 = CentroidLevel{c0.Cc, c0.rg, c0.csq, c0.cmax2, c0.n_slots};
             l2 = CentroidLevel{c1.Cc, c1.rg, c1.csq, c1.cmax2, c1.n_slots};
         }
@@ -3006,9 +3025,9 @@ int som_debug_operand_crc(som_handle* h, int32_t which, uint64_t* out) {
     case 4: rc = add(h->wn, half ? (size_t)h->K * sizeof(float) : 0); break;
     case 5: rc = add(h->wmax2, half ? 2 * sizeof(float) : 0); break;
     case 6:
-        if (h->ex.cen_ready)
+        if (h->ex.cen.ready)
             for (int lv = 0; lv < (h->wide ? 1 : 2) && rc == 0; ++lv) {
-                auto& c = h->ex.cen[lv];
+                auto& c = h->ex.cen.lv[lv];
                 if ((rc = add(c.Cc, (size_t)c.n_slots * h->D * sizeof(float)))) break;
                 if ((rc = add(c.rg, (size_t)c.n_slots * sizeof(float)))) break;
                 if ((rc = add(c.csq, (size_t)c.n_slots * sizeof(float)))) break;
@@ -3029,9 +3048,9 @@ int som_debug_operand_crc(som_handle* h, int32_t which, uint64_t* out) {
 int som_debug_exact_centroids(som_handle* h, int32_t level, float* C_out, float* r_out, float* csq_out, int32_t* n_slots_out) {
     DeviceGuard dev_guard(h);
     if (!h || !n_slots_out) return fail(h, "som_debug_exact_centroids: NULL argument");
-    if (!h->ex.cen_ready) return fail(h, "som_debug_exact_centroids: the handle holds no centroids (no launch has planned yet)");
+    if (!h->ex.cen.ready) return fail(h, "som_debug_exact_centroids: the handle holds no centroids (no launch has planned yet)");
     if (level < 0 || level >= (h->wide ? 1 : 2)) return fail(h, "som_debug_exact_centroids: no such level");
-    const auto& c = h->ex.cen[level];
+    const auto& c = h->ex.cen.lv[level];
     *n_slots_out = c.n_slots;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (C_out) if (int rc = d2h_blocking(h, C_out, c.Cc, (size_t)c.n_slots * h->D * sizeof(float))) return rc;
@@ -3152,6 +3171,68 @@ int som_debug_unit_sort_stats(som_handle* h, int64_t* counting, int64_t* radix) 
     return 0;
 }
 
+namespace {
+// one block of som_debug_exact_scratch_sizes / _held (include/somhip_test.h has the order): 59 values
+int64_t* put(int64_t* o, std::initializer_list<int64_t> v) { return std::copy(v.begin(), v.end(), o); }
+int64_t* put_sorted(int64_t* o, const exscratch::SortedSizes& s) {
+    return put(o, {s.cap, (int64_t)s.order, (int64_t)s.Xb_s, (int64_t)s.Xl_s, (int64_t)s.Xf_s, (int64_t)s.xsq_s, (int64_t)s.xerr_s, (int64_t)s.seed_s,
+                   (int64_t)s.sU_s, (int64_t)s.lastpos_s});
+}
+int64_t* put_block(int64_t* o, const exscratch::PassSizes& p, int levels, const exscratch::CentroidSizes (&c)[2], const exscratch::SortedSizes& s,
+                   const exscratch::PlanSizes& q) {
+    o = put(o, {p.stride, p.pairs, p.max_tiles, p.too_large ? 1 : 0, (int64_t)p.gmin, (int64_t)p.gflags, (int64_t)p.rowcnt, (int64_t)p.rowarg,
+                (int64_t)p.seed, (int64_t)p.plist, (int64_t)p.fb_list, (int64_t)p.tile_tab, (int64_t)p.ctr, levels});
+    for (const auto& l : c)
+        o = put(o, {l.n_slots, l.n_cstages, l.n_img_stages, (int64_t)l.Cc, (int64_t)l.rg, (int64_t)l.csq, (int64_t)l.cmax2, (int64_t)l.Cst, (int64_t)l.Cst_plain});
+    o = put_sorted(o, s);
+    return put(o, {q.stride, q.tiles, (int64_t)q.sk_keys, (int64_t)q.sk_keys2, (int64_t)q.sk_vals, (int64_t)q.sk_tmp, (int64_t)q.scout_g, (int64_t)q.tq,
+                   (int64_t)q.need, (int64_t)q.need2, (int64_t)q.glist, (int64_t)q.gcnt, (int64_t)q.tlist, (int64_t)q.tcnt, (int64_t)q.tile_counts,
+                   (int64_t)q.tile_ticket, (int64_t)q.items});
+}
+}  // namespace
+
+int som_debug_exact_scratch_sizes(const int64_t* geometry8, int64_t rows, int64_t stride_cap, int64_t* out) {
+    if (!geometry8 || !out || rows < 1 || stride_cap < 0 || geometry8[0] < 1 || geometry8[1] < 1) return 1;
+    const int64_t* v = geometry8;
+    const exscratch::Geometry g{(long)v[0], (int)v[1], (int)v[2], (int)v[3], v[4] != 0, (int)v[5], (long)v[6], (long)v[7]};
+    int64_t* o = out;
+    long stride = exscratch::first_stride(g, (long)rows, 0);
+    for (int i = 0; i < 16; ++i, stride = stride > 0 ? exscratch::next_stride(stride) : 0) *o++ = stride;
+    for (const long st : {exscratch::first_stride(g, (long)rows, 0), exscratch::first_stride(g, (long)rows, (long)stride_cap)})
+        o = put_block(o, exscratch::pass(g, st), exscratch::levels(g), {exscratch::centroids(g, 0), exscratch::centroids(g, 1)},
+                      exscratch::sorted(g, (long)rows), exscratch::plan(g, st));
+    return 0;
+}
+
+int som_debug_exact_scratch_held(som_handle* h, int64_t* out) {
+    if (!h || !out) return fail(h, "som_debug_exact_scratch_held: NULL argument");
+    const auto& ex = h->ex;
+    const PassScratch& p = ex.pass;
+    const PlanScratch& q = ex.pbuf;
+    const auto held = [](const SortedRows& s) {
+        return exscratch::SortedSizes{s.cap, s.order.cap, s.Xb_s.cap, s.Xl_s.cap, s.Xf_s.cap, s.xsq_s.cap, s.xerr_s.cap, s.seed_s.cap, s.sU_s.cap, s.lastpos_s.cap};
+    };
+    exscratch::PassSizes hp;
+    hp.stride = p.stride; hp.pairs = p.pairs; hp.max_tiles = p.max_tiles;
+    hp.gmin = p.gmin.cap; hp.gflags = p.gflags.cap; hp.rowcnt = p.rowcnt.cap; hp.rowarg = p.rowarg.cap; hp.seed = p.seed.cap; hp.plist = p.plist.cap;
+    hp.fb_list = p.fb_list.cap; hp.tile_tab = p.tile_tab.cap; hp.ctr = p.ctr.cap;
+    exscratch::CentroidSizes hc[2];
+    for (int lv = 0; lv < 2; ++lv) {
+        const auto& c = ex.cen.lv[lv];
+        hc[lv] = {c.n_slots, c.n_cstages, c.n_img_stages, c.Cc.cap, c.rg.cap, c.csq.cap, c.cmax2.cap, c.Cst.cap, c.Cst_plain.cap};
+    }
+    exscratch::PlanSizes hq;
+    hq.stride = q.stride; hq.tiles = q.stride / SK_TILE; hq.item_slots = q.item_slots;
+    hq.sk_keys = q.sk_keys.cap; hq.sk_keys2 = q.sk_keys2.cap; hq.sk_vals = q.sk_vals.cap; hq.sk_tmp = q.sk_tmp.cap; hq.scout_g = q.scout_g.cap; hq.tq = q.tq.cap;
+    hq.need = q.need.cap; hq.need2 = q.need2.cap; hq.glist = q.glist.cap; hq.gcnt = q.gcnt.cap; hq.tlist = q.tlist.cap; hq.tcnt = q.tcnt.cap;
+    hq.tile_counts = q.tile_counts.cap; hq.tile_ticket = q.tile_ticket.cap; hq.items = q.items.cap;
+    const exscratch::Geometry g = exact_geometry(h);
+    int64_t* o = put_block(out, hp, ex.cen.ready ? exscratch::levels(g) : 0, hc, held(ex.srt[0]), hq);
+    o = put_sorted(o, held(ex.srt[1]));
+    put(o, {g.K, g.D, g.dp, g.stage_bytes, g.wide ? 1 : 0, g.item_slots, g.pass_rows_override, g.pairs_hook, (int64_t)p.fbX.cap, (int64_t)p.fb_ids.cap});
+    return 0;
+}
+
 int som_debug_mfma16(som_handle* h, const uint16_t* a_host, const uint16_t* b_host, const float* c_host, float* d_host,
                      int32_t is_f16) {
     DeviceGuard dev_guard(h);
@@ -3174,29 +3255,29 @@ int som_debug_device_bytes(int64_t* out) {
 
 int som_debug_exact_chain_stats(som_handle* h, int64_t* carried_epochs) {
     if (!h || !carried_epochs) return fail(h, "som_debug_exact_chain_stats: NULL argument");
-    *carried_epochs = h->ex.lastpos_carried_epochs;
+    *carried_epochs = h->ex.stats.lastpos_carried_epochs;
     return 0;
 }
 
 int som_debug_exact_select_stats(som_handle* h, int64_t* fused_passes, int64_t* launched_passes, int64_t* ticket_tiles) {
     if (!h || !fused_passes || !launched_passes || !ticket_tiles) return fail(h, "som_debug_exact_select_stats: NULL argument");
-    *fused_passes = h->ex.sel_fused_passes;
-    *launched_passes = h->ex.sel_launched_passes;
-    *ticket_tiles = h->ex.sel_ticket_tiles;
+    *fused_passes = h->ex.stats.sel_fused_passes;
+    *launched_passes = h->ex.stats.sel_launched_passes;
+    *ticket_tiles = h->ex.stats.sel_ticket_tiles;
     return 0;
 }
 
 int som_debug_exact_plan_stats(som_handle* h, int64_t* fused_launches, int64_t* split_launches) {
     if (!h || !fused_launches || !split_launches) return fail(h, "som_debug_exact_plan_stats: NULL argument");
-    *fused_launches = h->ex.plan_fused_launches;
-    *split_launches = h->ex.plan_split_launches;
+    *fused_launches = h->ex.stats.plan_fused_launches;
+    *split_launches = h->ex.stats.plan_split_launches;
     return 0;
 }
 
 int som_debug_exact_plan_fold_stats(som_handle* h, int64_t* folded, int64_t* compared) {
     if (!h || !folded || !compared) return fail(h, "som_debug_exact_plan_fold_stats: NULL argument");
-    *folded = h->ex.plan_folded;
-    *compared = h->ex.plan_compared;
+    *folded = h->ex.stats.plan_folded;
+    *compared = h->ex.stats.plan_compared;
     return 0;
 }
 
@@ -3322,12 +3403,12 @@ int som_debug_exact_tile_blocks(som_handle* h, int32_t* blocks_out, int32_t* gro
     info2[0] = (int32_t)ex.last_plan_tiles; info2[1] = ex.last_plan_l2 ? 1 : 0;
     if (n_tiles == 0 || (!blocks_out && !groups_out)) return 0;
     if (ex.last_plan_tiles <= 0) return fail(h, "som_debug_exact_tile_blocks: the last launch ran no planned pass (up to 128 features)");
-    if (n_tiles > ex.last_plan_tiles || n_tiles * SK_TILE > ex.sk_stride) return fail(h, "som_debug_exact_tile_blocks: the last planned pass had fewer tiles");
+    if (n_tiles > ex.last_plan_tiles || n_tiles * SK_TILE > ex.pbuf.stride) return fail(h, "som_debug_exact_tile_blocks: the last planned pass had fewer tiles");
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (blocks_out) if (int rc = d2h_blocking(h, blocks_out, ex.tcnt, (size_t)n_tiles * sizeof(int32_t))) return rc;
+    if (blocks_out) if (int rc = d2h_blocking(h, blocks_out, ex.pbuf.tcnt, (size_t)n_tiles * sizeof(int32_t))) return rc;
     if (groups_out) {
         std::vector<int2> tc((size_t)n_tiles);
-        if (int rc = d2h_blocking(h, tc.data(), ex.tile_counts, (size_t)n_tiles * sizeof(int2))) return rc;
+        if (int rc = d2h_blocking(h, tc.data(), ex.pbuf.tile_counts, (size_t)n_tiles * sizeof(int2))) return rc;
         for (int64_t t = 0; t < n_tiles; ++t) groups_out[t] = tc[(size_t)t].y;
     }
     return 0;
@@ -3378,9 +3459,9 @@ int som_patch_order(int32_t x, int32_t y, int32_t* perm_out) {
 
 int som_exact_stats(som_handle* h, int64_t* rows, int64_t* rows_fallback, int64_t* passes) {
     if (!h) return 1;
-    if (rows) *rows = h->ex.rows_total;
-    if (rows_fallback) *rows_fallback = h->ex.rows_fallback;
-    if (passes) *passes = h->ex.chunks;
+    if (rows) *rows = h->ex.stats.rows_total;
+    if (rows_fallback) *rows_fallback = h->ex.stats.rows_fallback;
+    if (passes) *passes = h->ex.stats.chunks;
     return 0;
 }
 
@@ -3392,7 +3473,7 @@ int som_exact_top2_stats(som_handle* h, int64_t* rows, int64_t* rows_f32) {
 
 int som_exact_skip_stats(som_handle* h, int64_t* blocks_run, int64_t* blocks_total) {
     if (!h || !blocks_run || !blocks_total) return 1;
-    *blocks_run = h->ex.blocks_run; *blocks_total = h->ex.blocks_total;
+    *blocks_run = h->ex.stats.blocks_run; *blocks_total = h->ex.stats.blocks_total;
     return 0;
 }
 
@@ -3417,8 +3498,8 @@ int som_exact_refine_stats(som_handle* h, int64_t* pairs_in, int64_t* pairs_out)
 int som_exact_last_counts(som_handle* h, int32_t* counts_out, int64_t n) {
     DeviceGuard dev_guard(h);
     if (!h || !counts_out || n < 0) return fail(h, "som_exact_last_counts: bad argument");
-    if (!h->exact || n > h->ex.stride) return fail(h, "som_exact_last_counts: no screen pass of that many rows");
-    if (int rc = d2h_blocking(h, counts_out, h->ex.rowcnt, (size_t)n * sizeof(int32_t))) return rc;
+    if (!h->exact || n > h->ex.pass.stride) return fail(h, "som_exact_last_counts: no screen pass of that many rows");
+    if (int rc = d2h_blocking(h, counts_out, h->ex.pass.rowcnt, (size_t)n * sizeof(int32_t))) return rc;
     return 0;
 }
 
