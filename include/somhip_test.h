@@ -37,6 +37,30 @@ int som_debug_exact_centroids(som_handle* h, int32_t level, float* C_out, float*
 int som_debug_mfma16(som_handle* h, const uint16_t* a_host, const uint16_t* b_host, const float* c_host, float* d_host,
                      int32_t is_f16);
 
+/* Three small kernels of the exact mode's epoch on caller-supplied HOST arrays, copied to device buffers of the call's own and
+ * back (tests/test_gpu_radix_sort_hook.py, tests/test_gpu_select2_tiles_hook.py compare them with NumPy models).  Each call
+ * checks on the host that its input cannot lead the kernel out of those buffers, and launches nothing when it could.
+ *
+ * The stable radix sort of (keys, row index) pairs by the low `bits` bits of the keys (radix_sort_rows, csrc/update.hpp: the
+ * sort by unit takes it on large maps): keys [n] -> keys_out [n], vals_out [n] = the items' indices in sorted order.
+ * 1 <= n < 2^31, 1 <= bits <= 31; key bits from `bits` rounded up to a multiple of 8 on must be zero for a sorted result. */
+int som_debug_radix_sort(som_handle* h, const int32_t* keys, int64_t n, int32_t bits, int32_t* keys_out, int32_t* vals_out);
+
+/* exact_select2_kernel (csrc/bmu_exact.hpp): plist [n_groups][stride] row ids and rmin [n_groups][stride], gcount [n_groups] the
+ * lists' lengths, thr2 [n_rows].  Group g's list is compacted IN PLACE, in list order, to the entries i < gcount[g] with
+ * rmin[g][i] <= thr2[plist[g][i]]; gcount[g] becomes their number and *kept_total the sum over the groups.  What lies behind
+ * a list's survivors is not specified. */
+int som_debug_exact_select2(som_handle* h, int32_t* plist, const uint32_t* rmin, int64_t stride, int32_t* gcount, const uint32_t* thr2,
+                            int32_t n_groups, int64_t n_rows, int32_t* kept_total);
+
+/* exact_tiles_kernel (csrc/bmu_exact.hpp) on a grid of `blocks` workgroups: the lists' entries from gstart (NULL: zeros) to gcount
+ * cut into tiles of up to 128, group by group: tile_tab [table_entries][4] = {group, group * stride + first entry, entries, 0}.
+ * tile_tab and out3 = {n_tiles, overflow, pairs} go to the device as the caller filled them and come back as the kernel left
+ * them (it writes overflow only to raise it; with more than `capacity` pairs it writes no tile); gstart_out (NULL: none)
+ * likewise, and takes the lists' lengths.  Refused where the tiles would not fit in table_entries. */
+int som_debug_exact_tiles(som_handle* h, const int32_t* gcount, const int32_t* gstart, int32_t n_groups, int64_t stride, int64_t capacity,
+                          int32_t blocks, int64_t table_entries, int32_t* tile_tab, int32_t* out3, int32_t* gstart_out);
+
 /* bytes of device memory the engines of this process hold right now (every handle's buffers, scratch included): a closed
  * handle gives back all it took (tests/test_gpu_exact.py).  Returns non-zero for a NULL argument. */
 int som_debug_device_bytes(int64_t* out);

@@ -106,6 +106,9 @@ SIGNATURES = {
     "som_debug_operand_crc": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint64)]),
     "som_debug_exact_centroids": (C.c_int, [_H, C.c_int32, _F, _F, _F, _I]),
     "som_debug_mfma16": (C.c_int, [_H, C.c_void_p, C.c_void_p, _F, _F, C.c_int32]),
+    "som_debug_radix_sort": (C.c_int, [_H, _I, C.c_int64, C.c_int32, _I, _I]),
+    "som_debug_exact_select2": (C.c_int, [_H, _I, C.POINTER(C.c_uint32), C.c_int64, _I, C.POINTER(C.c_uint32), C.c_int32, C.c_int64, _I]),
+    "som_debug_exact_tiles": (C.c_int, [_H, _I, _I, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _I, _I, _I]),
     "som_debug_stamps": (C.c_int, [_H, C.c_int64, C.c_void_p]),
     "som_debug_device_bytes": (C.c_int, [C.POINTER(C.c_int64)]),
     "som_debug_qe_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -306,6 +306,7 @@ __global__ __launch_bounds__(1024) void exact_tiles_kernel(const int* __restrict
                                                            int* __restrict__ pairs_out = nullptr) {
     __shared__ long wsum[16];
     __shared__ int wtsum[16];
+    __shared__ int tpre[1024];                               // tiles before each thread's groups
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int per = (n_groups + 1023) / 1024;
     const int b = tid * per, e = min(b + per, n_groups);
@@ -341,27 +342,31 @@ __global__ __launch_bounds__(1024) void exact_tiles_kernel(const int* __restrict
     }
     // this block's share of the table: the entries [t_lo, t_hi)
     const int t_lo = (int)((long)ttotal * blockIdx.x / gridDim.x), t_hi = (int)((long)ttotal * (blockIdx.x + 1) / gridDim.x);
-    // (a group's tiles are written by its whole wave, sixty-four at a time: a popular group has a hundred and more, and one
-    //  thread writing them one by one set this launch's time)
-    int toff = tbefore + ti - ts;
-    for (int k = 0; k < per; ++k) {
-        const int g = b + k;
-        const bool on = g < e;
-        const int first = (on && gstart) ? gstart[g] : 0;
-        const int c = on ? gcount[g] - first : 0;
-        const int off = on ? (int)((long)g * gm_stride) + first : 0;
-        const int mine = toff;
-        toff += (c + EX_TR - 1) / EX_TR;
-        if (first_block && on && gstart_out) gstart_out[g] = first + c;
-        for (int src = 0; src < 64; ++src) {
-            const int c_s = __builtin_amdgcn_readlane(c, src);
-            if (c_s <= 0) continue;                           // (wave-uniform)
-            const int g_s = __builtin_amdgcn_readlane(g, src), off_s = __builtin_amdgcn_readlane(off, src);
-            const int t_s = __builtin_amdgcn_readlane(mine, src);
-            const int i_end = min((c_s + EX_TR - 1) / EX_TR, t_hi - t_s);
-            for (int i = max(0, t_lo - t_s) + lane; i < i_end; i += 64)
-                tile_tab[t_s + i] = make_int4(g_s, off_s + i * EX_TR, min(EX_TR, c_s - i * EX_TR), 0);
+    // A thread per table entry: the threads' exclusive tile prefixes go to LDS, entry t finds the thread-slot that holds it by
+    // binary search there -- the LAST slot whose prefix is <= t: the slots without tiles before it share that prefix --, then
+    // its group among the slot's `per` groups.  (A popular group has a hundred tiles and more: one thread, or one wave at a
+    // time, writing a group's tiles set this launch's time.)
+    tpre[tid] = tbefore + ti - ts;
+    if (first_block && gstart_out)
+        for (int g = b; g < e; ++g) gstart_out[g] = gcount[g];
+    __syncthreads();
+    for (int t = t_lo + tid; t < t_hi; t += 1024) {
+        int lo = 0, hi = 1023;                                // tpre[lo] <= t (tpre[0] = 0), and no slot above hi holds t
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (tpre[mid] <= t) lo = mid; else hi = mid - 1;
         }
+        int g = lo * per, t_g = tpre[lo], first = 0, c = 0;
+        const int g_last = min(g + per, n_groups) - 1;
+        for (;; ++g) {                                        // (t < ttotal: a group of the slot holds it)
+            first = gstart ? gstart[g] : 0;
+            c = gcount[g] - first;
+            const int nt = (c + EX_TR - 1) / EX_TR;
+            if (t < t_g + nt || g >= g_last) break;
+            t_g += nt;
+        }
+        const int i = t - t_g;
+        tile_tab[t] = make_int4(g, (int)((long)g * gm_stride) + first + i * EX_TR, min(EX_TR, c - i * EX_TR), 0);
     }
     if (first_block && tid == 1023) *n_tiles_out = ttotal;
 }
@@ -500,39 +505,69 @@ __global__ __launch_bounds__(256) void exact_thr2_kernel(uint32_t* __restrict__ 
     rowmin2[i] = (thr > 0.0f && thr < 3.0e38f) ? __float_as_uint(thr) : 0xFFFFFFFFu;
 }
 
-// One workgroup per group: its list compacted IN PLACE to the pairs whose refined minimum is within E2 of the row's
-// (chunks of 256 entries in order: a chunk is read whole before the survivors are written, never beyond where it was read).
+// One workgroup per group: its list compacted IN PLACE to the pairs whose refined minimum is within E2 of the row's,
+// in list order.  A TURN covers 1 024 entries, four a thread: entry (j, wave, lane) of the turn at c0 is c0 + 256 j + 64 wave + lane.
+// The sixteen (j, wave) ballot counts of a turn go through LDS, double-buffered, so a turn costs ONE barrier; every thread
+// carries the output position `out` in a register.  In place: a turn's survivors land below c0 + 1 024 (there are no more survivors than entries read), and every
+// entry at or above c0 + 1 024 is either in registers already (the next turn's, loaded before this turn's barrier) or not yet
+// needed; every read of a turn (and of the next one's prefetch) precedes the turn's barrier and every write follows it, so
+// no write can reach an entry before all of its turn's threads hold theirs.
 __global__ __launch_bounds__(256) void exact_select2_kernel(int* __restrict__ plist, const uint32_t* __restrict__ rmin, long gm_stride,
                                                             int* __restrict__ gcount, const uint32_t* __restrict__ thr2,
                                                             int* __restrict__ kept_total) {
-    __shared__ int wsum[4];
-    __shared__ int out_s;
+    constexpr int J = 4, TURN = 256 * J;
+    __shared__ __attribute__((aligned(16))) int wcnt[2][4][J];   // [turn & 1][wave][j]
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cnt = gcount[g];
     if (cnt <= 0) return;
     int* list = plist + (long)g * gm_stride;
     const uint32_t* rm = rmin + (long)g * gm_stride;
-    if (tid == 0) out_s = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < cnt; c0 += 256) {
-        const int i = c0 + tid;
-        int row = -1;
-        bool keep = false;
-        if (i < cnt) {
-            row = list[i];
-            keep = rm[i] <= thr2[row];                       // (exact_thr2_kernel: all ones where nothing bounds the row)
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int row[J];
+    uint32_t rv[J], tv[J];
+    // the entries of the turn at c0: list and rmin, then the thresholds the list addresses (exact_thr2_kernel: all ones where
+    // nothing bounds the row)
+    auto fetch = [&](int c0) {
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            const int i = c0 + 256 * j + tid;
+            row[j] = i < cnt ? list[i] : 0;
+            rv[j] = i < cnt ? rm[i] : 0u;
         }
-        const unsigned long long mk = __ballot(keep);
-        if (lane == 0) wsum[wave] = __popcll(mk);
-        __syncthreads();                                     // (every entry of the chunk is in registers)
-        int before = out_s;
-        for (int w = 0; w < wave; ++w) before += wsum[w];
-        if (keep) list[before + __popcll(mk & ((1ull << lane) - 1ull))] = row;
-        __syncthreads();
-        if (tid == 0) out_s += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < J; ++j) tv[j] = c0 + 256 * j + tid < cnt ? thr2[row[j]] : 0u;
+    };
+    fetch(0);
+    int out = 0;                                             // survivors so far: the same number in every thread
+    for (int c0 = 0, buf = 0; c0 < cnt; c0 += TURN, buf ^= 1) {
+        int r[J], rank[J], n_w[J];
+        bool keep[J];
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            r[j] = row[j];
+            keep[j] = c0 + 256 * j + tid < cnt && rv[j] <= tv[j];
+            const unsigned long long mk = __ballot(keep[j]);
+            rank[j] = (int)__popcll(mk & below);
+            n_w[j] = (int)__popcll(mk);
+        }
+        if (lane == 0) *reinterpret_cast<int4*>(wcnt[buf][wave]) = make_int4(n_w[0], n_w[1], n_w[2], n_w[3]);
+        if (c0 + TURN < cnt) fetch(c0 + TURN);               // (the next turn's entries: at or above c0 + 1 024)
+        __syncthreads();                                     // (every entry of the turn is in registers, and the next turn's)
+        int pos = out;
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            int mine = pos;                                  // first place of (j, this wave): the waves before it, in order
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const int c = wcnt[buf][w][j];
+                if (w < wave) mine += c;
+                pos += c;
+            }
+            if (keep[j]) list[mine + rank[j]] = r[j];
+        }
+        out = pos;
     }
-    if (tid == 0) { gcount[g] = out_s; atomicAdd(kept_total, out_s); }
+    if (tid == 0) { gcount[g] = out; atomicAdd(kept_total, out); }
 }
 
 // The float32 scores of one tile -- up to EX_TR rows of a group's list against the group's 64 units -- on

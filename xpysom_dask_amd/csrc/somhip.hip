@@ -3247,6 +3247,76 @@ int som_debug_mfma16(som_handle* h, const uint16_t* a_host, const uint16_t* b_ho
     return d2h_blocking(h, d_host, d, 1024);
 }
 
+int som_debug_radix_sort(som_handle* h, const int32_t* keys, int64_t n, int32_t bits, int32_t* keys_out, int32_t* vals_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || !keys || !keys_out || !vals_out) return fail(h, "som_debug_radix_sort: NULL argument");
+    if (n < 1 || n > 0x7fffffffL || bits < 1 || bits > 31) return fail(h, "som_debug_radix_sort: n or bits out of range");
+    DevBuf<int> kin, ko, vo, tmp;
+    int rc = 0;
+    if ((rc = kin.alloc(h, (size_t)n)) || (rc = ko.alloc(h, (size_t)n)) || (rc = vo.alloc(h, (size_t)n)) ||
+        (rc = tmp.alloc(h, radix_scratch_ints(n)))) return rc;
+    if (h2d_blocking(h, kin, keys, (size_t)n * sizeof(int))) return 1;
+    if ((rc = radix_sort_rows(h, kin, n, bits, ko, vo, tmp))) return rc;
+    if (d2h_blocking(h, keys_out, ko, (size_t)n * sizeof(int))) return 1;
+    return d2h_blocking(h, vals_out, vo, (size_t)n * sizeof(int));
+}
+
+int som_debug_exact_select2(som_handle* h, int32_t* plist, const uint32_t* rmin, int64_t stride, int32_t* gcount, const uint32_t* thr2,
+                            int32_t n_groups, int64_t n_rows, int32_t* kept_total) {
+    DeviceGuard dev_guard(h);
+    if (!h || !plist || !rmin || !gcount || !thr2 || !kept_total) return fail(h, "som_debug_exact_select2: NULL argument");
+    if (n_groups < 1 || stride < 1 || n_rows < 1 || (int64_t)n_groups * stride > 0x7fffffffL)
+        return fail(h, "som_debug_exact_select2: size out of range");
+    for (int g = 0; g < n_groups; ++g) {                      // (the kernel trusts its lists: nothing runs on one that leaves its buffers)
+        if (gcount[g] > stride) return fail(h, "som_debug_exact_select2: a list longer than the stride");
+        for (int i = 0; i < gcount[g]; ++i)
+            if (plist[g * stride + i] < 0 || plist[g * stride + i] >= n_rows) return fail(h, "som_debug_exact_select2: a list entry is no row");
+    }
+    const size_t cells = (size_t)n_groups * (size_t)stride;
+    DevBuf<int> dl, dc, dk;
+    DevBuf<uint32_t> dm, dt;
+    int rc = 0;
+    if ((rc = dl.alloc(h, cells)) || (rc = dm.alloc(h, cells)) || (rc = dc.alloc(h, (size_t)n_groups)) || (rc = dt.alloc(h, (size_t)n_rows)) ||
+        (rc = dk.alloc(h, 1))) return rc;
+    const int zero = 0;
+    if (h2d_blocking(h, dl, plist, cells * sizeof(int)) || h2d_blocking(h, dm, rmin, cells * sizeof(uint32_t)) ||
+        h2d_blocking(h, dc, gcount, (size_t)n_groups * sizeof(int)) || h2d_blocking(h, dt, thr2, (size_t)n_rows * sizeof(uint32_t)) ||
+        h2d_blocking(h, dk, &zero, sizeof(int))) return 1;
+    exact_select2_kernel<<<dim3((unsigned)n_groups), dim3(256), 0, h->stream>>>(dl, dm, stride, dc, dt, dk);
+    HIPCHK(h, hipGetLastError());
+    if (d2h_blocking(h, plist, dl, cells * sizeof(int)) || d2h_blocking(h, gcount, dc, (size_t)n_groups * sizeof(int))) return 1;
+    return d2h_blocking(h, kept_total, dk, sizeof(int));
+}
+
+int som_debug_exact_tiles(som_handle* h, const int32_t* gcount, const int32_t* gstart, int32_t n_groups, int64_t stride, int64_t capacity,
+                          int32_t blocks, int64_t table_entries, int32_t* tile_tab, int32_t* out3, int32_t* gstart_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || !gcount || !tile_tab || !out3) return fail(h, "som_debug_exact_tiles: NULL argument");
+    if (n_groups < 1 || stride < 1 || blocks < 1 || blocks > 64 || table_entries < 1 || (int64_t)n_groups * stride > 0x7fffffffL)
+        return fail(h, "som_debug_exact_tiles: size out of range");
+    int64_t pairs = 0, tiles = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const int64_t c = (int64_t)gcount[g] - (gstart ? gstart[g] : 0);
+        if (c < 0) return fail(h, "som_debug_exact_tiles: a list shorter than its start");
+        pairs += c; tiles += (c + EX_TR - 1) / EX_TR;
+    }
+    if (pairs <= capacity && tiles > table_entries) return fail(h, "som_debug_exact_tiles: the table does not hold the tiles");
+    DevBuf<int> dc, ds, dso, dout;
+    DevBuf<int4> dtab;
+    int rc = 0;
+    if ((rc = dc.alloc(h, (size_t)n_groups)) || (rc = ds.alloc(h, (size_t)n_groups)) || (rc = dso.alloc(h, (size_t)n_groups)) ||
+        (rc = dout.alloc(h, 3)) || (rc = dtab.alloc(h, (size_t)table_entries))) return rc;
+    if (h2d_blocking(h, dc, gcount, (size_t)n_groups * sizeof(int)) || h2d_blocking(h, dout, out3, 3 * sizeof(int)) ||
+        h2d_blocking(h, dtab, tile_tab, (size_t)table_entries * sizeof(int4))) return 1;
+    if (gstart && h2d_blocking(h, ds, gstart, (size_t)n_groups * sizeof(int))) return 1;
+    if (gstart_out && h2d_blocking(h, dso, gstart_out, (size_t)n_groups * sizeof(int))) return 1;
+    exact_tiles_kernel<<<dim3((unsigned)blocks), dim3(1024), 0, h->stream>>>(dc, n_groups, stride, capacity, dtab, dout.p, dout.p + 1,
+                                                                             gstart ? ds.p : nullptr, gstart_out ? dso.p : nullptr, dout.p + 2);
+    HIPCHK(h, hipGetLastError());
+    if (d2h_blocking(h, tile_tab, dtab, (size_t)table_entries * sizeof(int4)) || d2h_blocking(h, out3, dout, 3 * sizeof(int))) return 1;
+    return gstart_out ? d2h_blocking(h, gstart_out, dso, (size_t)n_groups * sizeof(int)) : 0;
+}
+
 int som_debug_device_bytes(int64_t* out) {
     if (!out) return 1;
     *out = g_dev_bytes.load();

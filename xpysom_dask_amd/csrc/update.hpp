@@ -54,10 +54,12 @@ constexpr int SEG_MAX_WAVES = 16;  // waves per workgroup (fewer when 2 * waves 
 // for these two jobs (keys of 10 .. 20 bits, values = row indices, 10^5 .. 10^7 items): per pass
 //   rs_hist_kernel     block = RS_BLOCK consecutive items: LDS histogram of the pass's digit -> table[digit * B + block]
 //   rs_scan_kernel     a wave per digit: exclusive scan of its block counts in place, its total -> tot[digit]
-//   rs_scatter_kernel  block = the same RS_BLOCK items, 256 at a time in item order, the waves one after the other: the first
-//                      destination of a (digit, block) run = the totals of the lower digits + the block's place in its digit; an item's
-//                      destination = its run's cursor + its rank among the wave's items of the same digit: the order of equal
-//                      digits is the order of the items -- STABLE, and the same order on every run (no atomics decide a place)
+//   rs_scatter_kernel  block = the same RS_BLOCK items, all loaded up front: item (q, wave, lane) = 256 q + 64 wave + lane.  The first
+//                      destination of a (digit, block) run = the totals of the lower digits + the block's place in its digit; every
+//                      (q, wave) leaves its count of each digit in an LDS cell, the digit's thread turns the cells into first
+//                      destinations in item order, and an item's destination = its cell + its rank among the wave's items of the
+//                      same digit: the order of equal digits is the order of the items -- STABLE, and the same order on every run
+//                      (no atomics decide a place; two barriers a block)
 // vin == nullptr: the values are the items' own indices (first pass of a sort of row ids).
 __global__ __launch_bounds__(256) void rs_hist_kernel(const int* __restrict__ keys, long n, int shift, int B, int* __restrict__ table) {
     __shared__ int hist[256];
@@ -94,49 +96,68 @@ __global__ __launch_bounds__(256) void rs_scan_kernel(int* __restrict__ table, i
 __global__ __launch_bounds__(256) void rs_scatter_kernel(const int* __restrict__ kin, const int* __restrict__ vin, long n, int shift,
                                                          int B, const int* __restrict__ table, const int* __restrict__ tot,
                                                          int* __restrict__ kout, int* __restrict__ vout) {
-    __shared__ int cur[256];                                 // next destination of every digit for this block
+    constexpr int Q = RS_BLOCK / 256;                        // 256-item steps of the block
+    __shared__ __attribute__((aligned(16))) int cell[4 * Q][256];   // [4 q + wave][digit]: the (step, wave)'s items of the digit, then their first destination
     __shared__ int wsum[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    {   // first destination of digit `tid`: the totals of the digits below it + this block's place inside the digit
-        const int mine = tot[tid];
-        int incl = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wave; ++w) before += wsum[w];
-        cur[tid] = before + incl - mine + table[(long)tid * B + blockIdx.x];
-    }
-    __syncthreads();
     const long i0 = (long)blockIdx.x * RS_BLOCK;
-    for (int q = 0; q < RS_BLOCK / 256; ++q) {
+    // every load of the block first: the items stay in registers, and no load waits behind a barrier
+    int key[Q], val[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
         const long i = i0 + q * 256 + tid;
-        const bool live = i < n;
-        const int key = live ? kin[i] : 0;
-        const int val = live ? (vin != nullptr ? vin[i] : (int)i) : 0;
-        const int dg = (key >> shift) & 255;
-        // the lanes of this wave with the same digit
+        key[q] = i < n ? kin[i] : 0;
+        val[q] = i < n ? (vin != nullptr ? vin[i] : (int)i) : 0;
+    }
+    const int mine = tot[tid];
+    const int place = table[(long)tid * B + blockIdx.x];
+    {
+        int4* z = reinterpret_cast<int4*>(&cell[0][0]);
+#pragma unroll
+        for (int k = 0; k < 4 * Q * 256 / 4 / 256; ++k) z[k * 256 + tid] = make_int4(0, 0, 0, 0);
+    }
+    // first destination of digit `tid`: the totals of the digits below it + this block's place inside the digit
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();                                         // (the cells are zero)
+    int cur = incl - mine + place;
+    for (int w = 0; w < wave; ++w) cur += wsum[w];
+    // an item's rank among its wave's items of the same digit (lower lane first); the digit's leader leaves their number in
+    // the (step, wave)'s cell -- one leader per cell, so no two lanes write one
+    int dgrank[Q];                                           // digit | rank << 8
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const bool live = i0 + q * 256 + tid < n;
+        const int dg = (key[q] >> shift) & 255;
         unsigned long long peers = __ballot(live);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
             const unsigned long long m = __ballot((dg >> b) & 1);
             peers &= ((dg >> b) & 1) ? m : ~m;
         }
-        const int leader = live ? (int)__builtin_ctzll(peers) : lane;
         const int rank = (int)__builtin_popcountll(peers & ((1ull << lane) - 1ull));
-        const int count = (int)__builtin_popcountll(peers);
-        int dest = 0;
-        for (int w = 0; w < 4; ++w) {                        // waves in item order: the sort is stable
-            if (wave == w) {
-                int old = 0;
-                if (live && lane == leader) { old = cur[dg]; cur[dg] = old + count; }
-                old = __shfl(old, leader, 64);
-                dest = old + rank;
-            }
-            __syncthreads();
+        if (live && rank == 0) cell[4 * q + wave][dg] = (int)__builtin_popcountll(peers);
+        dgrank[q] = dg | (rank << 8);
+    }
+    __syncthreads();
+    // thread d walks its digit's cells in item order (step, then wave): counts -> first destinations.  These are the places
+    // the waves would take one after the other: the order of equal digits is the order of the items -- STABLE
+    {
+        int c[4 * Q];
+#pragma unroll
+        for (int k = 0; k < 4 * Q; ++k) c[k] = cell[k][tid];
+#pragma unroll
+        for (int k = 0; k < 4 * Q; ++k) { cell[k][tid] = cur; cur += c[k]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        if (i0 + q * 256 + tid < n) {
+            const int dest = cell[4 * q + wave][dgrank[q] & 255] + (dgrank[q] >> 8);
+            kout[dest] = key[q]; vout[dest] = val[q];
         }
-        if (live) { kout[dest] = key; vout[dest] = val; }
     }
 }
 

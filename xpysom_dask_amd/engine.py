@@ -577,6 +577,40 @@ class HipEngine:
         self._check(self._lib.som_debug_unit_sort_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def debug_radix_sort(self, keys, bits):
+        """(sorted keys, their indices): the stable radix sort of csrc/update.hpp on int32 keys of `bits` bits."""
+        keys = np.ascontiguousarray(keys, dtype=np.int32)
+        ko, vo = np.empty_like(keys), np.empty_like(keys)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.som_debug_radix_sort(self._h, ip(keys), keys.size, int(bits), ip(ko), ip(vo)))
+        return ko, vo
+
+    def debug_exact_select2(self, plist, rmin, gcount, thr2):
+        """exact_select2_kernel on copies of plist, rmin [groups][stride], gcount [groups], thr2 [rows]: (plist, gcount, kept)."""
+        plist = np.array(plist, dtype=np.int32, order="C")
+        rmin = np.ascontiguousarray(rmin, dtype=np.uint32)
+        gcount = np.array(gcount, dtype=np.int32, order="C")
+        thr2 = np.ascontiguousarray(thr2, dtype=np.uint32)
+        assert plist.ndim == 2 and rmin.shape == plist.shape and gcount.shape == plist.shape[:1]
+        kept = C.c_int32(-1)
+        ip, up = (lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)))
+        self._check(self._lib.som_debug_exact_select2(self._h, ip(plist), up(rmin), plist.shape[1], ip(gcount), up(thr2),
+                                                      plist.shape[0], thr2.size, C.byref(kept)))
+        return plist, gcount, kept.value
+
+    def debug_exact_tiles(self, gcount, stride, capacity, blocks, table_entries, gstart=None, want_gstart_out=False):
+        """exact_tiles_kernel on a grid of `blocks`: (tile table [table_entries][4], pre-filled with -1, {n_tiles, overflow,
+        pairs} started as {-1, 0, -1}, gstart_out pre-filled with -1 or None)."""
+        gcount = np.ascontiguousarray(gcount, dtype=np.int32)
+        gs = None if gstart is None else np.ascontiguousarray(gstart, dtype=np.int32)
+        tab = np.full((int(table_entries), 4), -1, dtype=np.int32)
+        out3 = np.array([-1, 0, -1], dtype=np.int32)
+        gso = np.full(gcount.shape, -1, dtype=np.int32) if want_gstart_out else None
+        ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.som_debug_exact_tiles(self._h, ip(gcount), ip(gs), gcount.size, int(stride), int(capacity), int(blocks),
+                                                    int(table_entries), ip(tab), ip(out3), ip(gso)))
+        return tab, out3, gso
+
     def band_tables(self):
         """(bands on, entries [n][2], P1 [nt][Y][Y], P2 [X][nt * X]): the neighbourhood tables of the last build and the nonzero
         column ranges recorded with them, read back from the device (som_debug_band_tables, include/somhip_test.h)."""
