@@ -109,7 +109,8 @@ enum { SOM_BMU_ACTIVATION = 0,   /* configured activation distance: XPySom._winn
 /* timed kernels for som_profile_get */
 enum { SOM_K_BMU = 0, SOM_K_SEGSUM = 1, SOM_K_KRON = 2, SOM_K_MERGE = 3, SOM_K_PREP = 4,
        SOM_K_SCREEN = 5,   /* precision EXACT: the MFMA screen kernel alone (a part of SOM_K_BMU's time) */
-       SOM_K_COUNT = 6 };
+       SOM_K_FILL = 6,     /* som_impute*: the fill of the completed rows alone (csrc/impute.hpp; its search is SOM_K_BMU's) */
+       SOM_K_COUNT = 7 };
 
 typedef struct som_config {
     int32_t x, y, input_len;     /* map rows, cols, features: XPySom.__init__, xpysom.py:73 */
@@ -313,6 +314,29 @@ int som_bmu_distances(som_handle* h, const float* x_host, int64_t n_rows, int32_
 int som_bmu_distances_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids_out, float* dist_out);
 int som_unit_stats(som_handle* h, const float* x_host, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max);
 int som_unit_stats_device(som_handle* h, const void* x_dev, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max);
+/* Missing values, the completed rows (not in the reference; csrc/impute.hpp): each NaN of a row replaced by what the row's unit
+ * holds for that feature.  Only on a handle created with SOM_MISSING_NAN.
+ *   a_n   the unit som_bmu(ACTIVATION) names for row n on this handle and codebook: the masked search of csrc/bmu_masked_f32.hpp,
+ *         unchanged (a row with nothing observed takes unit 0)
+ *   out[n][d] = x[n][d]      where x[n][d] is observed (x == x), BIT FOR BIT: -0.0, +-Inf and denormals as they are
+ *   out[n][d] = W[a_n][d]    where x[n][d] is a NaN of any bit pattern: the float32 codebook value, bit for bit
+ * A row with nothing observed becomes W[0]; a complete row is returned as it is and touches no codebook memory.  No arithmetic is
+ * done on a value, so there is no tolerance: two calls, and the host and the device entry point on the same rows, return the
+ * same bits.  A codebook that itself holds a NaN (som_set_weights: the caller's doing) hands that NaN on.
+ * ids_out [n_rows] = a_n, host memory, or NULL.  n_rows == 0 writes nothing and returns 0.
+ * som_impute: x_host and out_host are float32 [n_rows][input_len] host arrays; the rows are staged as som_bmu stages them and
+ *   the result is copied back.  out_host == x_host is allowed.
+ * som_impute_device: x_dev as in som_bmu_device (borrowed for the call, the same argument checks, at most 2^31-1 rows; order the
+ *   engine behind the producers of BOTH arrays with som_sync_producer first).  out_dev: float32 [n_rows][input_len] in HBM, the
+ *   caller's; every element is stored.  out_dev == x_dev fills in place: only the NaNs are stored, every element is read before
+ *   it is written and by no other lane.  Neither pointer needs any alignment beyond a float's (aligned arrays with input_len % 4
+ *   == 0 move 16 bytes a lane).  The call returns only after the fill has completed on the handle's stream: any stream of the
+ *   caller may then read out_dev.
+ * Refused, with a message that names the call: a handle without SOM_MISSING_NAN; a NULL row or out pointer with n_rows > 0;
+ * n_rows < 0; ranges of x and out that overlap without being the same array.
+ * A query: resident rows, their ids, the weights, the monitor's state and the exact mode's plans stay as they were. */
+int som_impute(som_handle* h, const float* x_host, int64_t n_rows, float* out_host, int32_t* ids_out);
+int som_impute_device(som_handle* h, const void* x_dev, int64_t n_rows, void* out_dev, int32_t* ids_out);
 /* Label and value maps (not in the reference): what the rows a unit wins carry -- class labels, or columns of numbers the map was
  * not trained on.  a_n = the unit som_bmu(ACTIVATION) names for row n on this handle: the configured distance and precision
  * (SOM_MISSING_NAN: the masked search), the ids XPySom.predict / labels_map use -- not b_n above.  Outputs are host arrays

@@ -14,7 +14,7 @@ SOM_PREC = {"f32": 0, "bf16": 1, "f16": 3, "exact": 5}      # (ids 2 and 4: the 
 SOM_TOPO = {"rectangular": 0, "hexagonal": 1, "toroidal": 2}
 SOM_MISSING = {None: 0, "nan": 1}
 SOM_BMU_ACTIVATION, SOM_BMU_QUANTIZATION = 0, 1
-SOM_KERNELS = {"bmu": 0, "segsum": 1, "kron": 2, "merge": 3, "prep": 4, "screen": 5}
+SOM_KERNELS = {"bmu": 0, "segsum": 1, "kron": 2, "merge": 3, "prep": 4, "screen": 5, "fill": 6}
 
 
 class SomConfig(C.Structure):
@@ -86,6 +86,8 @@ SIGNATURES = {
     "som_bmu_distances_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _I, _F]),
     "som_unit_stats": (C.c_int, [_H, _F, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
     "som_unit_stats_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), _F]),
+    "som_impute": (C.c_int, [_H, _F, C.c_int64, _F, _I]),
+    "som_impute_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p, _I]),
     "som_unit_label_counts": (C.c_int, [_H, _F, _I, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "som_unit_label_counts_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "som_unit_value_sums": (C.c_int, [_H, _F, _F, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -38,6 +38,7 @@
 #include "diag.hpp"
 #include "monitor.hpp"
 #include "project.hpp"
+#include "impute.hpp"
 #include "moments.hpp"
 
 using namespace somhip;
@@ -2810,6 +2811,48 @@ int query_unit_value_sums(som_handle* h, const std::string& who, const float* x_
     if (int rc = d2h_blocking(h, sum, g.psums, KC * sizeof(double))) return rc;
     return d2h_blocking(h, sumsq, g.psums + KC, KC * sizeof(double));
 }
+
+// ---- missing values: the completed rows (impute.hpp) ----
+// out[n][d] = X[n][d] where observed, W[ids[n]][d] where NaN, on the handle's stream; out == X fills in place.  16 bytes a lane
+// where input_len and the three addresses as they ARE allow it (a caller's view may start at any float), else a float a lane.
+// The grid is bounded as qe_grid is; the kernel strides over its tiles of rows.
+int launch_impute(som_handle* h, const float* X, const int* ids, long N, float* out) {
+    const bool vec = h->D % 4 == 0 && (((uintptr_t)X | (uintptr_t)out | (uintptr_t)h->W.p) & 15) == 0;
+    const long tiles = cdiv(N, impute_tile_rows(vec ? h->D / 4 : h->D));
+    const dim3 grid((unsigned)std::min<long>(tiles, 4096));
+    Timed t(h, SOM_K_FILL);
+    if (vec) impute_rows_kernel<4><<<grid, dim3(256), 0, h->stream>>>(X, ids, h->W, N, h->D, out);
+    else impute_rows_kernel<1><<<grid, dim3(256), 0, h->stream>>>(X, ids, h->W, N, h->D, out);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int query_impute(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, float* out_host,
+                 void* out_dev, int32_t* ids_out) {
+    DeviceGuard dev_guard(h);
+    if (!h) return fail(h, who + ": NULL handle");
+    if (!h->masked) return fail(h, who + ": the handle was not created with SOM_MISSING_NAN: there is nothing to fill");
+    if (n_rows < 0) return fail(h, who + ": n_rows < 0");
+    if (n_rows == 0) return 0;
+    if (!x_host && !x_dev) return fail(h, who + ": the rows are NULL");
+    if (!out_host && !out_dev) return fail(h, who + ": out is NULL");
+    if (x_dev && n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    const size_t bytes = (size_t)n_rows * h->D * sizeof(float);
+    {
+        const uintptr_t a = x_host ? (uintptr_t)x_host : (uintptr_t)x_dev, b = out_host ? (uintptr_t)out_host : (uintptr_t)out_dev;
+        if (a != b && a < b + bytes && b < a + bytes) return fail(h, who + ": the rows and out overlap without being the same array");
+    }
+    if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
+    RowSet& q = h->q;
+    if (int rc = prepare(h, q, needs_xsq(h))) return rc;                 // (som_bmu ACTIVATION's own steps: the same ids)
+    if (int rc = run_activation_bmu(h, q.view())) return rc;
+    // host rows: filled where they were staged, in place, and copied back; device rows: into the caller's array
+    float* out = x_host ? q.X_owned.p : (float*)out_dev;
+    if (int rc = launch_impute(h, q.X, q.bmu, n_rows, out)) return rc;
+    if (x_host) if (int rc = d2h_blocking(h, out_host, out, bytes)) return rc;
+    if (ids_out) return d2h_blocking(h, ids_out, q.bmu, (size_t)n_rows * sizeof(int));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                          // the fill is complete when the call returns
+    return 0;
+}
 }  // namespace
 
 int som_bmu(som_handle* h, const float* x_host, int64_t n_rows, int32_t mode, int32_t* ids_out) { return query_bmu(h, "som_bmu", x_host, nullptr, n_rows, mode, ids_out); }
@@ -2820,6 +2863,8 @@ int som_quantization_error(som_handle* h, const float* x_host, int64_t n_rows, d
 int som_quantization_error_device(som_handle* h, const void* x_dev, int64_t n_rows, double* qe_out) { return query_quantization_error(h, "som_quantization_error_device", nullptr, x_dev, n_rows, qe_out); }
 int som_bmu_distances(som_handle* h, const float* x_host, int64_t n_rows, int32_t* ids_out, float* dist_out) { return query_bmu_distances(h, "som_bmu_distances", x_host, nullptr, n_rows, ids_out, dist_out); }
 int som_bmu_distances_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t* ids_out, float* dist_out) { return query_bmu_distances(h, "som_bmu_distances_device", nullptr, x_dev, n_rows, ids_out, dist_out); }
+int som_impute(som_handle* h, const float* x_host, int64_t n_rows, float* out_host, int32_t* ids_out) { return query_impute(h, "som_impute", x_host, nullptr, n_rows, out_host, nullptr, ids_out); }
+int som_impute_device(som_handle* h, const void* x_dev, int64_t n_rows, void* out_dev, int32_t* ids_out) { return query_impute(h, "som_impute_device", nullptr, x_dev, n_rows, nullptr, out_dev, ids_out); }
 int som_unit_stats(som_handle* h, const float* x_host, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max) { return query_unit_stats(h, "som_unit_stats", x_host, nullptr, n_rows, count, sum, sumsq, max); }
 int som_unit_stats_device(som_handle* h, const void* x_dev, int64_t n_rows, int64_t* count, double* sum, double* sumsq, float* max) { return query_unit_stats(h, "som_unit_stats_device", nullptr, x_dev, n_rows, count, sum, sumsq, max); }
 int som_unit_label_counts(som_handle* h, const float* x_host, const int32_t* labels_host, int64_t n_rows, int32_t n_classes, int64_t* counts) { return query_unit_label_counts(h, "som_unit_label_counts", x_host, nullptr, labels_host, n_rows, n_classes, counts); }

@@ -360,6 +360,23 @@ class HipEngine:
         self._check(self._lib.som_bmu_distances_device(self._h, C.c_void_p(dev_ptr), int(n_rows), self._ip(ids), self._fp(dist)))
         return ids, dist
 
+    # -- missing values: the completed rows (include/somhip.h, som_impute) -------------------
+    def impute(self, x):
+        """(out float32 like x, ids int32): every NaN of a row replaced by what the row's unit (the ACTIVATION search's) holds
+        for that feature, everything else bit for bit; a new array, x is not written.  Needs missing='nan'."""
+        x = self._rows_arg(x)
+        out = np.empty_like(x)
+        ids = np.empty((x.shape[0],), dtype=np.int32)
+        self._check(self._lib.som_impute(self._h, self._fp(x), x.shape[0], self._fp(out), self._ip(ids)))
+        return out, ids
+
+    def impute_device(self, dev_ptr, n_rows, out_ptr):
+        """impute of float32 rows that already live in HBM (`dev_ptr`: [n_rows][D], borrowed for the call) into the caller's
+        `out_ptr` ([n_rows][D] in HBM; the same pointer: in place).  Returns the ids; the fill is complete on return."""
+        ids = np.empty((int(n_rows),), dtype=np.int32)
+        self._check(self._lib.som_impute_device(self._h, C.c_void_p(dev_ptr), int(n_rows), C.c_void_p(out_ptr), self._ip(ids)))
+        return ids
+
     def _unit_stats_out(self):
         out = (np.empty((self.K,), dtype=np.int64), np.empty((self.K,), dtype=np.float64), np.empty((self.K,), dtype=np.float64),
                np.empty((self.K,), dtype=np.float32))

@@ -357,7 +357,8 @@ class XPySom:
                          features.  The codebook never receives a NaN from the data.  'euclidean' only, precision 'exact'
                          or 'f32' (both run the float32 masked kernel); every neighbourhood and topology; train (with
                          sample_weight, device rows), train_streaming, winner, predict, quantization, quantization_error,
-                         activation_response, win_map, labels_map.  topographic_error, activate and
+                         activation_response, win_map, labels_map, impute (every NaN of a row replaced by its best matching
+                         unit's value for that feature).  topographic_error, activate and
                          distance_from_weights raise NotImplementedError; the initialisers refuse data with a NaN
         """
         if sigma >= x or sigma >= y:
@@ -848,6 +849,94 @@ class XPySom:
         if not parts:
             return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float32)
         return np.concatenate([p[0] for p in parts]).astype(np.int64), np.concatenate([p[1] for p in parts])
+
+    def _impute_out(self, data, owner, ptr, n, out, eng):
+        """(pointer, object to return) of ``impute``'s result for device rows: checked here, before the engine is called."""
+        d = self._input_len
+        is_torch = type(owner).__module__.split(".")[0] == "torch"
+        if out is None:
+            if not is_torch:
+                raise ValueError("impute(): out=None allocates the result, which the library does only for torch tensors; "
+                                 "pass out= (out=data fills in place)")
+            import torch
+            res = torch.empty_like(owner)
+            return res.data_ptr(), res
+        if out is data:
+            if is_torch and (owner.dtype != data.dtype or not data.is_contiguous()):
+                raise ValueError("impute(): out=data needs contiguous float32 rows; these had to be converted, so a fill in "
+                                 "place would not reach them")
+            if not is_torch and data.__cuda_array_interface__["data"][1]:
+                raise ValueError("impute(): out is read-only")
+            return ptr, data
+        if type(out).__module__.split(".")[0] == "torch" and getattr(out, "is_cuda", False):
+            import torch
+            if out.dtype != torch.float32 or not out.is_contiguous():
+                raise ValueError("impute(): out must be a C-contiguous float32 array, got %s%s" % (
+                    out.dtype, "" if out.is_contiguous() else ", not contiguous"))
+            if tuple(out.shape) != (n, d):
+                raise ValueError("impute(): out has shape %r, the rows %r" % (tuple(out.shape), (n, d)))
+            if out.device.index != eng.device:
+                raise ValueError('impute(): out lives on cuda:%d, the engine on cuda:%d' % (out.device.index, eng.device))
+            torch.cuda.current_stream(out.device).synchronize()
+            out_ptr = out.data_ptr()
+        else:
+            cai = getattr(out, "__cuda_array_interface__", None)
+            if cai is None:
+                raise ValueError("impute(): out must be an array in device memory (a torch CUDA tensor or a "
+                                 "__cuda_array_interface__ object)")
+            if cai["typestr"] != "<f4" or cai.get("strides") is not None:
+                raise ValueError("impute(): out must be a C-contiguous float32 array")
+            if tuple(cai["shape"]) != (n, d):
+                raise ValueError("impute(): out has shape %r, the rows %r" % (tuple(cai["shape"]), (n, d)))
+            if cai["data"][1]:
+                raise ValueError("impute(): out is read-only")
+            eng.sync_producer(cai.get("stream"))
+            out_ptr = int(cai["data"][0])
+        nbytes = n * d * 4
+        if out_ptr != ptr and out_ptr < ptr + nbytes and ptr < out_ptr + nbytes:
+            raise ValueError("impute(): out overlaps the rows without being the same array")
+        return out_ptr, out
+
+    def impute(self, data, *, out=None, return_ids=False):
+        """The samples with every NaN replaced by the value their best matching unit holds for that feature; needs
+        ``missing='nan'``.  The unit is the one ``predict`` names (the search over the row's observed features); observed
+        values come back bit for bit (``-0.0``, ``inf`` and denormals as they are), the filled ones are the float32 codebook
+        values bit for bit; a row with nothing observed becomes unit 0's vector, a complete row is returned as it is.  If the
+        codebook itself holds a NaN (``_weights`` set by hand), that NaN is copied.  Train on ``[X | y]``, query with
+        ``y = NaN`` and read ``y`` off the result: the map as a predictor.
+
+        Host rows (array-like; a 1-D input is one sample and returns 1-D): a new float32 array of the input's shape, in
+        ``n_parallel`` chunks; the input is never modified and ``out`` must be ``None``.  Rows in HBM (a torch CUDA tensor or a
+        ``__cuda_array_interface__`` object) are searched and filled where they are, whole: ``out=None`` returns a new tensor
+        on the same device (torch only: the library allocates nothing else that it hands to a caller), ``out=data`` fills in
+        place and returns ``data``, any other ``out`` must be a writable C-contiguous float32 device array of the same shape
+        on the engine's device that does not partly overlap the rows.  ``return_ids=True`` returns ``(rows, ids)``, ids int64
+        and raveled as in ``predict``."""
+        if getattr(self, '_missing', None) != 'nan':
+            raise ValueError("impute() needs missing='nan': without it a NaN is a value like any other, and there is nothing to fill")
+        if out is not None and not _is_device_array(data):
+            raise ValueError("impute(): out is for rows in device memory; host rows return a new array")
+        q = self._device_query(data)
+        if q is not None:
+            eng, ptr, n, owner = q
+            out_ptr, res = self._impute_out(data, owner, ptr, n, out, eng)
+            ids = eng.impute_device(ptr, n, out_ptr) if n else np.zeros(0, np.int32)
+            return (res, ids.astype(np.int64)) if return_ids else res
+        if out is not None:
+            raise ValueError("impute(): out needs 2-dimensional rows in device memory")
+        data = _host_rows(data, self._engine)
+        one = data.ndim == 1
+        if one:
+            data = data[None, :]
+        if len(data):
+            self._check_input_len(data)
+        eng = self._upload_weights()
+        parts = [eng.impute(data[s:s + self._n_parallel]) for s in range(0, len(data), self._n_parallel)]
+        rows = np.concatenate([p[0] for p in parts]) if parts else np.empty(data.shape, dtype=np.float32)
+        ids = np.concatenate([p[1] for p in parts]).astype(np.int64) if parts else np.zeros(0, dtype=np.int64)
+        if one:
+            rows = rows[0]
+        return (rows, ids) if return_ids else rows
 
     def unit_statistics(self, data):
         """Per-unit statistics of the samples' distances to their best matching units, a ``UnitStatistics`` of ``(x, y)``
