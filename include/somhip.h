@@ -356,6 +356,28 @@ int som_unit_label_counts(som_handle* h, const float* x_host, const int32_t* lab
 int som_unit_label_counts_device(som_handle* h, const void* x_dev, const void* labels_dev, int64_t n_rows, int32_t n_classes, int64_t* counts);
 int som_unit_value_sums(som_handle* h, const float* x_host, const float* v_host, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq);
 int som_unit_value_sums_device(som_handle* h, const void* x_dev, const void* v_dev, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq);
+/* Data density per unit (not in the reference; csrc/density.hpp): Ultsch's P-matrix -- for every unit, how many rows lie within a
+ * radius of its weight vector.  The one map diagnostic that does not follow from BMU ids: a full n_rows x K x input_len scan, run
+ * on the float32 MFMA with a counting epilogue, the (n_rows, K) distances never written.  For radii r_1 .. r_R (1 <= R <= 8, host
+ * floats) and a pivot c (input_len host floats; NULL: no centring):
+ *   counts[j][k] = #{ n : sq(n, k) <= r2_j }      host array [n_radii][K], K = x * y, k = i * y + j
+ *   r2_j = float32(r_j * r_j), the product formed in double;   x' = fl32(x - c),  w' = fl32(w - c);
+ *   sq(n, k) = fl32( fmaf(-2, x'_n . w'_k, |w'_k|^2) + |x'_n|^2 ), the dot product a k-ordered float32 fma chain, each norm a
+ *   float32 sum of the rounded squares in one fixed order.  The comparison is inclusive.
+ * Always Euclidean and always float32, whatever the handle's activation distance and precision are (as som_quantization_error's
+ * distance is).  The GEMM form cancels on un-centred data; distances are translation invariant, so the caller passes a pivot near
+ * the data -- XPySom.density_map passes the midrange of the codebook, float32((min_k w_kd + max_k w_kd) / 2), which keeps
+ * small-integer data exact.  A row that holds a NaN or +-Inf is counted for no unit.
+ * Integer counts, added with integer atomics only: the same rows give the same counts in every call and under every launch
+ * geometry, and the host and the device entry point agree; counts of separate calls (chunks, shards, ranks) add.
+ * n_rows == 0 writes zeros.  Refused, with a message that names the call: a NULL radii / counts / rows pointer, n_rows < 0 or
+ * > 2^31-1, n_radii outside 1 .. 8, a radius that is negative, NaN or whose square is not finite in float32, and a handle created
+ * with SOM_MISSING_NAN (a distance over a row's observed features has no common scale across rows).
+ * A query: resident rows, their ids, the weights, the monitor's state and the exact mode's plans stay as they were.  Scratch is
+ * the handle's (the centred codebook: K * input_len floats), grown on demand, freed by som_destroy.
+ * The *_device form reads rows that already live in HBM (see som_bmu_device: borrowed for the call). */
+int som_unit_density(som_handle* h, const float* x_host, int64_t n_rows, const float* pivot, const float* radii, int32_t n_radii, int64_t* counts);
+int som_unit_density_device(som_handle* h, const void* x_dev, int64_t n_rows, const float* pivot, const float* radii, int32_t n_radii, int64_t* counts);
 
 /* Row moments, for the codebook initialisers (not in the reference; csrc/moments.hpp).  With d_n = x_n - pivot formed in float32
  * (pivot: input_len host floats, NULL = 0) and w_n the row's weight (NULL = 1):

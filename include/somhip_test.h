@@ -263,6 +263,16 @@ int som_debug_exact_scratch_held(som_handle* h, int64_t* out);
 #define SOM_MOMENTS_CHUNK_ROWS 256
 int som_debug_moments_plan(int64_t n_rows, int32_t input_len, int64_t* out6);
 
+/* The DENSITY scan's launch geometry (csrc/density.hpp, density_plan) for n_rows rows on a map of K units -- pure host arithmetic, NO
+ * device needed.  slots: workgroups of the scan the chip holds at once; forced_slabs > 0: the slab count SOM_DENSITY_SLABS asks
+ * for (read only under SOM_TEST_HOOKS=1), 0: none.  A workgroup owns one tile of 128 units and a slab of consecutive 128-row tiles:
+ *   unit tiles = ceil(K / 128), row tiles = ceil(n_rows / 128),
+ *   slabs asked for = clamp(forced_slabs or ceil(slots / unit tiles), 1, row tiles), row tiles per slab = ceil(row tiles / slabs
+ *   asked for), slabs = ceil(row tiles / row tiles per slab) -- the slabs that hold a row tile; the grid is unit tiles * slabs.
+ *   out4 = {unit tiles, row tiles, slabs, row tiles per slab}
+ *   Returns non-zero for a NULL out4, n_rows < 1 or > 2^31-1, K < 1, slots < 1 or forced_slabs < 0. */
+int som_debug_density_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t forced_slabs, int64_t* out4);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@
 #include "project.hpp"
 #include "impute.hpp"
 #include "moments.hpp"
+#include "density.hpp"
 
 using namespace somhip;
 
@@ -452,6 +453,13 @@ struct som_handle {
         DevBuf<long long> idx;
         DevBuf<float> rows;
     } mom;
+    // data density per unit (density.hpp; som_unit_density*): the one owner of its scratch, grown on demand and freed with the handle.
+    // Size rule: pivot D floats, Wc K * D floats (the centred codebook), wsq K floats, counts 8 * K (the largest radius count).  The
+    // rows' |x'|^2 go into the query set's xsq, which a query of n rows always holds (row_set.hpp).
+    struct DensityScratch {
+        DevBuf<float> pivot, Wc, wsq;
+        DevBuf<unsigned long long> counts;
+    } den;
     bool searched = false;       // the resident ids are those of a search since the last som_epoch_merge
     bool async_copies = false;   // SOM_ASYNC_COPIES=1: round 1's original copy path (fresh_process_stress.py)
     int prof = 0;            // som_profile_enable: 0 off, 1 every kernel family, 2 the BMU family only
@@ -1537,6 +1545,20 @@ int launch_dist_matrix(som_handle* h, long N, float* out) {
     return 0;
 }
 
+// the density scan (density.hpp) over the query set's rows: its geometry from the kernel's resident slots (density_plan)
+template <int R>
+int launch_unit_density(som_handle* h, const RowSet& q, int forced_slabs, const DensityRadii& rad, int n_radii) {
+    auto& g = h->den;
+    int per_cu = 1;
+    if (int rc = kernel_per_cu(h, (const void*)unit_density_f32_kernel<R>, 256, DEN_LDS_BYTES, &per_cu)) return rc;
+    const DensityPlan p = density_plan(q.N, h->K, resident_slots(h, per_cu), forced_slabs);
+    if (p.unit_tiles * p.slabs > 0x7fffffffL) return fail(h, "unit density: the grid exceeds 2^31-1 workgroups");
+    unit_density_f32_kernel<R><<<dim3((unsigned)(p.unit_tiles * p.slabs)), dim3(256), DEN_LDS_BYTES, h->stream>>>(
+        q.X, q.N, h->D, (int)round_up(h->D, F32_KC), g.pivot, q.xsq, g.Wc, g.wsq, h->K, (int)p.unit_tiles, p.row_tiles, p.per, rad, n_radii,
+        g.counts);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
 }  // namespace
 
 // ==============================================================================================
@@ -2812,6 +2834,53 @@ int query_unit_value_sums(som_handle* h, const std::string& who, const float* x_
     return d2h_blocking(h, sumsq, g.psums + KC, KC * sizeof(double));
 }
 
+// ---- data density per unit (density.hpp): how many rows lie within each radius of every unit's weight vector ----
+int query_density(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, const float* pivot,
+                  const float* radii, int32_t n_radii, int64_t* counts) {
+    DeviceGuard dev_guard(h);
+    if (!h || !radii || !counts || n_rows < 0 || (n_rows > 0 && !x_host && !x_dev)) return fail(h, who + ": bad argument");
+    if (n_radii < 1 || n_radii > DEN_MAX_RADII) return fail(h, who + ": n_radii must be between 1 and " + std::to_string(DEN_MAX_RADII));
+    if (h->masked) return fail(h, who + ": not defined on a handle created with SOM_MISSING_NAN: a distance over a row's observed "
+                                        "features has no common scale across rows");
+    DensityRadii rad;
+    for (int j = 0; j < DEN_MAX_RADII; ++j) rad.r2[j] = NAN;                // (a spare radius of the instance counts nothing)
+    for (int j = 0; j < n_radii; ++j) {
+        const float r2 = (float)((double)radii[j] * (double)radii[j]);
+        if (!(radii[j] >= 0.0f) || !std::isfinite(r2)) return fail(h, who + ": radius " + std::to_string(j) + " must be >= 0 with a finite float32 square");
+        rad.r2[j] = r2;
+    }
+    const size_t K = (size_t)h->K, RK = (size_t)n_radii * K;
+    if (n_rows == 0) { std::memset(counts, 0, RK * sizeof(int64_t)); return 0; }
+    if (n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
+    if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
+    RowSet& q = h->q; auto& g = h->den;
+    const int D = h->D;
+    if (int rc = g.pivot.reserve(h, (size_t)D)) return rc;
+    if (int rc = g.Wc.reserve(h, K * D)) return rc;
+    if (int rc = g.wsq.reserve(h, K)) return rc;
+    if (int rc = g.counts.reserve(h, (size_t)DEN_MAX_RADII * K)) return rc;
+    if (pivot) { if (int rc = h2d_blocking(h, g.pivot, pivot, (size_t)D * sizeof(float))) return rc; }
+    else HIPCHK(h, hipMemsetAsync(g.pivot, 0, (size_t)D * sizeof(float), h->stream));
+    density_center_units_kernel<<<dim3((unsigned)cdiv(h->K, 4)), dim3(256), 0, h->stream>>>(h->W, g.pivot, h->K, D, g.Wc, g.wsq);
+    density_row_sq_kernel<<<dim3((unsigned)std::min<long>(cdiv(q.N, 4), 4096)), dim3(256), 0, h->stream>>>(q.X, g.pivot, q.N, D, q.xsq);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemsetAsync(g.counts, 0, RK * sizeof(unsigned long long), h->stream));
+    int forced = 0;
+    if (const char* e = dev_env("SOM_DENSITY_SLABS")) forced = std::max(0, std::atoi(e));
+    {
+        Timed t(h, SOM_K_BMU);
+        int rc;
+        if (n_radii == 1) rc = launch_unit_density<1>(h, q, forced, rad, n_radii);
+        else if (n_radii == 2) rc = launch_unit_density<2>(h, q, forced, rad, n_radii);
+        else if (n_radii <= 4) rc = launch_unit_density<4>(h, q, forced, rad, n_radii);
+        else rc = launch_unit_density<8>(h, q, forced, rad, n_radii);
+        if (rc) return rc;
+    }
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the per-unit counts are copied out as int64_t");
+    return d2h_blocking(h, counts, g.counts, RK * sizeof(int64_t));
+}
+
 // ---- missing values: the completed rows (impute.hpp) ----
 // out[n][d] = X[n][d] where observed, W[ids[n]][d] where NaN, on the handle's stream; out == X fills in place.  16 bytes a lane
 // where input_len and the three addresses as they ARE allow it (a caller's view may start at any float), else a float a lane.
@@ -2871,6 +2940,8 @@ int som_unit_label_counts(som_handle* h, const float* x_host, const int32_t* lab
 int som_unit_label_counts_device(som_handle* h, const void* x_dev, const void* labels_dev, int64_t n_rows, int32_t n_classes, int64_t* counts) { return query_unit_label_counts(h, "som_unit_label_counts_device", nullptr, x_dev, labels_dev, n_rows, n_classes, counts); }
 int som_unit_value_sums(som_handle* h, const float* x_host, const float* v_host, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq) { return query_unit_value_sums(h, "som_unit_value_sums", x_host, nullptr, v_host, n_rows, n_cols, count, sum, sumsq); }
 int som_unit_value_sums_device(som_handle* h, const void* x_dev, const void* v_dev, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq) { return query_unit_value_sums(h, "som_unit_value_sums_device", nullptr, x_dev, v_dev, n_rows, n_cols, count, sum, sumsq); }
+int som_unit_density(som_handle* h, const float* x_host, int64_t n_rows, const float* pivot, const float* radii, int32_t n_radii, int64_t* counts) { return query_density(h, "som_unit_density", x_host, nullptr, n_rows, pivot, radii, n_radii, counts); }
+int som_unit_density_device(som_handle* h, const void* x_dev, int64_t n_rows, const float* pivot, const float* radii, int32_t n_radii, int64_t* counts) { return query_density(h, "som_unit_density_device", nullptr, x_dev, n_rows, pivot, radii, n_radii, counts); }
 
 // ---- row moments and the row gather (moments.hpp): queries that touch nothing of the engine's row sets, weights, ids or plans ----
 namespace {
@@ -2959,6 +3030,13 @@ int som_debug_moments_plan(int64_t n_rows, int32_t input_len, int64_t* out6) {
     if (!out6 || n_rows < 0 || input_len < 1) return 1;
     out6[0] = MOM_R; out6[1] = mom_tiles(input_len); out6[2] = mom_splits(n_rows, input_len); out6[3] = mom_split_cap(input_len);
     out6[4] = mom_sum_grid(n_rows); out6[5] = MOM_MAX_D;
+    return 0;
+}
+
+int som_debug_density_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t forced_slabs, int64_t* out4) {
+    if (!out4 || n_rows < 1 || n_rows > 0x7fffffffL || K < 1 || slots < 1 || forced_slabs < 0) return 1;
+    const DensityPlan p = density_plan(n_rows, K, slots, forced_slabs);
+    out4[0] = p.unit_tiles; out4[1] = p.row_tiles; out4[2] = p.slabs; out4[3] = p.per;
     return 0;
 }
 

@@ -19,6 +19,26 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+MAX_DENSITY_RADII = 8
+
+
+def check_radii(radii):
+    """The radii of a density query as a float32 array of 1 to 8 values, each >= 0 with a square that is finite in float32
+    (include/somhip.h, som_unit_density); anything else is a ValueError.  Needs no engine."""
+    try:
+        r = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError("radii must be numbers, got %r" % (radii,)) from None
+    if not 1 <= len(r) <= MAX_DENSITY_RADII:
+        raise ValueError("between 1 and %d radii, got %d" % (MAX_DENSITY_RADII, len(r)))
+    with np.errstate(over="ignore", invalid="ignore"):
+        sq = (r.astype(np.float64) ** 2).astype(np.float32)
+    bad = ~((r >= 0) & np.isfinite(sq))
+    if bad.any():
+        raise ValueError("a radius must be >= 0 and its square finite in float32, got %r" % (float(r[np.flatnonzero(bad)[0]]),))
+    return r
+
+
 class HipEngine:
     def __init__(self, x, y, input_len, *, distance="euclidean", neighborhood="gaussian",
                  std_coeff=0.5, compact_support=False, precision="exact", device=0, stream=None,
@@ -395,6 +415,31 @@ class HipEngine:
         """unit_stats of float32 rows that already live in HBM (`dev_ptr`: [n_rows][D], borrowed for the call)."""
         out, ptrs = self._unit_stats_out()
         self._check(self._lib.som_unit_stats_device(self._h, C.c_void_p(dev_ptr), int(n_rows), *ptrs))
+        return out
+
+    # -- data density per unit (include/somhip.h, som_unit_density) --------------------------
+    def _density_args(self, pivot, radii):
+        radii = check_radii(radii)
+        if pivot is not None:
+            pivot = _f32(pivot)
+            if pivot.shape != (self.D,):
+                raise ValueError("pivot must have one value per feature, got %r" % (pivot.shape,))
+        out = np.empty((len(radii), self.K), dtype=np.int64)
+        return out, (self._fp(pivot) if pivot is not None else None, self._fp(radii), len(radii), out.ctypes.data_as(C.POINTER(C.c_int64))), (pivot, radii)
+
+    def unit_density(self, x, pivot, radii):
+        """int64 (len(radii), K): per radius and unit, how many rows lie within the radius of the unit's weight vector (inclusive) --
+        the P-matrix.  Euclidean and float32 whatever the engine's distance and precision; `pivot` ((D,) or None) is subtracted from
+        rows and units before the GEMM-form distance is formed.  1 to 8 radii in one pass; integer counts, the same in every call."""
+        x = self._rows_arg(x)
+        out, args, _keep = self._density_args(pivot, radii)
+        self._check(self._lib.som_unit_density(self._h, self._fp(x), x.shape[0], *args))
+        return out
+
+    def unit_density_device(self, dev_ptr, n_rows, pivot, radii):
+        """unit_density of float32 rows that already live in HBM (`dev_ptr`: [n_rows][D], borrowed for the call)."""
+        out, args, _keep = self._density_args(pivot, radii)
+        self._check(self._lib.som_unit_density_device(self._h, C.c_void_p(dev_ptr), int(n_rows), *args))
         return out
 
     # -- label and value maps (include/somhip.h, som_unit_label_counts / som_unit_value_sums) --

@@ -317,6 +317,20 @@ def _linear_codebook(wsum, mean, cov, x, y):
     return mean[None, None, :] + cx[:, None, None] * ax[None, None, :] + cy[None, :, None] * ay[None, None, :]
 
 
+def _ustar(u, p):
+    """Ultsch's U*-matrix from a U-matrix ``u`` and a P-matrix ``p`` of the same shape, float64:
+    ``U* = U * ((P - mean P) / (mean P - max P) + 1)`` -- ``U`` where the density is the mean, 0 where it is the maximum.  A flat
+    density (``max P == mean P``) returns ``U`` unchanged."""
+    u = np.asarray(u, dtype=np.float64)
+    p = np.asarray(p, dtype=np.float64)
+    if u.shape != p.shape:
+        raise ValueError("the U-matrix is %r, the P-matrix %r" % (u.shape, p.shape))
+    mean, top = p.mean(), p.max()
+    if top == mean:
+        return u.copy()
+    return u * ((p - mean) / (mean - top) + 1.0)
+
+
 class XPySom:
     def __init__(self, x, y, input_len,
                  sigma=0, sigmaN=1,
@@ -358,8 +372,8 @@ class XPySom:
                          or 'f32' (both run the float32 masked kernel); every neighbourhood and topology; train (with
                          sample_weight, device rows), train_streaming, winner, predict, quantization, quantization_error,
                          activation_response, win_map, labels_map, impute (every NaN of a row replaced by its best matching
-                         unit's value for that feature).  topographic_error, activate and
-                         distance_from_weights raise NotImplementedError; the initialisers refuse data with a NaN
+                         unit's value for that feature).  topographic_error, activate, distance_from_weights,
+                         density_map and ustar_map raise NotImplementedError; the initialisers refuse data with a NaN
         """
         if sigma >= x or sigma >= y:
             warn('Warning: sigma is too high for the dimension of the map.')
@@ -958,6 +972,52 @@ class XPySom:
             sq += s2
             mx = np.maximum(mx, m)
         return UnitStatistics(hits.reshape(X, Y), tot.reshape(X, Y), sq.reshape(X, Y), mx.reshape(X, Y))
+
+    def _density_pivot(self):
+        """The midrange of the codebook the engine holds, float32 (D,): the point the density scan centres rows and units on."""
+        w = np.asarray(self._weights, dtype=np.float32).reshape(-1, self._input_len).astype(np.float64)
+        return ((w.min(axis=0) + w.max(axis=0)) / 2).astype(np.float32)
+
+    def density_map(self, data, radius):
+        """The data density per unit, Ultsch's P-matrix: int64 ``(x, y)``, element ``[i, j]`` the number of samples within
+        ``radius`` (Euclidean, inclusive) of unit ``(i, j)``'s weight vector.  A sequence of 1 to 8 radii gives
+        ``(len(radius), x, y)`` from ONE pass over the data.  Unlike every other per-unit map this does not follow from the
+        samples' best matching units: it is a full samples x units scan, counted on the device in float32 without ever
+        writing the distance matrix.  Rows and units are centred on the midrange of the codebook first (distances are
+        translation invariant; the GEMM form of the distance cancels on un-centred data), so a sample whose distance is within
+        a few parts in a thousand of the radius may fall on either side; a sample holding a NaN or an infinity is counted
+        nowhere.  Rows in HBM are counted where they are, whole; host rows in ``n_parallel`` chunks whose counts are added.
+        The counts of shards or ranks add as well.
+
+        Picking a radius: pass several in one call; Ultsch's Pareto radius is the one at which the median over the units of
+        ``P / n_samples`` is about 0.2.  ``ustar_map`` combines the result with the U-matrix.
+        Not defined with ``missing='nan'``."""
+        from .engine import check_radii
+        self._refuse_missing('density_map')
+        scalar = np.ndim(radius) == 0
+        radii = check_radii(radius)
+        eng, q, data = self._diag_query(data)
+        X, Y = self._weights.shape[:2]
+        pivot = self._density_pivot()
+        counts = np.zeros((len(radii), X * Y), dtype=np.int64)
+        if q is not None:
+            if q[2]:
+                counts += eng.unit_density_device(q[1], q[2], pivot, radii)
+        else:
+            for s in range(0, len(data), self._n_parallel):
+                counts += eng.unit_density(data[s:s + self._n_parallel], pivot, radii)
+        return counts[0].reshape(X, Y) if scalar else counts.reshape(len(radii), X, Y)
+
+    def ustar_map(self, data, radius):
+        """The U*-matrix (Ultsch): the U-matrix scaled down where the data is dense, ``U * ((P - mean P) / (mean P - max P) + 1)``
+        with ``U = distance_map()`` and ``P = density_map(data, radius)`` (one radius) -- ``U`` where the density is average, 0
+        where it is highest, above ``U`` where it is sparse; ``U`` unchanged where the density is flat.  It tells "far apart
+        because there is a gap in the data" from "far apart inside a dense cluster".  float64 ``(x, y)``."""
+        self._refuse_missing('ustar_map')
+        if np.ndim(radius) != 0:
+            raise ValueError("ustar_map() takes one radius, got %r" % (radius,))
+        p = self.density_map(data, radius)
+        return _ustar(self.distance_map(), p)
 
     def _column_query(self, eng, col, what, dtype_name, typestr, host):
         """(pointer, owner) of the labels or values that go with device rows: a device array is read where it is (its
