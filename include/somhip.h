@@ -378,6 +378,37 @@ int som_unit_value_sums_device(som_handle* h, const void* x_dev, const void* v_d
  * The *_device form reads rows that already live in HBM (see som_bmu_device: borrowed for the call). */
 int som_unit_density(som_handle* h, const float* x_host, int64_t n_rows, const float* pivot, const float* radii, int32_t n_radii, int64_t* counts);
 int som_unit_density_device(som_handle* h, const void* x_dev, int64_t n_rows, const float* pivot, const float* radii, int32_t n_radii, int64_t* counts);
+/* The k nearest units of every row (not in the reference; csrc/topk.hpp): the ranked list behind smoothed data histograms, soft
+ * labelling over the map, projection between units and rank-based topology measures.  The float32 MFMA scan with a top-k epilogue:
+ * the (n_rows, K) score matrix is never written.  ONE definition:
+ *   s_nk = the float32 activation score the float32 kernels compare for the handle's distance -- euclidean: fmaf(-2, x.w, |w|^2);
+ *   euclidean_no_opt: that + |x|^2; cosine: 1 - nan_to_num(x.w / sqrt(|x|^2 |w|^2)) -- with x.w the k-ordered float32 fma chain of
+ *   v_mfma_f32_32x32x2_f32 starting from 0 and the norms in NumPy's pairwise order: bit for bit the entries of som_distance_matrix
+ *   (XPySom.activate) in SOM_BMU_ACTIVATION mode.
+ *   The list of row n: the k units with the smallest s_nk, ascending; equal scores (-0.0 == +0.0) go to the lower unit id first -- a
+ *   stable sort by (score, id).  A score enters only if it is < +inf: NaN and +inf never do (-inf does).  A slot that cannot be
+ *   filled holds id -1, score NaN, distance NaN.  (cosine: nan_to_num turns a NaN quotient into score 1, as in som_distance_matrix.)
+ * Always float32 arithmetic, whatever the handle's precision: on 'f32' and 'exact' handles slot 0 is som_bmu's ACTIVATION id for every
+ * row that has a score below +inf.
+ *   ids_out[n][j], score_out[n][j], dist_out[n][j]: host arrays, row-major (n_rows, k); score_out and dist_out may be NULL.
+ *   dist[n][j] = sqrt(sum_d (x_nd - W[id][d])^2), the differences formed directly, in som_bmu_distances' arithmetic (same lanes, fma
+ *   chain, wave sum, sqrtf) -- always Euclidean, as som_quantization_error's distance is, and NOT what orders the list: with a
+ *   Euclidean activation it ascends along a row only up to rounding.  Skipped when dist_out is NULL.
+ * som_unit_rank_counts*: counts[j][u] (host array [k][K]) = the number of rows whose slot j holds unit u, counted on the device from the
+ * id lists -- the (n_rows, k) lists never leave HBM.  Integer atomics only: the same rows give the same counts in every call and
+ * under every launch geometry; the counts of separate calls (chunks, shards, ranks) add.  n_rows == 0 writes zeros.
+ * 1 <= k <= SOM_TOPK_MAX.  Refused, with a message that names the call: a NULL ids_out / counts / rows pointer, n_rows < 0 or
+ * > 2^31-1, k outside 1 .. SOM_TOPK_MAX, k > K = x * y, a handle created with SOM_MISSING_NAN (as som_bmu_top2), a distance other
+ * than euclidean, euclidean_no_opt, cosine (as som_distance_matrix), input_len >= 2^24.
+ * The codebook is scanned in parts where few rows would not fill the chip, the parts' lists merged by (score, id): the result is
+ * identical for every part count.  Rows run in passes of 262 144, so the scratch is bounded (the handle's, grown on demand, freed
+ * by som_destroy).  A query: resident rows, their ids, the weights, the monitor's state and the exact mode's plans stay as they were.
+ * The *_device form reads rows that already live in HBM (see som_bmu_device: borrowed for the call). */
+#define SOM_TOPK_MAX 8
+int som_bmu_topk(som_handle* h, const float* x_host, int64_t n_rows, int32_t k, int32_t* ids_out, float* score_out, float* dist_out);
+int som_bmu_topk_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t k, int32_t* ids_out, float* score_out, float* dist_out);
+int som_unit_rank_counts(som_handle* h, const float* x_host, int64_t n_rows, int32_t k, int64_t* counts);
+int som_unit_rank_counts_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t k, int64_t* counts);
 
 /* Row moments, for the codebook initialisers (not in the reference; csrc/moments.hpp).  With d_n = x_n - pivot formed in float32
  * (pivot: input_len host floats, NULL = 0) and w_n the row's weight (NULL = 1):

@@ -273,6 +273,16 @@ int som_debug_moments_plan(int64_t n_rows, int32_t input_len, int64_t* out6);
  *   Returns non-zero for a NULL out4, n_rows < 1 or > 2^31-1, K < 1, slots < 1 or forced_slabs < 0. */
 int som_debug_density_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t forced_slabs, int64_t* out4);
 
+/* The TOP-K scan's launch geometry (csrc/topk.hpp, topk_plan) for a pass of n_rows rows on a map of K units -- pure host arithmetic,
+ * NO device needed.  slots: workgroups of the scan the chip holds at once; forced_parts > 0: the part count SOM_TOPK_PARTS asks for
+ * (read only under SOM_TEST_HOOKS=1), 0: none.  A workgroup owns one tile of 128 rows and one part of the codebook's 128-unit stages:
+ *   row tiles = ceil(n_rows / 128), stages = ceil(K / 128),
+ *   parts asked for = clamp(forced_parts or ceil(slots / row tiles), 1, stages), stages per part = ceil(stages / parts asked for),
+ *   parts = ceil(stages / stages per part) -- the parts that hold a stage; the grid is row tiles x parts.
+ *   out4 = {row tiles, stages, parts, stages per part}
+ *   Returns non-zero for a NULL out4, n_rows < 1 or > 2^31-1, K < 1, slots < 1 or forced_parts < 0. */
+int som_debug_topk_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t forced_parts, int64_t* out4);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,11 @@ SIGNATURES = {
     "som_unit_density": (C.c_int, [_H, _F, C.c_int64, _F, _F, C.c_int32, C.POINTER(C.c_int64)]),
     "som_unit_density_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _F, _F, C.c_int32, C.POINTER(C.c_int64)]),
     "som_debug_density_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "som_bmu_topk": (C.c_int, [_H, _F, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _F, _F]),
+    "som_bmu_topk_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _F, _F]),
+    "som_unit_rank_counts": (C.c_int, [_H, _F, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "som_unit_rank_counts_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "som_debug_topk_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "som_row_moments": (C.c_int, [_H, _F, _F, C.c_int64, _F, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "som_row_moments_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, _F, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                          C.POINTER(C.c_double)]),

@@ -41,6 +41,7 @@
 #include "impute.hpp"
 #include "moments.hpp"
 #include "density.hpp"
+#include "topk.hpp"
 
 using namespace somhip;
 
@@ -460,6 +461,15 @@ struct som_handle {
         DevBuf<float> pivot, Wc, wsq;
         DevBuf<unsigned long long> counts;
     } den;
+    // the k nearest units (topk.hpp; som_bmu_topk*, som_unit_rank_counts*): the one owner of its scratch, grown on demand and freed with
+    // the handle.  Size rule, for a pass of P <= TOPK_PASS_ROWS rows cut into `parts` codebook parts: the lists ids / score / dist
+    // P * TOPK_MAX each (score and dist only once a call has asked for them), the partial lists part_sc / part_id parts * P * TOPK_MAX
+    // each, counts TOPK_MAX * K.
+    struct TopkScratch {
+        DevBuf<int> ids, part_id;
+        DevBuf<float> score, dist, part_sc;
+        DevBuf<unsigned long long> counts;
+    } topk;
     bool searched = false;       // the resident ids are those of a search since the last som_epoch_merge
     bool async_copies = false;   // SOM_ASYNC_COPIES=1: round 1's original copy path (fresh_process_stress.py)
     int prof = 0;            // som_profile_enable: 0 off, 1 every kernel family, 2 the BMU family only
@@ -1558,6 +1568,29 @@ int launch_unit_density(som_handle* h, const RowSet& q, int forced_slabs, const 
         g.counts);
     HIPCHK(h, hipGetLastError());
     return 0;
+}
+
+// the k nearest units (topk.hpp) of the pass's rows X[N][D] (xsq: their |x|^2, read unless the score is the Euclidean part): the scan
+// over `parts` codebook parts into the partial lists, the merge into g.ids (and g.score where the caller wants the scores).  Its
+// geometry from the kernel's resident slots.
+template <int MODE, int KK>
+int launch_topk(som_handle* h, const float* X, long N, const float* xsq, int k, int forced_parts, bool want_score) {
+    auto& g = h->topk;
+    int per_cu = 1;
+    if (int rc = kernel_per_cu(h, (const void*)bmu_topk_f32_kernel<MODE, KK>, 256, TOPK_LDS_BYTES, &per_cu)) return rc;
+    const TopkPlan p = topk_plan(N, h->K, resident_slots(h, per_cu), forced_parts);
+    if (p.parts > 65535) return fail(h, "top-k: more than 65535 codebook parts");
+    if (int rc = g.part_sc.reserve(h, (size_t)p.parts * N * TOPK_MAX)) return rc;
+    if (int rc = g.part_id.reserve(h, (size_t)p.parts * N * TOPK_MAX)) return rc;
+    bmu_topk_f32_kernel<MODE, KK><<<dim3((unsigned)p.row_tiles, (unsigned)p.parts), dim3(256), TOPK_LDS_BYTES, h->stream>>>(
+        X, N, h->D, (int)round_up(h->D, F32_KC), h->W, h->wsq, h->K, xsq, (int)p.stages, (int)p.per, g.part_sc, g.part_id);
+    topk_merge_kernel<KK><<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(g.part_sc, g.part_id, N, (int)p.parts, k, g.ids, want_score ? (float*)g.score : nullptr);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+template <int MODE>
+int launch_topk_mode(som_handle* h, const float* X, long N, const float* xsq, int k, int forced_parts, bool want_score) {
+    return k <= 4 ? launch_topk<MODE, 4>(h, X, N, xsq, k, forced_parts, want_score) : launch_topk<MODE, 8>(h, X, N, xsq, k, forced_parts, want_score);
 }
 }  // namespace
 
@@ -2881,6 +2914,95 @@ int query_density(som_handle* h, const std::string& who, const float* x_host, co
     return d2h_blocking(h, counts, g.counts, RK * sizeof(int64_t));
 }
 
+// ---- the k nearest units of every row (topk.hpp): ranked lists with scores and distances, and the per-unit rank counts ----
+// the checks the four entry points share
+int topk_check(som_handle* h, const std::string& who, bool null_arg, int64_t n_rows, int32_t k) {
+    if (!h || null_arg || n_rows < 0) return fail(h, who + ": bad argument");
+    if (k < 1 || k > TOPK_MAX) return fail(h, who + ": k must be between 1 and SOM_TOPK_MAX = " + std::to_string(TOPK_MAX));
+    if (k > h->K) return fail(h, who + ": k = " + std::to_string(k) + " exceeds the map's " + std::to_string(h->K) + " units");
+    if (h->masked) return fail(h, who + ": the top-k search is not defined on a handle created with SOM_MISSING_NAN");
+    if (h->cfg.distance > SOM_DIST_COSINE)
+        return fail(h, who + ": only the GEMM-form distances (euclidean, euclidean_no_opt, cosine)");
+    if (n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    // (the scan forms its staging offsets, a row of a tile times input_len, with a 24-bit multiply: topk.hpp)
+    if (h->D >= (1 << 24)) return fail(h, who + ": input_len must be below 2^24");
+    return 0;
+}
+// the rows are on the device (query_rows): rows [r0, r0 + P) of the query set into the lists g.ids (and g.score, g.dist)
+int run_topk_pass(som_handle* h, long r0, long P, int k, bool want_score, bool want_dist, int forced_parts) {
+    RowSet& q = h->q; auto& g = h->topk;
+    const float* X = q.X + r0 * (long)h->D;
+    const float* xsq = q.xsq + r0;
+    {
+        Timed t(h, SOM_K_BMU);
+        int rc;
+        if (h->cfg.distance == SOM_DIST_EUCLIDEAN) rc = launch_topk_mode<SCORE_EUCLID_PART>(h, X, P, xsq, k, forced_parts, want_score);
+        else if (h->cfg.distance == SOM_DIST_EUCLIDEAN_NO_OPT) rc = launch_topk_mode<SCORE_EUCLID_SQ>(h, X, P, xsq, k, forced_parts, want_score);
+        else rc = launch_topk_mode<SCORE_COSINE>(h, X, P, xsq, k, forced_parts, want_score);
+        if (rc) return rc;
+        if (want_dist) {
+            const long slots = P * k;
+            topk_dist_kernel<<<dim3((unsigned)std::min<long>(cdiv(slots, 4), 4096)), dim3(256), 0, h->stream>>>(X, g.ids, h->W, slots, k, h->D, g.dist);
+            HIPCHK(h, hipGetLastError());
+        }
+    }
+    return 0;
+}
+// what both queries do before their passes: the rows, the float32 codebook with |w|^2, the rows' |x|^2, the lists' scratch -- the
+// scores' and the distances' only where the caller asked for them
+int topk_begin(som_handle* h, const float* x_host, const void* x_dev, int64_t n_rows, bool want_score, bool want_dist, int* forced_parts) {
+    if (int rc = query_rows(h, x_host, x_dev, n_rows)) return rc;
+    if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
+    if (h->cfg.distance != SOM_DIST_EUCLIDEAN) if (int rc = row_sq(h, h->q.X, n_rows, h->q.xsq)) return rc;
+    auto& g = h->topk;
+    const size_t slots = (size_t)std::min<long>(n_rows, TOPK_PASS_ROWS) * TOPK_MAX;
+    if (int rc = g.ids.reserve(h, slots)) return rc;
+    if (want_score) if (int rc = g.score.reserve(h, slots)) return rc;
+    if (want_dist) if (int rc = g.dist.reserve(h, slots)) return rc;
+    *forced_parts = 0;
+    if (const char* e = dev_env("SOM_TOPK_PARTS")) *forced_parts = std::max(0, std::atoi(e));
+    return 0;
+}
+int query_topk(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, int32_t k, int32_t* ids_out,
+               float* score_out, float* dist_out) {
+    DeviceGuard dev_guard(h);
+    if (int rc = topk_check(h, who, !ids_out || (n_rows > 0 && !x_host && !x_dev), n_rows, k)) return rc;
+    if (n_rows == 0) return 0;
+    int forced = 0;
+    if (int rc = topk_begin(h, x_host, x_dev, n_rows, score_out != nullptr, dist_out != nullptr, &forced)) return rc;
+    auto& g = h->topk;
+    for (long r0 = 0; r0 < n_rows; r0 += TOPK_PASS_ROWS) {
+        const long P = std::min<long>(TOPK_PASS_ROWS, n_rows - r0);
+        if (int rc = run_topk_pass(h, r0, P, k, score_out != nullptr, dist_out != nullptr, forced)) return rc;
+        const size_t slots = (size_t)P * k, o = (size_t)r0 * k;
+        if (int rc = d2h_blocking(h, ids_out + o, g.ids, slots * sizeof(int))) return rc;
+        if (score_out) if (int rc = d2h_blocking(h, score_out + o, g.score, slots * sizeof(float))) return rc;
+        if (dist_out) if (int rc = d2h_blocking(h, dist_out + o, g.dist, slots * sizeof(float))) return rc;
+    }
+    return 0;
+}
+int query_rank_counts(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, int32_t k,
+                      int64_t* counts) {
+    DeviceGuard dev_guard(h);
+    if (int rc = topk_check(h, who, !counts || (n_rows > 0 && !x_host && !x_dev), n_rows, k)) return rc;
+    const size_t kK = (size_t)k * h->K;
+    if (n_rows == 0) { std::memset(counts, 0, kK * sizeof(int64_t)); return 0; }
+    int forced = 0;
+    if (int rc = topk_begin(h, x_host, x_dev, n_rows, false, false, &forced)) return rc;
+    auto& g = h->topk;
+    if (int rc = g.counts.reserve(h, (size_t)TOPK_MAX * h->K)) return rc;
+    HIPCHK(h, hipMemsetAsync(g.counts, 0, kK * sizeof(unsigned long long), h->stream));
+    for (long r0 = 0; r0 < n_rows; r0 += TOPK_PASS_ROWS) {
+        const long P = std::min<long>(TOPK_PASS_ROWS, n_rows - r0);
+        if (int rc = run_topk_pass(h, r0, P, k, false, false, forced)) return rc;
+        Timed t(h, SOM_K_BMU);
+        unit_rank_counts_kernel<<<dim3((unsigned)cdiv(P * k, 256)), dim3(256), 0, h->stream>>>(g.ids, P * k, k, h->K, g.counts);
+        HIPCHK(h, hipGetLastError());
+    }
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the rank counts are copied out as int64_t");
+    return d2h_blocking(h, counts, g.counts, kK * sizeof(int64_t));
+}
+
 // ---- missing values: the completed rows (impute.hpp) ----
 // out[n][d] = X[n][d] where observed, W[ids[n]][d] where NaN, on the handle's stream; out == X fills in place.  16 bytes a lane
 // where input_len and the three addresses as they ARE allow it (a caller's view may start at any float), else a float a lane.
@@ -2942,6 +3064,10 @@ int som_unit_value_sums(som_handle* h, const float* x_host, const float* v_host,
 int som_unit_value_sums_device(som_handle* h, const void* x_dev, const void* v_dev, int64_t n_rows, int32_t n_cols, int64_t* count, double* sum, double* sumsq) { return query_unit_value_sums(h, "som_unit_value_sums_device", nullptr, x_dev, v_dev, n_rows, n_cols, count, sum, sumsq); }
 int som_unit_density(som_handle* h, const float* x_host, int64_t n_rows, const float* pivot, const float* radii, int32_t n_radii, int64_t* counts) { return query_density(h, "som_unit_density", x_host, nullptr, n_rows, pivot, radii, n_radii, counts); }
 int som_unit_density_device(som_handle* h, const void* x_dev, int64_t n_rows, const float* pivot, const float* radii, int32_t n_radii, int64_t* counts) { return query_density(h, "som_unit_density_device", nullptr, x_dev, n_rows, pivot, radii, n_radii, counts); }
+int som_bmu_topk(som_handle* h, const float* x_host, int64_t n_rows, int32_t k, int32_t* ids_out, float* score_out, float* dist_out) { return query_topk(h, "som_bmu_topk", x_host, nullptr, n_rows, k, ids_out, score_out, dist_out); }
+int som_bmu_topk_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t k, int32_t* ids_out, float* score_out, float* dist_out) { return query_topk(h, "som_bmu_topk_device", nullptr, x_dev, n_rows, k, ids_out, score_out, dist_out); }
+int som_unit_rank_counts(som_handle* h, const float* x_host, int64_t n_rows, int32_t k, int64_t* counts) { return query_rank_counts(h, "som_unit_rank_counts", x_host, nullptr, n_rows, k, counts); }
+int som_unit_rank_counts_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t k, int64_t* counts) { return query_rank_counts(h, "som_unit_rank_counts_device", nullptr, x_dev, n_rows, k, counts); }
 
 // ---- row moments and the row gather (moments.hpp): queries that touch nothing of the engine's row sets, weights, ids or plans ----
 namespace {
@@ -3037,6 +3163,13 @@ int som_debug_density_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t for
     if (!out4 || n_rows < 1 || n_rows > 0x7fffffffL || K < 1 || slots < 1 || forced_slabs < 0) return 1;
     const DensityPlan p = density_plan(n_rows, K, slots, forced_slabs);
     out4[0] = p.unit_tiles; out4[1] = p.row_tiles; out4[2] = p.slabs; out4[3] = p.per;
+    return 0;
+}
+
+int som_debug_topk_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t forced_parts, int64_t* out4) {
+    if (!out4 || n_rows < 1 || n_rows > 0x7fffffffL || K < 1 || slots < 1 || forced_parts < 0) return 1;
+    const TopkPlan p = topk_plan(n_rows, K, slots, forced_parts);
+    out4[0] = p.row_tiles; out4[1] = p.stages; out4[2] = p.parts; out4[3] = p.per;
     return 0;
 }
 

@@ -39,6 +39,19 @@ def check_radii(radii):
     return r
 
 
+TOPK_MAX = 8
+
+
+def check_topk(k):
+    """The list length of a top-k query as an int between 1 and 8 (include/somhip.h, SOM_TOPK_MAX); anything else is a ValueError.
+    Needs no engine."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError("k must be an integer, got %r" % (k,))
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError("k must be between 1 and %d (SOM_TOPK_MAX), got %d" % (TOPK_MAX, k))
+    return int(k)
+
+
 class HipEngine:
     def __init__(self, x, y, input_len, *, distance="euclidean", neighborhood="gaussian",
                  std_coeff=0.5, compact_support=False, precision="exact", device=0, stream=None,
@@ -440,6 +453,53 @@ class HipEngine:
         """unit_density of float32 rows that already live in HBM (`dev_ptr`: [n_rows][D], borrowed for the call)."""
         out, args, _keep = self._density_args(pivot, radii)
         self._check(self._lib.som_unit_density_device(self._h, C.c_void_p(dev_ptr), int(n_rows), *args))
+        return out
+
+    # -- the k nearest units (include/somhip.h, som_bmu_topk / som_unit_rank_counts) --------------
+    def _topk_k(self, k):
+        k = check_topk(k)
+        if k > self.K:
+            raise ValueError("k = %d exceeds the map's %d units" % (k, self.K))
+        return k
+
+    def _topk_out(self, n, k, score, dist):
+        ids = np.empty((n, k), dtype=np.int32)
+        sc = np.empty((n, k), dtype=np.float32) if score else None
+        ds = np.empty((n, k), dtype=np.float32) if dist else None
+        return ids, sc, ds, (self._ip(ids), self._fp(sc) if score else None, self._fp(ds) if dist else None)
+
+    def bmu_topk(self, x, k, *, score=True, dist=True):
+        """(ids int32, score float32 or None, dist float32 or None), each (n, k): per row the k units with the smallest float32
+        activation score of the engine's distance, ascending, equal scores to the lower id; `score` those scores (bit for bit the
+        entries of distance_matrix), `dist` the Euclidean distance of the row to each listed unit.  Only scores below +inf enter; a
+        slot nothing fills holds -1 / NaN / NaN.  Always float32 arithmetic; 1 <= k <= 8 and k <= K."""
+        x = self._rows_arg(x)
+        k = self._topk_k(k)
+        ids, sc, ds, ptrs = self._topk_out(x.shape[0], k, score, dist)
+        self._check(self._lib.som_bmu_topk(self._h, self._fp(x), x.shape[0], k, *ptrs))
+        return ids, sc, ds
+
+    def bmu_topk_device(self, dev_ptr, n_rows, k, *, score=True, dist=True):
+        """bmu_topk of float32 rows that already live in HBM (`dev_ptr`: [n_rows][D], borrowed for the call)."""
+        k = self._topk_k(k)
+        ids, sc, ds, ptrs = self._topk_out(int(n_rows), k, score, dist)
+        self._check(self._lib.som_bmu_topk_device(self._h, C.c_void_p(dev_ptr), int(n_rows), k, *ptrs))
+        return ids, sc, ds
+
+    def unit_rank_counts(self, x, k):
+        """int64 (k, K): counts[j][u] = the rows whose j-th nearest unit (bmu_topk's slot j) is u, counted on the device -- the
+        lists are not copied out.  Integer counts, the same in every call; the counts of chunks add."""
+        x = self._rows_arg(x)
+        k = self._topk_k(k)
+        out = np.empty((k, self.K), dtype=np.int64)
+        self._check(self._lib.som_unit_rank_counts(self._h, self._fp(x), x.shape[0], k, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def unit_rank_counts_device(self, dev_ptr, n_rows, k):
+        """unit_rank_counts of float32 rows that already live in HBM (`dev_ptr`: [n_rows][D], borrowed for the call)."""
+        k = self._topk_k(k)
+        out = np.empty((k, self.K), dtype=np.int64)
+        self._check(self._lib.som_unit_rank_counts_device(self._h, C.c_void_p(dev_ptr), int(n_rows), k, out.ctypes.data_as(C.POINTER(C.c_int64))))
         return out
 
     # -- label and value maps (include/somhip.h, som_unit_label_counts / som_unit_value_sums) --

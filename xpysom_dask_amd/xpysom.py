@@ -331,6 +331,16 @@ def _ustar(u, p):
     return u * ((p - mean) / (mean - top) + 1.0)
 
 
+def _sdh(rank_counts):
+    """Pampalk's smoothed data histogram from the rank counts ``(s, ...)``: rank j weighs ``(s - j) / (s (s + 1) / 2)``."""
+    c = np.asarray(rank_counts, dtype=np.float64)
+    s = c.shape[0]
+    out = np.zeros(c.shape[1:], dtype=np.float64)
+    for j in range(s):                                   # (rank by rank, in order: one result on every NumPy)
+        out += c[j] * ((s - j) / (s * (s + 1) / 2.0))
+    return out
+
+
 class XPySom:
     def __init__(self, x, y, input_len,
                  sigma=0, sigmaN=1,
@@ -373,7 +383,8 @@ class XPySom:
                          sample_weight, device rows), train_streaming, winner, predict, quantization, quantization_error,
                          activation_response, win_map, labels_map, impute (every NaN of a row replaced by its best matching
                          unit's value for that feature).  topographic_error, activate, distance_from_weights,
-                         density_map and ustar_map raise NotImplementedError; the initialisers refuse data with a NaN
+                         density_map, ustar_map, nearest_units, rank_hits and smoothed_hits raise
+                         NotImplementedError; the initialisers refuse data with a NaN
         """
         if sigma >= x or sigma >= y:
             warn('Warning: sigma is too high for the dimension of the map.')
@@ -1018,6 +1029,69 @@ class XPySom:
             raise ValueError("ustar_map() takes one radius, got %r" % (radius,))
         p = self.density_map(data, radius)
         return _ustar(self.distance_map(), p)
+
+    def _topk_query(self, what, data, k):
+        """(engine, device query or None, host rows or None, k) of a ranked-list query, refused by name where it is not defined."""
+        from .engine import check_topk
+        self._refuse_missing(what)
+        if self._activation_distance_name not in ('euclidean', 'euclidean_no_opt', 'cosine'):
+            raise NotImplementedError("%s() ranks the units by the GEMM-form distances only (euclidean, euclidean_no_opt, cosine); "
+                                      "'%s' is a fused distance+argmin kernel here" % (what, self._activation_distance_name))
+        k = check_topk(k)
+        X, Y = self._weights.shape[:2]
+        if k > X * Y:
+            raise ValueError("%s(): k = %d exceeds the map's %d units" % (what, k, X * Y))
+        eng, q, data = self._diag_query(data)
+        return eng, q, data, k
+
+    def nearest_units(self, data, k, *, return_distance=True):
+        """The k nearest units of every sample: ``ids`` int64 ``(n, k)``, raveled as in ``predict``, and ``dist`` float32
+        ``(n, k)`` (``return_distance=False``: ``ids`` alone).  Row n lists the k units with the smallest activation distance to
+        sample n under ``activation_distance`` ('euclidean', 'euclidean_no_opt' or 'cosine'), nearest first, equal distances to the
+        lower unit id -- the ranking ``activate(data)`` and a stable argsort would give, found on the device without ever
+        writing the ``(n, K)`` matrix.  The search is float32 whatever ``precision`` is; with 'f32' and 'exact' column 0 is
+        ``predict(data)``.  ``dist[n, j]`` is the Euclidean distance of the sample to unit ``ids[n, j]``, formed from the
+        differences as in ``quantization_distances`` -- always Euclidean, and not what orders the list: with a Euclidean
+        activation it ascends along a row only up to rounding, with 'cosine' it need not ascend at all.  A sample holding a NaN
+        or an infinity has no distance below infinity to any unit under the Euclidean activations: its row is ``-1`` / NaN, as is
+        every slot beyond the units that have one.  ``1 <= k <= 8`` and ``k <= x * y``.  Rows in HBM are searched where they
+        are; host rows in ``n_parallel`` chunks.  Not defined with ``missing='nan'``."""
+        eng, q, data, k = self._topk_query('nearest_units', data, k)
+        if q is not None:
+            parts = [eng.bmu_topk_device(q[1], q[2], k, score=False, dist=return_distance)] if q[2] else []
+        else:
+            parts = [eng.bmu_topk(data[s:s + self._n_parallel], k, score=False, dist=return_distance)
+                     for s in range(0, len(data), self._n_parallel)]
+        ids = np.concatenate([p[0] for p in parts]).astype(np.int64) if parts else np.zeros((0, k), dtype=np.int64)
+        if not return_distance:
+            return ids
+        return ids, (np.concatenate([p[2] for p in parts]) if parts else np.zeros((0, k), dtype=np.float32))
+
+    def rank_hits(self, data, k):
+        """int64 ``(k, x, y)``: element ``[j, a, b]`` is the number of samples whose j-th nearest unit (``nearest_units``' column
+        j) is unit ``(a, b)``, counted on the device -- the ranked lists are never copied out.  With ``precision`` 'f32' or
+        'exact' ``rank_hits(data, 1)[0]`` equals ``activation_response(data)``.  The counts of chunks, shards and ranks add."""
+        return self._rank_hits('rank_hits', data, k)
+
+    def _rank_hits(self, what, data, k):
+        eng, q, data, k = self._topk_query(what, data, k)
+        X, Y = self._weights.shape[:2]
+        counts = np.zeros((k, X * Y), dtype=np.int64)
+        if q is not None:
+            if q[2]:
+                counts += eng.unit_rank_counts_device(q[1], q[2], k)
+        else:
+            for s in range(0, len(data), self._n_parallel):
+                counts += eng.unit_rank_counts(data[s:s + self._n_parallel], k)
+        return counts.reshape(k, X, Y)
+
+    def smoothed_hits(self, data, s):
+        """Pampalk's smoothed data histogram, float64 ``(x, y)``: every sample gives ``s - j`` points to its j-th nearest unit
+        (j = 0 .. s-1), divided by ``s (s + 1) / 2`` -- a hit histogram in which a sample votes for its ``s`` nearest units
+        instead of one, which shows the cluster structure of maps with more units than a plain hit count can fill.  ``s = 1`` is
+        ``activation_response``.  Formed on the host from ``rank_hits(data, s)``; it sums to the number of samples whose lists
+        are full."""
+        return _sdh(self._rank_hits('smoothed_hits', data, s))
 
     def _column_query(self, eng, col, what, dtype_name, typestr, host):
         """(pointer, owner) of the labels or values that go with device rows: a device array is read where it is (its
