@@ -410,6 +410,30 @@ int som_bmu_topk_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_
 int som_unit_rank_counts(som_handle* h, const float* x_host, int64_t n_rows, int32_t k, int64_t* counts);
 int som_unit_rank_counts_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t k, int64_t* counts);
 
+/* Sparse rows (not in the reference; csrc/sparse.hpp): rows in CSR -- indptr int64 [n_rows + 1] from 0, indices int32 [nnz] with the
+ * columns of a row strictly ascending (canonical: sorted, no duplicates), values float32 [nnz]; host arrays, the caller's.  The
+ * rows mean exactly what their dense float32 form means (an explicitly stored zero is an entry like any other) and are never made
+ * dense: bag-of-words rows of 10^4 .. 10^5 columns train and are queried at the cost of their entries.
+ *   som_set_data_csr            the resident training rows, uploaded once.  They replace resident dense rows (with their sample
+ *                               weights), as som_set_data* replace resident sparse rows.  som_epoch_accumulate and som_epoch then run
+ *                               the sparse epoch -- the search and the segment sums over the entries, everything behind them (the
+ *                               transform, the all-reduce, the merge) as for dense rows -- always eagerly; som_epoch_fetch returns
+ *                               its ids.  The staged, forced and faithful forms, the monitor and sample weights refuse sparse rows.
+ *   som_bmu_csr                 ids_out [n_rows], host memory; mode as in som_bmu
+ *   som_quantization_error_csr  the mean distance to the Euclidean BMU, every difference x_d - w_d formed directly (no |x|^2 - 2 x.w
+ *                               + |w|^2 cancellation), float32 per row, the rows added in double in a fixed order; n_rows == 0: NaN
+ * Distances: euclidean, euclidean_no_opt, cosine.  Always float32, on handles of precision F32 and EXACT alike: the score of unit k
+ * is the dense float32 kernels' formula on a float32 fma chain over the row's entries in CSR order -- the float32 argmin of the same
+ * scores in another summation order, so not bit for bit som_bmu's ids on the dense form where two scores are within rounding of
+ * each other.  Equal scores go to the lowest unit id; a row without entries takes the unit of least |w|^2 (cosine: unit 0).  No
+ * atomics: the ids do not depend on the launch geometry, and two epochs from the same state leave the same bits.  NaN and infinite
+ * values are outside the contract (an id still is a unit).
+ * Refused with a message, never a fault: indptr that does not start at 0 or decreases, a column outside [0, input_len) or out of
+ * order, more than 2^31-1 rows, a handle of precision BF16 / F16, a handle created with SOM_MISSING_NAN, another distance. */
+int som_set_data_csr(som_handle* h, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows);
+int som_bmu_csr(som_handle* h, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows, int32_t mode, int32_t* ids_out);
+int som_quantization_error_csr(som_handle* h, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows, double* out);
+
 /* Row moments, for the codebook initialisers (not in the reference; csrc/moments.hpp).  With d_n = x_n - pivot formed in float32
  * (pivot: input_len host floats, NULL = 0) and w_n the row's weight (NULL = 1):
  *   *wsum = sum_n w_n      s1[a] = sum_n w_n d_na      gram[a][b] = sum_n w_n d_na d_nb      (host arrays: s1 [input_len], gram

@@ -283,6 +283,12 @@ int som_debug_density_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t for
  *   Returns non-zero for a NULL out4, n_rows < 1 or > 2^31-1, K < 1, slots < 1 or forced_parts < 0. */
 int som_debug_topk_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t forced_parts, int64_t* out4);
 
+/* The per-unit SEGMENT SUMS the last accumulate left on the device, in front of the neighbourhood transform (dense rows: the run sum
+ * of csrc/update.hpp; sparse rows: sparse_segsum_kernel, csrc/sparse.hpp): S_out [K][input_len] = the sum of the rows every unit won,
+ * count_out [K] = how many.  Fails where the count column and the dense counts behind the sums differ, and on a handle created with
+ * SOM_MISSING_NAN.  (SOM_SPARSE_PARTS=n, read under SOM_TEST_HOOKS=1, forces the sparse search's part count.) */
+int som_debug_segment_sums(som_handle* h, float* S_out, float* count_out);
+
 #ifdef __cplusplus
 }
 #endif

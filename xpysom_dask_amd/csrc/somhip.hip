@@ -42,6 +42,7 @@
 #include "moments.hpp"
 #include "density.hpp"
 #include "topk.hpp"
+#include "sparse.hpp"
 
 using namespace somhip;
 
@@ -153,6 +154,21 @@ struct RowSet {
     // precision 'exact': the rows' measured operand rounding errors (bmu_exact.hpp) live in the second half of xsq.  The only place that knows.
     float* xerr() const { return err_half && xsq.p != nullptr ? xsq.p + cap : nullptr; }
     Rows view() const { return Rows{X, N, xsq, xerr(), Xb, xmax2, bmu, bmu2, wgt, resident(), ids_valid}; }
+};
+
+// One set of sparse rows in CSR (sparse.hpp) and everything derived from them: the one owner of these buffers.  The handle holds two --
+// `csr` the resident training rows (som_set_data_csr), `csr_q` the rows of a query (som_bmu_csr, som_quantization_error_csr), which only
+// grows.  The index and value arrays are padded to whole int4s (n_alloc entries): the search stages them 16 bytes a lane.
+struct CsrSet {
+    DevBuf<long long> indptr;    // [N + 1]
+    DevBuf<int> indices;         // [n_alloc] columns, strictly ascending inside a row (checked on the host: csr_check)
+    DevBuf<float> values;        // [n_alloc]
+    DevBuf<float> xsq;           // [N] |x|^2 (sparse_rownorm_kernel)
+    DevBuf<int> bmu;             // [N] the ids a search writes
+    long N = 0;
+    long long nnz = 0, n_alloc = 0;
+    bool resident = false;       // the handle's training rows are these (even where N == 0), not `res`
+    void release() { *this = CsrSet{}; }
 };
 
 // THE EXACT MODE'S SCRATCH (exact_scratch.hpp: how large; exact_host.hpp: reserve, one overload each): four owners.  Each holds its buffers
@@ -470,6 +486,14 @@ struct som_handle {
         DevBuf<float> score, dist, part_sc;
         DevBuf<unsigned long long> counts;
     } topk;
+    // sparse rows (sparse.hpp): the resident set, the query set, and the kernels' scratch, grown on demand and freed with the handle --
+    // WT D * round_up(K, 64) floats (the transposed codebook), part_sc / part_id parts * N (the parts' minima), ustart K + 1 (the
+    // sorted rows' first position per unit), dist N (the rows' distances to their units)
+    CsrSet csr, csr_q;
+    struct SparseScratch {
+        DevBuf<float> WT, part_sc, dist;
+        DevBuf<int> part_id, ustart;
+    } sp;
     bool searched = false;       // the resident ids are those of a search since the last som_epoch_merge
     bool async_copies = false;   // SOM_ASYNC_COPIES=1: round 1's original copy path (fresh_process_stress.py)
     int prof = 0;            // som_profile_enable: 0 off, 1 every kernel family, 2 the BMU family only
@@ -1592,6 +1616,134 @@ template <int MODE>
 int launch_topk_mode(som_handle* h, const float* X, long N, const float* xsq, int k, int forced_parts, bool want_score) {
     return k <= 4 ? launch_topk<MODE, 4>(h, X, N, xsq, k, forced_parts, want_score) : launch_topk<MODE, 8>(h, X, N, xsq, k, forced_parts, want_score);
 }
+
+// ---- sparse rows (sparse.hpp; som_set_data_csr, som_bmu_csr, som_quantization_error_csr) -------------------------------------
+// A bad argument is an error message here and never a fault on the device: the handle's configuration, then indptr (starts at 0,
+// never decreases), then every column (inside [0, input_len), strictly ascending inside its row -- canonical CSR).  All on the host.
+int csr_check(som_handle* h, const std::string& who, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows) {
+    if (!h) return 1;
+    if (n_rows < 0 || !indptr) return fail(h, who + ": bad argument");
+    if (is_half1(h)) return fail(h, who + ": sparse rows run float32 kernels: a handle of precision 'bf16' or 'f16' is refused (use 'exact' or 'f32')");
+    if (h->masked) return fail(h, who + ": sparse rows on a handle created with SOM_MISSING_NAN are not supported");
+    if (h->cfg.distance > SOM_DIST_COSINE) return fail(h, who + ": sparse rows serve the euclidean, euclidean_no_opt and cosine distances only");
+    if (n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows per GPU");
+    if (indptr[0] != 0) return fail(h, who + ": indptr[0] must be 0");
+    char msg[200];
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (indptr[r + 1] < indptr[r]) {
+            std::snprintf(msg, sizeof(msg), ": indptr decreases at row %lld", (long long)r);
+            return fail(h, who + msg);
+        }
+    if (indptr[n_rows] > 0 && (!indices || !values)) return fail(h, who + ": bad argument");
+    for (int64_t r = 0; r < n_rows; ++r)
+        for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
+            const int32_t c = indices[e];
+            if (c < 0 || c >= h->D) {
+                std::snprintf(msg, sizeof(msg), ": column index %d of row %lld is outside [0, input_len = %d)", (int)c, (long long)r, h->D);
+                return fail(h, who + msg);
+            }
+            if (e > indptr[r] && c <= indices[e - 1]) {
+                std::snprintf(msg, sizeof(msg), ": the columns of row %lld do not ascend strictly (canonical CSR: sorted, no duplicates)", (long long)r);
+                return fail(h, who + msg);
+            }
+        }
+    return 0;
+}
+
+// `s` takes the checked rows: the three arrays to the device (the buffers only grow), then |x|^2 per row
+int csr_take(som_handle* h, CsrSet& s, const int64_t* indptr, const int32_t* indices, const float* values, long n) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "indptr is copied as it is");
+    const long long nnz = indptr[n], n_alloc = round_up(nnz, 4) + 4;
+    s.N = 0; s.nnz = 0;
+    if (int rc = s.indptr.reserve(h, (size_t)n + 1)) return rc;
+    if (int rc = s.indices.reserve(h, (size_t)n_alloc)) return rc;
+    if (int rc = s.values.reserve(h, (size_t)n_alloc)) return rc;
+    if (int rc = s.xsq.reserve(h, (size_t)n)) return rc;
+    if (int rc = s.bmu.reserve(h, (size_t)n)) return rc;
+    if (int rc = h2d_blocking(h, s.indptr, indptr, ((size_t)n + 1) * sizeof(int64_t))) return rc;
+    if (nnz > 0) {
+        if (int rc = h2d_blocking(h, s.indices, indices, (size_t)nnz * sizeof(int32_t))) return rc;
+        if (int rc = h2d_blocking(h, s.values, values, (size_t)nnz * sizeof(float))) return rc;
+    }
+    s.N = n; s.nnz = nnz; s.n_alloc = n_alloc;
+    if (n > 0) {
+        sparse_rownorm_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 0, h->stream>>>(s.indptr, s.values, n, s.xsq);
+        HIPCHK(h, hipGetLastError());
+    }
+    return 0;
+}
+
+// the ids of `s`'s rows under score MODE into s.bmu: |w|^2 where it is stale, the transposed codebook (rebuilt for every search: the
+// codebook may have changed, and 8 K D bytes are little against the search), the scan over `parts` unit ranges, their merge
+template <int MODE>
+int launch_sparse_bmu(som_handle* h, CsrSet& s) {
+    if (s.N == 0) return 0;
+    if (const operands::Rebuilds rb = h->ops.decide_wsq(); rb.wsq) {
+        launch_codebook_wsq(h);
+        h->ops.commit(rb);
+    }
+    auto& g = h->sp;
+    const int Kp = (int)round_up(h->K, 64);
+    if (int rc = g.WT.reserve(h, (size_t)h->D * Kp)) return rc;
+    Timed t(h, SOM_K_BMU);
+    sparse_transpose_kernel<<<dim3((unsigned)(Kp / 64), (unsigned)cdiv(h->D, 64)), dim3(256), 0, h->stream>>>(h->W, h->K, h->D, Kp, g.WT);
+    // (17 KiB of LDS and four waves a workgroup: eight workgroups a CU)
+    long wanted = choose_parts(h, cdiv(s.N, SP_ROWS), resident_slots(h, 8), Kp / 64);
+    if (const char* e = dev_env("SOM_SPARSE_PARTS")) if (std::atoi(e) > 0) wanted = std::atoi(e);
+    const SparsePlan p = sparse_plan(s.N, h->K, wanted);
+    if (p.parts > 65535) return fail(h, "sparse search: more than 65535 codebook parts");
+    if (p.parts > 1) {
+        if (int rc = g.part_sc.reserve(h, (size_t)p.parts * s.N)) return rc;
+        if (int rc = g.part_id.reserve(h, (size_t)p.parts * s.N)) return rc;
+    }
+    if (h->debug) std::fprintf(stderr, "[somhip] sparse_bmu: row tiles=%ld groups=%d per=%d parts=%d U=%d\n", p.row_tiles, p.groups, p.per, p.parts, p.U);
+    const dim3 grid((unsigned)p.row_tiles, (unsigned)p.parts), block(256);
+#define SOM_SPARSE_BMU(U) sparse_bmu_kernel<MODE, U><<<grid, block, 0, h->stream>>>(s.indptr, s.indices, s.values, s.N, s.n_alloc, s.xsq, g.WT, h->wsq, h->K, Kp, p.per, p.parts, g.part_sc, g.part_id, s.bmu)
+    if (p.U == 4) SOM_SPARSE_BMU(4); else if (p.U == 2) SOM_SPARSE_BMU(2); else SOM_SPARSE_BMU(1);
+#undef SOM_SPARSE_BMU
+    if (p.parts > 1)
+        sparse_merge_kernel<<<dim3((unsigned)cdiv(s.N, 256)), dim3(256), 0, h->stream>>>(g.part_sc, g.part_id, s.N, p.parts, h->K, s.bmu);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+int run_sparse_bmu(som_handle* h, CsrSet& s, bool quantization) {
+    if (quantization) return launch_sparse_bmu<SCORE_EUCLID_SQRT>(h, s);
+    switch (h->cfg.distance) {
+    case SOM_DIST_EUCLIDEAN: return launch_sparse_bmu<SCORE_EUCLID_PART>(h, s);
+    case SOM_DIST_EUCLIDEAN_NO_OPT: return launch_sparse_bmu<SCORE_EUCLID_SQ>(h, s);
+    case SOM_DIST_COSINE: return launch_sparse_bmu<SCORE_COSINE>(h, s);
+    }
+    return fail(h, "sparse rows serve the euclidean, euclidean_no_opt and cosine distances only");
+}
+
+// SC[b] = sum of the resident sparse rows whose BMU is b, and their count: the sort by unit, every unit's first sorted position,
+// then one wave per (unit, column slab) -- every element of SC and of the dense counts behind it is stored, none is cleared first
+int sparse_segsum(som_handle* h, CsrSet& s) {
+    Timed t(h, SOM_K_SEGSUM);
+    auto& g = h->sp;
+    if (int rc = g.ustart.reserve(h, (size_t)h->K + 1)) return rc;
+    if (s.N > 0) {
+        if (int rc = reserve(h, h->seg.sort, s.N)) return rc;
+        if (int rc = sort_rows_by_unit(h, h->seg.sort, s.bmu, s.N)) return rc;
+    }
+    // (no rows: nothing was sorted and skey is not read -- every bound is 0)
+    sparse_unit_bounds_kernel<<<dim3((unsigned)cdiv(h->K + 1, 256)), dim3(256), 0, h->stream>>>(h->seg.sort.skey, s.N, h->K, g.ustart);
+    const int nslabs = (int)cdiv(h->D1p, SP_SLAB);
+    sparse_segsum_kernel<<<dim3((unsigned)cdiv((long)h->K * nslabs, 4)), dim3(256), 0, h->stream>>>(
+        s.indptr, s.indices, s.values, h->seg.sort.srow, g.ustart, h->K, h->D, h->D1p, nslabs, h->SC, h->SC + (size_t)h->K * h->D1p);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// one epoch over the resident sparse rows: always eager (never the captured graph, never the exact mode's plan); everything behind
+// the segment sums is the dense epoch's own
+int sparse_epoch_accumulate(som_handle* h, double sigma, double eta, int neigh_f64) {
+    h->early = som_handle::EarlyUpdate();
+    h->searched = true;
+    if (int rc = run_sparse_bmu(h, h->csr, false)) return rc;
+    if (int rc = sparse_segsum(h, h->csr)) return rc;
+    return run_transform(h, sigma, eta, neigh_f64);
+}
 }  // namespace
 
 // ==============================================================================================
@@ -1910,6 +2062,7 @@ static int adopt_rows(som_handle* h, const std::string& who, const void* x, int6
     DeviceGuard dev_guard(h);
     if (!h || n_rows < 0 || (!x && n_rows > 0)) return fail(h, who + ": bad argument");
     RowSet& s = h->res;
+    h->csr.release();                                    // (one resident row set: dense rows drop sparse ones, som_set_data_csr drops these)
     clear_sample_weights(h);                             // (weights belong to the rows they were set for)
     if (!host) s.X_owned.reset();
     s.ids_valid = false;
@@ -1944,6 +2097,15 @@ static int adopt_rows(som_handle* h, const std::string& who, const void* x, int6
 
 int som_set_data(som_handle* h, const float* x_host, int64_t n_rows) { return adopt_rows(h, "som_set_data", x_host, n_rows, true); }
 int som_set_data_device(som_handle* h, const void* x_dev, int64_t n_rows) { return adopt_rows(h, "som_set_data_device", x_dev, n_rows, false); }
+// resident sparse rows (sparse.hpp): checked on the host, uploaded once; they replace resident dense rows, with their weights, ids and plans
+int som_set_data_csr(som_handle* h, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows) {
+    DeviceGuard dev_guard(h);
+    if (int rc = csr_check(h, "som_set_data_csr", indptr, indices, values, n_rows)) return rc;
+    if (int rc = adopt_rows(h, "som_set_data_csr", nullptr, 0, true)) return rc;
+    if (int rc = csr_take(h, h->csr, indptr, indices, values, n_rows)) { h->csr.release(); return rc; }
+    h->csr.resident = true;
+    return 0;
+}
 
 // Order the engine behind whoever produced device rows handed to som_set_data_device: a
 // __cuda_array_interface__ `stream` value (1 = legacy default stream, 2 = per-thread default stream, else a
@@ -2055,6 +2217,7 @@ int capture_epoch_graph(som_handle* h) {
 int som_epoch_accumulate(som_handle* h, double sigma, double eta, int neigh_f64) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
+    if (h->csr.resident) return sparse_epoch_accumulate(h, sigma, eta, neigh_f64);
     const RowSet& res = h->res;
     if (!res.X && res.N > 0) return fail(h, "som_epoch_accumulate: no resident data (call som_set_data)");
     h->searched = true;
@@ -2088,6 +2251,7 @@ int som_epoch_accumulate(som_handle* h, double sigma, double eta, int neigh_f64)
 int som_epoch_accumulate_faithful(som_handle* h, double sigma, double eta, int neigh_f64) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
+    if (h->csr.resident) return fail(h, "som_epoch_accumulate_faithful: the resident rows are sparse (som_set_data_csr)");
     const Rows r = h->res.view();
     if (!r.X && r.N > 0) return fail(h, "som_epoch_accumulate_faithful: no resident data (call som_set_data)");
     if (h->swapped) return fail(h, "som_epoch_accumulate_faithful: mexican_hat with compact_support on the rectangular "
@@ -2111,6 +2275,7 @@ int som_epoch_accumulate_faithful(som_handle* h, double sigma, double eta, int n
 int som_epoch_accumulate_forced(som_handle* h, const int32_t* bmu_host, double sigma, double eta, int neigh_f64) {
     DeviceGuard dev_guard(h);
     if (!h || (!bmu_host && h->res.N > 0)) return fail(h, "som_epoch_accumulate_forced: bad argument");
+    if (h->csr.resident) return fail(h, "som_epoch_accumulate_forced: the resident rows are sparse (som_set_data_csr)");
     for (long i = 0; i < h->res.N; ++i)
         if (bmu_host[i] < 0 || bmu_host[i] >= h->K) return fail(h, "som_epoch_accumulate_forced: id out of range");
     h->ex.srt[0].lastpos_valid = false;                  // (ids from outside: the sorted rows' carried positions are not theirs)
@@ -2451,6 +2616,7 @@ int som_epoch(som_handle* h, double sigma, double eta, int neigh_f64) {
 int som_epoch_accumulate_begin(som_handle* h, double sigma, double eta, int neigh_f64) {
     DeviceGuard dev_guard(h);
     if (!h) return 1;
+    if (h->csr.resident) return fail(h, "som_epoch_accumulate_begin: the resident rows are sparse (som_set_data_csr): the staged epoch is not built for them");
     const Rows r = h->res.view();
     if (!r.X && r.N > 0) return fail(h, "som_epoch_accumulate_begin: no resident data (call som_set_data)");
     h->searched = true;
@@ -2512,6 +2678,10 @@ int som_epoch_fetch(som_handle* h, float* num, float* den, int32_t* bmu) {
             if (den) den[k] = acc[k * h->D1p + h->D];
         }
     }
+    if (bmu && h->csr.resident) {                        // (the sparse epoch's ids)
+        if (h->csr.N > 0) HIPCHK(h, hipMemcpy(bmu, h->csr.bmu, (size_t)h->csr.N * sizeof(int), hipMemcpyDeviceToHost));
+        return 0;
+    }
     if (bmu && h->res.N > 0) HIPCHK(h, hipMemcpy(bmu, h->res.bmu, (size_t)h->res.N * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -2568,6 +2738,7 @@ int som_epoch_measure_rows(som_handle* h) {
     if (!h) return 1;
     auto& mon = h->mon;
     if (!mon.on) return fail(h, "som_epoch_measure_rows: the monitor is off (call som_monitor(h, 1))");
+    if (h->csr.resident) return fail(h, "som_epoch_measure_rows: the resident rows are sparse (som_set_data_csr): the monitor does not measure them");
     if (!h->searched) return fail(h, "som_epoch_measure_rows: no search over the resident rows since the last som_epoch_merge "
                                      "(call a som_epoch_accumulate* form first)");
     const Rows r = h->res.view();
@@ -3045,6 +3216,50 @@ int query_impute(som_handle* h, const std::string& who, const float* x_host, con
     return 0;
 }
 }  // namespace
+
+// ---- queries on sparse rows (sparse.hpp): checked on the host, staged in the handle's sparse query set ----
+int som_bmu_csr(som_handle* h, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows, int32_t mode, int32_t* ids_out) {
+    DeviceGuard dev_guard(h);
+    if (int rc = csr_check(h, "som_bmu_csr", indptr, indices, values, n_rows)) return rc;
+    if (mode != SOM_BMU_ACTIVATION && mode != SOM_BMU_QUANTIZATION) return fail(h, "som_bmu_csr: unknown mode");
+    if (n_rows == 0) return 0;
+    if (!ids_out) return fail(h, "som_bmu_csr: bad argument");
+    if (int rc = csr_take(h, h->csr_q, indptr, indices, values, n_rows)) return rc;
+    if (int rc = run_sparse_bmu(h, h->csr_q, mode == SOM_BMU_QUANTIZATION)) return rc;
+    return d2h_blocking(h, ids_out, h->csr_q.bmu, (size_t)n_rows * sizeof(int));
+}
+int som_quantization_error_csr(som_handle* h, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n_rows, double* out) {
+    DeviceGuard dev_guard(h);
+    if (int rc = csr_check(h, "som_quantization_error_csr", indptr, indices, values, n_rows)) return rc;
+    if (!out) return fail(h, "som_quantization_error_csr: bad argument");
+    if (n_rows == 0) { *out = NAN; return 0; }          // numpy: mean of an empty array
+    CsrSet& q = h->csr_q;
+    if (int rc = csr_take(h, q, indptr, indices, values, n_rows)) return rc;
+    if (int rc = run_sparse_bmu(h, q, true)) return rc;
+    if (int rc = h->sp.dist.reserve(h, (size_t)n_rows)) return rc;
+    sparse_qe_kernel<<<dim3((unsigned)std::min<long>(cdiv(n_rows, 4), 4096)), dim3(256), 0, h->stream>>>(q.indptr, q.indices, q.values, q.bmu, h->W,
+                                                                                                       n_rows, h->D, h->sp.dist);
+    sparse_dsum_kernel<<<dim3(1), dim3(1024), 0, h->stream>>>(h->sp.dist, n_rows, h->dsum);
+    HIPCHK(h, hipGetLastError());
+    double s = 0.0;
+    if (int rc = d2h_blocking(h, &s, h->dsum, sizeof(double))) return rc;
+    *out = s / (double)n_rows;
+    return 0;
+}
+// the segment sums the last accumulate left (include/somhip_test.h): S [K][input_len], count [K]
+int som_debug_segment_sums(som_handle* h, float* S_out, float* count_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || !S_out || !count_out) return fail(h, "som_debug_segment_sums: bad argument");
+    if (h->masked) return fail(h, "som_debug_segment_sums: not on a handle created with SOM_MISSING_NAN");
+    std::vector<float> sc((size_t)h->K * (h->D1p + 1));
+    if (int rc = d2h_blocking(h, sc.data(), h->SC, sc.size() * sizeof(float))) return rc;
+    for (long k = 0; k < h->K; ++k) {
+        std::memcpy(S_out + k * h->D, sc.data() + k * h->D1p, (size_t)h->D * sizeof(float));
+        if (sc[k * h->D1p + h->D] != sc[(size_t)h->K * h->D1p + k]) return fail(h, "som_debug_segment_sums: the count column and the dense counts differ");
+        count_out[k] = sc[k * h->D1p + h->D];
+    }
+    return 0;
+}
 
 int som_bmu(som_handle* h, const float* x_host, int64_t n_rows, int32_t mode, int32_t* ids_out) { return query_bmu(h, "som_bmu", x_host, nullptr, n_rows, mode, ids_out); }
 int som_bmu_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t mode, int32_t* ids_out) { return query_bmu(h, "som_bmu_device", nullptr, x_dev, n_rows, mode, ids_out); }

@@ -130,6 +130,46 @@ class HipEngine:
         self._keepalive = keepalive
         self._weights_keepalive = None
 
+    # -- sparse rows (include/somhip.h, som_set_data_csr): csr = (indptr int64, indices int32, values float32) as
+    #    xpysom._csr_rows returns them; the rows are never made dense
+    def _csr_args(self, csr):
+        indptr, indices, values = csr
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        values = _f32(values)
+        if indptr.ndim != 1 or len(indptr) < 1 or indices.shape != values.shape or indices.ndim != 1 or len(indices) < indptr[-1]:
+            raise ValueError("csr must be (indptr (n + 1,), indices (nnz,), values (nnz,))")
+        keep = (indptr, indices, values)
+        return keep, (indptr.ctypes.data_as(C.POINTER(C.c_int64)), self._ip(indices), self._fp(values), len(indptr) - 1)
+
+    def set_data_csr(self, csr):
+        """Resident sparse training rows; they replace resident dense rows (and their weights)."""
+        keep, args = self._csr_args(csr)
+        self._check(self._lib.som_set_data_csr(self._h, *args))
+        self.n_rows = args[3]
+        self._keepalive = None
+        self._weights_keepalive = None
+
+    def bmu_csr(self, csr, quantization=False):
+        keep, args = self._csr_args(csr)
+        ids = np.empty((args[3],), dtype=np.int32)
+        mode = _lib.SOM_BMU_QUANTIZATION if quantization else _lib.SOM_BMU_ACTIVATION
+        self._check(self._lib.som_bmu_csr(self._h, *args, mode, self._ip(ids)))
+        return ids
+
+    def quantization_error_csr(self, csr):
+        keep, args = self._csr_args(csr)
+        out = C.c_double()
+        self._check(self._lib.som_quantization_error_csr(self._h, *args, C.byref(out)))
+        return out.value
+
+    def debug_segment_sums(self):
+        """(S (K, D), count (K,)): the per-unit segment sums the last accumulate left (include/somhip_test.h)."""
+        S = np.empty((self.K, self.D), dtype=np.float32)
+        c = np.empty((self.K,), dtype=np.float32)
+        self._check(self._lib.som_debug_segment_sums(self._h, self._fp(S), self._fp(c)))
+        return S, c
+
     def set_sample_weights(self, w):
         """Per-row weights of the resident rows (a host array of n_rows finite values >= 0); None clears them."""
         if w is None:

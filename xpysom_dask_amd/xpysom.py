@@ -8,6 +8,7 @@ formatting, pickling -- and hands everything below ``_update``/``_winner``/``_me
 to libsomhip through ctypes.  There is no ``xp=`` dispatch and no CPU path: without the HIP
 library (or a GPU) the compute methods raise.
 """
+import sys
 from collections import Counter, defaultdict, namedtuple
 from warnings import warn
 
@@ -126,9 +127,42 @@ def _device_weights(w):
     return int(cai["data"][0]), None, w, cai.get("stream")
 
 
+def _is_sparse(data):
+    """Is ``data`` a ``scipy.sparse`` matrix or array?  (Whoever holds one has imported scipy.sparse: it is not imported here.)"""
+    sp = sys.modules.get("scipy.sparse")
+    return sp is not None and sp.issparse(data)
+
+
+SPARSE_METHODS = "train, winner, predict and quantization_error"
+
+
+def _refuse_sparse(data, what="this method"):
+    if _is_sparse(data):
+        raise NotImplementedError("%s does not take sparse rows: %s do (or pass data.toarray())" % (what, SPARSE_METHODS))
+
+
+def _csr_rows(data, input_len):
+    """The rows of a ``scipy.sparse`` matrix or array as the engine takes them: ``(indptr int64 (n + 1,), indices int32 (nnz,),
+    values float32 (nnz,))`` in canonical CSR -- columns ascending inside a row, duplicates summed; explicitly stored zeros stay
+    entries.  Anything that is not CSR goes through ``.tocsr()``; a matrix that is not canonical is copied first: the caller's
+    is never modified, and the rows are never made dense."""
+    if data.ndim != 2:
+        raise ValueError('data must be 2-dimensional (n_samples, input_len)')
+    if data.shape[1] != input_len:
+        raise ValueError('Received %d features, expected %d.' % (data.shape[1], input_len))
+    csr = data if data.format == "csr" else data.tocsr()
+    if not csr.has_canonical_format:
+        if csr is data:
+            csr = csr.copy()
+        csr.sum_duplicates()                             # (sorts the columns too)
+    return (np.ascontiguousarray(csr.indptr, dtype=np.int64), np.ascontiguousarray(csr.indices, dtype=np.int32),
+            np.ascontiguousarray(csr.data, dtype=np.float32))
+
+
 def _host_rows(x, engine=None):
     """float32 host view of array-like input; device rows are copied back through ``engine()`` (analysis
     calls only; the engine is not created for host input)."""
+    _refuse_sparse(x)
     if hasattr(x, "is_cuda") and getattr(x, "is_cuda"):
         x = x.detach().cpu().numpy()
     elif getattr(x, "__cuda_array_interface__", None) is not None:
@@ -598,6 +632,7 @@ class XPySom:
 
     def _check_input_len(self, data):
         """Checks that the data in input is of the correct shape (xpysom.py:360-366)."""
+        _refuse_sparse(data)
         data_len = len(data[0])
         if self._input_len != data_len:
             msg = 'Received %d features, expected %d.' % (data_len, self._input_len)
@@ -607,6 +642,9 @@ class XPySom:
     def train(self, data, num_epochs, iter_beg=0, iter_end=None, verbose=False, *, sample_weight=None, monitor=False,
               callback=None):
         """Trains the SOM (batch algorithm); same contract as xpysom.py:458-594.
+
+        ``data`` may be a ``scipy.sparse`` matrix or array (not in the reference): see ``_train_sparse`` for what that means
+        and what it refuses.
 
         ``sample_weight`` (keyword-only; not in the reference) gives the rows unequal importance: one finite value >= 0
         per row of ``data``; a row of weight w adds w times its features to its BMU's sum and w to its count -- an
@@ -629,6 +667,8 @@ class XPySom:
         all-reduced before the merge.  Returns ``self``; ``_weights`` is float32 afterwards."""
         if iter_end is None:
             iter_end = num_epochs
+        if _is_sparse(data):
+            return self._train_sparse(data, num_epochs, iter_beg, iter_end, verbose, sample_weight, monitor, callback)
         monitored = _check_monitor(monitor, callback)    # (refused before an engine exists)
 
         rank, world = _dist.dist_info()
@@ -703,6 +743,61 @@ class XPySom:
             print('\n quantization error:', self.quantization_error(data))
         return self
 
+    def _sparse_engine(self, what):
+        """The engine for a call on sparse rows, or the error that names why they are refused (before an engine exists)."""
+        if self._activation_distance_name not in ('euclidean', 'euclidean_no_opt', 'cosine'):
+            raise NotImplementedError("sparse rows are served under the 'euclidean', 'euclidean_no_opt' and 'cosine' distances, "
+                                      "not %r" % (self._activation_distance_name,))
+        if self._precision not in ('exact', 'f32'):
+            raise ValueError("%s: sparse rows run float32 kernels: precision must be 'exact' or 'f32', not %r" % (what, self._precision))
+        if getattr(self, '_missing', None) is not None:
+            raise NotImplementedError("%s: sparse rows with missing='%s' are not supported" % (what, self._missing))
+        return self._upload_weights()
+
+    def _train_sparse(self, data, num_epochs, iter_beg, iter_end, verbose, sample_weight, monitor, callback):
+        """``train`` on a ``scipy.sparse`` matrix or array: the rows go to the device once, in CSR, and stay there for the
+        schedule; they are never made dense.  They mean what ``data.toarray()`` means, every stored value as a float32.  The
+        search and the segment sums are float32 kernels over the stored entries (under precision 'exact' and 'f32' alike): the
+        BMUs are float32 argmins of the dense kernels' scores in another summation order -- not bit for bit those of a dense
+        ``train`` on ``toarray()`` where two scores lie within rounding of each other; exact ties go to the lowest raveled
+        index, as everywhere.  Non-finite stored values are outside the contract.  Not with ``sample_weight``, ``monitor`` /
+        ``callback`` or an initialised process group."""
+        if sample_weight is not None:
+            raise NotImplementedError('sample_weight is not supported with sparse rows')
+        if monitor or callback is not None:
+            raise NotImplementedError('monitor=True (and callback) is not supported with sparse rows')
+        if _dist.dist_info()[1] > 1:
+            raise NotImplementedError('sparse rows are not supported under an initialised process group')
+        csr = _csr_rows(data, self._input_len)
+        eng = self._sparse_engine('train')
+        eng.set_data_csr(csr)
+        if getattr(eng, 'monitoring', False):            # an earlier monitored call's
+            eng.monitor(False)
+        try:
+            for iteration in range(iter_beg, iter_end):
+                eta = self._decay_function(self._learning_rate, self._learning_rateN, iteration, num_epochs)
+                sig = self._decay_function(self._sigma, self._sigmaN, iteration, num_epochs)
+                self._check_sigma(sig)
+                eng.epoch(sig, eta, isinstance(sig, np.generic))
+                if verbose:
+                    print('\r [ %d / %d ] %3.0f%%' % (iteration + 1, num_epochs, 100 * (iteration + 1) / num_epochs), end='')
+        finally:
+            self._weights = eng.get_weights().reshape(self._weights.shape)
+        if verbose:
+            print('\n quantization error:', self.quantization_error(data))
+        return self
+
+    def _sparse_ids(self, data, what):
+        """Raveled BMU ids of sparse rows, in chunks of n_parallel rows (row slices of the canonical CSR arrays)."""
+        indptr, indices, values = _csr_rows(data, self._input_len)
+        eng = self._sparse_engine(what)
+        out = []
+        for s in range(0, len(indptr) - 1, self._n_parallel):
+            e = min(s + self._n_parallel, len(indptr) - 1)
+            a, b = indptr[s], indptr[e]
+            out.append(eng.bmu_csr((indptr[s:e + 1] - a, indices[a:b], values[a:b])))
+        return np.concatenate(out).astype(np.int64) if out else np.zeros(0, dtype=np.int64)
+
     def _check_sigma(self, sig):
         """mexican_hat evaluates ``1 - 2/d*p`` with ``d = 2*std_coeff**2*sigma**2`` (neighborhoods.py:72, :94): a
         Python-float sigma of exactly 0 -- a linear schedule ending at sigmaN=0 -- raises there, in the reference, and
@@ -710,6 +805,15 @@ class XPySom:
         if self.neighborhood_func_name == 'mexican_hat' and not isinstance(sig, np.generic) \
                 and 2 * self._std_coeff ** 2 * sig ** 2 == 0:    # d, associated as neighborhoods.py:59 writes it
             raise ZeroDivisionError('float division by zero')
+
+    @staticmethod
+    def _dense_chunks(chunks):
+        """``chunks`` with every block checked on its way to the engine: train_streaming does not take sparse blocks."""
+        def checked():
+            for block in chunks():
+                _refuse_sparse(block[0] if isinstance(block, tuple) else block, 'train_streaming')
+                yield block
+        return checked
 
     def train_streaming(self, chunks, num_epochs, iter_beg=0, iter_end=None, *, monitor=False, callback=None):
         """``train`` for data that does not stay resident in HBM (or in host memory as one array).
@@ -726,6 +830,7 @@ class XPySom:
         if iter_end is None:
             iter_end = num_epochs
         monitored = _check_monitor(monitor, callback)
+        chunks = self._dense_chunks(chunks)              # (a sparse block is refused by name, not as an object array)
         eng = self._upload_weights()
         if monitored:
             eng.monitor(True)
@@ -762,6 +867,7 @@ class XPySom:
     def _device_query(self, x):
         """(engine, pointer, n_rows) for 2-D float32 rows that already live in HBM, else None: such rows are searched where
         they are (som_bmu_device), whole -- no host round trip, no n_parallel chunks (xpysom.py:379-396 on a CuPy array)."""
+        _refuse_sparse(x)
         shape = getattr(x, 'shape', None)
         if shape is None or len(shape) != 2:
             return None
@@ -797,6 +903,10 @@ class XPySom:
         ``(i, j)`` tuples (numpy.int64) for a matrix -- xpysom.py:370-408."""
         # the reference does not coerce x (xpysom.py:379-396): float64 rows against trained (float32) weights are scored in
         # float64 by NumPy.  Served for the 'euclidean' distance in the float32-exact modes; elsewhere x is taken as float32
+        if _is_sparse(x):                                   # sparse rows: searched as they are (see _train_sparse)
+            ids = self._sparse_ids(x, 'winner')
+            wi, wj = np.divmod(ids, self._weights.shape[1])
+            return list(map(tuple, np.vstack([wi, wj]).T))
         x64 = None
         if (isinstance(x, np.ndarray) and x.dtype == np.float64 and np.asarray(self._weights).dtype == np.float32
                 and self._activation_distance_name == 'euclidean' and self._precision in ('f32', 'exact')
@@ -833,7 +943,17 @@ class XPySom:
 
     def quantization_error(self, data):
         """Average distance between each input sample and its best matching unit
-        (always Euclidean, xpysom.py:673-707).  Returns a Python float."""
+        (always Euclidean, xpysom.py:673-707).  Returns a Python float.  Sparse rows (a ``scipy.sparse`` matrix or array) are
+        measured as they are: the differences x - w are formed directly, a float32 per row, the rows added in double."""
+        if _is_sparse(data):
+            indptr, indices, values = _csr_rows(data, self._input_len)
+            eng = self._sparse_engine('quantization_error')
+            total, n = 0.0, len(indptr) - 1
+            for s in range(0, n, self._n_parallel):
+                e = min(s + self._n_parallel, n)
+                a, b = indptr[s], indptr[e]
+                total += eng.quantization_error_csr((indptr[s:e + 1] - a, indices[a:b], values[a:b])) * (e - s)
+            return total / n if n else float('nan')
         q = self._device_query(data)
         if q is not None:
             eng, ptr, n, _owner = q
@@ -1256,7 +1376,9 @@ class XPySom:
         return bad / n if n else float('nan')
 
     def predict(self, data):
-        """Raveled BMU index of every sample (xpysom.py:608-617), batched."""
+        """Raveled BMU index of every sample (xpysom.py:608-617), batched.  Sparse rows are searched as they are."""
+        if _is_sparse(data):
+            return self._sparse_ids(data, 'predict')
         return self._ids_of(data).astype(np.int64)
 
     def _rows_by_unit(self, data):
