@@ -97,30 +97,60 @@ __global__ __launch_bounds__(256) void rownorm_bf16_kernel(const float* __restri
 }
 
 // initial accumulators B + |w~|^2/2 behind every W tile of a unit block
+// (scaled -- exact mode: the operands carry ex_scale factors, so does the accumulator: S (B + |w|^2/2), as prep_wsqh_kernel's;
+//  best64 -- the launch's per-row merge keys [0, n_rows) = all ones, in the same launch)
 __global__ __launch_bounds__(256) void prep_tiles_cin_kernel(const float* __restrict__ wn, int K,
                                                              const float* __restrict__ wmax2,
                                                              const float* __restrict__ xmax2, int n_kchunks,
                                                              long n_ublocks, int bn, int wfrag, int wtile,
-                                                             char* __restrict__ Wimg) {
+                                                             char* __restrict__ Wimg, int scaled = 0,
+                                                             unsigned long long* __restrict__ best64 = nullptr,
+                                                             long n_rows = 0) {
     long id = (long)blockIdx.x * 256 + threadIdx.x;
+    if (best64 != nullptr && id < n_rows) best64[id] = ~0ull;
     if (id >= n_ublocks * n_kchunks * bn) return;
     int within = (int)(id % bn);
     long tile = id / bn;                                   // (ublock * n_kchunks + kc)
     long u = (tile / n_kchunks) * bn + within;
     const float big = __builtin_sqrtf(*wmax2) * __builtin_sqrtf(*xmax2) * (1.0f + 1.0f / 1024.0f);
-    ((float*)(Wimg + tile * (long)wtile + wfrag))[within] = u < K ? __builtin_fmaf(0.5f, wn[u], big) : BF_PAD_NORM;
+    float S = 1.0f;
+    if (scaled) {                                          // (one scale after the other: nothing for a packed float32 operation to pair)
+        const float sx = ex_scale(*xmax2);
+        float wm2 = *wmax2;
+        asm volatile("" : "+v"(wm2) : "v"(sx));
+        S = sx * ex_scale(wm2);
+    }
+    ((float*)(Wimg + tile * (long)wtile + wfrag))[within] = u < K ? __builtin_fmaf(0.5f * S, wn[u], S * big) : BF_PAD_NORM;
 }
 
-template <int WS, int NWR, int NWC, class EL = Bf16>
+// GM (precision 'exact' beyond 800 features, bmu_exact.hpp): the same scan with a group-minimum epilogue -- VALUES only.  A wave's
+// 64 unit columns of a unit block are one screen group (the W image is in position order: group = NWC ub + wc).  Per finished
+// unit block a lane folds the 16 accumulator values it holds of each of its WS sample blocks, and ONE transposing reduction over
+// the four lane quads (v_permlane32_swap, then v_permlane16_swap: six swaps for the eight blocks, where eight butterflies take
+// sixteen) leaves quad q with the minima of sample blocks q and q + 4: lane l holds rows wave_row0 + l and wave_row0 + 64 + l, so
+// the wave's 128 rows are two coalesced stores into gmin[group][row] and their keep masks are two whole 64-bit words of gflags
+// ([row block][group], what exact_select_kernel reads).  Per row the lane keeps the minimum so far, the group that holds it and
+// the row's bound E(n); a group minimum is stored where it is <= minimum so far + E.  A wave sees only its column's groups of its
+// part: its minimum so far is a minimum over fewer groups than the final one, never below it, so what the final window m(n) + E(n)
+// needs was stored (the argument of bmu_exact.hpp for parts).  At the end (value, group) merges into out64 by atomicMin.
+// rowE[n] = E(n) of the pass's rows, +inf where the bound does not cover the row (exact_row_bounds_kernel, bmu_exact.hpp: the
+// bound's arithmetic stays out of this kernel -- the two rows a lane owns are what the compiler would pair into packed float32
+// operations; the one addition per row and unit block left here is kept apart by hand).
+template <int WS, int NWR, int NWC, class EL = Bf16, bool GM = false>
 __global__ __launch_bounds__(64 * NWR * NWC, 2) void bmu_bf16_tiled_kernel(const char* __restrict__ Ximg, long N,
                                                                            const char* __restrict__ Wimg,
                                                                            int n_ublocks, int n_kchunks, int K,
                                                                            unsigned long long* __restrict__ out64,
-                                                                           int n_sblocks, int n_parts) {
+                                                                           int n_sblocks, int n_parts,
+                                                                           uint32_t* __restrict__ gmin = nullptr, long gm_stride = 0,
+                                                                           unsigned long long* __restrict__ gflags = nullptr,
+                                                                           const float* __restrict__ rowE = nullptr) {
     using E = typename EL::T;
     using C = TileCfg<WS, NWR, NWC>;
     using bf16x8 = typename V8<E>::t;
     static_assert(NWR == 2 && TL_KS == 1, "two wave groups (sample halves), one MFMA k-step per stage");
+    static_assert(!GM || (WS == 8 && NWC * 64 == C::BN), "GM: eight sample blocks fold onto the four lane quads, a wave column is a group");
+    constexpr int GJ = GM ? WS * 16 / 64 : 1;            // GM: 64-row words of gflags (and rows per lane) a wave owns
     constexpr int TL_BM = C::BM, TL_BN = C::BN, TL_TILE = C::XTILE, TL_WFRAG = C::WFRAG, TL_WTILE = C::WTILE;
     constexpr int NG = NWC;                                                // waves per group
     constexpr int XPW = C::XPIECES / NG, WPW = (TL_WFRAG / 1024) / NG;     // 1 KiB DMA pieces per wave and stage
@@ -214,7 +244,57 @@ __global__ __launch_bounds__(64 * NWR * NWC, 2) void bmu_bf16_tiled_kernel(const
             for (int tu = 0; tu < 4; ++tu) cin[tu] = *(const f32x4*)(ws + c_off + tu * 64);
         }
     };
+    // GM: lane l <-> rows wave_row0 + 64 j + l: minimum so far, the group that holds it, the bound E(n).  A row the bound does not
+    // cover (NaN: bmu_bf16.hpp) keeps everything -- the select kernel drops it; a row behind the last one keeps nothing.
+    const long wave_row0 = sblock * (long)TL_BM + wr * (WS * 16);
+    const int n_groups = (K + 63) >> 6;
+    float run_min[GJ], row_e[GJ];
+    int run_arg[GJ];
+    if (GM) {
+#pragma unroll
+        for (int j = 0; j < GJ; ++j) {
+            const long r = wave_row0 + 64 * j + lane;
+            run_min[j] = __builtin_inff(); run_arg[j] = 0;
+            row_e[j] = r < N ? rowE[r] : __builtin_nanf("");
+        }
+    }
     auto reduce_block = [&](int ub) {                    // the 64 x 64 blocks of distances are complete
+        if constexpr (GM) {
+            uint32_t v[WS];                              // unsigned: every d' is a positive float, a NaN pattern is above them all
+#pragma unroll
+            for (int sb = 0; sb < WS; ++sb) {
+                uint32_t c0 = 0xFFFFFFFFu, c1 = 0xFFFFFFFFu;
+#pragma unroll
+                for (int tu = 0; tu < 4; ++tu) {
+                    c0 = min(min(c0, __float_as_uint(acc[tu][sb][0])), __float_as_uint(acc[tu][sb][1]));
+                    c1 = min(min(c1, __float_as_uint(acc[tu][sb][2])), __float_as_uint(acc[tu][sb][3]));
+                }
+                v[sb] = min(c0, c1);
+            }
+            const int g = ub * NWC + wc;                 // (wave-uniform; the last unit block may end in groups of padding only)
+            if (g >= n_groups) return;
+            unsigned long long mask[GJ];
+#pragma unroll
+            for (int j = 0; j < GJ; ++j) {
+                // lanes 0..31 keep the first operand's minimum over the two lane halves, lanes 32..63 the second's: sample blocks
+                // (4j, 4j + 2) and (4j + 1, 4j + 3); then rows of 16 lanes alike, even rows the first, odd rows the second
+                const auto s0 = __builtin_amdgcn_permlane32_swap(v[4 * j + 0], v[4 * j + 2], false, false);
+                const auto s1 = __builtin_amdgcn_permlane32_swap(v[4 * j + 1], v[4 * j + 3], false, false);
+                const auto s2 = __builtin_amdgcn_permlane16_swap(min(s0[0], s0[1]), min(s1[0], s1[1]), false, false);
+                const uint32_t m = min(s2[0], s2[1]);    // quad q: sample block 4j + q, i.e. row wave_row0 + 64 j + lane
+                const float f = __uint_as_float(m);
+                float thr = run_min[j] + row_e[j];
+                if (j + 1 < GJ) asm volatile("" : "+v"(run_min[j + 1]) : "v"(thr));   // (the next row's addition waits for this one: no pair)
+                const bool keep = f <= thr;
+                if (f < run_min[j]) run_arg[j] = g;
+                run_min[j] = __builtin_fminf(run_min[j], f);
+                if (keep) gmin[(long)g * gm_stride + wave_row0 + 64 * j + lane] = m;
+                mask[j] = __ballot(keep);
+            }
+            static_assert(!GM || GJ == 2, "two mask words per wave and group");
+            if (lane < GJ) gflags[ex_flag_index((wave_row0 >> 6) + lane, g, n_groups, gm_stride)] = lane ? mask[GJ - 1] : mask[0];
+            return;
+        }
 #pragma unroll
         for (int sb = 0; sb < WS; ++sb) {
             uint32_t c0 = 0xFFFFFFFFu, c1 = 0xFFFFFFFFu;
@@ -279,6 +359,15 @@ __global__ __launch_bounds__(64 * NWR * NWC, 2) void bmu_bf16_tiled_kernel(const
     if (wr == 0) run(std::false_type{}); else run(std::true_type{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA may land after the workgroup's LDS is released
 
+    if (GM) {
+        // the row minimum is the minimum so far after the last group: the plain value, every bit of it, and its group
+#pragma unroll
+        for (int j = 0; j < GJ; ++j) {
+            const long row = wave_row0 + 64 * j + lane;
+            if (row < N) atomicMin(out64 + row, ((unsigned long long)__float_as_uint(run_min[j]) << 32) | (uint32_t)run_arg[j]);
+        }
+        return;
+    }
 #pragma unroll
     for (int sb = 0; sb < WS; ++sb) {
         const uint32_t code = gbest[sb] & IDX_MASK;

@@ -52,6 +52,12 @@
 //                    E32_tau + 2 (operand term + accumulation term).
 // The bound is deliberately loose (worst-case rounding everywhere it is not measured): widening E only adds candidate
 // groups, and a candidate group costs one 64-unit re-score.
+// Long chains (beyond 128 features: the wide screen up to 800, the GM instance of the two-sided tiling -- bmu_bf16_tiled.hpp --
+// from 801 to 4096 on maps of >= 4096 units; euclidean and cosine).  The same E with the chain lengths of the tile images:
+// gamma_D over D = 32 ceil(D/32) terms (the float32 tile kernel's zero-padded chain) and n_mfma = ceil(D/32) MFMAs in the
+// screen's one chain, so cB = 2 (KAPPA n_mfma + 1) 2^-23 grows linearly with the row length: 2^-12.4 of Bm at 4096 features
+// (128 MFMAs).  4096 features is where the path stops (EX_LONG_MAX_KCHUNKS): nothing longer has been run.  The operand term
+// does not grow with D: it is measured per row and per codebook.
 //
 // TOP-2 (som_bmu_top2 / som_bmu_top2_device, euclidean, input_len <= 128: exact_top2_host.hpp).  Wanted: float32's best unit
 // k1 = first argmin_k s(k) and its second-best k2 = first argmin_{k != k1} s(k), s the float32 score above.  The window m + E
@@ -503,6 +509,18 @@ __global__ __launch_bounds__(256) void exact_thr2_kernel(uint32_t* __restrict__ 
     const ExactScales sc = ex_scales(xmax2, wmax2, werr2);
     const float thr = __uint_as_float(rowmin2[i]) + ex_refine_bound(eb, sc, xsq[i], xerr[i]);
     rowmin2[i] = (thr > 0.0f && thr < 3.0e38f) ? __float_as_uint(thr) : 0xFFFFFFFFu;
+}
+
+// rowE[n] = E(n) of a pass's rows for the screen beyond 800 features (bmu_bf16_tiled.hpp, GM: it keeps a group minimum within
+// rowE of the row's minimum so far): ex_row_bound as the select kernel evaluates it, +inf for a row the bound does not cover --
+// such a row keeps everything and the select kernel drops it.  One thread per row.
+__global__ __launch_bounds__(256) void exact_row_bounds_kernel(const float* __restrict__ xsq, const float* __restrict__ xerr, long n,
+                                                               const float* __restrict__ wmax2, const float* __restrict__ xmax2,
+                                                               const float* __restrict__ werr2, ExactBound eb, float* __restrict__ rowE) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float e = ex_row_bound(eb, ex_scales(xmax2, wmax2, werr2), xsq[i], xerr[i]);
+    rowE[i] = e == e ? e : __builtin_inff();
 }
 
 // One workgroup per group: its list compacted IN PLACE to the pairs whose refined minimum is within E2 of the row's,

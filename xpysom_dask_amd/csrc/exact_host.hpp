@@ -32,8 +32,9 @@ constexpr double EX_KAPPA = 6.0;     // measured through som_debug_mfma16: <= 2.
 ExactBound exact_bound(const som_handle* h) {
     const double u = std::ldexp(1.0, -24);
     // chain length of the float32 kernel (zero padded), MFMAs of the screen's one accumulator chain
-    const double Dl = h->wide ? 32.0 * h->ft_kchunks : 8.0 * h->fr_kg;
-    const double n_mfma = h->wide ? h->n_kchunks : h->ks32;
+    // (beyond 128 features -- the wide screen and the tiled one alike: the tile images' 32-feature chunks)
+    const double Dl = h->tiled ? 32.0 * h->ft_kchunks : 8.0 * h->fr_kg;
+    const double n_mfma = h->tiled ? h->n_kchunks : h->ks32;
     const double gamma = Dl * u / (1.0 - Dl * u);
     const double slop = 1.01;                             // the kernel evaluates E in float32
     ExactBound eb{};
@@ -211,10 +212,42 @@ int exact_screen_wide(som_handle* h, const __bf16* Ximg, long n, unsigned long l
     return 0;
 }
 
+// beyond 800 features: the GM instance of the two-sided tiling (bmu_bf16_tiled.hpp; a wave column of a unit block = a group).
+// Geometry and parts as launch_bmu_bf16_tiled_cfg's: the XCD-aware block order wants whole rounds of eight sample blocks, the parts
+// split on unit blocks -- four whole groups.  No lists: block skipping stays off on this path.
+int exact_screen_tiled(som_handle* h, const __bf16* Ximg, long n, unsigned long long* best64, const float* xsq, const float* xerr,
+                       const float* xmax2, const ExactBound& eb) {
+    using C = TileCfg<8, 2, 4>;
+    auto kern = bmu_bf16_tiled_kernel<8, 2, 4, ExactEl, true>;
+    const size_t lds = (size_t)C::LDS_BYTES;
+    int per_cu = 1;
+    if (int rc = kernel_per_cu(h, (const void*)kern, 64 * C::WAVES, lds, &per_cu)) return rc;
+    const long blocks = cdiv(n, C::BM);
+    if (blocks <= 0 || blocks > 0x7fffffffL) return fail(h, "exact: row count out of range");
+    const long slots = resident_slots(h, per_cu);
+    int parts = choose_parts(h, blocks, slots, h->n_ublocks);
+    if (h->n_ublocks >= 64 && blocks * 8 >= slots) parts = 8;   // (one XCD's resident workgroups share sample tiles through its L2)
+    if (h->env_bf16_parts > 0) parts = h->env_bf16_parts;
+    parts = std::max(1, std::min(parts, h->n_ublocks));
+    const long grid = round_up(blocks, 8) * parts;
+    if (grid > 0x7fffffffL) return fail(h, "exact: grid too large");
+    if (h->debug)
+        std::fprintf(stderr, "[somhip] exact screen (tiled): blocks=%ld per_cu=%d slots=%ld parts=%d ublocks=%d kchunks=%d\n", blocks, per_cu, slots,
+                     parts, h->n_ublocks, h->n_kchunks);
+    // the rows' bounds E(n) first, into the pass's seed buffer (no seed on this path: free)
+    float* rowE = h->ex.pass.seed;
+    exact_row_bounds_kernel<<<dim3((unsigned)cdiv(n, 256)), dim3(256), 0, h->stream>>>(xsq, xerr, n, h->wmax2, xmax2, h->wmax2 + 1, eb, rowE);
+    kern<<<dim3((unsigned)grid), dim3(64 * C::WAVES), lds, h->stream>>>(
+        (const char*)Ximg, n, h->Wst, h->n_ublocks, h->n_kchunks, h->K, best64, (int)blocks, parts, h->ex.pass.gmin, h->ex.pass.stride,
+        h->ex.pass.gflags, rowE);
+    return 0;
+}
+
 int exact_screen_ks(som_handle* h, const __bf16* Xb, long n, unsigned long long* best64, const float* xsq, const float* xerr,
                     const float* xmax2, const ExactBound& eb, const float* seed, const int* glist, const int* gcnt,
                     const ScreenSelect& sel, bool* selected) {
     *selected = false;
+    if (h->ex_long) return exact_screen_tiled(h, Xb, n, best64, xsq, xerr, xmax2, eb);
     if (h->wide)
         return for_kchunks(h, "exact: no wide screen instance for this input_len", [&](auto k) {
             return exact_screen_wide<decltype(k)::value>(h, Xb, n, best64, xsq, xerr, xmax2, eb, glist, gcnt); });
@@ -694,7 +727,7 @@ int exact_refine(som_handle* h, SortedRows& sr, long r0, long n, const float* xm
 int exact_rescore_round(som_handle* h, const float* X, const float* xsq, unsigned long long* best64, const int* gstart,
                         int* gstart_out, bool sorted_copy, bool count_pairs) {
     auto& ex = h->ex;
-    const int deint = (sorted_copy && !h->wide && (h->D & 7) == 0) ? 1 : 0;
+    const int deint = (sorted_copy && !h->tiled && (h->D & 7) == 0) ? 1 : 0;
     const PassCtr pc = pass_ctr(h);
     const int n_groups = pc.n_groups;
     int* gcount = pc.gcount(); PassCounters* const ctr = pc.tail();
@@ -703,8 +736,8 @@ int exact_rescore_round(som_handle* h, const float* X, const float* xsq, unsigne
     exact_tiles_kernel<<<dim3(exact_tiles_blocks(h)), dim3(1024), 0, h->stream>>>(gcount, n_groups, ex.pass.stride, ex.pass.stride * ex.pass.pairs, ex.pass.tile_tab, n_tiles,
                                                                                  &ctr->overflow, gstart, gstart_out,
                                                                                  (gstart == nullptr && gstart_out == nullptr && count_pairs) ? &ctr->pairs_in : nullptr);
-    if (h->wide) {
-        // beyond 128 features: the float32 tile image, chunk by chunk
+    if (h->tiled) {
+        // beyond 128 features (the wide screen and the tiled one): the float32 tile image, chunk by chunk
         if (!h->Wfimg) return fail(h, "exact: no float32 tile image");
         const bool cosine = h->cfg.distance == SOM_DIST_COSINE;
         const void* kern = cosine ? (const void*)exact_rescore_tiled_kernel<SCORE_COSINE>
@@ -864,7 +897,7 @@ int exact_pass(som_handle* h, ExactLaunch& L, SortedRows& sr, long r0, long n) {
     }
     // resident rows from their second epoch on: last epoch's BMU of every row caps the screen's keep threshold -- under a
     // plan the plan's prologue forms that seed from the operands it holds (exact_skip.hpp), else exact_seed_kernel
-    ex.seed_live = ex.sw.seed_on && !h->wide && have_last;
+    ex.seed_live = ex.sw.seed_on && !h->tiled && have_last;
     if (ex.seed_live && !lp.skip) {
         exact_seed_kernel<<<dim3((unsigned)cdiv(n * 16, 256)), dim3(256), 0, h->stream>>>(
             X + r0 * h->D, n, h->D, h->W, h->wsq, h->K, out + r0, xsq + r0, xerr + r0, h->wmax2, xmax2, h->wmax2 + 1, eb, ex.pass.seed);
@@ -1021,6 +1054,12 @@ int launch_bmu_exact(som_handle* h, const Rows& R) {
     const long units = (long)h->n_stages * h->stage_units;
     const unsigned wsqh_blocks = (unsigned)cdiv(std::max(units, N), 256);
     auto launch_wsqh = [&]() {
+        if (h->ex_long) {                                    // (the tile image: a C-in row behind every unit tile)
+            const long cin = (long)h->n_ublocks * h->n_kchunks * h->tl_bn;
+            prep_tiles_cin_kernel<<<dim3((unsigned)cdiv(std::max(cin, N), 256)), dim3(256), 0, h->stream>>>(
+                h->wn, h->K, h->wmax2, xmax2, h->n_kchunks, h->n_ublocks, h->tl_bn, h->tl_wfrag, h->tl_wtile, h->Wst, 1, h->best64, N);
+            return;
+        }
         prep_wsqh_kernel<<<dim3(wsqh_blocks), dim3(256), 0, h->stream>>>(
             h->wn, h->K, h->wmax2, xmax2, h->Wst, h->n_stages, h->stage_bytes, h->stage_units, h->best64, N, 1);
     };
@@ -1028,7 +1067,8 @@ int launch_bmu_exact(som_handle* h, const Rows& R) {
     if (wsqh_done) launch_wsqh();
     const int n_groups = (int)cdiv(h->K, EX_GROUP);
     const long chunk = std::min(exscratch::pass_rows(exact_geometry(h)), ex.pass.stride);
-    ExactLaunch L{R, exact_bound(h), n_groups, ex.sw.two_round >= 0 ? ex.sw.two_round != 0 : h->wide, {}, {}};
+    // (two re-score rounds by default beyond 128 features, on either screen: a pair costs 64 x D flop and a gather of D floats)
+    ExactLaunch L{R, exact_bound(h), n_groups, ex.sw.two_round >= 0 ? ex.sw.two_round != 0 : h->tiled, {}, {}};
     // THE FACTS.  Block skipping (exact_skip.hpp), one round, <= 128 features, maps of >= 4096 units: a plan needs, per row, SOME
     // unit whose distance bounds the distance to the BMU.  RESIDENT rows from their second epoch on have last epoch's BMU; every
     // other row set (query rows, streamed chunks, a row set's first epoch) -- and resident rows while last epoch's BMUs say
@@ -1041,7 +1081,7 @@ int launch_bmu_exact(som_handle* h, const Rows& R) {
     f.rows = (const void*)X; f.n_rows = N;
     const bool scout_size_ok = ex.sw.scout_on && n_groups <= 262144 &&
                                (ex.sw.skip_mode > 1 || policy::rows_worth_a_scout((double)N, (double)h->K, (double)h->D));
-    f.can_skip = exact_skip_wanted(h) && !h->wide && !L.two_round;
+    f.can_skip = exact_skip_wanted(h) && !h->tiled && !L.two_round;   // (up to 128 features; beyond 800 nothing skips: wide_can)
     f.scout_ok = f.can_skip && scout_size_ok;
     // beyond 128 features (exact_skip_wide.hpp): euclidean, resident rows with last epoch's BMUs, whole 64-unit groups
     f.wide = h->wide;

@@ -18,6 +18,7 @@ constexpr int K16_T = 4;              // resident screen (bmu_bf16_k16.hpp): 16-
 constexpr int K16_STAGE_UNITS = 16 * K16_T;
 constexpr int WD_T = 2;               // wide screen (bmu_bf16_wide.hpp): 16-unit tiles per stage
 constexpr int WD_STAGE_UNITS = 16 * WD_T;
+constexpr int EX_LONG_MAX_KCHUNKS = 128;   // long-chain screen (bmu_bf16_tiled.hpp, GM): 32-feature chunks it is offered at most
 constexpr int EX_GROUP = 64;          // units per group = one stage of the float32 stage image = one stage of the screen
 constexpr int EX_PAIRS = 64;          // least capacity of a pass in (row, group) pairs per row ON AVERAGE
 constexpr int EX_TR = 128;            // rows per re-score tile (4 waves x 32 rows against one 64-unit group)

@@ -342,6 +342,7 @@ struct som_handle {
     int n_ublocks = 0;       // tiled: unit blocks of tl_bn
     bool tl_big = false;     // tiled: 256 x 256 workgroup tiles (8 waves) instead of 128 x 128
     bool wide = false;       // bf16, 128 < input_len <= 800, big maps: samples resident in registers (bmu_bf16_wide.hpp)
+    bool ex_long = false;    // exact, 800 < input_len <= 4096, big maps: the screen is the GM instance of the two-sided tiling
     int tl_bm = 128, tl_bn = 128, tl_xtile = 0, tl_wfrag = 0, tl_wtile = 0;
     int dp = 0;              // feature stride of the bf16 row image
     int stage_bytes = 0;     // bytes of one codebook stage image
@@ -691,7 +692,7 @@ int prep_codebook_exact(som_handle* h, const operands::Rebuilds& r) {
     const float* Wex = h->ex_patch ? h->Wp : h->W;
     const float* qex = h->ex_patch ? h->wsq_p : h->wsq;
     const dim3 block(256);
-    if (h->wide) {
+    if (h->tiled) {
         // beyond 128 features: the float32 kernel's own |w|^2 as the norm term (euclidean) or none (cosine:
         // unit-length units, max |w| = 1), the units scaled by a power of two, their rounding errors measured
         const float* unit = h->cfg.distance == SOM_DIST_COSINE ? qex : nullptr;
@@ -702,9 +703,16 @@ int prep_codebook_exact(som_handle* h, const operands::Rebuilds& r) {
             HIPCHK(h, hipMemsetAsync(h->wmax2, 0, sizeof(float), h->stream));
             exact_copy_wsq_kernel<<<dim3((unsigned)cdiv(h->K, 1024)), dim3(1024), 0, h->stream>>>(qex, h->K, h->wn, h->wmax2);
         }
-        long total = (long)h->n_stages * WD_T * h->n_kchunks * 64;
-        prep_w_bf16_wide_kernel<ExactEl><<<dim3((unsigned)cdiv(total, 256)), block, 0, h->stream>>>(
-            Wex, h->K, h->D, h->n_kchunks, h->Wst, h->n_stages, unit, h->wmax2);
+        if (h->wide) {
+            long total = (long)h->n_stages * WD_T * h->n_kchunks * 64;
+            prep_w_bf16_wide_kernel<ExactEl><<<dim3((unsigned)cdiv(total, 256)), block, 0, h->stream>>>(
+                Wex, h->K, h->D, h->n_kchunks, h->Wst, h->n_stages, unit, h->wmax2);
+        } else {
+            // (beyond 800 features: the unit TILE image of the two-sided tiling, -w~ as the 'f16' mode's, in position order)
+            long total = (long)h->n_ublocks * h->n_kchunks * (h->tl_bn / 16) * TL_KS * 64;
+            prep_tiles_bf16_kernel<ExactEl><<<dim3((unsigned)cdiv(total, 256)), block, 0, h->stream>>>(
+                Wex, h->K, h->D, h->n_kchunks, h->n_ublocks, h->tl_bn, h->tl_wtile, -1.0f, unit, h->Wst, h->wmax2);
+        }
         HIPCHK(h, hipMemsetAsync(h->wmax2 + 1, 0, sizeof(float), h->stream));
         exact_werr_kernel<ExactEl><<<dim3((unsigned)cdiv(h->K, 4 * EX_WERR_UNITS)), block, 0, h->stream>>>(Wex, h->K, h->D, h->wmax2, h->wmax2 + 1, unit);
         return 0;
@@ -956,7 +964,7 @@ int launch_bmu_bf16_tiled_cfg(som_handle* h, const __bf16* Ximg, long N, int* ou
     HIPCHK(h, hipMemsetAsync(h->best64, 0xFF, (size_t)N * sizeof(unsigned long long), h->stream));
     const long grid = round_up(blocks, 8) * parts;
     if (grid > 0x7fffffffL) return fail(h, "bmu_bf16: grid too large");
-    kern<<<dim3((unsigned)grid), dim3(64 * C::WAVES), lds, h->stream>>>(
+    bmu_bf16_tiled_kernel<WS, NWR, NWC, E><<<dim3((unsigned)grid), dim3(64 * C::WAVES), lds, h->stream>>>(
         (const char*)Ximg, N, h->Wst, h->n_ublocks, h->n_kchunks, h->K, h->best64, (int)blocks, parts);
     bmu_finalize_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(h->best64, N, h->K, out);
     HIPCHK(h, hipGetLastError());
@@ -1842,7 +1850,8 @@ int som_create(const som_config* cfg, som_handle** out) {
         // the screen + re-score scheme covers the euclidean distance up to 128 features; everywhere else the
         // float32 kernels ARE the exact mode
         // (<= 128 features: the resident screen, euclidean; 129 .. 800 features on maps of >= 4096 units: the wide
-        //  screen, euclidean and cosine -- decided below, once the tiling is known)
+        //  screen, 801 .. 4096 features there: the tiled screen, both euclidean and cosine -- decided below, once the
+        //  tiling is known)
         if ((cfg->distance == SOM_DIST_EUCLIDEAN && cfg->input_len <= 128) ||
             ((cfg->distance == SOM_DIST_EUCLIDEAN || cfg->distance == SOM_DIST_COSINE) && cfg->input_len > 128)) h->exact = true;
         else h->cfg.precision = SOM_PREC_F32;
@@ -1871,7 +1880,12 @@ int som_create(const som_config* cfg, som_handle** out) {
     }
     h->wide = h->tiled && h->tl_big && h->n_kchunks <= 25;
     if (const char* e = dev_env("SOM_BF16_WIDE")) if (std::atoi(e) == 0) h->wide = false;   // A/B: the two-sided tiling
-    if (h->exact && h->tiled && !h->wide) {              // no exact screen on the two-sided tiling: the float32 kernels serve
+    // exact beyond the wide kernel's 25 chunks: the group-minimum instance of the two-sided tiling (bmu_bf16_tiled.hpp, GM) on
+    // maps of >= 4096 units, up to 4096 features -- a deliberate cap: the accumulation term of the bound grows with the chain
+    // (exact_bound) and nothing longer has been run.  SOM_EXACT_LONG=0: the float32 kernels, as below (A/B)
+    h->ex_long = h->exact && h->tiled && h->tl_big && h->n_kchunks > 25 && h->n_kchunks <= EX_LONG_MAX_KCHUNKS;
+    if (const char* e = dev_env("SOM_EXACT_LONG")) if (std::atoi(e) == 0) h->ex_long = false;
+    if (h->exact && h->tiled && !h->wide && !h->ex_long) {   // no exact screen there: the float32 kernels serve
         h->exact = false; h->f16 = false; h->tiled = false;
         h->cfg.precision = SOM_PREC_F32;
     }
@@ -2088,7 +2102,7 @@ static int adopt_rows(som_handle* h, const std::string& who, const void* x, int6
         // the rows, not inside the first epochs (gigabytes of fresh device memory can take a driver tens to hundreds of
         // milliseconds).  A refusal here is not an error: launch_bmu_exact asks again and settles it (smaller passes, no plan).
         bool ok = exact_reserve(h, n_rows) == 0;
-        if (ok && exact_skip_wanted(h) && !h->wide)
+        if (ok && exact_skip_wanted(h) && !h->wide && !h->ex_long)
             ok = exact_skip_reserve(h, h->ex.srt[0], n_rows, h->ex.pass.stride) == 0;
         if (!ok) { (void)hipGetLastError(); h->err.clear(); }
     }

@@ -394,8 +394,9 @@ class XPySom:
         Extra keyword-only arguments:
           precision      'exact' (the DEFAULT: the BMUs of 'f32' bit for bit -- hence its accumulators and its trained
                          codebook --, found by an IEEE-half MFMA screen and a float32 re-score of the units its error
-                         bound cannot rule out; where no screen applies -- small maps, the VALU distances -- the float32
-                         kernels themselves serve it), 'f32' (the exact-float32 MFMA kernels over every unit: the parity
+                         bound cannot rule out: euclidean up to 128 features on any map, euclidean and cosine up to 4096
+                         features on maps of >= 4096 units; where no screen applies -- longer rows, small maps beyond 128
+                         features, the VALU distances -- the float32 kernels themselves serve it), 'f32' (the exact-float32 MFMA kernels over every unit: the parity
                          mode the default is checked against), 'bf16' (bf16 MFMA distance GEMM: BMUs within the operand
                          rounding of float32's), or the same path on IEEE half operands, 'f16' (three more mantissa bits
                          at the same MFMA rate; rows and units must fit float16: norms <= 65504)
