@@ -97,7 +97,14 @@ enum { SOM_PREC_F32 = 0, SOM_PREC_BF16 = 1,
  * and every column of den is the unmasked den up to float32 summation order.
  * Scope: distance SOM_DIST_EUCLIDEAN; precision F32 or EXACT (both run the float32 masked kernel -- no screen applies);
  * every neighbourhood and topology; resident, device, weighted and streamed rows.  som_create refuses other distances and
- * BF16 / F16.  On such a handle som_epoch_fetch, som_epoch_accumulate_faithful, som_set_verify(n > 0), som_bmu_top2*,
+ * BF16 / F16 in som_config.precision.
+ * The SEARCH alone may run on the 16-bit matrix pipe: som_set_masked_search(h, SOM_PREC_BF16 | SOM_PREC_F16) (default
+ * SOM_PREC_F32: the kernel above).  The BMU is then the first minimum of s_nk = 1/2 sum_d m_nd q_kd - sum_d x~_nd w~_kd, x~ and
+ * w~ rounded to the operand type (x~ = 0 at the holes), q = w~ w~ carried as two bf16 images, float32 accumulation
+ * (csrc/bmu_masked_half.hpp): a near-best unit within the operand rounding, as BF16 / F16 are without missing values.  Every
+ * caller of the search inherits it -- epochs, streamed chunks, som_bmu*, som_quantization_error*, som_impute*, the unit
+ * statistics and maps, the monitor --; update, merge, QE and every reported distance stay the float32 kernels.  Rows holding
+ * +-inf are outside the 16-bit search's contract.  On such a handle som_epoch_fetch, som_epoch_accumulate_faithful, som_set_verify(n > 0), som_bmu_top2*,
  * som_bmu_f64 and som_distance_matrix fail with a message; som_epoch_fetch_masked reads the accumulator.
  * SOM_MISSING_NONE (the default): NaNs are ordinary values, every launch and result is what it is without this field. */
 enum { SOM_MISSING_NONE = 0, SOM_MISSING_NAN = 1 };
@@ -502,6 +509,12 @@ int som_epoch_metrics(som_handle* h, som_epoch_metrics_t* out);
  * environment variable SOM_VERIFY=n at som_create).  som_verify_stats: launches / rows checked so far.
  * (The test hooks that go with it -- som_debug_* -- are declared in include/somhip_test.h, not here.) */
 int som_set_verify(som_handle* h, int32_t n_rows);
+
+/* Missing values: which kernel searches the BMUs of a handle created with SOM_MISSING_NAN (see SOM_MISSING_NAN above) --
+ * SOM_PREC_F32 (the default), SOM_PREC_BF16 or SOM_PREC_F16.  Fails with a message on any other id and on a handle without
+ * SOM_MISSING_NAN.  Takes effect from the next search; som_get_masked_search: the current id (-1: no handle). */
+int som_set_masked_search(som_handle* h, int32_t prec);
+int som_get_masked_search(const som_handle* h);
 int som_verify_stats(som_handle* h, int64_t* launches, int64_t* rows_checked);
 
 /* precision EXACT, introspection (host arithmetic only, no device needed): the order in which the mode's operand images

@@ -13,6 +13,17 @@ SOM_NEIGH = {"gaussian": 0, "mexican_hat": 1, "bubble": 2, "triangle": 3}
 SOM_PREC = {"f32": 0, "bf16": 1, "f16": 3, "exact": 5}      # (ids 2 and 4: the retired split-operand modes)
 SOM_TOPO = {"rectangular": 0, "hexagonal": 1, "toroidal": 2}
 SOM_MISSING = {None: 0, "nan": 1}
+MISSING_SEARCH = ("f32", "bf16", "f16")                     # som_set_masked_search: SOM_PREC[...] of each
+
+
+def check_missing_search(missing, missing_search):
+    """The kernel that searches the BMUs under missing='nan': 'f32', 'bf16' or 'f16'; anything but 'f32' needs missing='nan'.
+    Needs no library."""
+    if missing_search not in MISSING_SEARCH:
+        raise ValueError("missing_search must be 'f32', 'bf16' or 'f16', got %r" % (missing_search,))
+    if missing_search != "f32" and missing != "nan":
+        raise ValueError("missing_search='%s' needs missing='nan'" % missing_search)
+    return missing_search
 SOM_BMU_ACTIVATION, SOM_BMU_QUANTIZATION = 0, 1
 SOM_KERNELS = {"bmu": 0, "segsum": 1, "kron": 2, "merge": 3, "prep": 4, "screen": 5, "fill": 6}
 
@@ -115,6 +126,8 @@ SIGNATURES = {
     "som_epoch_measure_shift": (C.c_int, [_H]),
     "som_epoch_metrics": (C.c_int, [_H, C.POINTER(EpochMetrics)]),
     "som_set_verify": (C.c_int, [_H, C.c_int32]),
+    "som_set_masked_search": (C.c_int, [_H, C.c_int32]),
+    "som_get_masked_search": (C.c_int, [_H]),
     "som_verify_stats": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "som_debug_corrupt_operands": (C.c_int, [_H, C.c_int32]),
     "som_debug_operand_crc": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint64)]),

@@ -33,6 +33,7 @@
 #include "bmu_f32_res.hpp"
 #include "bmu_f32_tiled.hpp"
 #include "bmu_masked_f32.hpp"
+#include "bmu_masked_half.hpp"
 #include "bmu_pairwise.hpp"
 #include "update.hpp"
 #include "diag.hpp"
@@ -245,6 +246,16 @@ struct som_handle {
     // D1p = round_up(UD + 1, 4).  Everything between level 0 and the merge sees UD features and nothing else.
     bool masked = false;
     int UD = 0;
+    // ... or, once som_set_masked_search picked SOM_PREC_BF16 / SOM_PREC_F16, the 16-bit MFMA masked search (bmu_masked_half.hpp) and
+    // its scratch, grown on demand and freed with the handle: img the three codebook images, round_up(K, 64) * round_up(D, 32) * 6
+    // bytes, rebuilt in front of every search; part_sc / part_id parts * N, the parts' minima
+    int masked_prec = SOM_PREC_F32;
+    struct MaskedHalfScratch {
+        DevBuf<char> img;
+        DevBuf<float> part_sc;
+        DevBuf<int> part_id;
+    } mh;
+    int env_masked_parts = 0;    // SOM_MASKED_PARTS: that search's part count (clamped to its stages)
     int ks32 = 0;            // bf16, 16x16x32 shape: ceil(D/32)
     bool tiled = false;      // bf16, input_len > 128: two-sided tiling (bmu_bf16_tiled.hpp)
     bool f16 = false;        // precision f16: _Float16 operands instead of __bf16 (the same kernels, som_common.hpp)
@@ -882,6 +893,56 @@ int launch_bmu_masked(som_handle* h, const float* X, long N, int* out) {
     return 0;
 }
 
+// missing values on the 16-bit matrix pipe (bmu_masked_half.hpp): the three codebook images, then the scan over `parts` ranges of
+// the stages and -- several parts -- their merge by (score, id).  The rows are read as they are.
+template <bool HALF>
+int launch_bmu_masked_half(som_handle* h, const float* X, long N, int* out) {
+    auto& g = h->mh;
+    const int KS = (int)cdiv(h->D, 32), n_stages = (int)cdiv(h->K, MH_STAGE_UNITS);
+    const long chunks = (long)n_stages * KS, blocks = cdiv(N, MH_WG_SAMPLES);
+    if (chunks > 0x7fffffffL) return fail(h, "bmu_masked_half: the codebook images exceed 2^31 chunks");
+    if (blocks <= 0 || blocks > 0x7fffffffL) return fail(h, "bmu_masked_half: row count out of range");
+    if (int rc = g.img.reserve(h, (size_t)chunks * MH_CHUNK_BYTES)) return rc;
+    {
+        Timed t(h, SOM_K_PREP);
+        prep_masked_half_kernel<HALF><<<dim3((unsigned)chunks), dim3(256), 0, h->stream>>>(h->W, h->K, h->D, KS, g.img);
+    }
+    const void* fn = nullptr;
+    size_t lds = mh_lds_bytes(KS <= MH_RES_KS ? KS : 1);
+    switch (KS <= MH_RES_KS ? KS : 0) {
+    case 0: fn = (const void*)bmu_masked_half_stream_kernel<HALF>; break;
+    case 1: fn = (const void*)bmu_masked_half_kernel<1, HALF>; break;
+    case 2: fn = (const void*)bmu_masked_half_kernel<2, HALF>; break;
+    case 3: fn = (const void*)bmu_masked_half_kernel<3, HALF>; break;
+    case 4: fn = (const void*)bmu_masked_half_kernel<4, HALF>; break;
+    }
+    int per_cu = 1;
+    if (int rc = kernel_per_cu(h, fn, 64 * MH_NW, lds, &per_cu)) return rc;
+    int parts = choose_parts(h, blocks, resident_slots(h, per_cu), n_stages);
+    if (h->env_masked_parts > 0) parts = h->env_masked_parts;   // (tests: the single-part and the merged paths at any size)
+    parts = std::max(1, std::min(parts, std::min(n_stages, 65535)));
+    if (parts > 1) {
+        if (int rc = g.part_sc.reserve(h, (size_t)parts * N)) return rc;
+        if (int rc = g.part_id.reserve(h, (size_t)parts * N)) return rc;
+    }
+    if (h->debug)
+        std::fprintf(stderr, "[somhip] bmu_masked_half: blocks=%ld per_cu=%d parts=%d stages=%d ks=%d\n", blocks, per_cu, parts, n_stages, KS);
+    Timed t(h, SOM_K_BMU);
+    const dim3 grid((unsigned)blocks, (unsigned)parts), block(64 * MH_NW);
+#define SOM_MASKED_HALF(KS32) bmu_masked_half_kernel<KS32, HALF><<<grid, block, lds, h->stream>>>(X, N, h->D, g.img, n_stages, h->K, out, g.part_sc, g.part_id)
+    switch (KS <= MH_RES_KS ? KS : 0) {
+    case 0: bmu_masked_half_stream_kernel<HALF><<<grid, block, lds, h->stream>>>(X, N, h->D, g.img, n_stages, KS, h->K, out, g.part_sc, g.part_id); break;
+    case 1: SOM_MASKED_HALF(1); break;
+    case 2: SOM_MASKED_HALF(2); break;
+    case 3: SOM_MASKED_HALF(3); break;
+    case 4: SOM_MASKED_HALF(4); break;
+    }
+#undef SOM_MASKED_HALF
+    if (parts > 1) sparse_merge_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(g.part_sc, g.part_id, N, parts, h->K, out);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 // best AND second-best unit under the sqrt'd Euclidean distance (topographic error)
 int launch_bmu_top2(som_handle* h, const float* X, long N, const float* xsq, int* out, int* out2) {
     constexpr int M = SCORE_EUCLID_SQRT;
@@ -1277,7 +1338,9 @@ int verify_bmu_launch(som_handle* h, const Rows& r) {
 
 // BMU of a row set's device rows with the configured activation distance (xpysom.py:410-417)
 int run_activation_bmu_launch(som_handle* h, const Rows& r) {
-    if (h->masked) {                                     // missing values: one kernel, no codebook operands to refresh
+    if (h->masked) {                                     // missing values: no codebook operands to refresh (the 16-bit search writes its own)
+        if (h->masked_prec == SOM_PREC_BF16) return launch_bmu_masked_half<false>(h, r.X, r.N, r.out);
+        if (h->masked_prec == SOM_PREC_F16) return launch_bmu_masked_half<true>(h, r.X, r.N, r.out);
         Timed t(h, SOM_K_BMU);
         return launch_bmu_masked(h, r.X, r.N, r.out);
     }
@@ -1953,6 +2016,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         if ((rc = h->np_dev.alloc(h, 1))) return bail(rc);
         if (const char* e = std::getenv("SOM_GRAPH")) h->use_graph = std::atoi(e) != 0;
         if (const char* e = dev_env("SOM_BF16_PARTS")) h->env_bf16_parts = std::atoi(e);
+        if (const char* e = dev_env("SOM_MASKED_PARTS")) h->env_masked_parts = std::atoi(e);
         if (const char* e = dev_env("SOM_F32_PARTS")) h->env_f32_parts = std::atoi(e);
         h->debug = std::getenv("SOM_DEBUG") != nullptr;
         if (const char* e = std::getenv("SOM_VERIFY")) h->verify_rows = std::max(0, std::atoi(e));
@@ -3453,6 +3517,21 @@ int som_set_verify(som_handle* h, int32_t n_rows) {
     h->verify_rows = n_rows;
     return 0;
 }
+
+int som_set_masked_search(som_handle* h, int32_t prec) {
+    if (!h) return 1;
+    if (!h->masked) return fail(h, "som_set_masked_search: the handle was not created with SOM_MISSING_NAN");
+    if (prec != SOM_PREC_F32 && prec != SOM_PREC_BF16 && prec != SOM_PREC_F16)
+        return fail(h, "som_set_masked_search: the masked search runs in SOM_PREC_F32, SOM_PREC_BF16 or SOM_PREC_F16");
+    if (prec != h->masked_prec) {                        // (a captured epoch holds the other search: the next one runs eagerly and sizes the scratch)
+        drop_graph(h);
+        h->graph_warm = 0;
+    }
+    h->masked_prec = prec;
+    return 0;
+}
+
+int som_get_masked_search(const som_handle* h) { return h ? h->masked_prec : -1; }
 
 int som_verify_stats(som_handle* h, int64_t* launches, int64_t* rows_checked) {
     if (!h) return 1;

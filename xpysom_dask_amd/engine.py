@@ -55,9 +55,10 @@ def check_topk(k):
 class HipEngine:
     def __init__(self, x, y, input_len, *, distance="euclidean", neighborhood="gaussian",
                  std_coeff=0.5, compact_support=False, precision="exact", device=0, stream=None,
-                 topology="rectangular", norm_p=0, norm_p_real=0.0, missing=None):
+                 topology="rectangular", norm_p=0, norm_p_real=0.0, missing=None, missing_search="f32"):
         if missing not in _lib.SOM_MISSING:
             raise ValueError("missing must be None or 'nan', got %r" % (missing,))
+        _lib.check_missing_search(missing, missing_search)
         self._lib = _lib.load()
         self._h = None
         self.K, self.D = int(x) * int(y), int(input_len)
@@ -79,6 +80,16 @@ class HipEngine:
         self.device = int(device)
         self.precision = precision
         self.missing = missing
+        self.missing_search = "f32"
+        if missing_search != "f32":
+            self.set_missing_search(missing_search)
+
+    def set_missing_search(self, missing_search):
+        """Which kernel searches the BMUs of an engine created with missing='nan' from the next search on: 'f32' (the float32
+        masked kernel), 'bf16' or 'f16' (the 16-bit MFMA masked search; include/somhip.h, som_set_masked_search)."""
+        _lib.check_missing_search(self.missing, missing_search)
+        self._check(self._lib.som_set_masked_search(self._h, _lib.SOM_PREC[missing_search]))
+        self.missing_search = missing_search
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc):

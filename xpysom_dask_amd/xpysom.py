@@ -386,7 +386,7 @@ class XPySom:
                  random_seed=None, n_parallel=0, compact_support=False,
                  xp=None,
                  use_dask=False, dask_chunks='auto',
-                 *, precision='exact', device=None, sharded_input=False, shard='contiguous', missing=None):
+                 *, precision='exact', device=None, sharded_input=False, shard='contiguous', missing=None, missing_search='f32'):
         """Same positional/keyword surface as the reference constructor (xpysom.py:73-82).
 
         ``xp``, ``use_dask`` and ``dask_chunks`` are accepted for source compatibility and
@@ -420,6 +420,12 @@ class XPySom:
                          unit's value for that feature).  topographic_error, activate, distance_from_weights,
                          density_map, ustar_map, nearest_units, rank_hits and smoothed_hits raise
                          NotImplementedError; the initialisers refuse data with a NaN
+          missing_search with missing='nan': the kernel that searches the BMUs -- 'f32' (the default: the float32 masked kernel),
+                         'bf16' or 'f16': the masked distance on the 16-bit matrix pipe, BMUs within the operand rounding of
+                         float32's as 'bf16' / 'f16' are without missing values (three 16-bit MFMAs per step; rows holding
+                         +-inf are outside its contract).  Only the pick changes: update, merge, quantization_error and every
+                         reported distance stay float32, and ``precision`` stays 'exact' or 'f32'.  Anything else, or a value
+                         other than 'f32' without missing='nan', is a ValueError
         """
         if sigma >= x or sigma >= y:
             warn('Warning: sigma is too high for the dimension of the map.')
@@ -511,7 +517,9 @@ class XPySom:
                 raise ValueError("missing='nan' is defined for activation_distance='euclidean' only, got '%s'" % activation_distance)
             if precision not in ('f32', 'exact'):
                 raise ValueError("missing='nan' runs the float32 masked kernel: precision 'exact' or 'f32', not '%s'" % precision)
+        from ._lib import check_missing_search
         self._missing = missing
+        self._missing_search = check_missing_search(missing, missing_search)
         self._precision = precision
         self._device = device
         self._sharded_input = sharded_input
@@ -530,6 +538,8 @@ class XPySom:
                       precision=self._precision, topology=self.topology)
             if getattr(self, '_missing', None) is not None:
                 kw['missing'] = self._missing
+                if getattr(self, '_missing_search', 'f32') != 'f32':
+                    kw['missing_search'] = self._missing_search
             if self._activation_distance_name.startswith('norm_p'):
                 p = self._activation_distance_kwargs.get('p', 2)
                 if isinstance(p, (float, np.floating)) and not float(p).is_integer():
@@ -1577,4 +1587,5 @@ class XPySom:
     def __setstate__(self, state):
         self.__dict__.update(state)
         self.__dict__.setdefault('_missing', None)        # (a pickle from before the keyword)
+        self.__dict__.setdefault('_missing_search', 'f32')
         self.__dict__.setdefault('history', [])
