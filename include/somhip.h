@@ -36,7 +36,8 @@ enum { SOM_DIST_EUCLIDEAN = 0,        /* 'euclidean'  -> euclidean_squared_dista
        SOM_DIST_COSINE = 2,           /* 'cosine'     -> cosine_distance, distances.py:45-59 */
        SOM_DIST_MANHATTAN = 3,        /* 'manhattan', 'manhattan_no_opt' -> distances.py:109-158 (incl. the `l1norm` CUDA kernel) */
        SOM_DIST_NORM_P = 4,           /* 'norm_p' -> norm_p_power_distance, distances.py:98-107 (even p: binomial form :77-96) */
-       SOM_DIST_NORM_P_NO_OPT = 5 };  /* 'norm_p_no_opt' -> norm_p_power_distance_generic, distances.py:61-75 */
+       SOM_DIST_NORM_P_NO_OPT = 5,    /* 'norm_p_no_opt' -> norm_p_power_distance_generic, distances.py:61-75 */
+       SOM_DIST_CHEBYSHEV = 6 };      /* 'chebyshev' (MiniSom's; not in the reference): max_d |x_d - w_d|, csrc/bmu_chebyshev.hpp */
 
 /* neighbourhood function on the rectangular topology: neighborhoods.py:14-33, :57-74, :99-130 */
 enum { SOM_NEIGH_GAUSSIAN = 0, SOM_NEIGH_MEXICAN_HAT = 1, SOM_NEIGH_BUBBLE = 2, SOM_NEIGH_TRIANGLE = 3 };

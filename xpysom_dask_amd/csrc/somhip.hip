@@ -44,6 +44,7 @@
 #include "density.hpp"
 #include "topk.hpp"
 #include "sparse.hpp"
+#include "bmu_chebyshev.hpp"
 
 using namespace somhip;
 
@@ -455,6 +456,7 @@ struct som_handle {
     // read once in som_create (experiments / A-B runs): forced part counts, launch-geometry printing
     int env_bf16_parts = 0;
     int env_f32_parts = 0;   // SOM_F32_PARTS: the float32 resident kernel's part count (clamped to [1, fr_stages])
+    int env_chebyshev_parts = 0;   // SOM_CHEBYSHEV_PARTS: the chebyshev kernel's part count (clamped to [1, unit blocks])
     bool debug = false;
     // per kernel function: the dynamic-LDS attribute is set and the occupancy queried once, not per launch
     struct KernelSlots { const void* fn; size_t lds; int per_cu; };
@@ -1222,6 +1224,37 @@ int launch_bmu_pairwise(som_handle* h, const float* X, long N, int p, bool even,
     return 0;
 }
 
+// 'chebyshev' (bmu_chebyshev.hpp): 128-row blocks x `parts` ranges of the 128-unit blocks; one part writes the ids itself,
+// several merge through best64.  The rows and the codebook are read as they are: no operand image, no cap on input_len.
+int launch_bmu_chebyshev(som_handle* h, const float* X, long N, int* out) {
+    const bool res = h->D <= CH_RES_D;
+    const void* fn = res ? (const void*)bmu_chebyshev_kernel<true> : (const void*)bmu_chebyshev_kernel<false>;
+    const size_t lds = ch_lds_bytes(h->D);
+    int per_cu = 1;
+    if (int rc = kernel_per_cu(h, fn, 256, lds, &per_cu)) return rc;
+    const long blocks = cdiv(N, CH_BM);
+    if (blocks <= 0 || blocks > 0x7fffffffL) return fail(h, "bmu_chebyshev: row count out of range");
+    const int n_ub = (int)cdiv(h->K, CH_BN);
+    int parts = choose_parts(h, blocks, resident_slots(h, per_cu), n_ub);
+    if (h->env_chebyshev_parts > 0) parts = h->env_chebyshev_parts;   // (tests: the single-part and the merged paths at any size)
+    parts = std::max(1, std::min(parts, std::min(n_ub, 65535)));
+    if (h->debug) std::fprintf(stderr, "[somhip] bmu_chebyshev: blocks=%ld per_cu=%d parts=%d unit_blocks=%d res=%d\n", blocks, per_cu, parts, n_ub, (int)res);
+    // 16-byte reads along the feature axis where every row starts on a 16-byte boundary
+    const int x_vec = h->D % 4 == 0 && (uintptr_t)X % 16 == 0, w_vec = h->D % 4 == 0 && (uintptr_t)(const float*)h->W % 16 == 0;
+    unsigned long long* out64 = nullptr;
+    if (parts > 1) {
+        if (int rc = h->best64.reserve(h, (size_t)N, 1024)) return rc;
+        out64 = h->best64;
+        ch_fill_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(out64, N);
+    }
+    const dim3 grid((unsigned)blocks, (unsigned)parts);
+    if (res) bmu_chebyshev_kernel<true><<<grid, dim3(256), lds, h->stream>>>(X, N, h->D, h->W, h->K, x_vec, w_vec, out, out64);
+    else bmu_chebyshev_kernel<false><<<grid, dim3(256), lds, h->stream>>>(X, N, h->D, h->W, h->K, x_vec, w_vec, out, out64);
+    if (parts > 1) bmu_finalize_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(out64, N, h->K, out);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 // ---- the sort by unit (unit_sort.hpp: the rule; update.hpp: the kernels) ----------------------------------------------------
 // The stable radix sort of update.hpp: (keys_in, row index) -> (keys_out, vals_out), `bits` key bits, 8 a pass.  scratch: two
 // pairs of n ints + the 256 x blocks table (radix_scratch_ints).  keys_in is left intact.
@@ -1356,6 +1389,7 @@ int run_activation_bmu_launch(som_handle* h, const Rows& r) {
     case SOM_DIST_MANHATTAN: return launch_bmu_pairwise(h, r.X, r.N, 1, false, r.out);
     case SOM_DIST_NORM_P_NO_OPT: return launch_bmu_pairwise(h, r.X, r.N, h->norm_p, false, r.out);
     case SOM_DIST_NORM_P: return launch_bmu_pairwise(h, r.X, r.N, h->norm_p, h->norm_p % 2 == 0, r.out);
+    case SOM_DIST_CHEBYSHEV: return launch_bmu_chebyshev(h, r.X, r.N, r.out);
     }
     return fail(h, "unknown distance id");
 }
@@ -1862,7 +1896,7 @@ int som_create(const som_config* cfg, som_handle** out) {
     if (!cfg) return fail(nullptr, "som_create: cfg is NULL");
     if (cfg->x < 1 || cfg->y < 1 || cfg->input_len < 1) return fail(nullptr, "som_create: x, y, input_len must be >= 1");
     if ((long)cfg->x * cfg->y > (1L << 30)) return fail(nullptr, "som_create: map too large");
-    if (cfg->distance < 0 || cfg->distance > SOM_DIST_NORM_P_NO_OPT) return fail(nullptr, "som_create: unknown distance id");
+    if (cfg->distance < 0 || cfg->distance > SOM_DIST_CHEBYSHEV) return fail(nullptr, "som_create: unknown distance id");
     if (cfg->norm_p < 0 || cfg->norm_p > PW_MAX_P) return fail(nullptr, "som_create: norm_p out of range (1..16)");
     if (cfg->norm_p_real != 0.0 && !(cfg->norm_p_real > 0.0 && cfg->norm_p_real <= 64.0))
         return fail(nullptr, "som_create: norm_p_real out of range (0 < p <= 64)");
@@ -2018,6 +2052,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         if (const char* e = dev_env("SOM_BF16_PARTS")) h->env_bf16_parts = std::atoi(e);
         if (const char* e = dev_env("SOM_MASKED_PARTS")) h->env_masked_parts = std::atoi(e);
         if (const char* e = dev_env("SOM_F32_PARTS")) h->env_f32_parts = std::atoi(e);
+        if (const char* e = dev_env("SOM_CHEBYSHEV_PARTS")) h->env_chebyshev_parts = std::atoi(e);
         h->debug = std::getenv("SOM_DEBUG") != nullptr;
         if (const char* e = std::getenv("SOM_VERIFY")) h->verify_rows = std::max(0, std::atoi(e));
         if (h->masked) h->verify_rows = 0;               // (the canary re-scores with the unmasked float32 kernel: not on these rows)

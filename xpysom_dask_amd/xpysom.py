@@ -22,7 +22,7 @@ TOPOLOGIES = ("hexagonal", "rectangular", "toroidal")
 NEIGHBORHOODS = {"gaussian": True, "mexican_hat": True, "bubble": True, "triangle": True}
 # distances.py:162-170 registry; False = valid reference name the engine does not cover yet
 DISTANCES = {"euclidean": True, "euclidean_no_opt": True, "manhattan": True, "manhattan_no_opt": True,
-             "cosine": True, "norm_p": True, "norm_p_no_opt": True}
+             "cosine": True, "norm_p": True, "norm_p_no_opt": True, "chebyshev": True}
 DEFAULT_BATCH_ROWS = 65536
 
 
