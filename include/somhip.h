@@ -34,7 +34,9 @@ typedef struct som_handle som_handle;
 enum { SOM_DIST_EUCLIDEAN = 0,        /* 'euclidean'  -> euclidean_squared_distance_part, distances.py:11-23 */
        SOM_DIST_EUCLIDEAN_NO_OPT = 1, /* 'euclidean_no_opt' -> euclidean_squared_distance, distances.py:25-31 */
        SOM_DIST_COSINE = 2,           /* 'cosine'     -> cosine_distance, distances.py:45-59 */
-       SOM_DIST_MANHATTAN = 3,        /* 'manhattan', 'manhattan_no_opt' -> distances.py:109-158 (incl. the `l1norm` CUDA kernel) */
+       SOM_DIST_MANHATTAN = 3,        /* 'manhattan', 'manhattan_no_opt' -> distances.py:109-158 (incl. the `l1norm` CUDA kernel);
+                                         csrc/bmu_manhattan.hpp, NumPy's pairwise summation order: input_len <= 4096 (beyond:
+                                         csrc/bmu_pairwise.hpp, which refuses input_len > 2400) */
        SOM_DIST_NORM_P = 4,           /* 'norm_p' -> norm_p_power_distance, distances.py:98-107 (even p: binomial form :77-96) */
        SOM_DIST_NORM_P_NO_OPT = 5,    /* 'norm_p_no_opt' -> norm_p_power_distance_generic, distances.py:61-75 */
        SOM_DIST_CHEBYSHEV = 6 };      /* 'chebyshev' (MiniSom's; not in the reference): max_d |x_d - w_d|, csrc/bmu_chebyshev.hpp */

@@ -45,6 +45,7 @@
 #include "topk.hpp"
 #include "sparse.hpp"
 #include "bmu_chebyshev.hpp"
+#include "bmu_manhattan.hpp"
 
 using namespace somhip;
 
@@ -457,6 +458,10 @@ struct som_handle {
     int env_bf16_parts = 0;
     int env_f32_parts = 0;   // SOM_F32_PARTS: the float32 resident kernel's part count (clamped to [1, fr_stages])
     int env_chebyshev_parts = 0;   // SOM_CHEBYSHEV_PARTS: the chebyshev kernel's part count (clamped to [1, unit blocks])
+    int env_manhattan_parts = 0;   // SOM_MANHATTAN_PARTS: the tiled manhattan kernel's part count (clamped to [1, unit blocks])
+    // 'manhattan' on the tiled kernel (bmu_manhattan.hpp): its feature schedule, built once for the handle's input_len
+    // (chunks == 0: bmu_pairwise_kernel serves the distance -- SOM_MANHATTAN_TILED=0, or an input_len the tile does not take)
+    struct Manhattan { DevBuf<MnChunk> sched; int chunks = 0, lines = 0, depth = 0; } mn;
     bool debug = false;
     // per kernel function: the dynamic-LDS attribute is set and the occupancy queried once, not per launch
     struct KernelSlots { const void* fn; size_t lds; int per_cu; };
@@ -1255,6 +1260,39 @@ int launch_bmu_chebyshev(som_handle* h, const float* X, long N, int* out) {
     return 0;
 }
 
+// 'manhattan' (bmu_manhattan.hpp): blocks of 128 rows (input_len <= 128; 64 rows beyond) x `parts` ranges of the 64-unit blocks, as launch_bmu_chebyshev; the feature
+// schedule is the handle's (som_create).  Without one the distance stays on bmu_pairwise_kernel, which refuses long rows by name.
+int launch_bmu_manhattan(som_handle* h, const float* X, long N, int* out) {
+    if (h->mn.chunks == 0) return launch_bmu_pairwise(h, X, N, 1, false, out);
+    const bool res = h->D <= MN_RES_D;
+    const void* fn = res ? (const void*)bmu_manhattan_kernel<true, 0, MN_RT_RES> : (const void*)bmu_manhattan_kernel<false, MN_STACK, MN_RT_DEEP>;
+    const size_t lds = mn_lds_bytes(h->D, h->mn.lines);
+    int per_cu = 1;
+    if (int rc = kernel_per_cu(h, fn, 256, lds, &per_cu)) return rc;
+    const long blocks = cdiv(N, mn_bm(res ? MN_RT_RES : MN_RT_DEEP));
+    if (blocks <= 0 || blocks > 0x7fffffffL) return fail(h, "bmu_manhattan: row count out of range");
+    const int n_ub = (int)cdiv(h->K, MN_BN);
+    int parts = choose_parts(h, blocks, resident_slots(h, per_cu), n_ub);
+    if (h->env_manhattan_parts > 0) parts = h->env_manhattan_parts;   // (tests: the single-part and the merged paths at any size)
+    parts = std::max(1, std::min(parts, std::min(n_ub, 65535)));
+    if (h->debug) std::fprintf(stderr, "[somhip] bmu_manhattan: blocks=%ld per_cu=%d parts=%d unit_blocks=%d chunks=%d lines=%d depth=%d res=%d\n", blocks, per_cu, parts, n_ub,
+                               h->mn.chunks, h->mn.lines, h->mn.depth, (int)res);
+    // 16-byte reads along the feature axis where every row starts on a 16-byte boundary
+    const int x_vec = h->D % 4 == 0 && (uintptr_t)X % 16 == 0, w_vec = h->D % 4 == 0 && (uintptr_t)(const float*)h->W % 16 == 0;
+    unsigned long long* out64 = nullptr;
+    if (parts > 1) {
+        if (int rc = h->best64.reserve(h, (size_t)N, 1024)) return rc;
+        out64 = h->best64;
+        ch_fill_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(out64, N);
+    }
+    const dim3 grid((unsigned)blocks, (unsigned)parts);
+    if (res) bmu_manhattan_kernel<true, 0, MN_RT_RES><<<grid, dim3(256), lds, h->stream>>>(X, N, h->D, h->W, h->K, h->mn.sched, h->mn.chunks, h->mn.lines, x_vec, w_vec, out, out64);
+    else bmu_manhattan_kernel<false, MN_STACK, MN_RT_DEEP><<<grid, dim3(256), lds, h->stream>>>(X, N, h->D, h->W, h->K, h->mn.sched, h->mn.chunks, h->mn.lines, x_vec, w_vec, out, out64);
+    if (parts > 1) bmu_finalize_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(out64, N, h->K, out);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
 // ---- the sort by unit (unit_sort.hpp: the rule; update.hpp: the kernels) ----------------------------------------------------
 // The stable radix sort of update.hpp: (keys_in, row index) -> (keys_out, vals_out), `bits` key bits, 8 a pass.  scratch: two
 // pairs of n ints + the 256 x blocks table (radix_scratch_ints).  keys_in is left intact.
@@ -1386,7 +1424,7 @@ int run_activation_bmu_launch(som_handle* h, const Rows& r) {
     case SOM_DIST_EUCLIDEAN: return launch_bmu_f32_any<SCORE_EUCLID_PART>(h, r.X, r.N, r.xsq, r.out);
     case SOM_DIST_EUCLIDEAN_NO_OPT: return launch_bmu_f32_any<SCORE_EUCLID_SQ>(h, r.X, r.N, r.xsq, r.out);
     case SOM_DIST_COSINE: return launch_bmu_f32_any<SCORE_COSINE>(h, r.X, r.N, r.xsq, r.out);
-    case SOM_DIST_MANHATTAN: return launch_bmu_pairwise(h, r.X, r.N, 1, false, r.out);
+    case SOM_DIST_MANHATTAN: return launch_bmu_manhattan(h, r.X, r.N, r.out);
     case SOM_DIST_NORM_P_NO_OPT: return launch_bmu_pairwise(h, r.X, r.N, h->norm_p, false, r.out);
     case SOM_DIST_NORM_P: return launch_bmu_pairwise(h, r.X, r.N, h->norm_p, h->norm_p % 2 == 0, r.out);
     case SOM_DIST_CHEBYSHEV: return launch_bmu_chebyshev(h, r.X, r.N, r.out);
@@ -2053,6 +2091,17 @@ int som_create(const som_config* cfg, som_handle** out) {
         if (const char* e = dev_env("SOM_MASKED_PARTS")) h->env_masked_parts = std::atoi(e);
         if (const char* e = dev_env("SOM_F32_PARTS")) h->env_f32_parts = std::atoi(e);
         if (const char* e = dev_env("SOM_CHEBYSHEV_PARTS")) h->env_chebyshev_parts = std::atoi(e);
+        if (const char* e = dev_env("SOM_MANHATTAN_PARTS")) h->env_manhattan_parts = std::atoi(e);
+        bool mn_tiled = h->cfg.distance == SOM_DIST_MANHATTAN && h->D <= MN_MAX_D;
+        if (const char* e = dev_env("SOM_MANHATTAN_TILED")) mn_tiled = mn_tiled && std::atoi(e) != 0;   // A/B: bmu_pairwise_kernel
+        if (mn_tiled) {
+            const std::vector<MnChunk> sched = mn_schedule(h->D, &h->mn.lines, &h->mn.depth);
+            if (h->mn.depth > MN_STACK) return bail(fail(h, "som_create: the manhattan schedule is deeper than the kernel's stack"));
+            if ((rc = h->mn.sched.alloc(h, sched.size()))) return bail(rc);
+            if (hipMemcpy(h->mn.sched, sched.data(), sched.size() * sizeof(MnChunk), hipMemcpyHostToDevice) != hipSuccess)
+                return bail(fail(h, "hipMemcpy of the manhattan schedule failed"));
+            h->mn.chunks = (int)sched.size();
+        }
         h->debug = std::getenv("SOM_DEBUG") != nullptr;
         if (const char* e = std::getenv("SOM_VERIFY")) h->verify_rows = std::max(0, std::atoi(e));
         if (h->masked) h->verify_rows = 0;               // (the canary re-scores with the unmasked float32 kernel: not on these rows)

@@ -400,6 +400,10 @@ class XPySom:
                          mode the default is checked against), 'bf16' (bf16 MFMA distance GEMM: BMUs within the operand
                          rounding of float32's), or the same path on IEEE half operands, 'f16' (three more mantissa bits
                          at the same MFMA rate; rows and units must fit float16: norms <= 65504)
+          (activation_distance: 'manhattan' / 'manhattan_no_opt' sum float32 terms in NumPy's pairwise order, bit for bit,
+                         on a register-tiled kernel for input_len <= 4096; longer rows are refused.  'norm_p' and
+                         'norm_p_no_opt' run one thread a row and are refused beyond input_len 2400.  'chebyshev', 'euclidean'
+                         and 'cosine' take any input_len)
           device         HIP device ordinal (default: LOCAL_RANK or 0)
           sharded_input  under an initialised process group: ``train(data)`` receives only this
                          rank's rows (default: every rank passes the full array and takes its slice)
