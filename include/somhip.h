@@ -420,6 +420,33 @@ int som_bmu_topk_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_
 int som_unit_rank_counts(som_handle* h, const float* x_host, int64_t n_rows, int32_t k, int64_t* counts);
 int som_unit_rank_counts_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t k, int64_t* counts);
 
+/* The k nearest ROWS of every unit (not in the reference; csrc/exemplar.hpp): the exemplar or medoid question -- the real item to draw
+ * in each cell of an image or document map, the nearest labelled sample of a unit, a representative for a unit no row hits.  It
+ * does not follow from BMU ids: the nearest row of a unit need not be won by that unit.  The float32 MFMA scan of som_bmu_topk reduced
+ * the other way round; the (n_rows, K) score matrix is never written.  ONE definition:
+ *   s_un = the float32 activation score of unit u and row n as som_distance_matrix (XPySom.activate) forms it in SOM_BMU_ACTIVATION
+ *   mode on an euclidean_no_opt or cosine handle -- euclidean_no_opt: fmaf(-2, x.w, |w|^2) + |x|^2; cosine: 1 - nan_to_num(x.w /
+ *   sqrt(|x|^2 |w|^2)) -- with x.w the k-ordered float32 fma chain of v_mfma_f32_32x32x2_f32 starting from 0 and the norms in NumPy's
+ *   pairwise order: bit for bit those entries (the MFMA's products commute).  An euclidean handle uses the euclidean_no_opt score:
+ *   its own score drops |x|^2, which is harmless when ranking the units of one row and wrong when ranking the rows of one unit.
+ *   The list of unit u: the k rows with the smallest s_un, ascending; equal scores (-0.0 == +0.0) go to the lower row id first -- a
+ *   stable sort by (score, row id).  A score enters only if it is < +inf: NaN and +inf never do (-inf does), so a row that holds a
+ *   NaN or an infinity is listed nowhere under the Euclidean scores.  A slot that cannot be filled (k > n_rows, rows that never
+ *   enter) holds id -1, score NaN, distance NaN.
+ *   ids_out[u][j], score_out[u][j], dist_out[u][j]: host arrays, row-major (K = x * y, k); ids index the call's rows; score_out and
+ *   dist_out may be NULL.  dist[u][j] = sqrt(sum_d (x_d - W[u][d])^2), the differences formed directly, in som_bmu_distances'
+ *   arithmetic -- always Euclidean and NOT what orders the list.  Skipped when dist_out is NULL.
+ * 1 <= k <= SOM_TOPK_MAX.  Refused, with a message that names the call: a NULL ids_out / rows pointer, n_rows < 0 or > 2^31-1, k
+ * outside 1 .. SOM_TOPK_MAX, a handle created with SOM_MISSING_NAN, a distance other than euclidean, euclidean_no_opt, cosine,
+ * input_len >= 2^24.  n_rows == 0 writes -1 / NaN.
+ * The rows are swept in parts where the map alone would not fill the chip, the parts' lists merged by (score, id): the result is
+ * identical for every part count.  Host rows are uploaded in passes of 1 048 576, the running lists joining the next pass's merge
+ * as one more part, so the result does not depend on the pass size; device rows are swept where they are.  A query: resident rows,
+ * their ids, the weights, the monitor's state and the exact mode's plans stay as they were.  Scratch is the handle's, grown on
+ * demand, freed by som_destroy.  The *_device form reads rows that already live in HBM (see som_bmu_device: borrowed for the call). */
+int som_unit_nearest_rows(som_handle* h, const float* x_host, int64_t n_rows, int32_t k, int32_t* ids_out, float* score_out, float* dist_out);
+int som_unit_nearest_rows_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t k, int32_t* ids_out, float* score_out, float* dist_out);
+
 /* Sparse rows (not in the reference; csrc/sparse.hpp): rows in CSR -- indptr int64 [n_rows + 1] from 0, indices int32 [nnz] with the
  * columns of a row strictly ascending (canonical: sorted, no duplicates), values float32 [nnz]; host arrays, the caller's.  The
  * rows mean exactly what their dense float32 form means (an explicitly stored zero is an entry like any other) and are never made

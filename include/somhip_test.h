@@ -283,6 +283,17 @@ int som_debug_density_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t for
  *   Returns non-zero for a NULL out4, n_rows < 1 or > 2^31-1, K < 1, slots < 1 or forced_parts < 0. */
 int som_debug_topk_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t forced_parts, int64_t* out4);
 
+/* The NEAREST-ROWS scan's launch geometry (csrc/exemplar.hpp, exemplar_plan) for a pass of n_rows rows on a map of K units -- pure host
+ * arithmetic, NO device needed.  slots: workgroups of the scan the chip holds at once; forced_parts > 0: the part count
+ * SOM_EXEMPLAR_PARTS asks for (read only under SOM_TEST_HOOKS=1, as is SOM_EXEMPLAR_PASS_ROWS, the host rows per pass), 0: none.  A
+ * workgroup owns one tile of 128 units and one part of the rows' 128-row stages:
+ *   unit tiles = ceil(K / 128), stages = ceil(n_rows / 128),
+ *   parts asked for = clamp(forced_parts or ceil(slots / unit tiles), 1, min(stages, 65535)), stages per part = ceil(stages / parts
+ *   asked for), parts = ceil(stages / stages per part) -- the parts that hold a stage; the grid is unit tiles x parts.
+ *   out4 = {unit tiles, stages, parts, stages per part}
+ *   Returns non-zero for a NULL out4, n_rows < 1 or > 2^31-1, K < 1, slots < 1 or forced_parts < 0. */
+int som_debug_exemplar_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t forced_parts, int64_t* out4);
+
 /* The per-unit SEGMENT SUMS the last accumulate left on the device, in front of the neighbourhood transform (dense rows: the run sum
  * of csrc/update.hpp; sparse rows: sparse_segsum_kernel, csrc/sparse.hpp): S_out [K][input_len] = the sum of the rows every unit won,
  * count_out [K] = how many.  Fails where the count column and the dense counts behind the sums differ, and on a handle created with

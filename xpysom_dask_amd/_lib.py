@@ -112,6 +112,9 @@ SIGNATURES = {
     "som_unit_rank_counts": (C.c_int, [_H, _F, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "som_unit_rank_counts_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "som_debug_topk_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    "som_unit_nearest_rows": (C.c_int, [_H, _F, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _F, _F]),
+    "som_unit_nearest_rows_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _F, _F]),
+    "som_debug_exemplar_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
     "som_set_data_csr": (C.c_int, [_H, C.POINTER(C.c_int64), _I, _F, C.c_int64]),
     "som_bmu_csr": (C.c_int, [_H, C.POINTER(C.c_int64), _I, _F, C.c_int64, C.c_int32, _I]),
     "som_quantization_error_csr": (C.c_int, [_H, C.POINTER(C.c_int64), _I, _F, C.c_int64, C.POINTER(C.c_double)]),

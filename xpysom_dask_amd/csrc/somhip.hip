@@ -43,6 +43,7 @@
 #include "moments.hpp"
 #include "density.hpp"
 #include "topk.hpp"
+#include "exemplar.hpp"
 #include "sparse.hpp"
 #include "bmu_chebyshev.hpp"
 #include "bmu_manhattan.hpp"
@@ -505,6 +506,13 @@ struct som_handle {
         DevBuf<float> score, dist, part_sc;
         DevBuf<unsigned long long> counts;
     } topk;
+    // the k nearest rows of every unit (exemplar.hpp; som_unit_nearest_rows*): the one owner of its scratch, grown on demand and freed
+    // with the handle.  Size rule, for a pass cut into `parts` row parts: the partial lists part_sc / part_id parts * K * TOPK_MAX each,
+    // the running lists run_sc / run_id / run_dist K * TOPK_MAX each.
+    struct ExemplarScratch {
+        DevBuf<int> part_id, run_id;
+        DevBuf<float> part_sc, run_sc, run_dist;
+    } exm;
     // sparse rows (sparse.hpp): the resident set, the query set, and the kernels' scratch, grown on demand and freed with the handle --
     // WT D * round_up(K, 64) floats (the transposed codebook), part_sc / part_id parts * N (the parts' minima), ustart K + 1 (the
     // sorted rows' first position per unit), dist N (the rows' distances to their units)
@@ -1758,6 +1766,34 @@ int launch_topk(som_handle* h, const float* X, long N, const float* xsq, int k, 
 template <int MODE>
 int launch_topk_mode(som_handle* h, const float* X, long N, const float* xsq, int k, int forced_parts, bool want_score) {
     return k <= 4 ? launch_topk<MODE, 4>(h, X, N, xsq, k, forced_parts, want_score) : launch_topk<MODE, 8>(h, X, N, xsq, k, forced_parts, want_score);
+}
+
+// the k nearest rows of every unit (exemplar.hpp) over the pass's rows X[N][D], listed as id0 + their index (xsq: their |x|^2): the scan
+// over `parts` row parts into the partial lists, the merge with the running lists of the passes before (have_run), the distances of
+// the slots this pass filled.  Its geometry from the kernel's resident slots.
+template <int MODE, int KK>
+int launch_exemplars(som_handle* h, const float* X, long N, const float* xsq, int id0, int k, int forced_parts, bool have_run, bool want_dist) {
+    auto& g = h->exm;
+    int per_cu = 1;
+    if (int rc = kernel_per_cu(h, (const void*)unit_nearest_rows_f32_kernel<MODE, KK>, 256, EX_LDS_BYTES, &per_cu)) return rc;
+    const ExemplarPlan p = exemplar_plan(N, h->K, resident_slots(h, per_cu), forced_parts);
+    if (int rc = g.part_sc.reserve(h, (size_t)p.parts * h->K * TOPK_MAX)) return rc;
+    if (int rc = g.part_id.reserve(h, (size_t)p.parts * h->K * TOPK_MAX)) return rc;
+    unit_nearest_rows_f32_kernel<MODE, KK><<<dim3((unsigned)p.unit_tiles, (unsigned)p.parts), dim3(256), EX_LDS_BYTES, h->stream>>>(
+        X, N, h->D, (int)round_up(h->D, F32_KC), h->W, h->wsq, h->K, xsq, id0, (int)p.stages, (int)p.per, g.part_sc, g.part_id);
+    exemplar_merge_kernel<KK><<<dim3((unsigned)cdiv(h->K, 256)), dim3(256), 0, h->stream>>>(g.part_sc, g.part_id, h->K, (int)p.parts, have_run ? 1 : 0,
+                                                                                            g.run_sc, g.run_id, g.run_dist);
+    if (want_dist)
+        exemplar_dist_kernel<KK><<<dim3((unsigned)std::min<long>(cdiv((long)h->K * k, 4), 4096)), dim3(256), 0, h->stream>>>(X, N, id0, g.run_id, h->W, h->K, k,
+                                                                                                                        h->D, g.run_dist);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+template <int KK>
+int launch_exemplars_mode(som_handle* h, const float* X, long N, const float* xsq, int id0, int k, int forced_parts, bool have_run, bool want_dist) {
+    // (euclidean too: the PART form drops |x|^2, which ranks the units of one row and not the rows of one unit)
+    return h->cfg.distance == SOM_DIST_COSINE ? launch_exemplars<SCORE_COSINE, KK>(h, X, N, xsq, id0, k, forced_parts, have_run, want_dist)
+                                              : launch_exemplars<SCORE_EUCLID_SQ, KK>(h, X, N, xsq, id0, k, forced_parts, have_run, want_dist);
 }
 
 // ---- sparse rows (sparse.hpp; som_set_data_csr, som_bmu_csr, som_quantization_error_csr) -------------------------------------
@@ -3336,6 +3372,55 @@ int query_rank_counts(som_handle* h, const std::string& who, const float* x_host
     return d2h_blocking(h, counts, g.counts, kK * sizeof(int64_t));
 }
 
+// ---- the k nearest rows of every unit (exemplar.hpp): per-unit lists of row ids with scores and distances ----
+int query_exemplars(som_handle* h, const std::string& who, const float* x_host, const void* x_dev, int64_t n_rows, int32_t k, int32_t* ids_out,
+                    float* score_out, float* dist_out) {
+    DeviceGuard dev_guard(h);
+    if (!h || !ids_out || n_rows < 0 || (n_rows > 0 && !x_host && !x_dev)) return fail(h, who + ": bad argument");
+    if (k < 1 || k > TOPK_MAX) return fail(h, who + ": k must be between 1 and SOM_TOPK_MAX = " + std::to_string(TOPK_MAX));
+    if (h->masked) return fail(h, who + ": the nearest rows of a unit are not defined on a handle created with SOM_MISSING_NAN");
+    if (h->cfg.distance > SOM_DIST_COSINE) return fail(h, who + ": only the GEMM-form distances (euclidean, euclidean_no_opt, cosine)");
+    if (n_rows > 0x7fffffffL) return fail(h, who + ": more than 2^31-1 rows in one call");
+    // (the scan forms its staging offsets, a row of a tile times input_len, with a 24-bit multiply: exemplar.hpp)
+    if (h->D >= (1 << 24)) return fail(h, who + ": input_len must be below 2^24");
+    const size_t K = (size_t)h->K;
+    const int KK = k <= 4 ? 4 : 8;
+    std::vector<int> id(K * KK, -1);
+    std::vector<float> sc(score_out ? K * KK : 0), ds(dist_out ? K * KK : 0);
+    if (n_rows > 0) {
+        if (int rc = refresh_codebook_operands(h, operands::Request::F32Units)) return rc;
+        auto& g = h->exm;
+        if (int rc = g.run_sc.reserve(h, K * TOPK_MAX)) return rc;
+        if (int rc = g.run_id.reserve(h, K * TOPK_MAX)) return rc;
+        if (int rc = g.run_dist.reserve(h, K * TOPK_MAX)) return rc;
+        int forced = 0;
+        long pass = x_host ? EX_PASS_ROWS : (long)n_rows;       // device rows are swept where they are; host rows staged in bounded passes
+        if (const char* e = dev_env("SOM_EXEMPLAR_PARTS")) forced = std::max(0, std::atoi(e));
+        if (const char* e = dev_env("SOM_EXEMPLAR_PASS_ROWS")) if (x_host && std::atol(e) > 0) pass = std::atol(e);
+        for (long r0 = 0; r0 < n_rows; r0 += pass) {
+            const long P = std::min<long>(pass, n_rows - r0);
+            if (int rc = query_rows(h, x_host ? x_host + (size_t)r0 * h->D : nullptr, x_dev, P)) return rc;
+            if (int rc = row_sq(h, h->q.X, P, h->q.xsq)) return rc;
+            Timed t(h, SOM_K_BMU);
+            const int rc = KK == 4 ? launch_exemplars_mode<4>(h, h->q.X, P, h->q.xsq, (int)r0, k, forced, r0 > 0, dist_out != nullptr)
+                                   : launch_exemplars_mode<8>(h, h->q.X, P, h->q.xsq, (int)r0, k, forced, r0 > 0, dist_out != nullptr);
+            if (rc) return rc;
+        }
+        if (int rc = d2h_blocking(h, id.data(), g.run_id, K * KK * sizeof(int))) return rc;
+        if (score_out) if (int rc = d2h_blocking(h, sc.data(), g.run_sc, K * KK * sizeof(float))) return rc;
+        if (dist_out) if (int rc = d2h_blocking(h, ds.data(), g.run_dist, K * KK * sizeof(float))) return rc;
+    }
+    // the first k of the KK slots, row-major (K, k); a slot nothing filled: -1 / NaN / NaN
+    for (size_t u = 0; u < K; ++u)
+        for (int j = 0; j < k; ++j) {
+            const int r = id[u * KK + j];
+            ids_out[u * k + j] = r;
+            if (score_out) score_out[u * k + j] = r < 0 ? NAN : sc[u * KK + j];
+            if (dist_out) dist_out[u * k + j] = r < 0 ? NAN : ds[u * KK + j];
+        }
+    return 0;
+}
+
 // ---- missing values: the completed rows (impute.hpp) ----
 // out[n][d] = X[n][d] where observed, W[ids[n]][d] where NaN, on the handle's stream; out == X fills in place.  16 bytes a lane
 // where input_len and the three addresses as they ARE allow it (a caller's view may start at any float), else a float a lane.
@@ -3445,6 +3530,8 @@ int som_bmu_topk(som_handle* h, const float* x_host, int64_t n_rows, int32_t k, 
 int som_bmu_topk_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t k, int32_t* ids_out, float* score_out, float* dist_out) { return query_topk(h, "som_bmu_topk_device", nullptr, x_dev, n_rows, k, ids_out, score_out, dist_out); }
 int som_unit_rank_counts(som_handle* h, const float* x_host, int64_t n_rows, int32_t k, int64_t* counts) { return query_rank_counts(h, "som_unit_rank_counts", x_host, nullptr, n_rows, k, counts); }
 int som_unit_rank_counts_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t k, int64_t* counts) { return query_rank_counts(h, "som_unit_rank_counts_device", nullptr, x_dev, n_rows, k, counts); }
+int som_unit_nearest_rows(som_handle* h, const float* x_host, int64_t n_rows, int32_t k, int32_t* ids_out, float* score_out, float* dist_out) { return query_exemplars(h, "som_unit_nearest_rows", x_host, nullptr, n_rows, k, ids_out, score_out, dist_out); }
+int som_unit_nearest_rows_device(som_handle* h, const void* x_dev, int64_t n_rows, int32_t k, int32_t* ids_out, float* score_out, float* dist_out) { return query_exemplars(h, "som_unit_nearest_rows_device", nullptr, x_dev, n_rows, k, ids_out, score_out, dist_out); }
 
 // ---- row moments and the row gather (moments.hpp): queries that touch nothing of the engine's row sets, weights, ids or plans ----
 namespace {
@@ -3547,6 +3634,13 @@ int som_debug_topk_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t forced
     if (!out4 || n_rows < 1 || n_rows > 0x7fffffffL || K < 1 || slots < 1 || forced_parts < 0) return 1;
     const TopkPlan p = topk_plan(n_rows, K, slots, forced_parts);
     out4[0] = p.row_tiles; out4[1] = p.stages; out4[2] = p.parts; out4[3] = p.per;
+    return 0;
+}
+
+int som_debug_exemplar_plan(int64_t n_rows, int32_t K, int64_t slots, int32_t forced_parts, int64_t* out4) {
+    if (!out4 || n_rows < 1 || n_rows > 0x7fffffffL || K < 1 || slots < 1 || forced_parts < 0) return 1;
+    const ExemplarPlan p = exemplar_plan(n_rows, K, slots, forced_parts);
+    out4[0] = p.unit_tiles; out4[1] = p.stages; out4[2] = p.parts; out4[3] = p.per;
     return 0;
 }
 

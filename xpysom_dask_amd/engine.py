@@ -553,6 +553,24 @@ class HipEngine:
         self._check(self._lib.som_unit_rank_counts_device(self._h, C.c_void_p(dev_ptr), int(n_rows), k, out.ctypes.data_as(C.POINTER(C.c_int64))))
         return out
 
+    # -- the k nearest rows of every unit (include/somhip.h, som_unit_nearest_rows) -------------
+    def unit_nearest_rows(self, x, k, *, score=True, dist=True):
+        """(ids int32, score float32 or None, dist float32 or None), each (K, k): per unit the k rows of `x` with the smallest
+        float32 activation score (the euclidean_no_opt score on a Euclidean engine, the cosine score on a cosine one: bit for bit
+        the entries of distance_matrix there), ascending, equal scores to the lower row id; `dist` the Euclidean distance of each
+        listed row to the unit.  Only scores below +inf enter; a slot nothing fills (k > n, rows that never enter) holds
+        -1 / NaN / NaN.  Always float32 arithmetic; 1 <= k <= 8."""
+        x = self._rows_arg(x)
+        ids, sc, ds, ptrs = self._topk_out(self.K, check_topk(k), score, dist)
+        self._check(self._lib.som_unit_nearest_rows(self._h, self._fp(x), x.shape[0], ids.shape[1], *ptrs))
+        return ids, sc, ds
+
+    def unit_nearest_rows_device(self, dev_ptr, n_rows, k, *, score=True, dist=True):
+        """unit_nearest_rows of float32 rows that already live in HBM (`dev_ptr`: [n_rows][D], borrowed for the call)."""
+        ids, sc, ds, ptrs = self._topk_out(self.K, check_topk(k), score, dist)
+        self._check(self._lib.som_unit_nearest_rows_device(self._h, C.c_void_p(dev_ptr), int(n_rows), ids.shape[1], *ptrs))
+        return ids, sc, ds
+
     # -- label and value maps (include/somhip.h, som_unit_label_counts / som_unit_value_sums) --
     def _check_columns(self, what, n):
         n = int(n)

@@ -365,6 +365,17 @@ def _ustar(u, p):
     return u * ((p - mean) / (mean - top) + 1.0)
 
 
+def _merge_unit_lists(chunks, k):
+    """The per-unit lists of consecutive row chunks -- ``(first row, ids (K, k), score, dist or None)`` each, ids counted inside
+    the chunk -- joined into the lists of all the rows: per unit the k lowest by (score, row index); an unfilled slot (-1) last.
+    ``(ids, dist or None)``."""
+    ids = np.concatenate([np.where(c[1] >= 0, c[1].astype(np.int64) + c[0], -1) for c in chunks], axis=1)
+    score = np.concatenate([np.where(c[1] >= 0, c[2], np.inf) for c in chunks], axis=1)
+    order = np.lexsort((np.where(ids >= 0, ids, np.iinfo(np.int64).max), score), axis=1)[:, :k]
+    dist = None if chunks[0][3] is None else np.take_along_axis(np.concatenate([c[3] for c in chunks], axis=1), order, axis=1)
+    return np.take_along_axis(ids, order, axis=1), dist
+
+
 def _sdh(rank_counts):
     """Pampalk's smoothed data histogram from the rank counts ``(s, ...)``: rank j weighs ``(s - j) / (s (s + 1) / 2)``."""
     c = np.asarray(rank_counts, dtype=np.float64)
@@ -1201,6 +1212,39 @@ class XPySom:
         if not return_distance:
             return ids
         return ids, (np.concatenate([p[2] for p in parts]) if parts else np.zeros((0, k), dtype=np.float32))
+
+    def nearest_samples(self, data, k=1, *, return_distance=True):
+        """The k nearest samples of every unit -- its exemplars: ``ids`` int64 ``(x, y, k)``, indices into ``data``, and ``dist``
+        float32 ``(x, y, k)`` (``return_distance=False``: ``ids`` alone).  Cell ``(i, j)`` lists the k samples with the smallest
+        activation distance to unit ``(i, j)``'s weight vector, nearest first, equal distances to the lower index -- the ranking
+        a stable argsort of each column of ``activate(data)`` would give on an 'euclidean_no_opt' or 'cosine' map ('euclidean'
+        ranks as 'euclidean_no_opt': its own score drops the samples' norms, which only the ranking of units may do), found on
+        the device without ever writing the ``(n, K)`` matrix.  It does not follow from ``predict``: a unit's nearest sample need
+        not be won by that unit, and a unit without hits still gets one.  ``dist[i, j, s]`` is the Euclidean distance of sample
+        ``ids[i, j, s]`` to the unit, formed from the differences as in ``quantization_distances`` -- always Euclidean, and not
+        what orders the list.  A sample holding a NaN or an infinity is listed nowhere under the Euclidean activations; a slot
+        beyond the samples that can be listed (``k > len(data)``) is ``-1`` / NaN.  ``1 <= k <= 8``.  Rows in HBM are searched
+        where they are; host rows in ``n_parallel`` chunks whose lists are merged by (score, index).  Under a process group a
+        rank answers for the rows it was given.  Not defined with ``missing='nan'``, for sparse rows, or for distances other
+        than the three above."""
+        from .engine import check_topk
+        _refuse_sparse(data, 'nearest_samples()')
+        self._refuse_missing('nearest_samples')
+        if self._activation_distance_name not in ('euclidean', 'euclidean_no_opt', 'cosine'):
+            raise NotImplementedError("nearest_samples() ranks the samples by the GEMM-form distances only (euclidean, euclidean_no_opt, "
+                                      "cosine); '%s' is a fused distance+argmin kernel here" % (self._activation_distance_name,))
+        k = check_topk(k)
+        eng, q, data = self._diag_query(data)
+        X, Y = self._weights.shape[:2]
+        if q is not None:
+            ids, _, dist = eng.unit_nearest_rows_device(q[1], q[2], k, score=False, dist=return_distance)
+        elif len(data) <= self._n_parallel:
+            ids, _, dist = eng.unit_nearest_rows(data, k, score=False, dist=return_distance)
+        else:
+            ids, dist = _merge_unit_lists([(s,) + eng.unit_nearest_rows(data[s:s + self._n_parallel], k, dist=return_distance)
+                                           for s in range(0, len(data), self._n_parallel)], k)
+        ids = ids.astype(np.int64).reshape(X, Y, k)
+        return (ids, dist.reshape(X, Y, k)) if return_distance else ids
 
     def rank_hits(self, data, k):
         """int64 ``(k, x, y)``: element ``[j, a, b]`` is the number of samples whose j-th nearest unit (``nearest_units``' column
