@@ -39,7 +39,16 @@ enum { SOM_DIST_EUCLIDEAN = 0,        /* 'euclidean'  -> euclidean_squared_dista
                                          csrc/bmu_pairwise.hpp, which refuses input_len > 2400) */
        SOM_DIST_NORM_P = 4,           /* 'norm_p' -> norm_p_power_distance, distances.py:98-107 (even p: binomial form :77-96) */
        SOM_DIST_NORM_P_NO_OPT = 5,    /* 'norm_p_no_opt' -> norm_p_power_distance_generic, distances.py:61-75 */
-       SOM_DIST_CHEBYSHEV = 6 };      /* 'chebyshev' (MiniSom's; not in the reference): max_d |x_d - w_d|, csrc/bmu_chebyshev.hpp */
+       SOM_DIST_CHEBYSHEV = 6,        /* 'chebyshev' (MiniSom's; not in the reference): max_d |x_d - w_d|, csrc/bmu_chebyshev.hpp */
+       SOM_DIST_TANIMOTO = 7 };       /* 'tanimoto' (not in the reference): the continuous Tanimoto / Jaccard distance, csrc/bmu_tanimoto.hpp.
+                                         Score of (row n, unit k), float32: s = 1 - p / (a + b - p); p = x_n . w_k, one chain of fused
+                                         multiply-adds on v_mfma_f32_32x32x2_f32 -- chunks of 32 features ascending, in a chunk the groups of
+                                         8 ascending, in a group features 0, 4, 1, 5, 2, 6, 3, 7 --; a = |x_n|^2 and b = |w_k|^2 once per row
+                                         and unit in NumPy's pairwise order; a + b - p <= 0 (both vectors zero): s = 0.  The BMU is the first
+                                         minimum of s, ties to the lower unit id under every launch geometry; a row holding a NaN or an
+                                         infinity (|x|^2 not finite) gets unit 0.  0/1 rows against a 0/1 codebook: exactly the Jaccard
+                                         distance.  input_len <= 4096; precision F32 or EXACT (both run this kernel); refused like
+                                         'chebyshev' with BF16 / F16, SOM_MISSING_NAN, CSR rows, the distance matrix, top-k and exemplars */
 
 /* neighbourhood function on the rectangular topology: neighborhoods.py:14-33, :57-74, :99-130 */
 enum { SOM_NEIGH_GAUSSIAN = 0, SOM_NEIGH_MEXICAN_HAT = 1, SOM_NEIGH_BUBBLE = 2, SOM_NEIGH_TRIANGLE = 3 };

@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SOM_LIB_PATH") or os.path.join(HERE, "libsomhip.so")   # override: kernel A/B builds
 
 SOM_DIST = {"euclidean": 0, "euclidean_no_opt": 1, "cosine": 2, "manhattan": 3, "manhattan_no_opt": 3,
-            "norm_p": 4, "norm_p_no_opt": 5, "chebyshev": 6}
+            "norm_p": 4, "norm_p_no_opt": 5, "chebyshev": 6, "tanimoto": 7}
 SOM_NEIGH = {"gaussian": 0, "mexican_hat": 1, "bubble": 2, "triangle": 3}
 SOM_PREC = {"f32": 0, "bf16": 1, "f16": 3, "exact": 5}      # (ids 2 and 4: the retired split-operand modes)
 SOM_TOPO = {"rectangular": 0, "hexagonal": 1, "toroidal": 2}

@@ -46,6 +46,7 @@
 #include "exemplar.hpp"
 #include "sparse.hpp"
 #include "bmu_chebyshev.hpp"
+#include "bmu_tanimoto.hpp"
 #include "bmu_manhattan.hpp"
 
 using namespace somhip;
@@ -458,6 +459,7 @@ struct som_handle {
     // read once in som_create (experiments / A-B runs): forced part counts, launch-geometry printing
     int env_bf16_parts = 0;
     int env_f32_parts = 0;   // SOM_F32_PARTS: the float32 resident kernel's part count (clamped to [1, fr_stages])
+    int env_tanimoto_parts = 0;    // SOM_TANIMOTO_PARTS: the tanimoto kernel's part count (clamped to [1, unit blocks])
     int env_chebyshev_parts = 0;   // SOM_CHEBYSHEV_PARTS: the chebyshev kernel's part count (clamped to [1, unit blocks])
     int env_manhattan_parts = 0;   // SOM_MANHATTAN_PARTS: the tiled manhattan kernel's part count (clamped to [1, unit blocks])
     // 'manhattan' on the tiled kernel (bmu_manhattan.hpp): its feature schedule, built once for the handle's input_len
@@ -1174,7 +1176,7 @@ int prep_rows_half(som_handle* h, RowSet& s) {
 bool needs_xsq(const som_handle* h) {
     if (h->exact) return true;                          // |x_n| scales the row's error bound (bmu_exact.hpp)
     return h->cfg.precision == SOM_PREC_F32 &&
-           (h->cfg.distance == SOM_DIST_EUCLIDEAN_NO_OPT || h->cfg.distance == SOM_DIST_COSINE);
+           (h->cfg.distance == SOM_DIST_EUCLIDEAN_NO_OPT || h->cfg.distance == SOM_DIST_COSINE || h->cfg.distance == SOM_DIST_TANIMOTO);
 }
 
 int row_sq(som_handle* h, const float* X, long N, float* out) {
@@ -1263,6 +1265,34 @@ int launch_bmu_chebyshev(som_handle* h, const float* X, long N, int* out) {
     const dim3 grid((unsigned)blocks, (unsigned)parts);
     if (res) bmu_chebyshev_kernel<true><<<grid, dim3(256), lds, h->stream>>>(X, N, h->D, h->W, h->K, x_vec, w_vec, out, out64);
     else bmu_chebyshev_kernel<false><<<grid, dim3(256), lds, h->stream>>>(X, N, h->D, h->W, h->K, x_vec, w_vec, out, out64);
+    if (parts > 1) bmu_finalize_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(out64, N, h->K, out);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// 'tanimoto' (bmu_tanimoto.hpp): 128-row blocks x `parts` ranges of the 128-unit blocks, as launch_bmu_chebyshev.  xsq: the
+// rows' |x|^2 (prepare), h->wsq: the codebook's (refresh_codebook_operands), both row_sq_f32_kernel's.
+int launch_bmu_tanimoto(som_handle* h, const float* X, long N, const float* xsq, int* out) {
+    if (!xsq) return fail(h, "bmu_tanimoto: no row norms");
+    const void* fn = (const void*)bmu_tanimoto_kernel;
+    int per_cu = 1;
+    if (int rc = kernel_per_cu(h, fn, 256, TN_LDS_BYTES, &per_cu)) return rc;
+    const long blocks = cdiv(N, TN_BM);
+    if (blocks <= 0 || blocks > 0x7fffffffL) return fail(h, "bmu_tanimoto: row count out of range");
+    const int n_ub = (int)cdiv(h->K, TN_BN);
+    int parts = choose_parts(h, blocks, resident_slots(h, per_cu), n_ub);
+    if (h->env_tanimoto_parts > 0) parts = h->env_tanimoto_parts;   // (tests: the single-part and the merged paths at any size)
+    parts = std::max(1, std::min(parts, std::min(n_ub, 65535)));
+    if (h->debug) std::fprintf(stderr, "[somhip] bmu_tanimoto: blocks=%ld per_cu=%d parts=%d unit_blocks=%d\n", blocks, per_cu, parts, n_ub);
+    // 16-byte reads along the feature axis where every row starts on a 16-byte boundary
+    const int x_vec = h->D % 4 == 0 && (uintptr_t)X % 16 == 0, w_vec = h->D % 4 == 0 && (uintptr_t)(const float*)h->W % 16 == 0;
+    unsigned long long* out64 = nullptr;
+    if (parts > 1) {
+        if (int rc = h->best64.reserve(h, (size_t)N, 1024)) return rc;
+        out64 = h->best64;
+        ch_fill_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(out64, N);
+    }
+    bmu_tanimoto_kernel<<<dim3((unsigned)blocks, (unsigned)parts), dim3(256), TN_LDS_BYTES, h->stream>>>(X, N, h->D, xsq, h->W, h->wsq, h->K, x_vec, w_vec, out, out64);
     if (parts > 1) bmu_finalize_kernel<<<dim3((unsigned)cdiv(N, 256)), dim3(256), 0, h->stream>>>(out64, N, h->K, out);
     HIPCHK(h, hipGetLastError());
     return 0;
@@ -1436,6 +1466,7 @@ int run_activation_bmu_launch(som_handle* h, const Rows& r) {
     case SOM_DIST_NORM_P_NO_OPT: return launch_bmu_pairwise(h, r.X, r.N, h->norm_p, false, r.out);
     case SOM_DIST_NORM_P: return launch_bmu_pairwise(h, r.X, r.N, h->norm_p, h->norm_p % 2 == 0, r.out);
     case SOM_DIST_CHEBYSHEV: return launch_bmu_chebyshev(h, r.X, r.N, r.out);
+    case SOM_DIST_TANIMOTO: return launch_bmu_tanimoto(h, r.X, r.N, r.xsq, r.out);
     }
     return fail(h, "unknown distance id");
 }
@@ -1970,7 +2001,8 @@ int som_create(const som_config* cfg, som_handle** out) {
     if (!cfg) return fail(nullptr, "som_create: cfg is NULL");
     if (cfg->x < 1 || cfg->y < 1 || cfg->input_len < 1) return fail(nullptr, "som_create: x, y, input_len must be >= 1");
     if ((long)cfg->x * cfg->y > (1L << 30)) return fail(nullptr, "som_create: map too large");
-    if (cfg->distance < 0 || cfg->distance > SOM_DIST_CHEBYSHEV) return fail(nullptr, "som_create: unknown distance id");
+    if (cfg->distance < 0 || cfg->distance > SOM_DIST_TANIMOTO) return fail(nullptr, "som_create: unknown distance id");
+    if (cfg->distance == SOM_DIST_TANIMOTO && cfg->input_len > TN_MAX_D) return fail(nullptr, "som_create: the tanimoto distance serves input_len <= 4096");
     if (cfg->norm_p < 0 || cfg->norm_p > PW_MAX_P) return fail(nullptr, "som_create: norm_p out of range (1..16)");
     if (cfg->norm_p_real != 0.0 && !(cfg->norm_p_real > 0.0 && cfg->norm_p_real <= 64.0))
         return fail(nullptr, "som_create: norm_p_real out of range (0 < p <= 64)");
@@ -2127,6 +2159,7 @@ int som_create(const som_config* cfg, som_handle** out) {
         if (const char* e = dev_env("SOM_MASKED_PARTS")) h->env_masked_parts = std::atoi(e);
         if (const char* e = dev_env("SOM_F32_PARTS")) h->env_f32_parts = std::atoi(e);
         if (const char* e = dev_env("SOM_CHEBYSHEV_PARTS")) h->env_chebyshev_parts = std::atoi(e);
+        if (const char* e = dev_env("SOM_TANIMOTO_PARTS")) h->env_tanimoto_parts = std::atoi(e);
         if (const char* e = dev_env("SOM_MANHATTAN_PARTS")) h->env_manhattan_parts = std::atoi(e);
         bool mn_tiled = h->cfg.distance == SOM_DIST_MANHATTAN && h->D <= MN_MAX_D;
         if (const char* e = dev_env("SOM_MANHATTAN_TILED")) mn_tiled = mn_tiled && std::atoi(e) != 0;   // A/B: bmu_pairwise_kernel

@@ -22,7 +22,8 @@ TOPOLOGIES = ("hexagonal", "rectangular", "toroidal")
 NEIGHBORHOODS = {"gaussian": True, "mexican_hat": True, "bubble": True, "triangle": True}
 # distances.py:162-170 registry; False = valid reference name the engine does not cover yet
 DISTANCES = {"euclidean": True, "euclidean_no_opt": True, "manhattan": True, "manhattan_no_opt": True,
-             "cosine": True, "norm_p": True, "norm_p_no_opt": True, "chebyshev": True}
+             "cosine": True, "norm_p": True, "norm_p_no_opt": True, "chebyshev": True, "tanimoto": True}
+TANIMOTO_MAX_INPUT_LEN = 4096     # csrc/bmu_tanimoto.hpp, TN_MAX_D
 DEFAULT_BATCH_ROWS = 65536
 
 
@@ -414,7 +415,11 @@ class XPySom:
           (activation_distance: 'manhattan' / 'manhattan_no_opt' sum float32 terms in NumPy's pairwise order, bit for bit,
                          on a register-tiled kernel for input_len <= 4096; longer rows are refused.  'norm_p' and
                          'norm_p_no_opt' run one thread a row and are refused beyond input_len 2400.  'chebyshev', 'euclidean'
-                         and 'cosine' take any input_len)
+                         and 'cosine' take any input_len.  'tanimoto' -- not in the reference -- is the continuous
+                         Tanimoto / Jaccard distance 1 - x.w / (|x|^2 + |w|^2 - x.w) for binary and count rows, a float32
+                         MFMA search of its own for input_len <= 4096: first minimum, ties to the lower unit, a row
+                         holding a NaN or an infinity gets unit 0; refused like 'chebyshev' with 'bf16' / 'f16',
+                         missing='nan', sparse rows, activate, nearest_units and nearest_samples)
           device         HIP device ordinal (default: LOCAL_RANK or 0)
           sharded_input  under an initialised process group: ``train(data)`` receives only this
                          rank's rows (default: every rank passes the full array and takes its slice)
@@ -507,6 +512,8 @@ class XPySom:
         if precision not in ('f32', 'exact') and activation_distance not in ('euclidean', 'cosine'):
             raise ValueError("precision '%s' implements the GEMM-form distances 'euclidean' and 'cosine'; "
                              "'%s' needs precision='f32'" % (precision, activation_distance))
+        if activation_distance == 'tanimoto' and input_len > TANIMOTO_MAX_INPUT_LEN:
+            raise ValueError("'tanimoto' serves input_len <= %d, got %d" % (TANIMOTO_MAX_INPUT_LEN, input_len))
         if activation_distance.startswith('norm_p'):
             p = activation_distance_kwargs.get('p', 2)
             if isinstance(p, (int, np.integer)) or (isinstance(p, (float, np.floating)) and float(p).is_integer()):
